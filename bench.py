@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the VectorBase kNN hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--workload NAME] [--full] [--dump-outputs DIR]
 
-One JSON line on stdout (rank 0).  Without --workload this is the north-star suite:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times exactly K steps of the workload (default: the headline, cfg3) and
+prints `value` and `ms_per_step` of those steps; `--dump-outputs DIR` writes what the last timed step returned (ordinals, scores, counts)
+as DIR/<name>.npy.  Everything else described below -- roofline and kernel times (an event pass of their own), the host-buffer form,
+parity, the CPU baseline, the sustained calibration, class-level rates and the sub-records -- runs with --full only.
+
+With --full and without --workload this is the north-star suite:
 
   headline   cfg3 = BASELINE.json configs[2]: 10M x 1536 fp16 corpus, ONE 1024-query batch per step, top-32,
              through the C-ABI call `tavb_search_device` + `tavb_synchronize`: the query batches (four in rotation) are RESIDENT
@@ -60,6 +65,7 @@ CHUNK_ROWS = 262_144           # generation granule of the synthetic corpus
 ORACLE_CHUNK = 1_000_000       # rows handed to the CPU oracle at a time (a reference-sized VectorBase)
 BATCH_ROTATION = 4             # different query batches that take turns in the timed region of a batched workload
 PARITY_QUERIES = 16
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     #            rows (total)  dim   dtype   queries/step  k   bound   seed
@@ -559,8 +565,34 @@ def kernel_times(ctx: Ctx) -> dict:
     return {name: ctx.eng.profile_read(kid) for name, kid in ids.items()}
 
 
-def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int, warmup: int, with_cpu: bool) -> dict:
-    """Time `steps` lookups of workload `wl` on the corpus already resident on this rank; returns the record (rank 0)."""
+def step_outputs(res) -> dict:
+    """What one step of the timed path hands its caller, as host arrays: (ordinals, scores) of a single lookup, (ordinals, scores, counts)
+    of a batch."""
+    names = ("ordinals", "scores", "counts")
+    return {n: np.array(x.cpu().numpy() if hasattr(x, "cpu") else x) for n, x in zip(names, res)}
+
+
+def dump_outputs(dirname: str, outputs: dict) -> None:
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy (float32 scores, float64 ordinals and counts: exact below 2**53), at most
+    DUMP_LIMIT_BYTES in all -- past that, the same seeded sample of leading rows of every array."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        lead = max(a.shape[0] for a in arrays.values() if a.ndim)
+        row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values() if a.ndim and a.shape[0] == lead)
+        keep = np.sort(np.random.default_rng(0).choice(lead, size=max(1, DUMP_LIMIT_BYTES // row_bytes), replace=False))
+        arrays = {n: (a[keep] if a.ndim and a.shape[0] == lead else a) for n, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int, warmup: int, with_cpu: bool, lean: bool = False) -> dict:
+    """Time `steps` lookups of workload `wl` on the corpus already resident on this rank; returns the record (rank 0).  `lean`: the timed
+    steps only (no event pass, host-buffer form, parity or CPU baseline).  `outputs` = what the last timed step returned."""
     args, eng, torch = ctx.args, ctx.eng, ctx.torch
     dim, k, nq = wl["dim"], wl["k"], wl["nq"]
     rows_local, rows_total = int(corpus.shape[0]), wl["rows_total"]
@@ -638,18 +670,36 @@ def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int,
     gc.disable()
     ctx.barrier()
     lat = []
+    last = None
     t0 = time.perf_counter()
     for i in range(steps):
         s0 = time.perf_counter_ns()
-        one_step(warmup + i)
+        last = one_step(warmup + i)
         lat.append((time.perf_counter_ns() - s0) / 1e3)
     t_loop = time.perf_counter() - t0
     ctx.barrier()
     elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
     gc.enable()
+    outputs = step_outputs(last) if last is not None else {}
+    del last
     if os.environ.get("TAVB_BENCH_DEBUG"):
         sys.stderr.write(f"[bench debug] {name}: loop {t_loop * 1e3:.2f} ms, sum of steps {sum(lat) / 1e3:.2f} ms, max step {max(lat) / 1e3:.3f} ms, "
                          f"closing barrier {(elapsed - t_loop) * 1e3:.2f} ms\n")
+    workload = (f"{name}: {rows_total}x{dim} {wl['dtype']}" + (f" over {ctx.world} GPUs ({rows_local} rows on rank 0)" if ctx.world > 1 else "")
+                + f", {nq} q/step, top-{k}, min_score {min_score:g}" + (f", subset of {len(subset)} ordinals (row list resident)" if subset is not None else ""))
+    timed = {
+        "workload": workload,
+        "queries_per_sec": steps * nq / elapsed,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3,
+        "p50_latency_us": float(np.percentile(lat, 50)),
+        "p99_latency_us": float(np.percentile(lat, 99)),
+        "min_latency_us": float(np.min(lat)),
+        "dtype": "f32" if wl["dtype"] == "fp32" else "f16 storage, f32 accumulate",
+    }
+    if lean:
+        return dict(timed, outputs=outputs) if ctx.rank == 0 else {}
     # ---- the same `steps` steps again with a HIP event pair around every kernel launch (on the library's stream): the kernel times of the
     #      roofline.  Kept out of the timed region: an event pair costs the stream ~0.03-0.07 ms of bubbles per launch (10 % of a 1.4 ms step).
     eng.profile_enable(True)
@@ -715,7 +765,6 @@ def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int,
         return {}
     sys.stderr.write(f"bench.py: {name}: {n_lookups[0]} lookups in this process (warm-up, timed steps, event pass, host-buffer form, answers)\n")
 
-    qps = steps * nq / elapsed
     esize = 2 if wl["dtype"] == "fp16" else 4
     shadow = False
     try:
@@ -780,20 +829,7 @@ def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int,
         "kernel_parts_ms_per_step": {p: kt[p][0] / steps for p in parts},
         "other_kernels_ms_per_step": {p: kt[p][0] / steps for p in kt if p not in parts and kt[p][1]},
     })
-    rec = {
-        "workload": f"{name}: {rows_total}x{dim} {wl['dtype']}"
-                    + (f" over {ctx.world} GPUs ({rows_local} rows on rank 0)" if ctx.world > 1 else "")
-                    + f", {nq} q/step, top-{k}, min_score {min_score:g}",
-        "queries_per_sec": qps,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": elapsed / steps * 1e3,
-        "p50_latency_us": float(np.percentile(lat, 50)),
-        "p99_latency_us": float(np.percentile(lat, 99)),
-        "min_latency_us": float(np.min(lat)),
-        "dtype": "f32" if wl["dtype"] == "fp32" else "f16 storage, f32 accumulate",
-        "roofline": roof,
-    }
+    rec = dict(timed, roofline=roof)
     if nq > 1:
         rec["query_batches_in_rotation"] = n_rot
         if searcher is None and flagged:
@@ -811,14 +847,13 @@ def run_record(ctx: Ctx, name: str, wl: dict, corpus, shard_lo: int, steps: int,
         rec["host_buffer_form"] = host_form
     if dist_extra:
         rec["exchange"] = dist_extra
-    if subset is not None:
-        rec["workload"] += f", subset of {len(subset)} ordinals (row list resident)"
     if not args.no_parity:
         rec["parity"] = parity_check(eng, corpus, shard_lo, wl, queries, sample, got, min_score, subset)
     if with_cpu and not args.no_cpu_baseline:
         n_host = min(rows_local, ORACLE_CHUNK)
         host = corpus[:n_host].float().cpu().numpy()
         rec["cpu_baseline"] = cpu_baseline(host, queries, k, rows_total, nq, wl.get("cpu_seconds", args.cpu_seconds), subset)
+    rec["outputs"] = outputs
     return rec
 
 
@@ -1017,9 +1052,10 @@ def headline_line(ctx: Ctx, rec: dict, name: str, wl: dict, scaling: str, sub: d
         },
         "p50_latency_us": rec["p50_latency_us"],
         "p99_latency_us": rec["p99_latency_us"],
-        "roofline": {k: v for k, v in rec["roofline"].items() if k not in ("pipe", "ms_per_step_with_events")},
-        "cpu_baseline": rec.get("cpu_baseline"),
     }
+    if "roofline" in rec:  # (--full: the event pass)
+        out["roofline"] = {k: v for k, v in rec["roofline"].items() if k not in ("pipe", "ms_per_step_with_events")}
+    out["cpu_baseline"] = rec.get("cpu_baseline")
     if getattr(ctx, "dry_run", False):
         out["dry_run"] = (f"{ctx.world} ranks sharing ONE GPU over {ctx.dist_backend}: this line proves that bench.py's N > 1 branches run "
                           "(rank != 0, per-rank timing gather, whole-corpus parity over every rank's rows, cfg4_weak); its rates are not measurements")
@@ -1111,20 +1147,31 @@ def run_cfg5(args, wl, emit: bool = True, steps: int | None = None, warmup: int 
         gc.collect()
         gc.disable()  # (as in run_record: no generation-2 collection inside the timed region)
         lat = []
+        last = None
         t0 = time.perf_counter()
         for i in range(n_steps):  # the timed region: un-instrumented
             s0 = time.perf_counter_ns()
-            one(n_warm + i)
+            last = one(n_warm + i)
             lat.append((time.perf_counter_ns() - s0) / 1e3)
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         gc.enable()
+        time_mode.last = last
         return el, lat
 
     subset = subset_of(args.cfg5_subset)
     one = make_one(args.cfg5_separate, subset)
     elapsed, lat = time_mode(one, steps, warmup)
-    if not args.cfg5_separate:  # the same steps again with HIP event pairs around the launches (kernel times)
+    if emit and args.dump_outputs:  # the six hit lists of the last timed user query
+        res = time_mode.last
+        lists = list(res.terms) + [res.messages, res.threads] if hasattr(res, "terms") else list(res)
+        outs = {}
+        for j, hits in enumerate(lists):
+            outs[f"lookup{j}_ordinals"] = np.array([h.item for h in hits], dtype=np.float64)
+            outs[f"lookup{j}_scores"] = np.array([h.score for h in hits], dtype=np.float32)
+        dump_outputs(args.dump_outputs, outs)
+    full = args.full or not emit  # (emit=False: a sub-record of the --full suite)
+    if full and not args.cfg5_separate:  # the same steps again with HIP event pairs around the launches (kernel times)
         eng.profile_enable(True)
         eng.profile_reset()
         for i in range(steps):
@@ -1148,7 +1195,7 @@ def run_cfg5(args, wl, emit: bool = True, steps: int | None = None, warmup: int 
                      "frac": alg / (elapsed / steps) / 1e9 / HBM_PEAK_GBS, "traffic": None},  # whole user query (kernels + copies + one sync) against the bytes the three passes must read
         "cpu_baseline": None,
     }
-    if not args.cfg5_separate:
+    if full and not args.cfg5_separate:
         ms, n = eng.profile_read(_native.KERNEL_SCAN)
         out["roofline"]["scan_kernel_ms_per_user_query"] = ms / steps
         out["roofline"]["scan_launches_per_user_query"] = n / steps
@@ -1169,7 +1216,7 @@ def run_cfg5(args, wl, emit: bool = True, steps: int | None = None, warmup: int 
         el_x, _ = time_mode(one_x, max(5, steps // 2), 2)
         n_x = max(5, steps // 2)
         out["variants"]["separate_calls"] = {"value": n_x / el_x, "ms_per_step": el_x / n_x * 1e3, "fused_speedup": (steps / elapsed) / (n_x / el_x)}
-    if not args.no_parity:
+    if full and not args.no_parity:
         out["parity"] = cfg5_parity(eng, one, user_queries[:2], {"terms": (terms, 50_043), "messages": (msgs, 50_044), "threads": (threads, 50_045)},
                                     dim, wl["dtype"], subset)
     del terms, msgs, threads
@@ -1347,7 +1394,7 @@ def selftest(args) -> int:
         return 0
     lines = {}
     for n in (1, 2):
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--workload", "cfg3", "--no-cpu-baseline", "--steps", str(args.steps or 10)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--workload", "cfg3", "--full", "--no-cpu-baseline", "--steps", str(args.steps or 10)]
         if args.rows:
             cmd += ["--rows", str(args.rows)]
         env = dict(os.environ)
@@ -1387,6 +1434,9 @@ def main() -> None:
     ap.add_argument("--no-calibration", action="store_true", help="skip roofline.sustained (the MFMA-only ablation + vendor GEMM after the headline): counter passes want the lookups only")
     ap.add_argument("--class-api", action="store_true", help="also time the workload through VectorBase.fuzzy_lookup_embedding(s) (always on in the default suite)")
     ap.add_argument("--selftest", action="store_true", help="on a box with >= 2 GPUs: cfg3 strong scaling at N = 2 over RCCL with full parity, next to N = 1 (one JSON line); skipped on one GPU")
+    ap.add_argument("--full", action="store_true", help="everything beside the timed steps: the event pass (roofline, kernel times, exchange), host-buffer form, parity "
+                    "against the CPU oracle, CPU baseline, sustained calibration, class-level rates and the north-star suite's sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.selftest:
         raise SystemExit(selftest(args))
@@ -1432,21 +1482,24 @@ def main() -> None:
     stream_ctx = torch.cuda.stream(ctx.backend.stream) if ctx.backend is not None else torch.cuda.stream(torch.cuda.current_stream(ctx.dev))
     with stream_ctx:
         corpus = gen_rows(ctx.eng, lo, hi, wl["dim"], wl["seed"], wl["dtype"], wl.get("kind", "gaussian"), wl["rows_total"], wl.get("cluster_rows", CLUSTER_ROWS))
-    rec = run_record(ctx, name, wl, corpus, lo, steps, warmup, with_cpu=(ctx.world == 1))
+    rec = run_record(ctx, name, wl, corpus, lo, steps, warmup, with_cpu=(ctx.world == 1), lean=not args.full)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, rec["outputs"])
+    class_api = args.class_api or (suite and args.full)
     if ctx.world == 1 and not ctx.distributed and ctx.rank == 0 and not any(o.startswith("mfma_ablate") for o in args.opt):
-        if rec["roofline"]["bound"] == "mfma" and rec["roofline"]["kernel"] == "mfma_scan_kernel" and wl["dtype"] == "fp16" and not args.no_calibration:
+        if args.full and rec["roofline"]["bound"] == "mfma" and rec["roofline"]["kernel"] == "mfma_scan_kernel" and wl["dtype"] == "fp16" and not args.no_calibration:
             rec["roofline"]["sustained"] = sustained_calibration(ctx, wl, corpus, rec["roofline"]["kernel_ms_per_step"])
-        if suite or args.class_api:
+        if class_api:
             rec["class_api"] = class_api_rates(ctx, wl, corpus, args.min_score, 5 if wl["nq"] > 1 else 50)
 
-    if ctx.distributed and wl["nq"] > 1 and (suite or args.class_api):
+    if ctx.distributed and wl["nq"] > 1 and class_api:
         api = sharded_class_api_rates(ctx, wl, corpus, lo, args.min_score, 5)
         if ctx.rank == 0:
             rec["class_api"] = api
 
     sub = None
     sub_skipped = []
-    if suite and not ctx.distributed and not args.no_sub:
+    if suite and args.full and not ctx.distributed and not args.no_sub:
         sub = {}
         # the single-query target on the same 10M-row corpus
         w2 = dict(WORKLOADS["cfg3_q1"], rows_total=wl["rows_total"], rows=wl["rows"])
@@ -1593,7 +1646,7 @@ def main() -> None:
         for label, fn in (("cfg2 group", g_cfg2), ("cfg1 group", g_cfg1), ("cfg4_shard", g_cfg4), ("cfg5", g_cfg5), ("3072-wide group", g_d3072),
                           ("cfg3_aniso group", g_aniso), ("cfg3_clustered", g_clustered), ("cfg3_dup", g_dup)):
             group(label, fn)
-    elif suite and ctx.distributed and not args.no_sub:  # (also the one-rank dry run of this code, TAVB_BENCH_FORCE_DIST=1)
+    elif suite and args.full and ctx.distributed and not args.no_sub:  # (also the one-rank dry run of this code, TAVB_BENCH_FORCE_DIST=1)
         # N > 1: beside the strong-scaling headline, BASELINE configs[3] as the north star words it -- 12.5M rows PER GPU (100M rows at N = 8),
         # the same 1024-query batches; `row_queries_per_sec` is the weak-scaling figure (rows x queries per second over all ranks)
         del corpus

@@ -216,3 +216,30 @@ def test_the_two_rank_dry_run_line_has_the_shape_of_an_n_gt_1_record():
     assert weak["row_queries_per_sec"] == bench.compact(weak["queries_per_sec"] * sum(weak["exchange"]["rows_per_rank"]), 4) or \
         abs(weak["row_queries_per_sec"] / (weak["queries_per_sec"] * sum(weak["exchange"]["rows_per_rank"])) - 1) < 1e-3
     assert line["cpu_baseline"] is None  # (rank 0 at N = 1 only)
+
+
+def test_dumped_outputs_are_float_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: what the last timed step returned, as float32 / float64 .npy files; past the size limit the same seeded
+    sample of rows of every array, so that two builds compare output for output."""
+    import numpy as np
+
+    rng = np.random.default_rng(0)
+    ords = rng.integers(0, 10_000_000, size=(1024, 32)).astype(np.int64)
+    scs = rng.random((1024, 32)).astype(np.float32)
+    cnts = np.full(1024, 32, dtype=np.int32)
+    out = bench.step_outputs((ords, scs, cnts))
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("ordinals", "scores", "counts")}
+    assert got["ordinals"].dtype == np.float64 and got["scores"].dtype == np.float32 and got["counts"].dtype == np.float64
+    np.testing.assert_array_equal(got["ordinals"], ords)
+    np.testing.assert_array_equal(got["scores"], scs)
+    np.testing.assert_array_equal(got["counts"], cnts)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (32 * 8 + 32 * 4 + 8))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    small = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("ordinals", "scores", "counts")}
+    assert sum(a.nbytes for a in small.values()) <= bench.DUMP_LIMIT_BYTES and len(small["ordinals"]) == 100
+    rows = [int(np.flatnonzero((ords == r).all(axis=1))[0]) for r in small["ordinals"].astype(np.int64)]
+    np.testing.assert_array_equal(small["scores"], scs[rows])
+    for n, a in small.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "c" / f"{n}.npy"))

@@ -265,19 +265,27 @@ def test_scoredint_is_a_plain_dataclass():
     assert a.score == 0.75
 
 
-def test_scoredint_matches_the_reference_dataclass():
-    """Same fields, repr, equality and keyword construction as vectorbase.py:50-55 (needs /root/reference)."""
+def scored_int_observations(cls) -> dict:
+    """Fields, repr, tuple form and equality of a ScoredInt class (tests/golden/make_reference_answers.py records the reference's)."""
     import dataclasses
 
-    from oracle import ref_loader
+    a = cls(item=7, score=0.25)
+    return {"fields": [f.name for f in dataclasses.fields(a)], "repr": repr(a), "astuple": list(dataclasses.astuple(a)),
+            "eq_positional": a == cls(7, 0.25), "ne_other_item": a != cls(8, 0.25)}
 
-    if not ref_loader.reference_available():
-        pytest.skip("reference checkout not present")
-    ref = ref_loader.load_reference_vectorbase().ScoredInt
-    ours, theirs = ScoredInt(item=7, score=0.25), ref(item=7, score=0.25)
-    assert [f.name for f in dataclasses.fields(ours)] == [f.name for f in dataclasses.fields(theirs)]
-    assert repr(ours) == repr(theirs) and dataclasses.astuple(ours) == dataclasses.astuple(theirs)
-    assert (ours == ScoredInt(7, 0.25)) and (theirs == ref(7, 0.25)) and (ours != ScoredInt(8, 0.25))
+
+def test_scoredint_matches_the_reference_dataclass():
+    """Same fields, repr, equality and keyword construction as vectorbase.py:50-55 (the reference's, stored in
+    tests/golden/reference_answers.json)."""
+    import json
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tests", "golden", "reference_answers.json")) as f:
+        theirs = json.load(f)["scored_int"]
+    ours = scored_int_observations(ScoredInt)
+    assert ours == theirs
+    assert ours["eq_positional"] and ours["ne_other_item"]
 
 
 def test_batch_lookup_as_arrays_and_shadow_env_knob_on_a_fake_engine(monkeypatch):

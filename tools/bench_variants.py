@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Run bench.py over a list of variants (one child process each) and print one compact line per variant.
+"""Run bench.py --full over a list of variants (one child process each) and print one compact line per variant (roofline and kernel times
+included: they come from --full's event pass).
 
     python tools/bench_variants.py OUTDIR "name: args ..." "name2: args ..."
 """
@@ -21,7 +22,7 @@ def main():
         while argv and "=" in argv[0] and not argv[0].startswith("-"):
             k, v = argv.pop(0).split("=", 1)
             env[k] = v
-        proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, env=env, timeout=900)
+        proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + argv, capture_output=True, text=True, env=env, timeout=900)
         lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
         if proc.returncode != 0 or not lines:
             print(f"{name}: FAILED rc={proc.returncode} {proc.stderr[-400:]!r}")

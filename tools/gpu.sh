@@ -6,7 +6,7 @@
 #   opttests:OPTS:EXPR  the same under TAVB_ENGINE_OPTIONS=OPTS (every engine of the test process gets those options)   -> gpu_opttests.log
 #   fuzz:BASES       tests/test_gpu_fuzz.py once per seed base of the comma-separated list (TAVB_FUZZ_BASE)             -> fuzz_<base>.log
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command (bench.py --gpus 1 --steps 20 --warmup 5) + a digest of the line  -> bench_default.json
+#   bench            the whole suite (bench.py --gpus 1 --steps 20 --warmup 5 --full) + a digest of the line  -> bench_default.json
 #   dist1            the N > 1 code path on a one-rank communicator (TAVB_BENCH_FORCE_DIST=1)               -> bench_dist1.json
 #   dist2[:ROWS], dist8[:ROWS]  the N = 2 (N = 8) branches of bench.py on ONE GPU: the ranks under torch.distributed.run share cuda:0, gloo, the lookups' exchange
 #                    through the host (TAVB_BENCH_DIST_BACKEND=gloo); ROWS rows in the strong-scaling corpus and per rank of cfg4_weak (default 2000000)  -> bench_dist2.json
@@ -30,7 +30,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 LABEL=$1; shift
 O=$R/gpurun_out/$LABEL; mkdir -p "$O"
-Q="--no-cpu-baseline --no-parity --no-sub --no-calibration"
+Q="--full --no-cpu-baseline --no-parity --no-sub --no-calibration"
 
 digest() { # file
 python - "$1" <<'PY'
@@ -64,17 +64,17 @@ for step in "$@"; do
     fuzz) for b in ${arg//,/ }; do TAVB_FUZZ_BASE=$b timeout 900 python -m pytest tests/test_gpu_fuzz.py -q -m gpu > $O/fuzz_$b.log 2>&1; echo "fuzz base $b rc=$? $(tail -1 $O/fuzz_$b.log)"; done ;;
     smoke) timeout 180 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
     bench)
-      timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+      timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
       echo "bench rc=$? in $(( $(date +%s) - S )) s, line bytes: $(wc -c < $O/bench_default.json)"; tail -3 $O/bench_default.err; digest $O/bench_default.json ;;
     dist1)
-      TAVB_BENCH_FORCE_DIST=1 timeout 900 python bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_dist1.json 2> $O/bench_dist1.err
+      TAVB_BENCH_FORCE_DIST=1 timeout 900 python bench.py --gpus 1 --steps 10 --warmup 2 --full --no-cpu-baseline > $O/bench_dist1.json 2> $O/bench_dist1.err
       echo "dist1 rc=$? line bytes: $(wc -c < $O/bench_dist1.json)"; tail -3 $O/bench_dist1.err; digest $O/bench_dist1.json ;;
     dist2|dist8)
       NP=${step%%:*}; NP=${NP#dist}
       ROWS=2000000; [ "$arg" != "dist$NP" ] && ROWS=$arg
       PORT=$(python -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
       TAVB_BENCH_DIST_BACKEND=gloo timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP --master-addr 127.0.0.1 --master-port $PORT \
-        bench.py --gpus $NP --steps 5 --warmup 2 --rows $ROWS > $O/bench_dist$NP.json 2> $O/bench_dist$NP.err
+        bench.py --gpus $NP --steps 5 --warmup 2 --rows $ROWS --full > $O/bench_dist$NP.json 2> $O/bench_dist$NP.err
       echo "dist$NP rc=$? line bytes: $(wc -c < $O/bench_dist$NP.json)"; grep -v "^W0\|^\*\*\*\|OMP_NUM\|Gloo\|socket.cpp" $O/bench_dist$NP.err | tail -5; digest $O/bench_dist$NP.json
       python -c "import json; d=json.loads(open('$O/bench_dist$NP.json').read().strip().splitlines()[-1]); print('exchange', d.get('exchange')); print('weak', d['sub']['cfg4_weak'].get('exchange'), d['sub']['cfg4_weak'].get('parity')); print(d.get('dry_run'))" ;;
     parity100m) timeout 1700 python tools/parity_leg_time.py > $O/parity100m.txt 2>&1; echo "parity100m rc=$?"; tail -5 $O/parity100m.txt ;;
@@ -128,7 +128,7 @@ for step in "$@"; do
       python -c "import json; d=json.load(open('$O/pmc_traffic.json')); print({k:(round(v['traffic_bytes_per_step']/1e9,3), v['launches_per_step']) for k,v in d.items()})" ;;
     pmcw) pmc cfg3_write "" "--workload cfg3 --steps 2 --warmup 1" WRITE_SIZE; tail -12 $O/pmc_cfg3_write.md ;;
     trace)
-      ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_default -o x -- python $R/bench.py --no-cpu-baseline --no-parity --steps 4 --warmup 1 > $O/trace_default.log 2>&1; echo "trace default rc=$?"
+      ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_default -o x -- python $R/bench.py --full --no-cpu-baseline --no-parity --steps 4 --warmup 1 > $O/trace_default.log 2>&1; echo "trace default rc=$?"
         timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_headline -o x -- python $R/bench.py $Q --steps 20 --warmup 5 > $O/trace_headline.log 2>&1; echo "trace headline rc=$?" )
       for t in default headline; do
         db=$(find $O/trace_$t -name "*results.db" 2>/dev/null | head -1); [ -n "$db" ] && python tools/rocpd_summary.py $db > $O/trace_$t.md 2>> $O/trace_err.log

@@ -1,7 +1,7 @@
 set -u
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r6z; mkdir -p $O
-Q="--no-cpu-baseline --no-parity --no-sub --no-calibration"
+Q="--full --no-cpu-baseline --no-parity --no-sub --no-calibration"
 cd /tmp
 for spec in "c2b32:--workload cfg2_b32 --steps 20 --warmup 5" "shard:--workload cfg3 --rows 1250000 --steps 20 --warmup 5" ; do
   n=${spec%%:*}; a=${spec#*:}
