@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 /* bumped whenever an entry point, a signature, an option or a kernel id changes incompatibly; the binding refuses a library of another version */
-#define TAVB_ABI_VERSION 6
+#define TAVB_ABI_VERSION 7
 
 #define TAVB_OK 0
 #define TAVB_E_INVALID (-1)     /* bad argument */
@@ -53,6 +53,8 @@ extern "C" {
 
 /* Largest k served by the fused select-while-streaming kernels. */
 #define TAVB_MAX_FUSED_K 256
+/* Largest k of tavb_search_topk / tavb_search_subset_topk (exact top-k after one corpus pass, sorted in LDS). */
+#define TAVB_MAX_LARGE_K 16384
 /* Largest number of queries one streaming pass serves (bigger batches are split). */
 #define TAVB_MAX_STREAM_QUERIES 8
 
@@ -148,6 +150,17 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   256 or 512), lists of up to "direct_group_keys" keys (default 32768) merged on the host; "last_direct" = 3.  The
  *                   device-resident calls (tavb_search_device, tavb_search_allgather) take the same scan + ONE merge launch ("last_direct" = 4).
  *                   Either way the answers are the single-query lookups' bit for bit.  profiles/r06_group_sweep.md
+ *   "large_k"       1 (default): the Python binding routes lookups of TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K through tavb_search_topk /
+ *                   tavb_search_subset_topk; 0: through the emit-all pass of tavb_search_all as before (the library itself reads it nowhere else)
+ *   "topk_buckets"  64-multiple in 256 .. 4096 (default 1024): histogram buckets of a large-k lookup's score pass, linear over
+ *                   [max(min_score, 0), 1] (LDS per workgroup: 4 bytes per bucket and query of the pass)
+ *   "topk_boundary_keys" 64 .. TAVB_MAX_LARGE_K (default 16384): keys a query's boundary list holds; a boundary bucket with more keys is
+ *                   refined (re-bucketed from the score array) until it fits -- rounds are enqueued up front, about 3 to 5 on corpora of more rows
+ *                   than this, none on smaller ones
+ *   "topk_scores_bytes" >= 4096 (default 1 GiB): most bytes of the dense score array of one corpus pass (4 bytes per row and query): a
+ *                   large-k batch serves fewer than TAVB_MAX_STREAM_QUERIES queries per pass where 8 would need more
+ *   "last_topk_refine" (read only) refinement rounds the last large-k lookup needed (the most of any of its queries; 0 on ordinary data
+ *                   up to ~16k rows per boundary bucket)
  */
 int tavb_set_option(tavb_ctx* ctx, const char* name, int64_t value);
 int tavb_get_option(tavb_ctx* ctx, const char* name, int64_t* out_value);
@@ -252,6 +265,18 @@ int tavb_search_all(tavb_ctx* ctx, const float* query_host, float min_score, int
 int tavb_search_subset_all(tavb_ctx* ctx, const float* query_host, const int64_t* rows_host, int64_t n_subset, float min_score, int64_t max_out,
                            int64_t* out_positions, float* out_scores, int64_t* out_count, int64_t* out_total);
 
+/* Exact top-k beyond the fused selection: TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K (any k from 1 is accepted) after ONE corpus pass per
+ * group of up to TAVB_MAX_STREAM_QUERIES queries -- the reference's argpartition + argsort (vectorbase.py:176-187) for the top-1000
+ * candidates a re-ranker takes.  The pass is the streaming scan's arithmetic (scores equal tavb_search's bit for bit), writes one 4-byte
+ * score per row and query and a histogram of the passing scores; a boundary search, its refinement, a compaction and a sort in LDS follow
+ * on the device without a host round trip (tavb_topk.hip).  Device memory beyond the corpus: the score array of one group (options
+ * "topk_scores_bytes", "topk_buckets", "topk_boundary_keys") and O(nq (k + boundary keys)).  Semantics, ordering, `ordinal_base`, outputs:
+ * those of tavb_search_batch; any nq, one synchronise per call.  The subset form returns subset POSITIONS (like tavb_search_subset). */
+int tavb_search_topk(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
+                     int32_t* out_counts);
+int tavb_search_subset_topk(tavb_ctx* ctx, const float* query_host, const int64_t* rows_host, int64_t n_subset, int32_t k, float min_score,
+                            int64_t* out_positions, float* out_scores, int32_t* out_count);
+
 /* Continuation ("cursor") forms: the next k hits strictly AFTER the hit
  * (after_score, after_ordinal) in the (score descending, ordinal ascending) order.
  * Feeding the last hit of one page as the cursor of the next enumerates every row
@@ -338,7 +363,8 @@ int tavb_remap_key_positions(tavb_ctx* ctx, tavb_key* dev_keys, int64_t count, c
  * kernel ids: 0 = streaming scan (dot + score + select), 1 = list merge,
  *             2 = MFMA batched scan (256-query tile: the last phase of the threshold ladder), 3 = normalise,
  *             4 = f32->f16 convert, 5 = the earlier phases of the ladder (either MFMA tile), 6 = 32-query MFMA tile
- *             (last phase), 7 = candidate rescoring of the 256-query tile, 8 = the all-gather of tavb_search_allgather. */
+ *             (last phase), 7 = candidate rescoring of the 256-query tile, 8 = the all-gather of tavb_search_allgather,
+ *             9 = the selection of a large-k lookup (refinement, compaction, finish; its score pass counts as 0). */
 #define TAVB_KERNEL_SCAN 0
 #define TAVB_KERNEL_MERGE 1
 #define TAVB_KERNEL_MFMA 2
@@ -348,7 +374,8 @@ int tavb_remap_key_positions(tavb_ctx* ctx, tavb_key* dev_keys, int64_t count, c
 #define TAVB_KERNEL_SKINNY 6 /* 32-query MFMA tile (small batches; every batch on fp32 corpora) */
 #define TAVB_KERNEL_RESCORE 7 /* exact fp32-query rescoring of the 256-query tile's candidates (+ query preparation) */
 #define TAVB_KERNEL_EXCHANGE 8 /* the RCCL all-gather of tavb_search_allgather (stream time between its two events: includes waiting for the slowest rank) */
-#define TAVB_KERNEL_COUNT 9
+#define TAVB_KERNEL_TOPK 9 /* boundary refinement + compaction + exact finish of tavb_search_topk / tavb_search_subset_topk */
+#define TAVB_KERNEL_COUNT 10
 int tavb_profile_enable(tavb_ctx* ctx, int32_t on);
 int tavb_profile_reset(tavb_ctx* ctx);
 int tavb_profile_read(tavb_ctx* ctx, int32_t kernel_id, double* out_total_ms, int64_t* out_launches);

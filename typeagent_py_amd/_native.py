@@ -16,13 +16,14 @@ from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, 
 
 import numpy as np
 
-ABI_VERSION = 6  # include/tavb.h TAVB_ABI_VERSION this binding was written against
+ABI_VERSION = 7  # include/tavb.h TAVB_ABI_VERSION this binding was written against
 TAVB_F32 = 0
 TAVB_F16 = 1
 MAX_FUSED_K = 256
+MAX_LARGE_K = 16384  # TAVB_MAX_LARGE_K: largest k of tavb_search_topk (exact top-k after one corpus pass)
 MAX_STREAM_QUERIES = 8
 
-KERNEL_SCAN, KERNEL_MERGE, KERNEL_MFMA, KERNEL_NORMALIZE, KERNEL_CONVERT, KERNEL_MFMA_SAMPLE, KERNEL_SKINNY, KERNEL_RESCORE, KERNEL_EXCHANGE = range(9)
+KERNEL_SCAN, KERNEL_MERGE, KERNEL_MFMA, KERNEL_NORMALIZE, KERNEL_CONVERT, KERNEL_MFMA_SAMPLE, KERNEL_SKINNY, KERNEL_RESCORE, KERNEL_EXCHANGE, KERNEL_TOPK = range(10)
 COMM_ID_BYTES = 128
 
 _LIB_NAME = os.environ.get("TAVB_LIBRARY", "libtavb.so")  # "libtavb_debug.so": the ASan/UBSan host build (`make -C csrc debug`)
@@ -58,6 +59,8 @@ _SIGNATURES = [
     ("tavb_search_all", c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     ("tavb_search_subset_all", c_int,
      [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    ("tavb_search_topk", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_subset_topk", c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, POINTER(c_int32)]),
     ("tavb_search_after", c_int,
      [c_void_p, c_void_p, c_int32, c_float, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int32)]),
     ("tavb_search_subset_after", c_int,
@@ -473,6 +476,35 @@ class Engine:
             rc = self.lib.tavb_search_batch(self._h, _addr(a), nq, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
         return ords, scs, cnts
+
+    def search_topk(self, queries, k: int, thrs):
+        """Exact top-k for any 1 <= k <= MAX_LARGE_K after one corpus pass per 8 queries (tavb_search_topk): queries f32 [nq, dim]; thrs
+        float32 [nq] (or one for all) -> (ordinals [nq,k], scores [nq,k], counts [nq]), the layout of `search_batch`."""
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        ords = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        cnts = np.zeros(nq, dtype=np.int32)
+        with self._lock:
+            rc = self.lib.tavb_search_topk(self._h, _addr(a), nq, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_subset_topk(self, q, rows: np.ndarray, k: int, thr: np.float32):
+        """`search_topk` of one query over a subset (rows: int64 corpus row per subset position) -> (positions int64[m], scores float32[m])."""
+        a = self._query(q)
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        pos = np.empty(k, dtype=np.int64)
+        scs = np.empty(k, dtype=np.float32)
+        cnt = c_int32(0)
+        with self._lock:
+            rc = self.lib.tavb_search_subset_topk(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)), _addr(pos), _addr(scs), byref(cnt))
+        _check(self.lib, rc)
+        m = int(cnt.value)
+        return pos[:m], scs[:m]
 
     # message re-rank on the device ---------------------------------------------
     def set_row_messages(self, row_to_message: np.ndarray) -> None:

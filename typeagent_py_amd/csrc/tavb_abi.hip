@@ -158,6 +158,13 @@ struct tavb_ctx {
   int last_shadow = 0;     // the last lookup's filter pass read the shadow
   Buffer d_accept, d_bits;  // message re-rank: accepted message ordinals, their bitmap
   Buffer d_emit;            // survivors of tavb_search_all: a counter, then the keys
+  // large-k lookups (tavb_search_topk, tavb_topk.hip): the dense score array of a group of queries and the workspace of the selection
+  Buffer d_topk_scores, d_topk;
+  int64_t large_k = 1;                       // option: 1 = the binding routes TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K through tavb_search_topk
+  int64_t topk_buckets = 1024;               // option: histogram buckets of the score pass
+  int64_t topk_boundary_keys = 16384;        // option: capacity of a query's boundary list (more keys in the boundary bucket: refinement)
+  int64_t topk_scores_bytes = (int64_t)1 << 30;  // option: most bytes of one group's score array (queries per corpus pass are cut to fit)
+  int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
   // load path (tavb_upload_rows): two pinned staging slots + two device scratch slots, recycled through events
   Buffer h_ring[2] = {{nullptr, 0, true}, {nullptr, 0, true}};
   Buffer d_ring[2];
@@ -549,6 +556,8 @@ int tavb_destroy(tavb_ctx* c) {
   c->d_accept.release();
   c->d_bits.release();
   c->d_emit.release();
+  c->d_topk_scores.release();
+  c->d_topk.release();
   for (int i = 0; i < 2; ++i) {
     c->h_ring[i].release();
     c->d_ring[i].release();
@@ -702,6 +711,17 @@ int tavb_set_option(tavb_ctx* c, const char* name, int64_t v) {
   } else if (n == "graph_max_bytes") {
     if (v < 0) return fail(TAVB_E_INVALID, "graph_max_bytes must be >= 0");
     c->graph_max_bytes = v;
+  } else if (n == "large_k") {
+    c->large_k = v ? 1 : 0;
+  } else if (n == "topk_buckets") {
+    if (v < 256 || v > 4096 || v % 64 != 0) return fail(TAVB_E_INVALID, "topk_buckets must be a multiple of 64 in 256 .. 4096");
+    c->topk_buckets = v;
+  } else if (n == "topk_boundary_keys") {
+    if (v < 64 || v > TAVB_MAX_LARGE_K) return fail(TAVB_E_INVALID, "topk_boundary_keys must be 64 .. %d", TAVB_MAX_LARGE_K);
+    c->topk_boundary_keys = v;
+  } else if (n == "topk_scores_bytes") {
+    if (v < 4096) return fail(TAVB_E_INVALID, "topk_scores_bytes must be >= 4096");
+    c->topk_scores_bytes = v;
   } else {
     return fail(TAVB_E_INVALID, "unknown option '%s'", name);
   }
@@ -765,6 +785,11 @@ int tavb_get_option(tavb_ctx* c, const char* name, int64_t* out) {
   else if (n == "direct_group_keys") *out = c->direct_group_keys;
   else if (n == "graph_max_bytes") *out = c->graph_max_bytes;
   else if (n == "last_graph") *out = c->last_graph;
+  else if (n == "large_k") *out = c->large_k;
+  else if (n == "topk_buckets") *out = c->topk_buckets;
+  else if (n == "topk_boundary_keys") *out = c->topk_boundary_keys;
+  else if (n == "topk_scores_bytes") *out = c->topk_scores_bytes;
+  else if (n == "last_topk_refine") *out = c->last_topk_refine;
   else if (n == "comm_world") *out = c->comm ? c->comm_world : 0;
   else if (n == "comm_rank") *out = c->comm ? c->comm_rank : -1;
   else if (n == "last_tier") *out = c->last_tier;
@@ -1328,6 +1353,172 @@ int tavb_search_all(tavb_ctx* c, const float* query_host, float min_score, int64
 int tavb_search_subset_all(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, float min_score, int64_t max_out,
                            int64_t* out_positions, float* out_scores, int64_t* out_count, int64_t* out_total) {
   return search_all_impl(c, query_host, rows_host, n_subset, true, min_score, max_out, out_positions, out_scores, out_count, out_total);
+}
+
+// ---- exact top-k beyond the fused selection (tavb_topk.hip): queries on the device (d_q [nq, dim]) over n_pos positions (d_rows: the
+// subset's rows, or null) -> out_keys [nq][k] sorted, zero-filled, + out_rounds [nq], both in pinned host memory.  Per group of up to
+// TAVB_MAX_STREAM_QUERIES queries (fewer where the score array would pass topk_scores_bytes or the vector tier's LDS would overflow):
+// a memset, ONE score pass, the refinement rounds topk_refine_rounds asks for, the compaction and the finish -- every launch's grid is
+// fixed on the host, nothing is read back before the caller's one synchronise.
+static int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
+                            u64_t* out_keys, int32_t* out_rounds) {
+  const int nb = (int)c->topk_buckets, cap = (int)c->topk_boundary_keys;
+  int64_t per = tavb::topk_queries_per_pass(c->dim, c->dtype, nb);
+  per = std::min<int64_t>(per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
+  per = std::min<int64_t>(per, nq);
+  const int rounds = tavb::topk_refine_rounds(n_pos, cap);
+  if (int rc = c->d_topk_scores.reserve((size_t)per * n_pos * sizeof(uint32_t))) return rc;
+  if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)per, k, nb, cap, rounds))) return rc;
+  tavb::ScanGeometry g = c->geom;
+  if (g.waves < 1) g.waves = 1;
+  if (g.waves > 16) g.waves = 16;
+  g.blocks = scan_blocks_for(c, n_pos, g.waves, 2);
+  // the passes over the score array: 4 bytes per row and query, ~8 rows per thread and a grid of a few workgroups per CU in all
+  const int sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (n_pos + 2047) / 2048), std::max<int64_t>(1, 2048 / per));
+  for (int q0 = 0; q0 < nq; q0 += (int)per) {
+    const int n = (int)std::min<int64_t>(per, nq - q0);
+    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, nb, rounds), c->stream));
+    tavb::ScanParams p{};
+    p.corpus = c->corpus;
+    p.row_ids = d_rows;
+    p.queries = d_q + (size_t)q0 * c->dim;
+    p.lists = nullptr;
+    p.n_pos = n_pos;
+    p.dim = c->dim;
+    p.dtype = c->dtype;
+    p.nq = n;
+    p.k = 1;
+    p.index_base = 0u;
+    p.key_bound = ~0ull;
+    p.group = 0;
+    p.topk_scores = reinterpret_cast<unsigned*>(c->d_topk_scores.ptr);
+    p.topk_hist = reinterpret_cast<unsigned*>(c->d_topk.ptr);
+    p.topk_buckets = nb;
+    tavb::TopkLaunch t{};
+    for (int i = 0; i < TAVB_MAX_GROUPED_QUERIES; ++i) p.min_score[i] = (i < n) ? min_scores[q0 + i] : INFINITY;
+    for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
+      const float ms = i < n ? min_scores[q0 + i] : INFINITY;
+      float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
+      if (lo > 1.0f) lo = 1.0f;
+      p.topk_lo[i] = t.lo[i] = lo;
+      p.topk_scale[i] = t.scale[i] = lo < 1.0f ? (float)nb / (1.0f - lo) : 0.0f;
+    }
+    {
+      Timed tm(c, TAVB_KERNEL_SCAN);
+      hipError_t e = tavb::launch_scan_topk(p, g, c->stream, &c->last_tier);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k score pass launch failed: %s", hipGetErrorString(e));
+    }
+    t.scores = p.topk_scores;
+    t.workspace = c->d_topk.ptr;
+    t.n_pos = n_pos;
+    t.nq = n;
+    t.k = k;
+    t.buckets = nb;
+    t.cap = cap;
+    t.rounds = rounds;
+    t.blocks = sel_blocks;
+    t.out_keys = out_keys + (size_t)q0 * k;
+    t.out_rounds = out_rounds + q0;
+    Timed tm(c, TAVB_KERNEL_TOPK);
+    for (int r = 0; r < rounds; ++r) {
+      hipError_t e = tavb::launch_topk_refine(t, r, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k refinement launch failed: %s", hipGetErrorString(e));
+    }
+    hipError_t e = tavb::launch_topk_compact(t, c->stream);
+    if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k selection launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+static int check_topk_args(tavb_ctx* c, int k) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!c->corpus && c->rows != 0) return fail(TAVB_E_NO_CORPUS, "no corpus set (call tavb_set_corpus first)");
+  if (c->dim <= 0) return fail(TAVB_E_NO_CORPUS, "no corpus set (call tavb_set_corpus first)");
+  if (k < 1 || k > TAVB_MAX_LARGE_K) return fail(TAVB_E_INVALID, "k must be 1 .. %d (got %d)", TAVB_MAX_LARGE_K, k);
+  return TAVB_OK;
+}
+
+// the pinned keys [nq][k] + rounds [nq] of a large-k lookup
+static int reserve_topk_out(tavb_ctx* c, int nq, int k, u64_t** keys, int32_t** rounds) {
+  const size_t kbytes = (size_t)nq * k * sizeof(u64_t);
+  if (int rc = c->h_out.reserve(kbytes + (size_t)nq * sizeof(int32_t))) return rc;
+  *keys = reinterpret_cast<u64_t*>(c->h_out.ptr);
+  *rounds = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->h_out.ptr) + kbytes);
+  return TAVB_OK;
+}
+
+static void note_rounds(tavb_ctx* c, const int32_t* rounds, int nq) {
+  int m = 0;
+  for (int q = 0; q < nq; ++q) m = std::max(m, (int)rounds[q]);
+  c->last_topk_refine = m;
+}
+
+int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
+                     int32_t* out_counts) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  if (c->rows == 0) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const size_t qbytes = (size_t)nq * c->dim * sizeof(float);
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = c->h_stage.reserve(qbytes)) return rc;
+  if (int rc = c->d_queries.reserve(qbytes)) return rc;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  parallel_copy(c->h_stage.ptr, queries_host, qbytes);
+  TAVB_HIP(hipMemcpyAsync(c->d_queries.ptr, c->h_stage.ptr, qbytes, hipMemcpyHostToDevice, c->stream));
+  if (int rc = search_topk_impl(c, reinterpret_cast<const float*>(c->d_queries.ptr), nq, k, min_scores, nullptr, c->rows, keys, rounds)) return rc;
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  decode(keys, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int32_t k, float min_score,
+                            int64_t* out_positions, float* out_scores, int32_t* out_count) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
+  if (!query_host || !out_positions || !out_scores || !out_count) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  if (n_subset == 0 || c->rows == 0) {
+    *out_count = 0;
+    return TAVB_OK;
+  }
+  if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
+  if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");
+  DeviceGuard guard(c->device);
+  const size_t qbytes = (size_t)c->dim * sizeof(float);
+  const size_t rbytes = (size_t)n_subset * sizeof(int32_t);
+  const size_t qoff = (rbytes + 255) & ~(size_t)255;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = c->h_stage.reserve(qoff + qbytes)) return rc;
+  if (int rc = c->d_queries.reserve(qbytes)) return rc;
+  if (int rc = c->d_rows.reserve(rbytes)) return rc;
+  if (int rc = reserve_topk_out(c, 1, k, &keys, &rounds)) return rc;
+  int32_t* r32 = reinterpret_cast<int32_t*>(c->h_stage.ptr);
+  for (int64_t i = 0; i < n_subset; ++i) {
+    const int64_t r = rows_host[i];
+    if (r < 0 || r >= c->rows) return fail(TAVB_E_INVALID, "subset row %lld out of range [0, %lld)", (long long)r, (long long)c->rows);
+    r32[i] = (int32_t)r;
+  }
+  memcpy(reinterpret_cast<char*>(c->h_stage.ptr) + qoff, query_host, qbytes);
+  TAVB_HIP(hipMemcpyAsync(c->d_rows.ptr, c->h_stage.ptr, rbytes, hipMemcpyHostToDevice, c->stream));
+  TAVB_HIP(hipMemcpyAsync(c->d_queries.ptr, reinterpret_cast<char*>(c->h_stage.ptr) + qoff, qbytes, hipMemcpyHostToDevice, c->stream));
+  if (int rc = search_topk_impl(c, reinterpret_cast<const float*>(c->d_queries.ptr), 1, k, &min_score, reinterpret_cast<const int32_t*>(c->d_rows.ptr),
+                                n_subset, keys, rounds))
+    return rc;
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  decode(keys, 1, k, 0, out_positions, out_scores, out_count);
+  note_rounds(c, rounds, 1);
+  return TAVB_OK;
 }
 
 int tavb_set_row_messages(tavb_ctx* c, const int32_t* dev_row_to_msg, int64_t rows, int64_t n_messages) {

@@ -35,6 +35,19 @@ __device__ __forceinline__ u64 make_key(float score, uint32_t index) {
   return ((u64)__float_as_uint(score) << 32) | (u64)(0xFFFFFFFFu - index);
 }
 
+// Large-k lookups (tavb_topk.hip): the dense per-query score array holds the score BITS of every row that passed min_score and this
+// sentinel for every other row (passing scores are in [0, 1]: their bits never reach it).
+constexpr uint32_t kScoreNone = 0xFFFFFFFFu;
+
+// Histogram bucket of a passing score: min(nb - 1, floor((s - lo) * scale)) with lo = max(min_score, 0) and scale = nb / (1 - lo) (0 when
+// lo >= 1), both computed once on the host.  Monotone in s (a rounded subtract and a rounded multiply by a positive constant are), the same
+// two operations wherever it is evaluated -- the score pass and the boundary search of the compaction agree bucket for bucket.
+__device__ __forceinline__ int topk_bucket(float s, float lo, float scale, int nb) {
+  const float t = (s - lo) * scale;
+  if (!(t > 0.0f)) return 0;
+  return t < (float)(nb - 1) ? (int)t : nb - 1;
+}
+
 __device__ __forceinline__ u64 shfl_u64(u64 v, int src_lane) {
   int lo = __shfl((int)(uint32_t)v, src_lane, kWave);
   int hi = __shfl((int)(uint32_t)(v >> 32), src_lane, kWave);

@@ -29,6 +29,13 @@ struct ScanParams {
   // rows of "its" x in that XCD's L2 after the first one read them.  0 = the plain form (gridDim.y = 1, nq <= TAVB_MAX_STREAM_QUERIES).
   int32_t group;
   float min_score[TAVB_MAX_GROUPED_QUERIES];  // one per query (the plain form reads the first TAVB_MAX_STREAM_QUERIES)
+  // score pass of a large-k lookup (launch_scan_topk, plain form only): instead of selecting, every row's score goes to topk_scores [nq][n_pos]
+  // (kScoreNone: did not pass) and every passing score is counted in topk_hist [nq][topk_buckets] (topk_bucket with topk_lo / topk_scale)
+  unsigned* topk_scores;
+  unsigned* topk_hist;
+  int32_t topk_buckets;
+  float topk_lo[TAVB_MAX_STREAM_QUERIES];
+  float topk_scale[TAVB_MAX_STREAM_QUERIES];
 };
 
 struct ScanGeometry {
@@ -46,6 +53,35 @@ hipError_t launch_scan(const ScanParams& p, const ScanGeometry& g, hipStream_t s
 // single 1536-wide query handed over INSIDE the kernel arguments (`host_query`: 1536 floats on the host; `p.queries` is not read): no copy in front of
 // the launch.  Returns false -- nothing launched -- when the shape or geometry has no such variant; otherwise `*err` is the launch result.
 bool launch_scan_inline_query(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, const float* host_query, int* tier_used, hipError_t* err);
+
+// the score pass of a large-k lookup (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES) queries, index_base 0, the streaming kernels'
+// arithmetic row for row -- the scores are those the fused selection sees, bit for bit -- with ScanParams::topk_* as the output
+hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// queries per score pass that keep the vector tier's LDS (queries + histograms) within budget: 1, 2, 4 or 8
+int topk_queries_per_pass(int dim, int dtype, int buckets);
+
+// After the score pass of `nq` queries over n_pos positions: boundary search, refinement, compaction and the exact finish -> out_keys
+// [nq][k] (sorted best first, zero-filled) and out_rounds [nq] (refinement rounds each query needed), both device-writable (pinned host
+// memory).  Workspace: topk_workspace_bytes(); the score pass's histograms [nq][buckets] lead it, and its first topk_head_bytes() bytes
+// must be zero when the score pass starts (one memset).  tavb_topk.hip
+struct TopkLaunch {
+  const unsigned* scores;  // [nq][n_pos]
+  void* workspace;
+  int64_t n_pos;
+  int32_t nq, k, buckets, cap, rounds;  // rounds: refinement launches enqueued (topk_refine_rounds)
+  int32_t blocks;                      // workgroups per query of the refinement and compaction passes
+  float lo[TAVB_MAX_STREAM_QUERIES], scale[TAVB_MAX_STREAM_QUERIES];
+  unsigned long long* out_keys;
+  int32_t* out_rounds;
+};
+constexpr int kTopkRefineBuckets = 4096;  // sub-buckets of one refinement round
+size_t topk_workspace_bytes(int nq, int k, int buckets, int cap, int rounds);
+size_t topk_head_bytes(int nq, int buckets, int rounds);
+int topk_refine_rounds(int64_t n_pos, int cap);
+// refinement round r (0 .. rounds - 1; returns at once for a query whose boundary already fits `cap`), then the compaction, then the finish
+hipError_t launch_topk_refine(const TopkLaunch& t, int round, hipStream_t stream);
+hipError_t launch_topk_compact(const TopkLaunch& t, hipStream_t stream);
+hipError_t launch_topk_finish(const TopkLaunch& t, hipStream_t stream);
 
 // every row with score >= min_score[0] (and key < key_bound), unsorted: out[0 .. *counter) (entries past `capacity` are dropped, still counted)
 hipError_t launch_scan_emit(const ScanParams& p, int blocks, unsigned long long* out, unsigned long long capacity, unsigned long long* counter,

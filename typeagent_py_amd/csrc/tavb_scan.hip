@@ -72,6 +72,7 @@ __device__ __forceinline__ float dot_slice<_Float16>(f32x4 raw, const float* __r
 // Per-wave selection state for NQ queries.
 template <int NQ, int KPL>
 struct Selector {
+  static constexpr bool kScorePass = false;
   WaveTopK<KPL> top[NQ];
   u64 thr[NQ];  // key at rank k-1: a candidate must beat it (wave-uniform)
 
@@ -111,6 +112,63 @@ __device__ __forceinline__ QueryGroup query_group(const ScanParams& p) {
   return g;
 }
 
+// The epilogue of the score pass of a large-k lookup (launch_scan_topk) in place of the Selector: the same score of the same row (wave_sum,
+// cosine_to_score, >= min_score, NaN never passes), but instead of a selection the score bits go to the dense score array -- one 4-byte
+// vector store from lane 0 per row and query -- and a passing score is counted in the workgroup's LDS histogram, flushed to the global one
+// with atomics at the end (nonzero buckets only).  `hist` is the LDS the Selector would use as merge scratch.
+template <int NQ>
+struct ScoreSink {
+  static constexpr bool kScorePass = true;
+  unsigned* hist;     // LDS [NQ][nb]
+  unsigned* scores;   // [nq][n_pos]
+  unsigned* ghist;    // [nq][nb]
+  int64_t n_pos;
+  int nb, n_live;
+  float lo[NQ], scale[NQ];
+
+  __device__ __forceinline__ void setup(const ScanParams& p, const QueryGroup& qg, void* lds) {
+    hist = reinterpret_cast<unsigned*>(lds);
+    scores = p.topk_scores;
+    ghist = p.topk_hist;
+    n_pos = p.n_pos;
+    nb = p.topk_buckets;
+    n_live = qg.n;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      lo[q] = p.topk_lo[q];
+      scale[q] = p.topk_scale[q];
+    }
+  }
+  __device__ __forceinline__ void clear() {
+    for (int i = threadIdx.x; i < NQ * nb; i += blockDim.x) hist[i] = 0u;
+    __syncthreads();
+  }
+  __device__ __forceinline__ void offer(int q, float partial, uint32_t index, float min_score, int, int lane, u64) {
+    const float dot = wave_sum(partial);
+    const float s = wave_uniform(cosine_to_score(dot));
+    if (q < n_live) {  // uniform
+      const bool pass = s >= min_score;  // NaN never passes, like numpy's >=
+      if (lane == 0) {
+        scores[(size_t)q * n_pos + index] = pass ? __float_as_uint(s) : kScoreNone;
+        if (pass) atomicAdd(&hist[q * nb + topk_bucket(s, lo[q], scale[q], nb)], 1u);
+      }
+    }
+  }
+  __device__ __forceinline__ void flush() {
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_live * nb; i += blockDim.x) {
+      const unsigned v = hist[i];
+      if (v) atomicAdd(&ghist[i], v);
+    }
+  }
+};
+
+template <int NQ, int KPL, typename SEL>
+__device__ __forceinline__ void start_epilogue(SEL& sel, const ScanParams& p, const QueryGroup& qg, void* lds) {
+  if constexpr (SEL::kScorePass) sel.setup(p, qg, lds);
+  sel.clear();
+}
+
 template <int NQ, int KPL>
 __device__ __forceinline__ void finish_block(Selector<NQ, KPL>& sel, const ScanParams& p, const QueryGroup& qg, u64* scratch, int wave,
                                              int n_waves, int lane) {
@@ -121,6 +179,14 @@ __device__ __forceinline__ void finish_block(Selector<NQ, KPL>& sel, const ScanP
       if (wave == 0) sel.top[q].store(p.lists + ((size_t)(qg.q0 + q) * gridDim.x + blockIdx.x) * (size_t)p.k, p.k, lane);
     }
   }
+}
+
+template <int NQ, int KPL, typename SEL>
+__device__ __forceinline__ void end_epilogue(SEL& sel, const ScanParams& p, const QueryGroup& qg, u64* scratch, int wave, int n_waves, int lane) {
+  if constexpr (SEL::kScorePass)
+    sel.flush();
+  else
+    finish_block<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -134,7 +200,7 @@ struct InlineQuery {
 };
 struct NoInlineQuery {};
 
-template <typename T, int CH, int NQ, int KPL, int U, bool NT, bool PIPE, int MAXT, typename QA = NoInlineQuery>
+template <typename T, int CH, int NQ, int KPL, int U, bool NT, bool PIPE, int MAXT, typename QA = NoInlineQuery, typename SEL = Selector<NQ, KPL>>
 __global__ void __launch_bounds__(MAXT) scan_fixed_kernel(const ScanParams p, const QA qa) {
   constexpr int EPL = Elem<T>::EPL;
   constexpr int D = CH * 64 * EPL;
@@ -175,8 +241,8 @@ __global__ void __launch_bounds__(MAXT) scan_fixed_kernel(const ScanParams p, co
 #pragma unroll
   for (int q = 0; q < NQ; ++q) minsc[q] = (q < qg.n) ? p.min_score[qg.q0 + q] : __builtin_inff();  // never passes
 
-  Selector<NQ, KPL> sel;
-  sel.clear();
+  SEL sel;
+  start_epilogue<NQ, KPL>(sel, p, qg, scratch);
 
   const char* corpus = reinterpret_cast<const char*>(p.corpus);
   const int32_t* row_ids = p.row_ids;
@@ -258,13 +324,13 @@ __global__ void __launch_bounds__(MAXT) scan_fixed_kernel(const ScanParams p, co
     }
   }
 
-  finish_block<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
+  end_epilogue<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
 }
 
 // ---------------------------------------------------------------------------
 // tier 2: dim % (16 bytes) == 0, runtime chunk loop, queries staged in LDS
 // ---------------------------------------------------------------------------
-template <typename T, int NQ, int KPL, bool NT>
+template <typename T, int NQ, int KPL, bool NT, typename SEL = Selector<NQ, KPL>>
 __global__ void __launch_bounds__(1024) scan_vec_kernel(const ScanParams p) {
   constexpr int EPL = Elem<T>::EPL;
   constexpr int U = 2;  // rows per wave iteration (4 rows measured no faster and spills at 128 VGPRs)
@@ -293,8 +359,8 @@ __global__ void __launch_bounds__(1024) scan_vec_kernel(const ScanParams p) {
 #pragma unroll
   for (int q = 0; q < NQ; ++q) minsc[q] = (q < qg.n) ? p.min_score[qg.q0 + q] : __builtin_inff();
 
-  Selector<NQ, KPL> sel;
-  sel.clear();
+  SEL sel;
+  start_epilogue<NQ, KPL>(sel, p, qg, scratch);
   const char* corpus = reinterpret_cast<const char*>(p.corpus);
   const int32_t* row_ids = p.row_ids;
   const int64_t row_bytes = (int64_t)D * sizeof(T);
@@ -342,13 +408,13 @@ __global__ void __launch_bounds__(1024) scan_vec_kernel(const ScanParams p) {
       }
     }
   }
-  finish_block<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
+  end_epilogue<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
 }
 
 // ---------------------------------------------------------------------------
 // tier 3: any dim, element loads, queries read from global (L1/L2 resident)
 // ---------------------------------------------------------------------------
-template <typename T, int NQ, int KPL>
+template <typename T, int NQ, int KPL, typename SEL = Selector<NQ, KPL>>
 __global__ void __launch_bounds__(1024) scan_scalar_kernel(const ScanParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   u64* scratch = reinterpret_cast<u64*>(smem);
@@ -364,8 +430,8 @@ __global__ void __launch_bounds__(1024) scan_scalar_kernel(const ScanParams p) {
   float minsc[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) minsc[q] = (q < qg.n) ? p.min_score[qg.q0 + q] : __builtin_inff();
-  Selector<NQ, KPL> sel;
-  sel.clear();
+  SEL sel;
+  start_epilogue<NQ, KPL>(sel, p, qg, scratch);
   const T* corpus = reinterpret_cast<const T*>(p.corpus);
   const int32_t* row_ids = p.row_ids;
   for (int64_t pos = (int64_t)blockIdx.x * n_waves + wave; pos < n_pos; pos += stride) {
@@ -385,7 +451,7 @@ __global__ void __launch_bounds__(1024) scan_scalar_kernel(const ScanParams p) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) sel.offer(q, acc[q], (uint32_t)pos + p.index_base, minsc[q], k, lane, p.key_bound);
   }
-  finish_block<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
+  end_epilogue<NQ, KPL>(sel, p, qg, scratch, wave, n_waves, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -633,6 +699,87 @@ hipError_t launch_scan(const ScanParams& p, const ScanGeometry& g, hipStream_t s
   if (tier == 1) return f16 ? dispatch_fixed<_Float16, 3>(p, g, stream, nqt, kpl) : dispatch_fixed<float, 6>(p, g, stream, nqt, kpl);
   if (tier == 2) return f16 ? dispatch_vec<_Float16>(p, g, stream, nqt, kpl) : dispatch_vec<float>(p, g, stream, nqt, kpl);
   return f16 ? dispatch_scalar<_Float16>(p, g, stream, nqt, kpl) : dispatch_scalar<float>(p, g, stream, nqt, kpl);
+}
+
+// ---------------------------------------------------------------------------
+// score pass of a large-k lookup (tavb_topk.hip takes it from there): the kernel families above with the ScoreSink epilogue, picked by
+// the rule launch_scan's auto mode applies to one query -- tier 1 for a single aligned 1536-wide query, the vector tier for aligned rows,
+// the scalar tier otherwise -- so that every row's score is the one the fused lookup of that query computes, bit for bit (the three
+// tiers' per-row arithmetic differs only between the element loop of tier 3 and the 16-byte slices of tiers 1 and 2).
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kTopkLdsBudget = 150 * 1024;
+
+inline size_t topk_vec_lds(int nqt, int dim, int buckets) { return (((size_t)nqt * dim * sizeof(float)) + 15 & ~(size_t)15) + (size_t)nqt * buckets * 4; }
+
+template <typename T, int NQ>
+hipError_t go_topk_vec(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
+  const size_t lds = topk_vec_lds(NQ, p.dim, p.topk_buckets);
+  auto kern = scan_vec_kernel<T, NQ, 1, true, ScoreSink<NQ>>;
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
+  hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
+  return hipGetLastError();
+}
+
+template <typename T, int NQ>
+hipError_t go_topk_scalar(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
+  const size_t lds = (size_t)NQ * p.topk_buckets * 4;
+  auto kern = scan_scalar_kernel<T, NQ, 1, ScoreSink<NQ>>;
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
+  hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
+  return hipGetLastError();
+}
+
+template <typename T, int CH>
+hipError_t go_topk_fixed(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
+  const size_t lds = (size_t)p.topk_buckets * 4;
+  auto kern = scan_fixed_kernel<T, CH, 1, 1, 2, true, false, 1024, NoInlineQuery, ScoreSink<1>>;
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
+  hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p, NoInlineQuery{});
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dispatch_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t s, int tier, int nqt) {
+  if (tier == 2) {
+    if (nqt == 1) return go_topk_vec<T, 1>(p, g, s);
+    if (nqt == 2) return go_topk_vec<T, 2>(p, g, s);
+    if (nqt == 4) return go_topk_vec<T, 4>(p, g, s);
+    return go_topk_vec<T, 8>(p, g, s);
+  }
+  if (nqt == 1) return go_topk_scalar<T, 1>(p, g, s);
+  if (nqt == 2) return go_topk_scalar<T, 2>(p, g, s);
+  if (nqt == 4) return go_topk_scalar<T, 4>(p, g, s);
+  return go_topk_scalar<T, 8>(p, g, s);
+}
+
+}  // namespace
+
+int topk_queries_per_pass(int dim, int dtype, int buckets) {
+  const int epl = dtype == TAVB_F16 ? 8 : 4;
+  if (dim % epl != 0) return (size_t)8 * buckets * 4 <= kTopkLdsBudget ? 8 : 4;  // scalar tier: only the histograms live in LDS
+  int n = TAVB_MAX_STREAM_QUERIES;
+  while (n > 1 && topk_vec_lds(n, dim, buckets) > kTopkLdsBudget) n /= 2;
+  return n;
+}
+
+hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used) {
+  if (p.nq < 1 || p.nq > TAVB_MAX_STREAM_QUERIES || p.group != 0 || p.dim < 1 || p.index_base != 0 || !p.topk_scores || !p.topk_hist ||
+      p.topk_buckets < 64 || p.topk_buckets % 64 != 0)
+    return hipErrorInvalidValue;
+  const bool f16 = p.dtype == TAVB_F16;
+  const int epl = f16 ? 8 : 4;
+  const bool aligned = ((uintptr_t)p.corpus % 16) == 0 && (p.dim % epl) == 0;
+  const int nqt = p.nq <= 1 ? 1 : p.nq <= 2 ? 2 : p.nq <= 4 ? 4 : 8;
+  // (the fused lookup of ONE query -- what these scores must equal -- takes tier 1 at 1536 and the vector tier for other aligned widths
+  //  whenever one query's LDS fits, which is the case up to far beyond the widths served here)
+  int tier = (aligned && p.dim == 1536 && nqt == 1) ? 1 : aligned ? 2 : 3;
+  if (tier == 2 && topk_vec_lds(nqt, p.dim, p.topk_buckets) > kTopkLdsBudget) return hipErrorInvalidValue;  // (topk_queries_per_pass sizes the groups)
+  if (tier == 3 && (size_t)nqt * p.topk_buckets * 4 > kTopkLdsBudget) return hipErrorInvalidValue;
+  if (tier_used) *tier_used = tier;
+  if (tier == 1) return f16 ? go_topk_fixed<_Float16, 3>(p, g, stream) : go_topk_fixed<float, 6>(p, g, stream);
+  return f16 ? dispatch_topk<_Float16>(p, g, stream, tier, nqt) : dispatch_topk<float>(p, g, stream, tier, nqt);
 }
 
 }  // namespace tavb

@@ -1,0 +1,328 @@
+// Exact top-k for k beyond the fused selection (TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K), after ONE corpus pass.
+//
+// The score pass (launch_scan_topk, tavb_scan.hip) leaves, per query, the score bits of every row (kScoreNone for rows below min_score)
+// and a histogram of the passing scores in `buckets` linear buckets over [max(min_score, 0), 1].  From there, with no host round trip:
+//   boundary   the bucket b* where the count from the top first reaches need = min(k, survivors): every key above it is a sure hit
+//              (fewer than need of them), the keys inside it hold the rest.  Recomputed by every workgroup that needs it (a few
+//              thousand L2-resident counters, one wave) instead of a launch of its own.
+//   refine     while b* holds more keys than the boundary list takes (`cap`): the keys inside it -- a range of 64-bit keys, score bits
+//              and position -- are counted again in kTopkRefineBuckets sub-ranges, read from the score array, and the boundary moves
+//              into the sub-range where the count reaches need.  Every round divides the range by 4096, so a fixed number of rounds
+//              (topk_refine_rounds, enqueued up front; a round whose query already fits returns at once) ends with at most `cap` keys
+//              whatever the data: 5000 identical rows need three.
+//   compact    keys above the range -> the sure list, keys inside it -> the boundary list (wave-aggregated appends).
+//   finish     one workgroup per query: the sure keys sorted (bitonic, LDS), then the best need - sure of the boundary keys (sorted the
+//              same way: every boundary key ranks below every sure key), written straight into the caller's pinned [nq, k] keys.
+// Keys are (score bits << 32) | (0xFFFFFFFF - position): unique, so the boundary search always ends and equal scores order by
+// ascending position, as everywhere in this library.
+
+#include "tavb_device.h"
+#include "tavb_internal.h"
+
+namespace tavb {
+
+namespace {
+
+constexpr int kB2 = kTopkRefineBuckets;
+constexpr uint32_t kOneBits = 0x3F800000u;  // 1.0f: the largest score
+
+struct TopkState {
+  u64 ka, kb;      // the boundary range of keys (inclusive)
+  unsigned above;  // keys above kb: the sure hits
+  unsigned inb;    // keys inside [ka, kb]
+  unsigned need;   // min(k, survivors)
+  int rounds;      // refinement rounds applied
+  int empty;       // no survivor at all
+};
+
+// Workspace: hist [nq][buckets] | rhist [rounds][nq][kB2] | cnt [nq][4] | meta [nq][4]  (the head, zeroed before the score pass)
+//            | sure [nq][k] | bnd [nq][cap]
+struct Layout {
+  unsigned* hist;
+  unsigned* rhist;
+  unsigned* cnt;  // [q][0] sure keys, [q][1] boundary keys
+  int* meta;      // [q][0] need, [q][1] refinement rounds
+  u64* sure;
+  u64* bnd;
+};
+
+__host__ __device__ inline size_t head_bytes(int nq, int buckets, int rounds) {
+  const size_t words = (size_t)nq * buckets + (size_t)rounds * nq * kB2 + (size_t)nq * 8;
+  return (words * 4 + 255) & ~(size_t)255;
+}
+
+__host__ __device__ inline Layout layout(const TopkLaunch& t) {
+  Layout l;
+  unsigned* w = reinterpret_cast<unsigned*>(t.workspace);
+  l.hist = w;
+  l.rhist = l.hist + (size_t)t.nq * t.buckets;
+  l.cnt = l.rhist + (size_t)t.rounds * t.nq * kB2;
+  l.meta = reinterpret_cast<int*>(l.cnt + (size_t)t.nq * 4);
+  l.sure = reinterpret_cast<u64*>(reinterpret_cast<char*>(t.workspace) + head_bytes(t.nq, t.buckets, t.rounds));
+  l.bnd = l.sure + (size_t)t.nq * t.k;
+  return l;
+}
+
+// One wave: in h[0 .. n) (n a multiple of 64, counts per bucket, bucket n - 1 the best), the bucket j where the count from the top first
+// reaches `need` (1 <= need <= total): *above = keys in buckets above j, *in = keys in j.  Lane l sums buckets [n - (l+1) n/64, n - l n/64).
+__device__ void find_from_top(const unsigned* __restrict__ h, int n, unsigned need, int lane, int* j_out, unsigned* above_out, unsigned* in_out,
+                              unsigned* total_out) {
+  const int per = n / 64;
+  const int top = n - lane * per;
+  unsigned sum = 0;
+  for (int b = top - per; b < top; ++b) sum += h[b];
+  unsigned pre = sum;  // inclusive prefix over lanes 0 .. lane
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned t = __shfl_up(pre, d, 64);
+    if (lane >= d) pre += t;
+  }
+  const unsigned total = __shfl(pre, 63, 64);
+  const unsigned long long hit = __ballot(pre >= need);
+  const int L = hit ? __ffsll(hit) - 1 : 63;
+  unsigned cum = __shfl(pre - sum, L, 64);
+  const int topL = n - L * per;
+  int j = topL - per;
+  unsigned above = cum, in = 0;
+  for (int b = topL - 1; b >= topL - per; --b) {  // (the same walk in every lane)
+    const unsigned v = h[b];
+    if (cum + v >= need) {
+      j = b;
+      above = cum;
+      in = v;
+      break;
+    }
+    cum += v;
+  }
+  *j_out = j;
+  *above_out = above;
+  *in_out = in;
+  *total_out = total;
+}
+
+// smallest score bits x in [0, 1.0f] whose bucket is >= target (kOneBits + 1 when there is none)
+__device__ uint32_t first_bits_at_least(int target, float lo, float scale, int nb) {
+  uint32_t a = 0, b = kOneBits + 1;
+  while (a < b) {
+    const uint32_t m = a + (b - a) / 2;
+    if (topk_bucket(__uint_as_float(m), lo, scale, nb) >= target)
+      b = m;
+    else
+      a = m + 1;
+  }
+  return a;
+}
+
+// The boundary of query q after `rounds` refinement rounds (fewer when it fits `cap` sooner).  One wave, every lane gets the result.
+__device__ TopkState resolve(const TopkLaunch& t, const Layout& l, int q, int rounds, int lane) {
+  TopkState s{};
+  int j;
+  unsigned above, in, total;
+  const unsigned* h0 = l.hist + (size_t)q * t.buckets;
+  // total first (need = min(k, total)), then the search with that need
+  find_from_top(h0, t.buckets, 0xFFFFFFFFu, lane, &j, &above, &in, &total);
+  if (total == 0) {
+    s.empty = 1;
+    s.ka = 1;
+    s.kb = 0;
+    return s;
+  }
+  s.need = total < (unsigned)t.k ? total : (unsigned)t.k;
+  find_from_top(h0, t.buckets, s.need, lane, &j, &above, &in, &total);
+  const float lo = t.lo[q], scale = t.scale[q];
+  const uint32_t a = first_bits_at_least(j, lo, scale, t.buckets);
+  const uint32_t b = first_bits_at_least(j + 1, lo, scale, t.buckets) - 1;
+  s.ka = (u64)a << 32;
+  s.kb = ((u64)b << 32) | 0xFFFFFFFFull;
+  s.above = above;
+  s.inb = in;
+  for (int r = 0; r < rounds && s.inb > (unsigned)t.cap; ++r) {
+    const u64 w = s.kb - s.ka + 1;
+    const u64 step = w / kB2 + (w % kB2 != 0);
+    find_from_top(l.rhist + ((size_t)r * t.nq + q) * kB2, kB2, s.need - s.above, lane, &j, &above, &in, &total);
+    const u64 ka = s.ka + (u64)j * step;
+    const u64 kb = ka + step - 1;
+    s.ka = ka;
+    s.kb = kb < s.kb ? kb : s.kb;
+    s.above += above;
+    s.inb = in;
+    s.rounds = r + 1;
+  }
+  return s;
+}
+
+__device__ __forceinline__ u64 row_key(uint32_t bits, int64_t pos) { return ((u64)bits << 32) | (u64)(0xFFFFFFFFu - (uint32_t)pos); }
+
+__global__ void __launch_bounds__(256) topk_refine_kernel(const TopkLaunch t, int round) {
+  __shared__ unsigned lh[kB2];
+  __shared__ TopkState st;
+  const Layout l = layout(t);
+  const int q = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x < 64) {
+    const TopkState s = resolve(t, l, q, round, lane);
+    if (lane == 0) st = s;
+  }
+  for (int i = threadIdx.x; i < kB2; i += blockDim.x) lh[i] = 0u;
+  __syncthreads();
+  const TopkState s = st;
+  if (s.empty || s.inb <= (unsigned)t.cap) return;  // (the whole workgroup: this query's boundary fits already)
+  const u64 w = s.kb - s.ka + 1;
+  const u64 step = w / kB2 + (w % kB2 != 0);
+  const unsigned* __restrict__ sc = t.scores + (size_t)q * t.n_pos;
+  for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < t.n_pos; pos += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t v = sc[pos];
+    if (v == kScoreNone) continue;
+    const u64 key = row_key(v, pos);
+    if (key >= s.ka && key <= s.kb) atomicAdd(&lh[(key - s.ka) / step], 1u);
+  }
+  __syncthreads();
+  unsigned* gh = l.rhist + ((size_t)round * t.nq + q) * kB2;
+  for (int i = threadIdx.x; i < kB2; i += blockDim.x) {
+    const unsigned v = lh[i];
+    if (v) atomicAdd(&gh[i], v);
+  }
+}
+
+// append `key` (where `flag`) to list[0 .. limit) through *counter: one atomic per wave (all 64 lanes must be here)
+__device__ __forceinline__ void wave_append(bool flag, u64 key, unsigned* counter, u64* list, unsigned limit, int lane) {
+  const unsigned long long m = __ballot(flag);
+  if (!m) return;
+  unsigned base = 0;
+  if (lane == 0) base = atomicAdd(counter, (unsigned)__popcll(m));
+  base = __shfl(base, 0, 64);
+  if (flag) {
+    const unsigned idx = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    if (idx < limit) list[idx] = key;
+  }
+}
+
+__global__ void __launch_bounds__(256) topk_compact_kernel(const TopkLaunch t) {
+  __shared__ TopkState st;
+  const Layout l = layout(t);
+  const int q = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (threadIdx.x < 64) {
+    const TopkState s = resolve(t, l, q, t.rounds, lane);
+    if (lane == 0) {
+      st = s;
+      if (blockIdx.x == 0) {
+        l.meta[q * 4 + 0] = (int)s.need;
+        l.meta[q * 4 + 1] = s.rounds;
+      }
+    }
+  }
+  __syncthreads();
+  const TopkState s = st;
+  if (s.empty) return;
+  const unsigned* __restrict__ sc = t.scores + (size_t)q * t.n_pos;
+  u64* sure = l.sure + (size_t)q * t.k;
+  u64* bnd = l.bnd + (size_t)q * t.cap;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + wave * 64; base < t.n_pos; base += stride) {  // wave-uniform trip count
+    const int64_t pos = base + lane;
+    const uint32_t v = pos < t.n_pos ? sc[pos] : kScoreNone;
+    const u64 key = row_key(v, pos);
+    const bool live = v != kScoreNone;
+    wave_append(live && key > s.kb, key, &l.cnt[q * 4 + 0], sure, (unsigned)t.k, lane);
+    wave_append(live && key >= s.ka && key <= s.kb, key, &l.cnt[q * 4 + 1], bnd, (unsigned)t.cap, lane);
+  }
+}
+
+// descending bitonic sort of src[0 .. n) in LDS (sk: room for the next power of two), the first n_out written to dst
+__device__ void sort_desc_to(const u64* __restrict__ src, int n, u64* sk, u64* dst, int n_out) {
+  if (n <= 0) return;  // (uniform)
+  int P = 2;
+  while (P < n) P <<= 1;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) sk[i] = i < n ? src[i] : 0ull;
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = threadIdx.x; i < P / 2; i += blockDim.x) {
+        const int lo = 2 * i - (i & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const u64 a = sk[lo], b = sk[hi];
+        if ((a < b) == desc) {
+          sk[lo] = b;
+          sk[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < n_out; i += blockDim.x) dst[i] = sk[i];
+  __syncthreads();  // (sk is reused)
+}
+
+__global__ void __launch_bounds__(1024) topk_finish_kernel(const TopkLaunch t) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  u64* sk = reinterpret_cast<u64*>(smem);
+  const Layout l = layout(t);
+  const int q = blockIdx.x;
+  const unsigned need = (unsigned)l.meta[q * 4 + 0];
+  const unsigned n_sure = min(l.cnt[q * 4 + 0], need);
+  const unsigned n_bnd = min(l.cnt[q * 4 + 1], (unsigned)t.cap);
+  const unsigned take = min(need - n_sure, n_bnd);
+  u64* out = t.out_keys + (size_t)q * t.k;
+  sort_desc_to(l.sure + (size_t)q * t.k, (int)n_sure, sk, out, (int)n_sure);
+  sort_desc_to(l.bnd + (size_t)q * t.cap, (int)n_bnd, sk, out + n_sure, (int)take);
+  for (int i = (int)(n_sure + take) + threadIdx.x; i < t.k; i += blockDim.x) out[i] = 0ull;
+  if (threadIdx.x == 0) t.out_rounds[q] = l.meta[q * 4 + 1];
+}
+
+int pow2_at_least(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+bool valid(const TopkLaunch& t) {
+  return t.nq >= 1 && t.nq <= TAVB_MAX_STREAM_QUERIES && t.k >= 1 && t.k <= TAVB_MAX_LARGE_K && t.buckets >= 64 && t.buckets % 64 == 0 &&
+         t.cap >= 64 && t.cap <= TAVB_MAX_LARGE_K && t.rounds >= 0 && t.blocks >= 1 && t.n_pos > 0 && t.scores && t.workspace && t.out_keys &&
+         t.out_rounds;
+}
+
+}  // namespace
+
+size_t topk_workspace_bytes(int nq, int k, int buckets, int cap, int rounds) {
+  return head_bytes(nq, buckets, rounds) + (size_t)nq * ((size_t)k + cap) * sizeof(u64);
+}
+
+size_t topk_head_bytes(int nq, int buckets, int rounds) { return head_bytes(nq, buckets, rounds); }
+
+int topk_refine_rounds(int64_t n_pos, int cap) {
+  if (n_pos <= cap) return 0;  // the boundary bucket can never hold more than the list takes
+  // the first boundary range spans < 2^62 keys (score bits <= 1.0f = 0x3F800000 < 2^30, then the 32 position bits); every round leaves at
+  // most ceil(width / kB2) of them
+  unsigned long long w = 1ull << 62;
+  int r = 0;
+  while (w > (unsigned long long)cap) {
+    w = w / kB2 + 1;
+    ++r;
+  }
+  return r;
+}
+
+hipError_t launch_topk_refine(const TopkLaunch& t, int round, hipStream_t stream) {
+  if (!valid(t) || round < 0 || round >= t.rounds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topk_refine_kernel, dim3(t.blocks, t.nq), dim3(256), 0, stream, t, round);
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_compact(const TopkLaunch& t, hipStream_t stream) {
+  if (!valid(t)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topk_compact_kernel, dim3(t.blocks, t.nq), dim3(256), 0, stream, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_finish(const TopkLaunch& t, hipStream_t stream) {
+  if (!valid(t)) return hipErrorInvalidValue;
+  const size_t lds = (size_t)pow2_at_least(t.k > t.cap ? t.k : t.cap) * sizeof(u64);  // <= 16384 keys: 128 KiB
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(topk_finish_kernel), (int)lds)) return e;
+  hipLaunchKernelGGL(topk_finish_kernel, dim3(t.nq), dim3(1024), lds, stream, t);
+  return hipGetLastError();
+}
+
+}  // namespace tavb

@@ -50,7 +50,7 @@ MODEL_DEFAULT_MIN_SCORES: dict[str, float] = {
     "text-embedding-ada-002": 0.93,
 }
 
-_PAGE = _native.MAX_FUSED_K  # most hits the fused select-while-streaming kernels return; beyond: one emit-all pass + host sort
+_PAGE = _native.MAX_FUSED_K  # most hits the fused select-while-streaming kernels return; beyond: the exact large-k route up to MAX_LARGE_K (`_large_k`), then one emit-all pass + host sort
 
 
 try:  # whole-matrix digests of the "full" host watch
@@ -569,6 +569,12 @@ class VectorBase:
             raise ValueError("max_hits must be >= 0")
         return max_hits, _native.f32_threshold(min_score)
 
+    @staticmethod
+    def _large_k(eng, max_hits: int) -> bool:
+        """max_hits past the fused selection that the exact device top-k takes (tavb_search_topk): a single-GPU engine with the
+        "large_k" option on (the default); device groups and test doubles keep the emit-all route."""
+        return _PAGE < max_hits <= _native.MAX_LARGE_K and isinstance(eng, _native.Engine) and eng.get_option("large_k") != 0
+
     def fuzzy_lookup_embedding(
         self,
         embedding: NormalizedEmbedding,
@@ -583,6 +589,10 @@ class VectorBase:
         if predicate is None:
             if 1 <= max_hits <= _PAGE:
                 ids, scs = eng.search(embedding, max_hits, thr)  # fused select-while-streaming
+            elif self._large_k(eng, max_hits):
+                ords, scs2, cnts = eng.search_topk(eng._query(embedding).reshape(1, -1), max_hits, thr)  # one pass, exact top-k on the device
+                m = int(cnts[0])
+                ids, scs = ords[0, :m], scs2[0, :m]
             else:
                 # more hits than the fused selection holds, or max_hits == 0 (every survivor, sorted: the `[-0:]` quirk,
                 # :186-187): ONE pass emits all survivors, the host sorts them
@@ -641,6 +651,8 @@ class VectorBase:
                 rows = np.where(subset < 0, subset + n, subset)
             if 1 <= max_hits <= _PAGE:
                 pos, scs = eng.search_subset(embedding, rows, max_hits, thr)
+            elif self._large_k(eng, max_hits):
+                pos, scs = eng.search_subset_topk(embedding, rows, max_hits, thr)
             else:
                 pos, scs = eng.search_all(embedding, thr, None if max_hits == 0 else max_hits, subset_rows=rows)
         return list(map(ScoredInt, subset[pos].tolist(), scs.tolist()))  # (the caller's ordinals at the returned positions, :229)
@@ -680,6 +692,10 @@ class VectorBase:
                 return np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
             return [[] for _ in range(len(queries))]
         if not (1 <= max_hits <= _PAGE):
+            eng = self._sync_device()
+            if self._large_k(eng, max_hits):  # ONE call: a corpus pass per 8 queries, each query's own threshold
+                ords, scs, cnts = eng.search_topk(queries, max_hits, thr)
+                return _scored_lists(ords, scs, cnts, max_hits)
             return [self.fuzzy_lookup_embedding(q, max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
         eng = self._sync_device()
         ords, scs, cnts = eng.search_batch(queries, max_hits, thr)
