@@ -102,6 +102,34 @@ class FakeEngine:
     def search_subset_resident(self, q, dev_rows, k, thr):
         return self.search_subset(q, dev_rows.astype(np.int64), k, thr)
 
+    # -- device-resident forms (torch CPU tensors stand in for device / pinned memory) ----------------------------------------
+    def set_corpus_tensor(self, tensor, rows=None, ordinal_base=0, sync_torch=True):
+        self.corpus = tensor.float().numpy()
+        self.rows = tensor.shape[0] if rows is None else int(rows)
+        self.dim = tensor.shape[1]
+        self.ordinal_base = int(ordinal_base)
+
+    @staticmethod
+    def _write(out_keys, keys):
+        """what the kernels do: nq x k keys at out_keys' first element, row q at q * k -- refused, as by the binding, when that is not out_keys"""
+        nq, k = keys.shape
+        if out_keys.dtype.itemsize != 8 or not out_keys.is_contiguous() or out_keys.numel() < nq * k:
+            raise ValueError(f"out_keys {tuple(out_keys.shape)} stride {out_keys.stride()} cannot take {nq} x {k} keys")
+        out_keys.view(-1)[: nq * k].numpy().view(np.uint64)[:] = keys.reshape(-1)
+
+    def search_device(self, dev_queries, k, thr, out_keys=None):
+        self.device_calls = getattr(self, "device_calls", 0) + 1
+        self._write(out_keys, np.stack([self._keys(q, k, np.float32(thr)) for q in dev_queries.numpy()]))
+        return out_keys
+
+    def search_subset_device(self, dev_query, dev_rows, k, thr, out_keys=None):
+        self.device_calls = getattr(self, "device_calls", 0) + 1
+        pos, sc = self.search_subset(dev_query.numpy().reshape(-1), dev_rows.numpy().astype(np.int64), k, np.float32(thr))
+        keys = np.zeros((1, k), dtype=np.uint64)
+        keys[0, : len(pos)] = (sc.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - pos.astype(np.uint64))
+        self._write(out_keys, keys)
+        return out_keys
+
     # -- split form (device groups) ----------------------------------------------------------------------------------
     def _keys(self, q, k, thr, bound=None):
         sc = self._scores(q)

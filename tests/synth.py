@@ -63,3 +63,31 @@ def make_clustered_corpus(n: int, d: int, seed: int, cluster_rows: int = 100, sp
     if n_queries:
         q /= np.linalg.norm(q, axis=1, keepdims=True)
     return v.astype(np.float32), q.astype(np.float32), cl, qc
+
+
+ANISO_C = float(np.sqrt(3.0))  # bench.py ANISO_C: |c * mu| over |g|; cosine between two rows ~ c^2 / (1 + c^2) = 0.75
+
+
+def _aniso_direction(d: int, seed: int) -> np.ndarray:
+    mu = np.random.default_rng(seed * 1_000_003 + 999_979).standard_normal(d).astype(np.float32)
+    return mu / np.linalg.norm(mu)
+
+
+def make_aniso_corpus(n: int, d: int, seed: int) -> np.ndarray:
+    """Host restatement of bench.py's `kind="aniso"` recipe (not its bytes: bench draws on the device): one unit direction mu per seed;
+    row = normalise(g + ANISO_C * sqrt(d) * mu), g standard normal.  Mean pairwise cosine 0.75, so a query of the same distribution
+    (`aniso_queries`) scores almost every row near 0.875: thousands of survivors at min_score 0.85 and near-ties at any rank."""
+    mu = _aniso_direction(d, seed)
+    v = np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
+    v += np.float32(ANISO_C * np.sqrt(d)) * mu
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    return v.astype(np.float32)
+
+
+def aniso_queries(count: int, d: int, seed: int) -> np.ndarray:
+    """`count` unit queries from the distribution of `make_aniso_corpus(.., d, seed)`'s rows (bench.py aniso_queries)."""
+    mu = _aniso_direction(d, seed)
+    q = np.random.default_rng(seed + 23).standard_normal((count, d)).astype(np.float32)
+    q += np.float32(ANISO_C * np.sqrt(d)) * mu
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    return q.astype(np.float32)

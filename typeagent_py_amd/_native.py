@@ -558,6 +558,21 @@ class Engine:
         _check(self.lib, rc)
 
     # device-resident forms ---------------------------------------------------
+    def _check_out_keys(self, out_keys, nq: int, k: int) -> None:
+        """The kernels write nq * k keys at out_keys.data_ptr(), row q at q * k: anything but a contiguous int64 tensor of at least that many
+        elements, in this device's memory or in pinned host memory (which the device writes directly), is refused before any launch."""
+        torch = self._torch
+        if not isinstance(out_keys, torch.Tensor) or out_keys.dtype != torch.int64:
+            raise ValueError("out_keys must be an int64 torch tensor")
+        if not out_keys.is_contiguous():
+            raise ValueError("out_keys must be contiguous (the kernels write row q of the result at q * k)")
+        if out_keys.numel() < nq * k:
+            raise ValueError(f"out_keys holds {out_keys.numel()} keys; this lookup writes {nq} x {k} = {nq * k}")
+        dev = out_keys.device
+        on_device = dev.type == "cuda" and (dev.index if dev.index is not None else torch.cuda.current_device()) == self.device
+        if not on_device and not (dev.type == "cpu" and out_keys.is_pinned()):
+            raise ValueError(f"out_keys must live on cuda:{self.device} or in pinned host memory")
+
     def search_device(self, dev_queries, k: int, thr: float, out_keys=None):
         """dev_queries: torch f32 [nq, dim] on this device -> torch int64 [nq, k] of packed keys (async)."""
         torch = self._torch
@@ -565,6 +580,7 @@ class Engine:
         nq = dev_queries.shape[0]
         if out_keys is None:
             out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
         with self._lock:
             rc = self.lib.tavb_search_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -578,6 +594,7 @@ class Engine:
         assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
         if out_keys is None:
             out_keys = torch.empty((1, k), dtype=torch.int64, device=dev_query.device)
+        self._check_out_keys(out_keys, 1, k)
         with self._lock:
             rc = self.lib.tavb_search_subset_device(self._h, c_void_p(dev_query.data_ptr()), c_void_p(dev_rows.data_ptr()),
                                                     dev_rows.shape[0], k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
@@ -607,6 +624,7 @@ class Engine:
         nq = dev_queries.shape[0]
         if out_keys is None:
             out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
         with self._lock:
             rc = self.lib.tavb_search_allgather(self._h, c_void_p(dev_queries.data_ptr()), nq, k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)

@@ -56,6 +56,7 @@ class FusedIndexQuery:
         self._pinned_q = None
         self._dev_q = None
         self._pinned_keys = None
+        self._shape = None  # (nq, dim, TERMS_K, MESSAGES_K, THREADS_K) the buffers and views above were made for
 
     def set_corpus(self, name: str, tensor, rows: int | None = None) -> None:
         """name in {"terms", "messages", "threads"}; tensor: contiguous f32/f16 [N, D] on this device."""
@@ -64,6 +65,10 @@ class FusedIndexQuery:
         n = tensor.shape[0] if rows is None else int(rows)
         self.corpora[name] = (tensor, n)
 
+    def _has(self, name: str) -> bool:
+        entry = self.corpora.get(name)
+        return entry is not None and entry[1] > 0
+
     def _use(self, name: str) -> bool:
         entry = self.corpora.get(name)
         if entry is None or entry[1] == 0:
@@ -71,77 +76,89 @@ class FusedIndexQuery:
         self.engine.set_corpus_tensor(entry[0], rows=entry[1], ordinal_base=0, sync_torch=False)
         return True
 
+    def _alloc(self, nq: int, dim: int, n_keys: int):
+        """(pinned f32 [nq, dim] queries, device f32 [nq, dim] queries, pinned int64 [n_keys] result keys) of one run shape."""
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        pinned_q = torch.empty((nq, dim), dtype=torch.float32).pin_memory()
+        dev_q = torch.empty((nq, dim), dtype=torch.float32, device=dev)
+        return pinned_q, dev_q, torch.zeros(n_keys, dtype=torch.int64).pin_memory()
+
     def run(self, term_queries, message_query=None, thread_query=None, message_subset=None) -> FusedResult:
         torch = self.torch
         tq = np.ascontiguousarray(term_queries, dtype=np.float32).reshape(-1, np.shape(term_queries)[-1]) if len(term_queries) else np.zeros((0, 0), np.float32)
         T = tq.shape[0]
         dim = tq.shape[1] if T else (len(message_query) if message_query is not None else len(thread_query))
         nq = T + 2
-        kmax = max(self.TERMS_K, self.MESSAGES_K, self.THREADS_K)
-        if self._pinned_q is None or self._pinned_q.shape != (nq, dim):
-            dev = torch.device("cuda", self.device)
-            self._pinned_q = torch.empty((nq, dim), dtype=torch.float32).pin_memory()
-            self._dev_q = torch.empty((nq, dim), dtype=torch.float32, device=dev)
+        tk, mk, hk = int(self.TERMS_K), int(self.MESSAGES_K), int(self.THREADS_K)
+        # the subset is checked before anything is enqueued: an error raised after the H2D copy of the queries would leave that copy reading
+        # the pinned query buffer the next run() writes
+        subset = rows = None
+        if message_query is not None and message_subset is not None and self._has("messages"):
+            subset = np.asarray(message_subset, dtype=np.int64).reshape(-1)
+            n = self.corpora["messages"][1]
+            rows = np.where(subset < 0, subset + n, subset)
+            if ((rows < 0) | (rows >= n)).any():
+                raise IndexError("message subset ordinal out of range")
+        shape = (nq, dim, tk, mk, hk)
+        if self._shape != shape:
             # the result keys land in pinned host memory straight from the last kernel of every lookup (no device buffer, no copy back, no
             # memset launch in front: at the reference's scale a user query is launch-bound -- ten submissions were 98 us, profiles/r06_raw/
-            # cfg5_reference_scale.txt); the views handed to the engine are made once per shape (a tensor slice costs 2-3 us of host time)
-            self._pinned_keys = torch.zeros((nq, kmax), dtype=torch.int64).pin_memory()
-            self._keys_np = self._pinned_keys.numpy()
+            # cfg5_reference_scale.txt); the views handed to the engine are made once per shape (a tensor slice costs 2-3 us of host time).
+            # Each lookup gets a contiguous block of its own k per query -- [T, TERMS_K], [1, MESSAGES_K], [1, THREADS_K] -- because the
+            # kernels write row q of a lookup at q * k: a slice of a wider buffer would be strided, and a cache kept across a change of the
+            # K attributes would be too small.
+            self._pinned_q, self._dev_q, self._pinned_keys = self._alloc(nq, dim, T * tk + mk + hk)
+            keys = self._pinned_keys
+            self._keys_np = keys.numpy()
             self._host_q = self._pinned_q.numpy()
             self._views = {
-                "tq": self._dev_q[:T], "tk": self._pinned_keys[:T, : self.TERMS_K],
-                "mq": self._dev_q[T : T + 1], "mq1": self._dev_q[T], "mk": self._pinned_keys[T : T + 1, : self.MESSAGES_K],
-                "hq": self._dev_q[T + 1 : T + 2], "hk": self._pinned_keys[T + 1 : T + 2, : self.THREADS_K],
+                "tq": self._dev_q[:T], "tk": keys[: T * tk].view(T, tk),
+                "mq": self._dev_q[T : T + 1], "mq1": self._dev_q[T], "mk": keys[T * tk : T * tk + mk].view(1, mk),
+                "hq": self._dev_q[T + 1 : T + 2], "hk": keys[T * tk + mk :].view(1, hk),
             }
+            self._shape = shape
         host_q, views, keys_np = self._host_q, self._views, self._keys_np
         if T:
             host_q[:T] = tq
         host_q[T] = 0 if message_query is None else np.asarray(message_query, dtype=np.float32)
         host_q[T + 1] = 0 if thread_query is None else np.asarray(thread_query, dtype=np.float32)
         thr = _native.f32_threshold
-        subset = None
         ran_t = ran_m = ran_h = False
         with torch.cuda.stream(self.stream):
             self._dev_q.copy_(self._pinned_q, non_blocking=True)
             if T and self._use("terms"):
-                self.engine.search_device(views["tq"], self.TERMS_K, float(thr(self.TERMS_MIN)), out_keys=views["tk"])
+                self.engine.search_device(views["tq"], tk, float(thr(self.TERMS_MIN)), out_keys=views["tk"])
                 ran_t = True
             if message_query is not None and self._use("messages"):
-                if message_subset is not None:
-                    subset = np.asarray(message_subset, dtype=np.int64).reshape(-1)
-                    n = self.corpora["messages"][1]
-                    rows = np.where(subset < 0, subset + n, subset)
-                    if ((rows < 0) | (rows >= n)).any():
-                        raise IndexError("message subset ordinal out of range")
+                if subset is not None:
                     if len(rows):
                         d_rows = torch.from_numpy(rows.astype(np.int32)).to(self._dev_q.device, non_blocking=True)
-                        self.engine.search_subset_device(views["mq1"], d_rows, self.MESSAGES_K, float(thr(self.MESSAGES_MIN)), out_keys=views["mk"])
+                        self.engine.search_subset_device(views["mq1"], d_rows, mk, float(thr(self.MESSAGES_MIN)), out_keys=views["mk"])
                         ran_m = True
                 else:
-                    self.engine.search_device(views["mq"], self.MESSAGES_K, float(thr(self.MESSAGES_MIN)), out_keys=views["mk"])
+                    self.engine.search_device(views["mq"], mk, float(thr(self.MESSAGES_MIN)), out_keys=views["mk"])
                     ran_m = True
             if thread_query is not None and self._use("threads"):
-                self.engine.search_device(views["hq"], self.THREADS_K, float(thr(self.THREADS_MIN)), out_keys=views["hk"])
+                self.engine.search_device(views["hq"], hk, float(thr(self.THREADS_MIN)), out_keys=views["hk"])
                 ran_h = True
         self.stream.synchronize()
-        # (a lookup that did not run leaves last call's keys in its rows: empty them; the others were overwritten in full by their merge kernels)
+        # (a lookup that did not run leaves last call's keys in its block: empty it; the others were overwritten in full by their merge kernels)
+        t_keys, m_keys, h_keys = keys_np[: T * tk].reshape(T, tk), keys_np[T * tk : T * tk + mk].reshape(1, mk), keys_np[T * tk + mk :].reshape(1, hk)
         if T and not ran_t:
-            keys_np[:T] = 0
+            t_keys[:] = 0
         if not ran_m:
-            keys_np[T] = 0
+            m_keys[:] = 0
         if not ran_h:
-            keys_np[T + 1] = 0
-        if T and self.TERMS_K < kmax:
-            keys_np[:T, self.TERMS_K :] = 0
-        keys_np[T, self.MESSAGES_K :] = 0
-        keys_np[T + 1, self.THREADS_K :] = 0
-        ords, scs, cnts = _native.decode_keys(keys_np)
+            h_keys[:] = 0
 
-        def hits(row: int, remap=None) -> list[ScoredInt]:
+        def hits(block, row: int = 0, remap=None) -> list[ScoredInt]:
+            ords, scs, cnts = block
             m = int(cnts[row])
             items = ords[row, :m].tolist()
             if remap is not None:
                 items = [int(remap[i]) for i in items]
             return [ScoredInt(int(i), float(s)) for i, s in zip(items, scs[row, :m].tolist())]
 
-        return FusedResult([hits(i) for i in range(T)], hits(T, subset), hits(T + 1))
+        terms = _native.decode_keys(t_keys) if T else None
+        return FusedResult([hits(terms, i) for i in range(T)], hits(_native.decode_keys(m_keys), 0, subset), hits(_native.decode_keys(h_keys)))
