@@ -136,6 +136,10 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "early_exact"   1 (default): with wide_fallback, a batch MOST of whose queries (> nq / 2) already hold, before the last and biggest filter phase, a band that
  *                   extrapolates past the band buffer (every query next to more near-duplicates than a band holds) skips that phase, its selection and the
  *                   rescoring, and all its queries take the exact split-plane form at once; "last_doomed" (read only; synchronises) = that count
+ *   "mfma_shape"    16 (default) / 32: the MFMA of the 256-query filter tile, v_mfma_f32_16x16x32_f16 or v_mfma_f32_32x32x16_f16 (same tile, same
+ *                   answers bit for bit; 16 is faster on cfg3, measured in profiles/r09_mfma_shape.md).  The routing: tavb_plan_filter_shape.  The SPLIT exact form, the 128-query
+ *                   tile, "mfma_bdirect", "mfma_sched" and the ablations other than 256 / 258 always run 32x32x16.  "last_mfma_shape" (read only) = the
+ *                   shape the last filter launch of the 128/256-query tile ran on (0 before the first)
  *   "mfma_bdirect"  0 (default) / 1: the 256-query tile takes its query operand in MFMA-fragment-major order straight from L2 into registers
  *                   (no LDS staging; three corpus slots instead of two): measured +0.8 %, kept as an option (profiles/r04_cfg3_kernel.md section 10)
  *   "small_direct_bytes" host-synchronous lookups of one query (tavb_search) or a few (tavb_search_batch with nq <= 8; <= 4 for k > 64) on corpora up
@@ -413,6 +417,12 @@ int tavb_profile_read(tavb_ctx* ctx, int32_t kernel_id, double* out_total_ms, in
  * a negative error code.  No reference counterpart (the reference scans once, vectorbase.py:176); a pure function, needs no context and no
  * GPU -- what lets a committed profile be checked against the code that ships (tests/test_bench_contract.py). */
 int tavb_plan_ladder(int64_t rows, int32_t nq, int32_t n_cu, int64_t* out_bounds, int32_t cap);
+
+/* The MFMA shape (16 = v_mfma_f32_16x16x32_f16, 32 = v_mfma_f32_32x32x16_f16) a filter launch of the 128/256-query tile runs on, given the
+ * option "mfma_shape" (16 or 32), the query tile (128 or 256), whether the launch is the SPLIT exact form, whether "mfma_bdirect" is on, and the
+ * measurement options "mfma_sched" and "mfma_ablate".  Returns 16 or 32, or a negative error code for a shape or tile out of range (the
+ * rule "mfma_shape" is validated by).  A pure function, needs no context and no GPU. */
+int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate);
 
 #ifdef __cplusplus
 }

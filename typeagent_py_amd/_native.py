@@ -84,6 +84,7 @@ _SIGNATURES = [
     ("tavb_profile_reset", c_int, [c_void_p]),
     ("tavb_profile_read", c_int, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int64)]),
     ("tavb_plan_ladder", c_int, [c_int64, c_int32, c_int32, POINTER(c_int64), c_int32]),
+    ("tavb_plan_filter_shape", c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
 ]
 
 ABI_SYMBOLS = [name for name, _, _ in _SIGNATURES]
@@ -108,6 +109,15 @@ def plan_ladder(rows: int, nq: int, n_cu: int = 256) -> list[int]:
     n = lib.tavb_plan_ladder(int(rows), int(nq), int(n_cu), buf, 16)
     _check(lib, n if n < 0 else 0)
     return [int(buf[i]) for i in range(n + 1)]
+
+
+def plan_filter_shape(shape: int, query_tile: int = 256, split: bool = False, bdirect: bool = False, sched: int = 0, ablate: int = 0) -> int:
+    """The MFMA shape (16 or 32) a filter launch of the 128/256-query tile runs on under these options (tavb_plan_filter_shape); raises on
+    a shape or tile the engine refuses.  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_filter_shape(int(shape), int(query_tile), int(bool(split)), int(bool(bdirect)), int(sched), int(ablate))
+    _check(lib, r if r < 0 else 0)
+    return int(r)
 
 
 def library_path() -> str:

@@ -184,6 +184,8 @@ struct tavb_ctx {
   Buffer h_out{nullptr, 0, true};  // pinned + device-visible: the last kernel of a synchronous lookup writes its keys straight here
   Buffer h_lists{nullptr, 0, true};  // pinned + device-visible: per-workgroup lists of a small single-query lookup (merged on the host)
   Buffer h_flag{nullptr, 0, true};   // pinned: the work list of flagged queries read back by the one route that needs a host round trip (fp32 corpus, k > 64)
+  int64_t mfma_shape = 16;      // option: MFMA of the 256-query filter tile, 16 = v_mfma_f32_16x16x32_f16, 32 = v_mfma_f32_32x32x16_f16 (profiles/r09_mfma_shape.md)
+  int64_t last_mfma_shape = 0;  // option "last_mfma_shape" (get): the MFMA shape the last filter launch of the 128/256-query tile ran on (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
   int64_t band_max = tavb::kBandMax;  // option: keys of a query's band the wide tile's selection hands to the rescoring (256 .. kBandMax); a band that does not fit flags the query
   int64_t early_exact = 1;    // option: ... and a batch found to be mostly such queries BEFORE the last filter phase skips that phase (needs wide_fallback)
@@ -682,6 +684,9 @@ int tavb_set_option(tavb_ctx* c, const char* name, int64_t v) {
     c->wide_fallback = v ? 1 : 0;
   } else if (n == "mfma_bdirect") {
     c->mfma_bdirect = v ? 1 : 0;
+  } else if (n == "mfma_shape") {
+    if (tavb_plan_filter_shape((int32_t)v, 256, 0, 0, 0, 0) < 0) return TAVB_E_INVALID;
+    c->mfma_shape = v;
   } else if (n == "small_direct_keys") {
     if (v < 64 || v > (1 << 20)) return fail(TAVB_E_INVALID, "small_direct_keys must be 64 .. 1048576");
     c->small_direct_keys = v;
@@ -795,6 +800,8 @@ int tavb_get_option(tavb_ctx* c, const char* name, int64_t* out) {
     }
   }
   else if (n == "mfma_bdirect") *out = c->mfma_bdirect;
+  else if (n == "mfma_shape") *out = c->mfma_shape;
+  else if (n == "last_mfma_shape") *out = c->last_mfma_shape;
   else if (n == "last_direct") *out = c->last_direct;
   else if (n == "inline_query") *out = c->inline_query;
   else if (n == "small_direct_keys") *out = c->small_direct_keys;
@@ -2434,6 +2441,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   p.active_max = r.active_max;
   p.split_plane = r.split_plane;
   p.bdirect = r.bdirect ? 1 : 0;
+  p.shape = (int)c->mfma_shape;
   const std::vector<int64_t> bounds = ladder_bounds(c->rows, splits, r.nq_pad, r.skinny, r.ladder, c->mfma_sample_rows, c->mfma_ladder);  // phase i scans rows [bounds[i], bounds[i+1])
   const int n_phases = (int)bounds.size() - 1;
   const int kc = wide ? (int)c->band_max : k;  // keys per query of the running selection between phases
@@ -2483,6 +2491,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
       Timed t(c, r.active ? TAVB_KERNEL_RESCORE : !last ? TAVB_KERNEL_MFMA_SAMPLE : (r.skinny ? TAVB_KERNEL_SKINNY : TAVB_KERNEL_MFMA));
       hipError_t e = launch(pp);
       if (e != hipSuccess) return fail(TAVB_E_HIP, "mfma scan launch failed (phase %d): %s", ph, hipGetErrorString(e));
+      if (wide && pp.split_plane == 0) c->last_mfma_shape = tavb::mfma_tile_shape(pp);
     }
     if (wide) {
       Timed t(c, r.active ? TAVB_KERNEL_RESCORE : TAVB_KERNEL_MERGE);
@@ -2904,6 +2913,19 @@ int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, co
     return run_tile_ladder(c, r, d_out, nullptr);
   }
   return search_device_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, index_base, d_out);
+}
+
+extern "C" int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate) {
+  if (shape != 16 && shape != 32) return fail(TAVB_E_INVALID, "mfma_shape must be 16 or 32");
+  if (query_tile != 128 && query_tile != 256) return fail(TAVB_E_INVALID, "query_tile must be 128 or 256");
+  tavb::MfmaParams p{};
+  p.shape = shape;
+  p.wide_tile = query_tile;
+  p.split_plane = split ? 1 : 0;
+  p.bdirect = bdirect ? 1 : 0;
+  p.sched = sched;
+  p.ablate = ablate;
+  return tavb::mfma_tile_shape(p);
 }
 
 extern "C" int tavb_plan_ladder(int64_t rows, int32_t nq, int32_t n_cu, int64_t* out_bounds, int32_t cap) {

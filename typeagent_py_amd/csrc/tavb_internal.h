@@ -208,8 +208,10 @@ struct MfmaParams {
   int32_t wide_tile;    // 128/256-query kernel only: queries per tile, 128 or 256 (0 = 256)
   const float* band;    // 128/256-query kernel only, optional [nq_padded]: band selection (keep every key within band[q] of the k-th best)
   unsigned* lost;       // ... [nq_padded]: atomicMax of the score level (bits) below which a query lost band rows to a buffer that could not hold its band
+  int32_t shape;        // 256-query filter tile: 16 = v_mfma_f32_16x16x32_f16, anything else = v_mfma_f32_32x32x16_f16 (see mfma_tile_shape)
 };
 hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream);
+int mfma_tile_shape(const MfmaParams& p);  // M = N of the MFMA the 128/256-query kernel launch_mfma_scan picks for p runs on: 16 or 32
 hipError_t launch_sample_thresholds(const unsigned long long* keys, int nq, int k, const float* floor, float* thr, hipStream_t stream);
 int mfma_query_tile(int nq);              // queries per workgroup tile: 128 where that leaves less padding (<= 128, 257..384, 513..640 queries), else 256
 int mfma_query_tile_for(int nq, int64_t rows, int n_cu);  // ... and 128 on a corpus so small that 256-query tiles leave half of the CUs idle

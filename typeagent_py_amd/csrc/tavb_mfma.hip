@@ -357,6 +357,13 @@ __device__ __forceinline__ void wait_vmcnt() {
 //     corpus slot (3 x 40 + 2 x 16 KiB): a round then stages query slab S + 1 first and corpus slab S + 2 behind it, and the
 //     wait in front of quarter 3 is counted (`vmcnt(10)`: everything but the ten corpus pieces of slab S + 2 has landed).
 //     HBM-bound: 5.8 TB/s at 128 queries (profiles/r02_mid_batch.md).
+//   * M16 (the default of the 256-query filter tile, option mfma_shape = 16; profiles/r09_mfma_shape.md): the same tile, ring, barrier and
+//     epilogue on v_mfma_f32_16x16x32_f16.  The kernel runs at the board's power limit; in bare MFMA loops on random data the chip held a
+//     higher clock on this shape at the same cycles per flop, which is the expected source of the gain (profiles/r09_mfma_shape.md).  A wave's 160 x 128 is 10 x 8 blocks of 16 x 16 (f32x4: the same 320 registers, 60 blocks in AGPRs, 20 in
+//     VGPRs); a quarter is one k32 slice x one 80-row half x the 8 query fragments = 40 MFMAs, the four quarters of a step (rows 0-79, k32 #0)
+//     (80-159, #0) (0-79, #1) | barrier | (80-159, #1).  Row fragments double-buffer (5 + 5); the 8 query fragments serve two quarters and are
+//     reloaded in place in quarters 1 and 3, so the operands stay at 72 registers.  Per k32 slice a wave still reads 10 row and 8 query
+//     fragments of 1 KiB: LDS bytes per flop are unchanged.  The SPLIT and BD forms and the 128-query tile stay on 32x32x16.
 // Measured and rejected (profiles/r02_cfg3_ablation.md): touching the corpus lines of the step 1 / 2 / 4 steps ahead
 // into L2 with one 4-byte load per line (-3 .. -6 %); other piece-per-quarter schedules (no difference).
 // ---------------------------------------------------------------------------------------------
@@ -394,6 +401,17 @@ constexpr int staging_piece_at(int q, int i) {
   return -1;
 }
 
+// M16 issue order of a 40-MFMA quarter: MFMA i multiplies row fragment m16_row_frag(i) by query fragment m16_query_frag(i) (query fragment
+// outermost); m16_last_reader: the last MFMA of a quarter that reads a given query (or row) fragment as an operand
+constexpr int m16_query_frag(int i) { return i / 5; }
+constexpr int m16_row_frag(int i) { return i % 5; }
+constexpr int m16_last_reader(bool query, int f) {
+  int last = -1;
+  for (int i = 0; i < 40; ++i)
+    if ((query ? m16_query_frag(i) : m16_row_frag(i)) == f) last = i;
+  return last;
+}
+
 // SPLIT: the queries arrive as TWO fp16 planes (q = hi + lo to 2^-22) and a tile runs its K loop twice over the corpus rows, once per plane, into
 // the same accumulators: fp32 query x fp16 row like the 64-query exact tile, at the wide tile's rate -- the bounded fallback for batches in which
 // MANY queries have more near-duplicates than a band holds (tavb_rescore.hip).  Twice the MFMAs; only this instantiation pays for it.
@@ -402,7 +420,7 @@ constexpr int staging_piece_at(int q, int i) {
 // coalesced 16 B-per-lane load out of L2 straight into the registers the MFMA reads; four register sets rotate, the loads run three quarters
 // (~1.2 us) ahead.  Per K step the LDS then moves 120 KiB instead of 216 (no query slab written, no query fragments read); the price is that
 // both row halves of the workgroup load the same fragments (L2 -> CU traffic 104 KiB per step instead of 72).
-template <int ABL, int NI, int N3, int N0, int N1, bool SPLIT = false, bool BD = false>
+template <int ABL, int NI, int N3, int N0, int N1, bool SPLIT = false, bool BD = false, bool M16 = false>
 __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p) {
   using G = WideGeom<NI>;
   constexpr int BN = G::QT, NT = G::NT, SLOT_B6 = G::SLOT_B, PIECES_B6 = G::PIECES_B, B_RING6 = G::B_RING;
@@ -412,8 +430,10 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   constexpr int CTRL6 = BD ? 3 * SLOT_A6 : G::CTRL;
   constexpr int PIECES6 = BD ? PIECES_A6 : G::PIECES;
   static_assert(!BD || (NI == 4 && !SPLIT), "the direct query operand is built for the 256-query tile");
+  static_assert(!M16 || (NI == 4 && !SPLIT && !BD), "the 16x16x32 form is built for the 256-query filter tile");
+  constexpr int QM = M16 ? 40 : NT;  // MFMAs per quarter
   static_assert(N3 + N0 + N1 == PIECES6, "every piece of a step is issued exactly once");
-  static_assert(N3 <= NT && N0 <= NT && N1 <= NT && NI + 5 <= NT, "one piece / one fragment read behind an MFMA at most");
+  static_assert(N3 <= QM && N0 <= QM && N1 <= QM && NI + 5 <= NT, "one piece / one fragment read behind an MFMA at most");
   extern __shared__ __align__(16) unsigned char smem[];
   float* thr_lds = reinterpret_cast<float*>(smem + CTRL6);
   int* cnt_lds = reinterpret_cast<int*>(smem + CTRL6 + BN * 4);
@@ -477,6 +497,7 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   //      (l & 7) ^ ((row >> 1) & 7); with row = 8 * piece + (l >> 3) that is (l & 7) ^ (4 * (piece & 1) + (l >> 4)).
   int st_even, st_odd;
   uint32_t frag_x, a_lane, b_lane;
+  uint32_t frag_x16, a_lane16, b_lane16;  // M16: lane l = row / query l & 15 of a 16-row fragment, halves 8 (l >> 4) .. + 7 of a k32 slice
   {
     int zero = 0;
     asm volatile("" : "+v"(zero));
@@ -488,6 +509,10 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
     frag_x = (uint32_t)(((ln >> 5) ^ ((frag_row >> 1) & 7)) << 4);  // byte (k16 << 5) ^ frag_x within the 128-byte row
     a_lane = (uint32_t)((wm * 160 + frag_row) * 128);              // + mi * 4096
     b_lane = (uint32_t)(B_RING6 + (wn * G::WQ + frag_row) * 128);    // + ni * 4096
+    const int frag_row16 = ln & 15;
+    frag_x16 = (uint32_t)(((ln >> 4) ^ ((frag_row16 >> 1) & 7)) << 4);  // byte (k32 << 6) ^ frag_x16 within the 128-byte row
+    a_lane16 = (uint32_t)((wm * 160 + frag_row16) * 128);              // + row fragment * 2048
+    b_lane16 = (uint32_t)(B_RING6 + (wn * G::WQ + frag_row16) * 128);    // + query fragment * 2048
   }
   const __amdgpu_buffer_rsrc_t rsrc_b =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sgpr_ptr(qbase)), 0, (int)(BN * row_bytes) + (SPLIT ? (int)p.split_plane : 0), 0x00020000);
@@ -561,9 +586,13 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   __syncthreads();  // step 0 landed everywhere, thresholds initialised (the waits above are counted: nothing is drained)
 
   typedef int i32x4 __attribute__((ext_vector_type(4)));
-  constexpr int NA_TILES = G::NA;
-  f32x16 acc_a[NA_TILES];
-  f32x16 acc_v[NT - NA_TILES > 0 ? NT - NA_TILES : 1];
+  // M16: 10 x 8 blocks of 16 x 16 (f32x4) per wave, the same 320 registers; the 20 blocks of rows 80 .. 159 x queries 64 .. 127 of the wave
+  // accumulate in VGPRs, the other 60 in AGPRs (the 32 x 32 form's 15 / 5 split)
+  using Acc = std::conditional_t<M16, f32x4, f32x16>;
+  constexpr int NACC = M16 ? 80 : NT;
+  constexpr int NA_TILES = M16 ? 60 : G::NA;
+  Acc acc_a[NA_TILES];
+  Acc acc_v[NACC - NA_TILES > 0 ? NACC - NA_TILES : 1];
 #define TAVB_MFMA6_A(ACC, A, B) \
   asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
 #define TAVB_MFMA6_V(ACC, A, B) \
@@ -572,8 +601,16 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=a"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
 #define TAVB_MFMA6_V0(ACC, A, B) \
   asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
+#define TAVB_MFMA16_A(ACC, A, B) \
+  asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
+#define TAVB_MFMA16_V(ACC, A, B) \
+  asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
+#define TAVB_MFMA16_A0(ACC, A, B) \
+  asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
+#define TAVB_MFMA16_V0(ACC, A, B) \
+  asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(ACC) : "v"(__builtin_bit_cast(i32x4, A)), "v"(__builtin_bit_cast(i32x4, B)))
 
-  f16x8 a0[5], b0[NI], a1[5], b1[NI];
+  f16x8 a0[5], b0[M16 ? 2 * NI : NI], a1[5], b1[M16 ? 1 : NI];  // M16: b0 = the wave's 8 query fragments of a k32 slice (b1 unused)
   f16x8 b2[BD ? NI : 1], b3[BD ? NI : 1];  // BD: four rotating sets of query fragments (quarter q multiplies set q, the loads for quarter q + 3 fill set (q + 3) & 3)
   constexpr int BQ_SLICE = (BN / 32) * 1024;  // bytes of one k16 slice of the tile's queries in fragment-major order
   int bq_soff = 0;                            // BD: byte offset (from the tile's queries) of the slice to load next; wraps with the tile
@@ -598,12 +635,21 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
       bq_load(b0);
       bq_load(b1);
       bq_load(b2);
+    } else if constexpr (M16) {
+      const unsigned char* abase16 = smem + (a_lane16 + frag_x16);
+      const unsigned char* bbase16 = smem + (b_lane16 + frag_x16);
+#pragma unroll
+      for (int n = 0; n < 2 * NI; ++n) b0[n] = *reinterpret_cast<const f16x8*>(bbase16 + n * 2048);
+#pragma unroll
+      for (int m = 0; m < 5; ++m) a0[m] = *reinterpret_cast<const f16x8*>(abase16 + m * 2048);
     } else {
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) b0[ni] = *reinterpret_cast<const f16x8*>(bbase + ni * 4096);
     }
+    if constexpr (!M16) {
 #pragma unroll
-    for (int mi = 0; mi < 5; ++mi) a0[mi] = *reinterpret_cast<const f16x8*>(abase + mi * 4096);
+      for (int mi = 0; mi < 5; ++mi) a0[mi] = *reinterpret_cast<const f16x8*>(abase + mi * 4096);
+    }
   }
   int rd = 0, rd_a = 0;  // ring slots (query, corpus) of the step being multiplied
 
@@ -658,12 +704,84 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
     if constexpr (BD) bq_soff = (bq_soff + BQ_SLICE == bq_tile_bytes) ? 0 : bq_soff + BQ_SLICE;
     if constexpr ((ABL & 1) != 0) asm volatile("" ::"v"(fa[0]), "v"(fa[4]), "v"(fb[0]), "v"(fb[NI - 1]));
   };
+  // M16 quarter Q: the 5 row fragments of rows 80 H .. 80 H + 79 (H = Q & 1) of k32 slice Q >> 1 (fa) x the 8 query fragments of that slice (b0),
+  // query fragment outermost: MFMA i = 5 n + m multiplies row fragment m by query fragment n.  Behind them, in program order: the 5 row fragments of
+  // the next quarter (the other row half; slot `nslot_a`, k32 slice NKK) into na, and the query fragments IN PLACE -- in quarters 1 and 3 all
+  // eight, of slice NKK (the next quarter's), b0[n] behind MFMA 5 n + 9, the last one, b0[7], behind MFMA 5 of the next quarter.  Every fragment
+  // read thus sits at least five MFMAs behind the last MFMA that reads its register as SrcA / SrcB (the row fragments: a0[m] / a1[m] is last read
+  // by MFMA 35 + m and reloaded behind MFMA m of the next quarter).  The ISA's table of required wait states for XDL (MFMA) operations has a
+  // write-after-read row for SrcC only ("XDL read VGPR SrcC, VALU write of the same VGPR": 3 wait states at four passes); SrcA / SrcB are read
+  // when the MFMA issues.  Five MFMA issues cover even the SrcC figure, so no s_nop is needed anywhere in the loop (the static_asserts below
+  // measure each distance from the issue order, m16_query_frag / m16_row_frag).
+  auto quarter16 = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&na)[5], int nslot_a, int nslot, auto nkk_tag) {
+    constexpr int Q = decltype(q_tag)::value;
+    constexpr bool FIRST = decltype(first_tag)::value;  // first quarter of a tile for these accumulators: C = 0
+    constexpr int NKK = decltype(nkk_tag)::value;
+    constexpr int H = Q & 1;
+    const uint32_t kx = (uint32_t)(NKK << 6) ^ frag_x16;
+    const unsigned char* abase = smem + nslot_a * SLOT_A6 + (a_lane16 + (H ^ 1) * 5 * 2048 + kx);
+    const unsigned char* bbase = smem + nslot * SLOT_B6 + (b_lane16 + kx);
+    auto mfma_at = [&](auto i_tag) {
+      constexpr int I = decltype(i_tag)::value;
+      constexpr int n = m16_query_frag(I), m = m16_row_frag(I), mr = 5 * H + m;
+      constexpr bool VB = mr >= 5 && n >= 4;  // accumulator block in VGPRs
+      constexpr int J = VB ? (mr - 5) * 4 + (n - 4) : (mr < 5 ? mr * 8 + n : 40 + (mr - 5) * 4 + n);
+      if constexpr ((ABL & 1) == 0) {
+        if constexpr (FIRST) {
+          if constexpr (VB)
+            TAVB_MFMA16_V0(acc_v[J], fa[m], b0[n]);
+          else
+            TAVB_MFMA16_A0(acc_a[J], fa[m], b0[n]);
+        } else {
+          if constexpr (VB)
+            TAVB_MFMA16_V(acc_v[J], fa[m], b0[n]);
+          else
+            TAVB_MFMA16_A(acc_a[J], fa[m], b0[n]);
+        }
+      }
+      if constexpr ((ABL & 32) == 0) {
+        // a reload sits behind MFMA I of this quarter; its register was last read by MFMA m16_last_reader(...) of the previous quarter (row
+        // fragments, b0[7]) or of this one (b0[0 .. 6]): the distance counts the MFMAs issued in between, from the issue order itself
+        if constexpr (I < 5) {
+          static_assert(I + QM - m16_last_reader(false, I) >= 5, "five MFMAs between the last read of a row fragment and its reload");
+          na[I] = *reinterpret_cast<const f16x8*>(abase + I * 2048);
+        }
+        if constexpr ((Q & 1) == 1 && I >= 9 && (I - 9) % 5 == 0) {
+          static_assert(I - m16_last_reader(true, (I - 9) / 5) >= 5, "five MFMAs between the last read of a query fragment and its reload");
+          b0[(I - 9) / 5] = *reinterpret_cast<const f16x8*>(bbase + ((I - 9) / 5) * 2048);
+        }
+        if constexpr ((Q & 1) == 0 && I == 5) {
+          static_assert(I + QM - m16_last_reader(true, 7) >= 5, "five MFMAs between the last read of a query fragment and its reload");
+          b0[7] = *reinterpret_cast<const f16x8*>(bbase + 7 * 2048);
+        }
+      }
+      if constexpr ((ABL & 2) == 0) {
+        constexpr int PC = staging_piece_at<QM, N3, N0, N1>(Q, I);
+        if constexpr (PC >= 0) stage_piece(std::integral_constant<int, PC>{});
+      }
+    };
+    [&]<int... I>(std::integer_sequence<int, I...>) { (mfma_at(std::integral_constant<int, I>{}), ...); }
+    (std::make_integer_sequence<int, QM>{});
+    if constexpr ((ABL & 1) != 0) asm volatile("" ::"v"(fa[0]), "v"(fa[4]), "v"(b0[0]), "v"(b0[7]));
+  };
   using Q0 = std::integral_constant<int, 0>;
   using Q1 = std::integral_constant<int, 1>;
   using Q2 = std::integral_constant<int, 2>;
   using Q3 = std::integral_constant<int, 3>;
   auto step = [&](auto first_tag) {
-    if constexpr (BD) {
+    if constexpr (M16) {
+      // (rows 0-79, k32 #0) (rows 80-159, #0) (rows 0-79, #1) | barrier | (rows 80-159, #1): the first two quarters of a tile start the accumulators
+      quarter16(Q0{}, first_tag, a0, a1, rd_a, rd, Q0{});
+      quarter16(Q1{}, first_tag, a1, a0, rd_a, rd, Q1{});
+      quarter16(Q2{}, std::false_type{}, a0, a1, rd_a, rd, Q1{});
+      if constexpr ((ABL & 2) == 0) wait_vmcnt<0>();
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      TAVB_BARRIER();
+      const int nxt_a = rd_a ^ 1;
+      quarter16(Q3{}, std::false_type{}, a1, a0, nxt_a, rd ^ 1, Q0{});
+      rd ^= 1;
+      rd_a = nxt_a;
+    } else if constexpr (BD) {
       quarter(Q0{}, first_tag, a0, b0, a1, b3, rd_a, rd, Q1{});
       quarter(Q1{}, std::false_type{}, a1, b1, a0, b0, rd_a, rd, Q2{});
       quarter(Q2{}, std::false_type{}, a0, b2, a1, b1, rd_a, rd, Q3{});
@@ -696,24 +814,82 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
     const bool tile_full = row0 + BM6 <= r_end;  // wave-uniform: every row of this tile belongs to the row range
     if constexpr ((ABL & 1) != 0) {  // MFMAs ablated: give the accumulators a value
 #pragma unroll
-      for (int i = 0; i < NA_TILES; ++i)
+      for (int i = 0; i < NA_TILES; ++i) acc_a[i] = Acc{};
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc_a[i][r] = 0.f;
-#pragma unroll
-      for (int i = 0; i < NT - NA_TILES; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_v[i][r] = 0.f;
+      for (int i = 0; i < NACC - NA_TILES; ++i) acc_v[i] = Acc{};
     }
     step(std::true_type{});
 #pragma unroll 1
     for (int kt = 1; kt < steps_per_tile; ++kt) step(std::false_type{});
 
     // ---- epilogue: admission test on the raw dot products, append .  The asm MFMAs are invisible
-    //      to the compiler's hazard recognizer: a 32x32x16 MFMA needs 18 wait states before its result may be read.
+    //      to the compiler's hazard recognizer: a 32x32x16 MFMA needs 18 wait states before its result may be read (a 16x16x32 one fewer).
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     int zero_e = 0;
     asm volatile("" : "+v"(zero_e));
     const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero_e));
+    if constexpr (M16) {
+      // 16 x 16 blocks: lane l holds query l & 15 of its block, rows 4 (l >> 4) + r, r = 0 .. 3.  One test per (query fragment n, row half h): the
+      // 20 scores a lane holds there, 1280 per wave, all against the lane's one threshold.  Pass 0: the VGPR blocks (h = 1, n >= 4), pass 1: the rest.
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+          const int ql = wn * G::WQ + n * 16 + (lane_e & 15);
+          const float thr = thr_lds[ql];
+          const float thr_pre = fmaf(thr, 2.0f, -1.0f) - 4.8e-7f;  // score > thr implies dot > thr_pre (as in the 32 x 32 form)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            constexpr int VT = NACC - NA_TILES;
+            const bool vb = h == 1 && n >= 4;
+            if (vb != (pass == 0)) continue;
+            f32x4 dots[5];
+#pragma unroll
+            for (int m = 0; m < 5; ++m) {
+              const int mr = 5 * h + m;
+              dots[m] = vb ? acc_v[((mr - 5) * 4 + (n - 4) + VT) % VT] : acc_a[(mr < 5 ? mr * 8 + n : 40 + (mr - 5) * 4 + n) % NA_TILES];
+            }
+            float top = dots[0][0];
+#pragma unroll
+            for (int m = 0; m < 5; ++m)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) top = __builtin_fmaxf(top, dots[m][r]);
+            TAVB_SB();  // one group at a time
+            const bool any = ((ABL & ~3072) == 0 || ABL == 512) && (top > thr_pre);
+            if constexpr (ABL == 512) asm volatile("" ::"s"(__builtin_amdgcn_ballot_w64(any)));
+            if constexpr ((ABL & ~3072) != 0 && ABL != 512) asm volatile("" ::"v"(top));
+            if (ABL != 512 && __builtin_amdgcn_ballot_w64(any) != 0ull) {
+              // as in the 32 x 32 form: one v_cmp per accumulator register gives a wave mask of four rows x 16 queries in an SGPR pair
+              const int64_t row_base = row0 + wm * 160 + h * 80 + 4 * (lane_e >> 4);  // + 16 m + r
+              const int64_t left64 = r_end - row_base;
+              const int rows_left = tile_full ? 80 : (int)(left64 < 80 ? left64 : 80);
+#pragma unroll
+              for (int m = 0; m < 5; ++m) {
+                float sc[4];
+                u64 mk[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  sc[j] = fmaf(dots[m][j], 0.5f, 0.5f);
+                  asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(mk[j]) : "v"(sc[j]), "v"(thr));
+                }
+                if ((mk[0] | mk[1] | mk[2] | mk[3]) == 0ull) continue;  // wave-uniform
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  const int r_off = 16 * m + j;
+                  if (mk[j] == 0ull) continue;
+                  if (((mk[j] >> lane_e) & 1ull) != 0ull && r_off < rows_left) {
+                    const int pos = lds_add_rtn(&cnt_lds[ql], 1);
+                    if (pos + 1 > CAPW - BM6) lds_store_i32(need_compact, 1);
+                    float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
+                    s1 = (s1 > 1.0f) ? 1.0f : s1;
+                    if (pos < CAPW) my_cand[(size_t)ql * CAPW + pos] = make_key(s1, (uint32_t)(row_base + r_off) + p.index_base);
+                  }
+                }
+              }
+            }
+          }
+        }
+    } else {
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass)
 #pragma unroll
@@ -768,6 +944,7 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
           }
         }
       }
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TAVB_BARRIER();
     if (*need_compact != 0) {  // workgroup-uniform: read after the barrier
@@ -1585,6 +1762,13 @@ hipError_t launch_select_band(const unsigned long long* cand, const int* counts,
   return hipGetLastError();
 }
 
+int mfma_tile_shape(const MfmaParams& p) {
+  // the 16x16x32 form exists for the 256-query filter tile (not SPLIT, not BD) and its two like-for-like ablations; everything else is 32x32x16
+  if (p.shape != 16 || p.wide_tile == 128 || p.split_plane > 0) return 32;
+  if (p.ablate != 0) return (p.ablate == 256 || p.ablate == 258) ? 16 : 32;
+  return (p.bdirect || p.sched != 0) ? 32 : 16;
+}
+
 hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream) {
   const int tile = p.wide_tile == 128 ? 128 : BN;
   if (!mfma_supported(p.dim, p.k) || p.nq_padded % tile != 0 || p.n_splits < 1) return hipErrorInvalidValue;
@@ -1640,6 +1824,13 @@ hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream) {
         case 257: return go(mfma_scan_kernel<257, 2, 6, 4, 4>, NT6, LDS128);  // neither: staging, fragment reads, barriers
         case 264: return go(mfma_scan_kernel<264, 2, 6, 4, 4>, NT6, LDS128);  // no admissions, query operand cache resident
         default: return go(mfma_scan_kernel<0, 2, 6, 4, 4>, NT6, LDS128);
+      }
+    }
+    if (mfma_tile_shape(p) == 16) {  // v_mfma_f32_16x16x32_f16: the default
+      switch (p.ablate) {
+        case 256: return go(mfma_scan_kernel<256, 4, 8, 6, 4, false, false, true>, NT6, LDS256);  // everything except admissions
+        case 258: return go(mfma_scan_kernel<258, 4, 8, 6, 4, false, false, true>, NT6, LDS256);  // no LDS-DMA, no admissions
+        default: return go(mfma_scan_kernel<0, 4, 8, 6, 4, false, false, true>, NT6, LDS256);
       }
     }
     if (p.bdirect && p.ablate == 0) return go(mfma_scan_kernel<0, 4, 4, 3, 3, false, true>, NT6, 3 * SLOT_A6 + BN * 8 + 16);  // queries in fragment-major order (query_prepare_kernel)
