@@ -132,19 +132,28 @@ def test_array_arguments_go_through_the_buffer_protocol_or_fall_back():
 
 
 def test_every_workspace_of_a_context_is_released_by_tavb_destroy():
-    """`Buffer` members of the context are freed one by one in tavb_destroy (no destructor: the device must be current): round 5 found the
-    fp16 shadow -- half an fp32 corpus' bytes -- missing from that list.  Source-level check, so that the next buffer cannot be forgotten."""
+    """`Buffer` members of the context are freed by tavb_destroy through tavb_ctx::for_each_buffer (no destructor: the device must be
+    current): round 5 found the fp16 shadow -- half an fp32 corpus' bytes -- missing from the list tavb_destroy kept by hand then.
+    Source-level check, so that the next buffer cannot be forgotten: every declared Buffer is named in for_each_buffer, and tavb_destroy
+    releases through it."""
     import re
 
-    src = open(os.path.join(ROOT, "typeagent_py_amd", "csrc", "tavb_abi.hip")).read()
+    csrc = os.path.join(ROOT, "typeagent_py_amd", "csrc")
+    hdr = open(os.path.join(csrc, "tavb_ctx.h")).read()
     names = set()
-    for m in re.finditer(r"^\s*Buffer\s+([^;]+);", src, re.M):
+    for m in re.finditer(r"^\s*Buffer\s+([^;]+);", hdr, re.M):
         for part in m.group(1).split(","):
             mm = re.match(r"\s*([dh]_[a-z_0-9]*)", part)
             if mm:
                 names.add(mm.group(1))
     assert {"d_shadow", "d_queries_pad", "h_ring", "d_gather"} <= names and len(names) >= 25
+    start = hdr.index("void for_each_buffer(F&& f) {")
+    body = hdr[start : hdr.index("\n  }\n", start)]
+    listed = set(re.findall(r"&([dh]_[a-z_0-9]+)\b", body))
+    assert names <= listed, sorted(names - listed)
+    for ring in ("h_ring", "d_ring"):  # both slots of the load path's rings
+        assert f"&{ring}[0]" in body and f"&{ring}[1]" in body
+    src = open(os.path.join(csrc, "tavb_abi.hip")).read()
     start = src.index("int tavb_destroy(tavb_ctx* c) {")
-    body = src[start : src.index("\n}\n", start)]
-    released = set(re.findall(r"c->([a-z_0-9]+)(?:\[i\])?\.release\(\)", body))
-    assert names <= released, sorted(names - released)
+    destroy = src[start : src.index("\n}\n", start)]
+    assert re.search(r"c->for_each_buffer\(\[\]\(Buffer& b\) \{ b\.release\(\); \}\)", destroy)

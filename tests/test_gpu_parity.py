@@ -875,7 +875,7 @@ def test_mfma_batch_against_oracle(n, nq, k, ms, splits):
 
 
 def _ladder_phases(rows: int, sample: int, growth: int) -> int:
-    """Phase count of the threshold ladder (tavb_abi.hip, tavb_search_device_dispatch)."""
+    """Phase count of the threshold ladder (tavb_route.hip, run_tile_ladder)."""
     sample = (sample + 255) // 256 * 256
     if sample <= 0 or rows < 8 * sample:
         return 1

@@ -1,6 +1,6 @@
 """GPU suite: the routes of the device-resident lookup, one table.
 
-`tavb_search_device_dispatch` (csrc/tavb_abi.hip) picks one of about ten routes for a batch: the grouped streaming scan, the streaming tiers
+`tavb_search_device_dispatch` (csrc/tavb_route.hip) picks one of about ten routes for a batch: the grouped streaming scan, the streaming tiers
 1-3 (8 queries per pass, 4 beyond k = 64), the 32/64-query tile (over the fp32 rows, or over the fp16 shadow of an fp32 corpus), the 128/256-query
 tile with rescoring (fp16 rows, the fp32 shadow, the zero-padded copy of odd widths) and its exact fallbacks (the 64-query exact tile, the
 split-plane form, for fp32 beyond k = 64 a re-run on the streaming kernels).  Every entry of ROUTES names the options that force one of them and

@@ -1,0 +1,226 @@
+// Row-sharded corpora: the RCCL binding of libtavb.so -- tavb_comm_*, tavb_search_allgather, tavb_allgather_merge.  The only file that
+// includes RCCL's header (the context holds the communicator as an opaque pointer).  Host code only.
+
+#include <dlfcn.h>
+#include <rccl/rccl.h>  // types and prototypes only: the functions are resolved with dlsym (tavb_comm_init)
+
+#include <chrono>
+#include <mutex>
+#include <thread>
+
+#include "tavb_ctx.h"
+
+using namespace tavb::host;
+
+// ---- RCCL (resolved at run time: libtavb.so has no link-time dependency on librccl) -------------------------------------------
+namespace {
+ncclComm_t comm_of(const tavb_ctx* c) { return static_cast<ncclComm_t>(c->comm); }
+
+struct Rccl {
+  void* handle = nullptr;
+  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
+  decltype(&ncclCommInitRank) CommInitRank = nullptr;
+  decltype(&ncclCommDestroy) CommDestroy = nullptr;
+  decltype(&ncclCommAbort) CommAbort = nullptr;  // (optional: only the timeout path needs it)
+  decltype(&ncclAllGather) AllGather = nullptr;
+  decltype(&ncclGetErrorString) GetErrorString = nullptr;
+};
+Rccl g_rccl;
+std::once_flag g_rccl_once;
+std::string g_rccl_error;
+
+int load_rccl() {
+  std::call_once(g_rccl_once, [] {
+    // the copy the process already has (torch ships one with the same SONAME) before a fresh one from the ROCm tree
+    const char* names[] = {"librccl.so.1", "librccl.so"};
+    for (const char* n : names)
+      if (!g_rccl.handle) g_rccl.handle = dlopen(n, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);
+    for (const char* n : names)
+      if (!g_rccl.handle) g_rccl.handle = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
+    if (!g_rccl.handle) {
+      const char* e = dlerror();
+      g_rccl_error = std::string("cannot load librccl.so.1: ") + (e ? e : "not found");
+      return;
+    }
+    g_rccl.GetUniqueId = reinterpret_cast<decltype(g_rccl.GetUniqueId)>(dlsym(g_rccl.handle, "ncclGetUniqueId"));
+    g_rccl.CommInitRank = reinterpret_cast<decltype(g_rccl.CommInitRank)>(dlsym(g_rccl.handle, "ncclCommInitRank"));
+    g_rccl.CommDestroy = reinterpret_cast<decltype(g_rccl.CommDestroy)>(dlsym(g_rccl.handle, "ncclCommDestroy"));
+    g_rccl.CommAbort = reinterpret_cast<decltype(g_rccl.CommAbort)>(dlsym(g_rccl.handle, "ncclCommAbort"));
+    g_rccl.AllGather = reinterpret_cast<decltype(g_rccl.AllGather)>(dlsym(g_rccl.handle, "ncclAllGather"));
+    g_rccl.GetErrorString = reinterpret_cast<decltype(g_rccl.GetErrorString)>(dlsym(g_rccl.handle, "ncclGetErrorString"));
+    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.CommDestroy || !g_rccl.AllGather || !g_rccl.GetErrorString)
+      g_rccl_error = "librccl.so.1 lacks one of ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather / ncclGetErrorString";
+  });
+  if (!g_rccl_error.empty()) return fail(TAVB_E_UNSUPPORTED, "%s", g_rccl_error.c_str());
+  return TAVB_OK;
+}
+static_assert(TAVB_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "the rendezvous id is RCCL's");
+
+#define TAVB_RCCL(expr)                                                                                             \
+  do {                                                                                                              \
+    ncclResult_t r__ = (expr);                                                                                      \
+    if (r__ != ncclSuccess) return fail(TAVB_E_HIP, "%s failed: %s (%s:%d)", #expr, g_rccl.GetErrorString(r__), __FILE__, __LINE__); \
+  } while (0)
+
+}  // namespace
+
+// tavb_synchronize with an exchange in flight and "comm_timeout_ms" set: polls the stream; when the deadline passes (a peer never joined the
+// all-gather, or died in it) the communicator is ABORTED -- ncclCommAbort makes the collective's kernel return, so the stream drains -- and the
+// context is left without one (tavb_comm_init again to rejoin): TAVB_E_TIMEOUT, never a process stuck in a collective for ever.
+int tavb::host::comm_wait_or_abort(tavb_ctx* c) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const auto deadline = t0 + std::chrono::milliseconds(c->comm_timeout_ms);
+  int polls = 0;
+  for (;;) {
+    const hipError_t e = hipStreamQuery(c->stream);
+    if (e == hipSuccess) {
+      c->comm_inflight = false;
+      return TAVB_OK;
+    }
+    if (e != hipErrorNotReady) return fail(TAVB_E_HIP, "hipStreamQuery failed: %s", hipGetErrorString(e));
+    if (std::chrono::steady_clock::now() >= deadline) break;
+    if (++polls > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));  // (the first polls spin: a lookup of a small shard is that short)
+  }
+  ncclComm_t comm = comm_of(c);
+  c->comm = nullptr;
+  c->comm_rank = 0;
+  c->comm_world = 1;
+  c->comm_inflight = false;
+  const long long waited = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
+  if (g_rccl.CommAbort) (void)g_rccl.CommAbort(comm);
+  (void)hipStreamSynchronize(c->stream);  // (drains once the aborted collective has let go of the stream)
+  return fail(TAVB_E_TIMEOUT, "the exchange did not complete within %lld ms (option comm_timeout_ms): a peer never joined the all-gather; "
+              "the communicator was aborted -- tavb_comm_init to rejoin", waited);
+}
+
+extern "C" {
+
+int tavb_comm_unique_id(void* out_id) {
+  if (!out_id) return fail(TAVB_E_INVALID, "null out_id");
+  if (int rc = load_rccl()) return rc;
+  ncclUniqueId id;
+  TAVB_RCCL(g_rccl.GetUniqueId(&id));
+  memcpy(out_id, id.internal, TAVB_COMM_ID_BYTES);
+  return TAVB_OK;
+}
+
+int tavb_comm_init(tavb_ctx* c, const void* id_bytes, int32_t rank, int32_t world) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!id_bytes) return fail(TAVB_E_INVALID, "null id");
+  if (world < 1 || rank < 0 || rank >= world) return fail(TAVB_E_INVALID, "rank %d out of range for world %d", rank, world);
+  if (c->comm) return fail(TAVB_E_INVALID, "this context already has a communicator (tavb_comm_destroy first)");
+  if (int rc = load_rccl()) return rc;
+  DeviceGuard guard(c->device);
+  ncclUniqueId id;
+  memcpy(id.internal, id_bytes, TAVB_COMM_ID_BYTES);
+  // the exchange buffers come first: a rank that cannot have them fails HERE, in a collective every rank is still free to fail in, and no
+  // exchange of up to comm_reserve_keys keys allocates anything afterwards (8 MiB + world x 8 MiB at the default)
+  if (int rc = c->d_xlocal.reserve((size_t)c->comm_reserve_keys * sizeof(u64_t))) return rc;
+  if (int rc = c->d_gather.reserve((size_t)c->comm_reserve_keys * sizeof(u64_t) * world)) return rc;
+  ncclComm_t comm = nullptr;
+  TAVB_RCCL(g_rccl.CommInitRank(&comm, world, id, rank));
+  c->comm = comm;
+  c->comm_rank = rank;
+  c->comm_world = world;
+  c->comm_inflight = false;
+  return TAVB_OK;
+}
+
+int tavb_comm_destroy(tavb_ctx* c) {
+  if (!c || !c->comm) return TAVB_OK;
+  DeviceGuard guard(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  ncclComm_t comm = comm_of(c);
+  c->comm = nullptr;
+  c->comm_rank = 0;
+  c->comm_world = 1;
+  if (g_rccl.CommDestroy) TAVB_RCCL(g_rccl.CommDestroy(comm));
+  return TAVB_OK;
+}
+
+// local [nq, k] lists (device; nullptr = this rank FAILED: it sends TAVB_KEY_PEER_FAILED in every slot) -> ncclAllGather on the context's
+// stream -> merge kernel -> out_keys [nq, k].  Nothing here allocates: the lists travel through the buffers tavb_comm_init reserved, in chunks
+// of whole queries when they hold more than comm_reserve_keys keys (every rank makes the same call, so every rank cuts the same chunks).
+static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32_t k, tavb_key* out_keys) {
+  const int64_t reserve_keys = (int64_t)(c->d_xlocal.cap / sizeof(u64_t));
+  const int qc = (int)std::min<int64_t>(nq, std::max<int64_t>(1, reserve_keys / k));  // queries per chunk
+  if ((size_t)qc * k * sizeof(u64_t) * c->comm_world > c->d_gather.cap || (size_t)qc * k * sizeof(u64_t) > c->d_xlocal.cap)
+    return fail(TAVB_E_INVALID, "the exchange buffers of this communicator are gone (tavb_comm_init reserves them)");
+  u64_t* gathered = reinterpret_cast<u64_t*>(c->d_gather.ptr);
+  if (!local) (void)hipMemsetAsync(c->d_xlocal.ptr, 0xFF, (size_t)qc * k * sizeof(u64_t), c->stream);
+  if (c->comm_stall_ms > 0) {  // fault injection: one shot
+    (void)tavb::launch_stall((int)c->comm_stall_ms, c->stream);
+    c->comm_stall_ms = 0;
+  }
+  c->comm_inflight = true;
+  for (int q0 = 0; q0 < nq; q0 += qc) {
+    const int qn = std::min(qc, nq - q0);
+    const u64_t* src = local ? local + (size_t)q0 * k : reinterpret_cast<const u64_t*>(c->d_xlocal.ptr);
+    {
+      Timed t(c, TAVB_KERNEL_EXCHANGE);
+      TAVB_RCCL(g_rccl.AllGather(src, gathered, (size_t)qn * k, ncclUint64, comm_of(c), c->stream));
+    }
+    Timed t(c, TAVB_KERNEL_MERGE);
+    hipError_t e = tavb::launch_merge(gathered, c->comm_world, qn, k, /*query_major=*/false, reinterpret_cast<u64_t*>(out_keys) + (size_t)q0 * k, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "merge launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+int tavb_search_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, float min_score, tavb_key* out_keys) {
+  // argument errors every rank makes alike (the ranks make the same call) return at once ...
+  if (int rc = check_ctx(c)) return rc;
+  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
+  if (k > TAVB_MAX_FUSED_K)
+    return fail(TAVB_E_UNSUPPORTED, "k=%d exceeds the fused-select limit %d; page with tavb_search_after / tavb_search_subset_after", k, TAVB_MAX_FUSED_K);
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (!dev_queries || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (!c->comm || (c->comm_world == 1 && !c->comm_force)) return tavb_search_device(c, dev_queries, nq, k, min_score, out_keys);
+  DeviceGuard guard(c->device);
+  // ... everything that can fail on ONE rank -- the state of its shard, an allocation, a launch -- still joins the collectives, with
+  // TAVB_KEY_PEER_FAILED lists, so that the peers are never left waiting in ncclAllGather for a rank that has returned an error to its caller.
+  // Lists of up to comm_reserve_keys keys live in the buffer tavb_comm_init reserved: no allocation between here and the all-gather.
+  const size_t list_keys = (size_t)nq * k;
+  int rc_local = TAVB_OK;
+  u64_t* local = nullptr;
+  if ((rc_local = require_corpus(c)) != TAVB_OK) {
+  } else if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    rc_local = fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  else if (list_keys * sizeof(u64_t) <= c->d_xlocal.cap) local = reinterpret_cast<u64_t*>(c->d_xlocal.ptr);
+  else if (c->comm_fail_alloc) rc_local = fail(TAVB_E_NOMEM, "injected failure of the list allocation (option comm_fail_alloc)");
+  else if ((rc_local = c->d_local.reserve(list_keys * sizeof(u64_t))) == TAVB_OK) local = reinterpret_cast<u64_t*>(c->d_local.ptr);
+  std::vector<float> ms((size_t)nq, min_score);
+  if (rc_local != TAVB_OK) {
+  } else if (c->comm_fail_rank >= 0 && c->comm_fail_rank == c->comm_rank) {  // fault injection (option "comm_fail_rank"): what a failed launch / allocation inside the local search looks like
+    rc_local = fail(TAVB_E_HIP, "injected failure of the local search on rank %d (option comm_fail_rank)", c->comm_rank);
+  } else if (c->rows == 0) {  // an empty shard still takes part in the collectives
+    const hipError_t e = hipMemsetAsync(local, 0, list_keys * sizeof(u64_t), c->stream);
+    if (e != hipSuccess) rc_local = fail(TAVB_E_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+  } else {
+    rc_local = tavb_search_device_dispatch(c, dev_queries, nq, k, ms.data(), (uint32_t)c->ordinal_base, local);
+  }
+  // a failed rank's lists = TAVB_KEY_PEER_FAILED (all bits set) in every slot: it sorts above every real key, so it leads every merged list on
+  // EVERY rank -- the peers' answers would silently miss this shard otherwise; tavb_decode_keys turns it into TAVB_E_PEER
+  const std::string local_error = rc_local != TAVB_OK ? g_last_error : std::string();
+  const int rc_x = exchange_and_merge(c, rc_local == TAVB_OK ? local : nullptr, nq, k, out_keys);
+  if (rc_local != TAVB_OK) {
+    g_last_error = local_error;
+    return rc_local;
+  }
+  return rc_x;
+}
+
+int tavb_allgather_merge(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  if (nq < 1 || k < 1 || k > TAVB_MAX_FUSED_K) return fail(TAVB_E_INVALID, "bad list shape");
+  if (!dev_local_keys || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  if (!c->comm || (c->comm_world == 1 && !c->comm_force)) {
+    if (reinterpret_cast<const void*>(dev_local_keys) != reinterpret_cast<const void*>(out_keys))
+      TAVB_HIP(hipMemcpyAsync(out_keys, dev_local_keys, (size_t)nq * k * sizeof(u64_t), hipMemcpyDefault, c->stream));
+    return TAVB_OK;
+  }
+  return exchange_and_merge(c, reinterpret_cast<const u64_t*>(dev_local_keys), nq, k, out_keys);
+}
+
+}  // extern "C"

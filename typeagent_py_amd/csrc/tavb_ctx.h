@@ -1,0 +1,348 @@
+// What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the lookups), tavb_route.hip
+// (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the context itself and the internal
+// functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
+// tavb_search_device_dispatch lives in tavb::host, whose symbols stay inside the library.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tavb_internal.h"
+
+typedef unsigned long long u64_t;
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+
+extern thread_local std::string g_last_error;  // what tavb_last_error returns (tavb_abi.hip)
+int fail(int code, const char* fmt, ...);      // sets it, returns `code`
+
+#define TAVB_HIP(expr)                                                                                     \
+  do {                                                                                                     \
+    hipError_t e__ = (expr);                                                                               \
+    if (e__ != hipSuccess)                                                                                 \
+      return ::tavb::host::fail(TAVB_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+  } while (0)
+
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// bumped by every (re)allocation or release of a workspace: captured HIP graphs hold raw pointers into these buffers
+extern std::atomic<unsigned long long> g_alloc_epoch;  // (contexts on several threads share it; tavb_abi.hip)
+
+struct Buffer {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  bool pinned_host = false;
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return TAVB_OK;
+    size_t want = std::max(bytes, cap * 2);
+    want = (want + 255) & ~(size_t)255;
+    ++g_alloc_epoch;
+    if (ptr) {
+      hipError_t e = pinned_host ? hipHostFree(ptr) : hipFree(ptr);
+      ptr = nullptr;
+      cap = 0;
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "free of workspace failed: %s", hipGetErrorString(e));
+    }
+    hipError_t e = pinned_host ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : hipMalloc(&ptr, want);
+    if (e != hipSuccess) {
+      ptr = nullptr;
+      return fail(TAVB_E_NOMEM, "workspace allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
+    }
+    cap = want;
+    return TAVB_OK;
+  }
+  void release() {
+    if (ptr) ++g_alloc_epoch;
+    if (ptr) (void)(pinned_host ? hipHostFree(ptr) : hipFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+  }
+};
+
+struct PendingTiming {
+  int kernel;
+  hipEvent_t start, stop;
+};
+
+}  // namespace host
+}  // namespace tavb
+
+struct tavb_ctx {
+  using Buffer = tavb::host::Buffer;
+  using PendingTiming = tavb::host::PendingTiming;
+
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int n_cu = 256;
+
+  const void* corpus = nullptr;
+  int64_t rows = 0;
+  int32_t dim = 0;
+  int32_t dtype = TAVB_F32;
+  int64_t ordinal_base = 0;
+
+  tavb::ScanGeometry geom{0, 16, 2, 1, 0, 0};
+  int64_t mfma_min_batch = 65;  // batches from this size up use the 128/256-query tile + rescoring (smaller ones the 32/64-query tile) ...
+  // ... and on corpora of `mfma_big_bytes` (256 MiB) or more already from `mfma_min_batch_big` = 33 queries (round 5): padded to 128 queries the wide
+  // tile serves 33 / 48 / 64 queries over 10M fp16 rows in 5.42 / 5.48 / 5.46 ms against 5.54 / 5.81 / 5.91 ms on the 64-query split-plane tile,
+  // and 64 queries over 1M fp32 rows (through the fp16 shadow) in 0.85 ms against 2.17 ms (profiles/r05_raw/b64.txt).  On small corpora its ~40
+  // launches per batch cost more than the 64-query tile's pass.
+  int64_t mfma_min_batch_big = 33;
+  int64_t mfma_big_bytes = (int64_t)256 << 20;
+  // ... and on FP32 corpora of `mfma_big_bytes_f32` (2 GiB) or more from `mfma_min_batch_big_f32` = 5 queries (round 6): the wide tile streams the fp16
+  // shadow -- half the bytes of the fp32 rows the 32-query fp32 tile reads -- and its candidates are rescored with the fp32 rows: 5 / 8 / 16 / 32
+  // queries over 1M x 1536 fp32 rows in 0.76 / 0.77 / 0.78 / 0.79 ms against 1.14 / 1.16 / 1.21 / 1.24 ms (profiles/r06_raw/f32_mid.txt); 32 queries
+  // over 700k / 400k / 200k / 100k rows: 0.64 / 0.48 / 0.36 / 0.53 ms against 0.95 / 0.61 / 0.40 / 0.22 (f32_few.txt: the wide path's ~0.35 ms of
+  // selection and rescoring launches against half a pass).  Batches of 2 .. 4 queries (one pass of the fp32 streaming scan) from TWICE that size:
+  // 1M rows 0.77 against 0.92 .. 0.97 ms, 700k rows 0.64 against 0.68, 400k rows 0.48 against 0.39.  Single queries keep the fp32 scan (option
+  // f32_shadow = 2 moves them too).  Needs the shadow (f32_shadow >= 1: +50 % device memory, built on first use); without the memory for it the fp32
+  // kernels serve the batch.
+  // End of round 6 (tools/regime_sweep.py, profiles/r06_raw/regime_sweep_before.md, after the wide path's launch diet): 5+ queries from 1e9 bytes
+  // (165k x 1536 rows: 0.26 ms through the shadow against 0.27 .. 0.33 on the fp32 tile, whose workgroups start compacting with their second
+  // tile; at 120k rows the fp32 tile still wins, 0.17 .. 0.21 against 0.24), 2 .. 4 queries from 4 GiB as before (500k rows: 0.45 either way),
+  // and 33+ queries at ANY size (`mfma_min_batch_f32`): one tile of the 64-query fp32 kernel is 82 us of fp32 matrix work however small the
+  // corpus -- 64 queries over 1000 / 5000 / 20000 fp32 rows 0.189 / 0.202 / 0.204 ms against 0.087 / 0.112 / 0.140 for 65 queries on the wide tile.
+  int64_t mfma_min_batch_big_f32 = 5;
+  int64_t mfma_big_bytes_f32 = 1000000000;
+  int64_t mfma_few_bytes_f32 = (int64_t)4 << 30;
+  int64_t mfma_min_batch_f32 = 33;
+  int64_t mfma_splits = 0;  // 0 = auto
+  int64_t mfma_ablate = 0;
+  int64_t mfma_sched = 0;
+  int64_t mfma_tile = 0;  // 0 = auto (128 queries per tile up to 128 queries, else 256)
+  int64_t mfma_sample_rows = 0;  // rows of the first (threshold-seeding) phase: 0 = auto (two tiles per workgroup), -1 = one phase, no seeding
+  int64_t skinny_min_batch_f32 = 5;   // fp32 corpus: batches from this size up use the 32-query MFMA tile
+  int64_t skinny_min_batch_f16 = 3;   // fp16 corpus: batches from this size up to mfma_min_batch - 1 use it
+  int64_t mfma_ladder = 4;            // each further phase scans this many times the rows scanned so far (0 = seed once)
+
+  Buffer d_queries, d_queries_f16, d_lists, d_out, d_rows, d_cand, d_thr, d_sample_keys;
+  Buffer d_counts;  // 256-query tile: keys left per candidate buffer
+  Buffer d_delta, d_approx, d_flag, d_fb_queries, d_norm;  // exact rescoring of the 256-query tile (tavb_rescore.hip)
+  Buffer d_minscores;      // per-query thresholds of a batch on the device: [nq_pad] min_scores, then [nq_pad] exclusive admission floors (the tile paths)
+  Buffer d_fb_cand;        // what the 64-query exact tile ranked highest for the flagged queries: [slots][64] keys, rescored into the callers' rows
+  Buffer d_shadow;         // fp32 corpora (and fp16 ones whose width is not a multiple of 64): fp16 copy of rows [0, norm_rows), each padded with zeros to a
+                           // multiple of 64 halves -- the filter operand of the 128/256-query tile
+  Buffer d_queries_pad;    // the queries of a batch zero-padded to that width (odd widths only)
+  int64_t f32_shadow = 1;  // option: 1 = batches of mfma_min_batch+ queries on fp32 corpora go through that shadow (+50 % HBM); 2 = every lookup on
+                           // fp32 corpora of f32_shadow_min_bytes and more (half the bytes per pass); 0 = never
+  int64_t f32_shadow_min_bytes = (int64_t)2 << 30;  // level 2 only: fp32 corpora from this size up (below it the extra launches cost more than half a pass saves)
+  int last_shadow = 0;     // the last lookup's filter pass read the shadow
+  Buffer d_accept, d_bits;  // message re-rank: accepted message ordinals, their bitmap
+  Buffer d_emit;            // survivors of tavb_search_all: a counter, then the keys
+  // large-k lookups (tavb_search_topk, tavb_topk.hip): the dense score array of a group of queries and the workspace of the selection
+  Buffer d_topk_scores, d_topk;
+  int64_t large_k = 1;                       // option: 1 = the binding routes TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K through tavb_search_topk
+  int64_t topk_buckets = 1024;               // option: histogram buckets of the score pass
+  int64_t topk_boundary_keys = 16384;        // option: capacity of a query's boundary list (more keys in the boundary bucket: refinement)
+  int64_t topk_scores_bytes = (int64_t)1 << 30;  // option: most bytes of one group's score array (queries per corpus pass are cut to fit)
+  int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
+  // sorted lookups (tavb_search_sorted: every survivor, or any k): the keys of one query at or above its boundary, then their sort
+  // (tavb_sort.hip); the decoded results leave through h_out in pieces of at most sort_stage_keys
+  Buffer d_sort_keys, d_sort_ws;
+  Buffer h_sort_info{nullptr, 0, true};  // pinned: meta [nq][4] + per-block key counts [nq][blocks] of one group
+  int64_t sort_all = 1;                   // option: 1 = the binding routes max_hits == 0 and max_hits > TAVB_MAX_LARGE_K through tavb_search_sorted
+  int64_t sort_stage_keys = (int64_t)1 << 21;  // option: most results decoded into pinned memory before they are copied to the caller (12 B each)
+  int64_t sort_small_keys = 16384;        // option: sorts of up to this many keys run in one workgroup (0 .. tavb::kSortSmallMax); faster than
+                                          // the multi-pass sort at every size up to the LDS limit (16384: 0.145 against 0.192 ms, profiles/r08_sort_all.md)
+  // load path (tavb_upload_rows): two pinned staging slots + two device scratch slots, recycled through events
+  Buffer h_ring[2] = {{nullptr, 0, true}, {nullptr, 0, true}};
+  Buffer d_ring[2];
+  hipEvent_t ring_done[2] = {nullptr, nullptr};
+  const int32_t* row_to_msg = nullptr;  // borrowed device map chunk row -> message ordinal
+  int64_t row_to_msg_rows = 0, n_messages = 0;
+  int64_t norm_rows = 0;  // rows of the corpus covered by the cached row-norm maxima (d_norm) -- and, for fp32 corpora, by the fp16 shadow
+  Buffer h_stage{nullptr, 0, true};
+  Buffer h_out{nullptr, 0, true};  // pinned + device-visible: the last kernel of a synchronous lookup writes its keys straight here
+  Buffer h_lists{nullptr, 0, true};  // pinned + device-visible: per-workgroup lists of a small single-query lookup (merged on the host)
+  Buffer h_flag{nullptr, 0, true};   // pinned: the work list of flagged queries read back by the one route that needs a host round trip (fp32 corpus, k > 64)
+  int64_t mfma_shape = 16;      // option: MFMA of the 256-query filter tile, 16 = v_mfma_f32_16x16x32_f16, 32 = v_mfma_f32_32x32x16_f16 (profiles/r09_mfma_shape.md)
+  int64_t last_mfma_shape = 0;  // option "last_mfma_shape" (get): the MFMA shape the last filter launch of the 128/256-query tile ran on (0: none yet)
+  int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
+  int64_t band_max = tavb::kBandMax;  // option: keys of a query's band the wide tile's selection hands to the rescoring (256 .. kBandMax); a band that does not fit flags the query
+  int64_t early_exact = 1;    // option: ... and a batch found to be mostly such queries BEFORE the last filter phase skips that phase (needs wide_fallback)
+  int64_t wide_fallback = 1;  // option: batches of 256+ queries re-run MANY (> 64) flagged queries on the 256-query tile's exact (split-plane) form
+  int64_t small_direct_bytes = (int64_t)128 << 20;  // option: single-query lookups on corpora up to this size take the one-launch path (0 = never)
+  int64_t small_direct_keys = 8192;                 // option: most keys the per-workgroup lists of such a lookup may hold (the grid is cut to fit; x 2 for a batch of 2 .. 8 queries)
+  int64_t last_direct = 0;                          // option "last_direct" (get): 1 when the last lookup took it, 2 = with the query inside the kernel arguments
+  int64_t inline_query = 1;                         // option: 1536-wide single queries of that path ride in the kernel arguments (no H2D copy before the launch)
+  // the GROUPED form of that path (ScanParams::group): batches of 2 .. direct_group_max_nq queries in one launch of gridDim.y query groups
+  int64_t direct_group_max_nq = TAVB_MAX_GROUPED_QUERIES;  // option: biggest batch that may take it (0 / 1 = never: batches of up to 8 keep the plain form, bigger ones the tiles)
+  int64_t direct_group = 0;                         // option: queries per group, 1 / 2 / 4 / 8, taken whatever the cost model says (0 = plan_direct_group)
+  int64_t direct_group_wgs = 0;                     // option: most workgroups of such a launch (row workgroups x groups); 0 = plan_direct_group (256 or 512)
+  bool dispatch_no_group = false;                   // set by tavb_search_batch around its fall-through: the host-synchronous cost model already said no
+  int64_t direct_group_keys = 32768;                // option: most keys the lists of such a launch may hold (nq x workgroups-per-group x k; 256 KiB over PCIe)
+
+  bool profiling = false;
+  double total_ms[TAVB_KERNEL_COUNT] = {0};
+  int64_t launches[TAVB_KERNEL_COUNT] = {0};
+  std::vector<PendingTiming> pending;
+  std::vector<hipEvent_t> free_events;
+
+  int last_tier = 0;
+  int pending_nq = 0, pending_k = 0;  // shape of the lookup enqueued by tavb_search_begin
+
+  // small corpora (the reference's own scale: 10k x 1536, 41 us per call as three submissions): the H2D copy of the query, the scan and the merge
+  // of a single-query lookup replayed as ONE captured HIP graph.  A few (corpus, k, min_score) shapes are kept.  OFF by default: measured on
+  // MI355X / ROCm 7.2 (profiles/r03_latency_cfg1.md) the replay takes 48.3 us against 41.3 us for the three plain submissions -- hipGraphLaunch
+  // costs more than it saves for a 3-node graph; the GPU-side floor of the lookup is the two kernels (scan 14.8 us + merge 11.8 us).
+  struct SmallGraph {
+    const void* corpus = nullptr;
+    int64_t rows = 0;
+    int32_t dim = 0, dtype = 0, k = 0;
+    uint32_t thr_bits = 0;
+    unsigned long long epoch = 0, geom_tag = 0;
+    hipGraphExec_t exec = nullptr;
+    int seen = 0;  // calls with this shape so far (the first one runs un-captured: it sizes the workspaces)
+    unsigned long long last_used = 0;
+  };
+  SmallGraph graphs[4];
+  unsigned long long graph_clock = 0;
+  int64_t graph_max_bytes = 0;  // option "graph_max_bytes": single-query lookups on corpora up to this size replay a graph (0 = never, the default)
+  int64_t last_graph = 0;                          // option "last_graph" (get): 1 when the last lookup was a graph replay
+
+  // row-sharded corpora: this context's RCCL communicator (tavb_comm_init) and the buffers of the exchange
+  void* comm = nullptr;  // an ncclComm_t: only tavb_comm.hip includes RCCL's header
+  int comm_rank = 0, comm_world = 1;
+  int64_t comm_force = 0;  // option: run the all-gather + merge even in a world of one (tests, dry runs of the N > 1 path)
+  int64_t comm_fail_rank = -1;  // option (fault injection): the local search of tavb_search_allgather "fails" on this rank of the communicator
+  int64_t comm_fail_alloc = 0;  // option (fault injection): the per-call allocations of tavb_search_allgather "fail" (lists beyond comm_reserve_keys)
+  int64_t comm_stall_ms = 0;    // option (fault injection): the next exchange is held up on the stream for this long, as by a peer that is late
+  int64_t comm_timeout_ms = 0;  // option: tavb_synchronize gives an exchange in flight this long before it aborts the communicator (0 = wait for ever)
+  // keys of the exchange buffers reserved by tavb_comm_init (d_xlocal: that many, d_gather: x world): an exchange of up to that many keys per
+  // rank allocates NOTHING between entering the call and ncclAllGather; a bigger one goes through the same buffers in chunks of whole queries
+  int64_t comm_reserve_keys = (int64_t)1 << 20;
+  bool comm_inflight = false;   // an exchange was enqueued since the last successful tavb_synchronize
+  Buffer d_local;   // this shard's [nq, k] lists when they do not fit d_xlocal
+  Buffer d_xlocal;  // this shard's lists of an exchange up to comm_reserve_keys keys; the TAVB_KEY_PEER_FAILED lists of a rank that failed
+  Buffer d_gather;  // the all-gathered [world][chunk queries][k]
+
+  // EVERY Buffer declared above, once: tavb_destroy releases through this, so a workspace that is listed here cannot be left behind (round 5
+  // found the fp16 shadow -- half an fp32 corpus' bytes -- missing from the list tavb_destroy then kept by hand).
+  // tests/test_abi_symbols.py checks the declarations against this body.
+  template <class F>
+  void for_each_buffer(F&& f) {
+    for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
+                      &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk,
+                      &d_sort_keys, &d_sort_ws, &h_sort_info, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
+                      &d_local, &d_xlocal, &d_gather})
+      f(*b);
+  }
+};
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+
+struct Timed {
+  tavb_ctx* c;
+  int kernel;
+  hipEvent_t a = nullptr, b = nullptr;
+  Timed(tavb_ctx* ctx, int k) : c(ctx), kernel(k) {
+    if (!c->profiling) return;
+    auto get = [&](hipEvent_t* ev) {
+      if (!c->free_events.empty()) {
+        *ev = c->free_events.back();
+        c->free_events.pop_back();
+        return true;
+      }
+      return hipEventCreate(ev) == hipSuccess;
+    };
+    if (get(&a) && get(&b)) {
+      (void)hipEventRecord(a, c->stream);
+    } else {
+      a = b = nullptr;
+    }
+  }
+  ~Timed() {
+    if (!a) return;
+    (void)hipEventRecord(b, c->stream);
+    c->pending.push_back({kernel, a, b});
+  }
+};
+
+int drain_timings(tavb_ctx* c);                                // tavb_abi.hip
+void parallel_copy(void* dst, const void* src, size_t bytes);  // tavb_abi.hip: host -> pinned, on a few threads when it is worth them
+
+inline int check_ctx(const tavb_ctx* c) {
+  if (!c) return fail(TAVB_E_INVALID, "null context");
+  return TAVB_OK;
+}
+
+// after check_ctx, by every lookup that reads the corpus
+inline int require_corpus(const tavb_ctx* c) {
+  if (c->dim <= 0 || (!c->corpus && c->rows != 0)) return fail(TAVB_E_NO_CORPUS, "no corpus set (call tavb_set_corpus first)");
+  return TAVB_OK;
+}
+
+inline u64_t host_key(float score, uint32_t index) {
+  uint32_t bits;
+  memcpy(&bits, &score, sizeof bits);
+  return ((u64_t)bits << 32) | (u64_t)(0xFFFFFFFFu - index);
+}
+
+// key -> (position + base, score)
+inline void decode_key(u64_t key, int64_t base, int64_t* ordinal, float* score) {
+  const uint32_t hi = (uint32_t)(key >> 32), lo = (uint32_t)key;
+  memcpy(score, &hi, sizeof *score);
+  *ordinal = (int64_t)(0xFFFFFFFFu - lo) + base;
+}
+
+inline void decode(const u64_t* keys, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts) {
+  for (int q = 0; q < nq; ++q) {
+    int m = 0;
+    for (int i = 0; i < k; ++i) {
+      const u64_t key = keys[(size_t)q * k + i];
+      if (key == 0) break;  // lists are sorted: the first empty slot ends the list
+      decode_key(key, base, &ordinals[(size_t)q * k + i], &scores[(size_t)q * k + i]);
+      ++m;
+    }
+    counts[q] = m;
+  }
+}
+
+// ---- tavb_route.hip
+// the context's scan geometry with `waves` brought into 1 .. 16 (`blocks` is the caller's to set)
+tavb::ScanGeometry clamped_geometry(const tavb_ctx* c);
+int scan_blocks_for(const tavb_ctx* c, int64_t n_pos, int waves, int unroll);
+// The arguments of a streaming-scan launch over the context's corpus: `nq` queries at d_q, n_pos positions (d_rows: a subset's rows, or
+// null), per-workgroup lists at `lists` (null where the launch writes none).  min_score[0 .. fill) = the queries' thresholds, then +inf;
+// the slots from `fill` on stay zero (TAVB_MAX_GROUPED_QUERIES in the one-launch and score-pass forms, TAVB_MAX_STREAM_QUERIES elsewhere).
+// `group` and the topk_* members are left zero for the caller.
+tavb::ScanParams scan_params(const tavb_ctx* c, const float* d_q, const int32_t* d_rows, int64_t n_pos, int nq, int k, uint32_t index_base,
+                             u64_t key_bound, u64_t* lists, const float* min_scores /*host, nq*/, int fill);
+struct DirectGroupPlan {
+  int group;   // queries per group
+  int blocks;  // row workgroups per group
+  bool worth;  // predicted faster than the other routes (or forced by the `direct_group` option)
+};
+DirectGroupPlan plan_direct_group(const tavb_ctx* c, int nq, int k, int full_blocks, bool host);
+// Core: queries on device (f32 [nq, dim]) -> sorted key lists d_out [nq, k] (async on the stream).
+int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_row_ids, int64_t n_pos,
+                       uint32_t index_base, u64_t* d_out, u64_t key_bound = ~0ull);
+
+// ---- tavb_comm.hip
+int comm_wait_or_abort(tavb_ctx* c);
+
+}  // namespace host
+}  // namespace tavb
+
+// tavb_route.hip.  Not part of the public ABI.
+int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, uint32_t index_base, u64_t* d_out);

@@ -26,7 +26,7 @@
 //     BAND (`compact_to_band`: the k-th best score by bisection on the score bits, no sort; everything within 2 delta_q below it
 //     stays) and the threshold rises to the band's cut.  At the end of a launch the buffers are left as they are;
 //     `select_band_kernel` (one workgroup per QUERY) picks the band over all row ranges and derives the next admission threshold.
-//   * the host scans the corpus in phases of growing size (threshold ladder, tavb_abi.hip): the k-th best score after a
+//   * the host scans the corpus in phases of growing size (threshold ladder, tavb_route.hip): the k-th best score after a
 //     phase seeds the admission thresholds of the next (`thr_in`).
 //
 // Two kernel families live here: the 256-query fp16 tile described above and, at the end of the file, a 32/64-query tile
@@ -78,7 +78,7 @@ struct MfmaDeviceParams {
   int32_t active_max;
   int64_t split_plane;  // 256-query tile, SPLIT form: bytes from the high to the low plane of the queries ([2][nq_padded][dim] fp16); 0 otherwise
   const int* gate;      // optional device-side counter: the whole launch returns at once when *gate > gate_max (a filter phase of a batch already known to need
-  int32_t gate_max;     // the exact form: tavb_abi.hip::run_tile_ladder)
+  int32_t gate_max;     // the exact form: tavb_route.hip::run_tile_ladder)
   const float* band;    // 128/256-query tile, optional [nq_padded]: keep every key within band[q] below the k-th best (band selection)
   unsigned* lost;       // ... [nq_padded]: atomicMax of the score bits below which a query LOST band rows (a band that did not fit a buffer)
 };

@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(256) query_prepare_kernel(const float* __restr
 //   * SLOT mode (slot_query != nullptr): the workgroup serves slot blockIdx.x of the device-side work list of flagged queries (live when
 //     slot < *slot_active and slot_min < *slot_active <= slot_max): the candidates at approx[slot] / cand_cnt[slot] are what an EXACT
 //     tile (fp32 query as hi + lo fp16 planes, or fp32 MFMAs) ranked highest -- its best k and every row within a small band below the
-//     k-th (tavb_abi.hip: kExactBand) -- and belong to query slot_query[slot].  Their scores come out of the matrix pipe's accumulation
+//     k-th (tavb_route.hip: kExactBand) -- and belong to query slot_query[slot].  Their scores come out of the matrix pipe's accumulation
 //     order; scoring them again HERE gives them the streaming kernels' arithmetic, so that a query served by a fallback returns the
 //     same float32 scores (and the same order among near-ties) as `fuzzy_lookup_embedding` on its own.  Nothing is flagged.
 // KPL: result keys per lane (1: k <= 64, 4: k <= 256).
