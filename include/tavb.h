@@ -116,7 +116,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                           (with TAVB_KEY_PEER_FAILED lists) and returns its error, every other rank's lists decode to TAVB_E_PEER
  *   "comm_reserve_keys"     keys per rank of the exchange buffers tavb_comm_init reserves (default 2^20 = 8 MiB + world x 8 MiB; set BEFORE tavb_comm_init):
  *                           an exchange of up to that many keys (nq x k) allocates nothing between entering tavb_search_allgather and ncclAllGather;
- *                           bigger ones travel through the same buffers in chunks of whole queries (every rank cuts the same chunks)
+ *                           bigger ones travel through the same buffers in chunks of whole queries (cut by the value tavb_comm_init read: set the same on every rank);
+ *                           "up to that many" is judged by the value tavb_comm_init read, not by what the buffers happen to hold after a re-init with a smaller reserve
  *   "comm_timeout_ms"       0 (default) = tavb_synchronize waits for an exchange for ever; > 0: after that many milliseconds the communicator is
  *                           aborted (ncclCommAbort: the stream drains), the context is left without one and tavb_synchronize returns TAVB_E_TIMEOUT
  *   "comm_fail_alloc"       fault injection: 1 = the per-call list allocation of tavb_search_allgather (lists beyond comm_reserve_keys) fails; the rank
@@ -155,7 +156,7 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   device-resident calls (tavb_search_device, tavb_search_allgather) take the same scan + ONE merge launch ("last_direct" = 4).
  *                   Either way the answers are the single-query lookups' bit for bit.  profiles/r06_group_sweep.md
  *   "large_k"       1 (default): the Python binding routes lookups of TAVB_MAX_FUSED_K < k <= TAVB_MAX_LARGE_K through tavb_search_topk /
- *                   tavb_search_subset_topk; 0: through the emit-all pass of tavb_search_all as before (the library itself reads it nowhere else)
+ *                   tavb_search_subset_topk (a device group: tavb_search_topk_device on every shard); 0: through the emit-all pass of tavb_search_all as before (the library itself reads it nowhere else)
  *   "topk_buckets"  64-multiple in 256 .. 4096 (default 1024): histogram buckets of a large-k lookup's score pass, linear over
  *                   [max(min_score, 0), 1] (LDS per workgroup: 4 bytes per bucket and query of the pass)
  *   "topk_boundary_keys" 64 .. TAVB_MAX_LARGE_K (default 16384): keys a query's boundary list holds; a boundary bucket with more keys is
@@ -266,6 +267,11 @@ int tavb_search_messages_subset(tavb_ctx* ctx, const float* query_host, const in
 int tavb_search_begin(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const tavb_key* cursor);
 int tavb_search_end(tavb_ctx* ctx, int32_t nq, int32_t k, tavb_key* out_keys_host);
 int tavb_merge_keys_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out);
+/* tavb_merge_keys_host for lists of any length up to TAVB_MAX_LARGE_K (the lists of tavb_search_topk_device, one per shard): n_lists
+ * (1 .. 64) sorted, zero-padded lists per query, [n_lists, nq, k] -> out [nq, k], the best k of their union, sorted and zero-padded.  Real
+ * keys must be unique (they carry global ordinals or positions).  A query one of whose lists leads with TAVB_KEY_PEER_FAILED comes back as
+ * that key in every slot.  A pure host helper: no context, no GPU. */
+int tavb_merge_topk_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out);
 
 /* Every row with score >= min_score in ONE pass -- the reference's `np.flatnonzero(scores >= min_score)`
  * (vectorbase.py:179, 219) -- sorted best first on the host; the first min(total, max_out) are returned, *out_total is the
@@ -328,7 +334,16 @@ int tavb_search_subset_after(tavb_ctx* ctx, const float* query_host, const int64
 int tavb_search_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, float min_score,
                        tavb_key* dev_out_keys);
 
-/* Subset form of the above: one query (device, float32 [dim]) against the rows listed in
+/* tavb_search_topk / tavb_search_subset_topk with the queries already on the device (float32 [nq, dim]) and nothing waited for: 1 <= k <=
+ * TAVB_MAX_LARGE_K, min_scores: nq thresholds on the HOST (read before the call returns), out_keys [nq, k]: sorted, zero-padded lists in
+ * device memory or device-writable pinned memory, written on the context's stream.  dev_rows == NULL (n_subset 0): the whole corpus, keys
+ * carry ordinal_base + row (ordinal_base + rows must stay below 2^32 - 1, as for tavb_search_device).  dev_rows: device int32 [n_subset],
+ * wrapped and range-checked by the caller, with nq == 1: the subset form, keys carry subset POSITIONS.  An empty corpus or subset gives
+ * empty lists.  "last_topk_refine" is valid after the next tavb_synchronize. */
+int tavb_search_topk_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                            int64_t n_subset, tavb_key* out_keys);
+
+/* Subset form of tavb_search_device: one query (device, float32 [dim]) against the rows listed in
  * dev_rows (device int32 [n_subset], already wrapped / range-checked by the caller); keys carry
  * subset POSITIONS.  Asynchronous.  Used by the fused multi-index submission. */
 int tavb_search_subset_device(tavb_ctx* ctx, const float* dev_query, const int32_t* dev_rows, int64_t n_subset,
@@ -346,6 +361,13 @@ int tavb_search_subset_resident(tavb_ctx* ctx, const float* query_host, const in
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */
 int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k,
                       tavb_key* dev_out_keys);
+
+/* tavb_merge_device for lists of any length up to TAVB_MAX_LARGE_K: n_lists (1 .. 64) sorted, zero-padded lists per query of up to 65535,
+ * dev_lists [n_lists, nq, k] -- or, with n_lists NEGATIVE, -n_lists lists in query-major order [nq, -n_lists, k] -- -> out_keys [nq, k]
+ * (device or device-writable pinned memory), what tavb_merge_topk_host returns for the same lists, the rule for TAVB_KEY_PEER_FAILED
+ * included.  Every key finds its own rank with binary searches in the other lists (tavb_topk.hip): real keys must be unique.
+ * Asynchronous; timed under TAVB_KERNEL_MERGE. */
+int tavb_merge_topk_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out_keys);
 
 /* Decode host copies of keys into ordinals/scores/counts (pure host helper). */
 int tavb_decode_keys(const tavb_key* keys_host, int32_t nq, int32_t k, int64_t* out_ordinals, float* out_scores,
@@ -383,6 +405,16 @@ int tavb_search_allgather(tavb_ctx* ctx, const float* dev_queries, int32_t nq, i
  * of a predicate, :191-201): dev_local_keys [nq, k] sorted lists with GLOBAL ordinals / positions -> out_keys [nq, k] merged over all
  * ranks (device or device-writable pinned memory).  Asynchronous; collective. */
 int tavb_allgather_merge(tavb_ctx* ctx, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys);
+/* The two calls above for 1 <= k <= TAVB_MAX_LARGE_K (the top 1000 of a corpus too big for one GPU): tavb_search_topk_device on every
+ * rank (min_scores: nq thresholds on the host, the same on every rank), the all-gather, the merge of tavb_merge_topk_device.  The
+ * protocol is that of tavb_search_allgather step by step: argument errors every rank makes alike return at once -- among them a k above
+ * "comm_reserve_keys" (one query's list must fit the reserved buffers) and a world of more than 64 ranks; whatever fails on one rank, the
+ * workspaces of its local lookup included, still joins every chunk of the exchange with TAVB_KEY_PEER_FAILED lists; nothing allocates
+ * between entry and ncclAllGather while nq x k keys fit the reserve, bigger exchanges travel in chunks of whole queries (64 queries per
+ * chunk at k = 16384 and the default reserve); "comm_fail_rank", "comm_fail_alloc", "comm_stall_ms", "comm_force" and "comm_timeout_ms"
+ * act as they do there.  Without a communicator: tavb_search_topk_device / a copy. */
+int tavb_search_topk_allgather(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, tavb_key* out_keys);
+int tavb_allgather_merge_topk(tavb_ctx* ctx, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys);
 /* keys [count] that carry POSITIONS into a list -> the same keys carrying dev_map[position] (int32 [map_len]): a rank's subset search
  * (tavb_search_subset_device) numbers the part of the caller's subset that lies in its shard; the map leads back to the positions in the
  * caller's whole list.  In place, asynchronous.  The map must be monotonic for the lists to stay sorted among equal scores. */

@@ -56,6 +56,7 @@ _SIGNATURES = [
     ("tavb_search_begin", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     ("tavb_search_end", c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_merge_keys_host", c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    ("tavb_merge_topk_host", c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_search_all", c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     ("tavb_search_subset_all", c_int,
      [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
@@ -70,15 +71,19 @@ _SIGNATURES = [
     ("tavb_search_subset_after", c_int,
      [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int32)]),
     ("tavb_search_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
+    ("tavb_search_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_search_subset_device", c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
     ("tavb_search_subset_resident", c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_comm_unique_id", c_int, [c_void_p]),
     ("tavb_comm_init", c_int, [c_void_p, c_void_p, c_int32, c_int32]),
     ("tavb_comm_destroy", c_int, [c_void_p]),
     ("tavb_search_allgather", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
     ("tavb_allgather_merge", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    ("tavb_search_topk_allgather", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    ("tavb_allgather_merge_topk", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_remap_key_positions", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64]),
     ("tavb_profile_enable", c_int, [c_void_p, c_int32]),
     ("tavb_profile_reset", c_int, [c_void_p]),
@@ -647,6 +652,32 @@ class Engine:
         _check(self.lib, rc)
         return out_keys
 
+    def search_topk_device(self, dev_queries, k: int, thrs, out_keys=None, dev_rows=None):
+        """`search_topk` / `search_subset_topk` with the queries on the device and nothing waited for (tavb_search_topk_device): dev_queries
+        torch f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> torch int64 [nq, k] sorted, zero-padded keys
+        carrying global ordinals -- or, with dev_rows (torch int32 [S], valid corpus rows; one query), subset positions.  `out_keys`: a
+        device tensor or a PINNED host tensor.  Async: `synchronize()` before reading."""
+        torch = self._torch
+        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.numel() % max(self.dim, 1) == 0
+        nq = dev_queries.numel() // self.dim if self.dim else 0
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        if dev_rows is not None:
+            assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
+        if dev_rows is not None and dev_rows.shape[0] == 0:  # (an empty tensor has no address to tell the library "a subset" by)
+            self.synchronize()
+            out_keys.view(-1)[: nq * k].zero_()
+            torch.cuda.current_stream(self.device).synchronize()
+            return out_keys
+        with self._lock:
+            rc = self.lib.tavb_search_topk_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t),
+                                                  None if dev_rows is None else c_void_p(dev_rows.data_ptr()),
+                                                  0 if dev_rows is None else int(dev_rows.shape[0]), c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
     def search_subset_device(self, dev_query, dev_rows, k: int, thr: float, out_keys=None):
         """dev_query: torch f32 [1, dim] or [dim]; dev_rows: torch int32 [S] (valid corpus rows) ->
         torch int64 [1, k] packed keys carrying subset positions (async)."""
@@ -703,6 +734,34 @@ class Engine:
         _check(self.lib, rc)
         return out_keys
 
+    def search_topk_allgather(self, dev_queries, k: int, thrs, out_keys=None):
+        """Collective `search_topk_device` (tavb_search_topk_allgather): every rank passes the same queries and thresholds and gets the
+        merged whole-corpus key lists [nq, k], 1 <= k <= MAX_LARGE_K.  `out_keys`: a device tensor or a PINNED host tensor.  Async."""
+        torch = self._torch
+        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.shape[1] == self.dim
+        nq = dev_queries.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
+        with self._lock:
+            rc = self.lib.tavb_search_topk_allgather(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def allgather_merge_topk(self, dev_local_keys, out_keys=None):
+        """`allgather_merge` for lists of up to MAX_LARGE_K keys (tavb_allgather_merge_topk).  Async; collective."""
+        torch = self._torch
+        assert dev_local_keys.dtype == torch.int64 and dev_local_keys.is_contiguous() and dev_local_keys.dim() == 2
+        nq, k = dev_local_keys.shape
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_local_keys.device)
+        self._check_out_keys(out_keys, nq, k)
+        with self._lock:
+            rc = self.lib.tavb_allgather_merge_topk(self._h, c_void_p(dev_local_keys.data_ptr()), nq, k, c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
     def remap_key_positions(self, dev_keys, dev_map) -> None:
         """In place: keys carrying list positions -> keys carrying dev_map[position] (int32 device tensor).  Async."""
         torch = self._torch
@@ -720,6 +779,25 @@ class Engine:
             out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_lists.device)
         with self._lock:
             rc = self.lib.tavb_merge_device(self._h, c_void_p(dev_lists.data_ptr()), n_lists, nq, k, c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+
+    def merge_topk_device(self, dev_lists, out_keys=None, query_major: bool = False):
+        """`merge_device` for lists of up to MAX_LARGE_K keys (tavb_merge_topk_device): dev_lists torch int64 [n_lists, nq, k] -- or
+        [nq, n_lists, k] with query_major -- of sorted, zero-padded lists with unique keys, n_lists <= 64 -> [nq, k] (async)."""
+        torch = self._torch
+        assert dev_lists.dtype == torch.int64 and dev_lists.is_contiguous() and dev_lists.dim() == 3
+        if query_major:
+            nq, n_lists, k = dev_lists.shape
+        else:
+            n_lists, nq, k = dev_lists.shape
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_lists.device)
+        self._check_out_keys(out_keys, nq, k)
+        with self._lock:
+            rc = self.lib.tavb_merge_topk_device(self._h, c_void_p(dev_lists.data_ptr()), -n_lists if query_major else n_lists, nq, k,
+                                                 c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 
@@ -745,6 +823,19 @@ def merge_keys(lists: np.ndarray) -> np.ndarray:
     n_lists, nq, k = a.shape
     out = np.empty((nq, k), dtype=np.uint64)
     _check(lib, lib.tavb_merge_keys_host(_addr(a), n_lists, nq, k, _addr(out)))
+    return out
+
+
+def merge_topk_keys(lists: np.ndarray) -> np.ndarray:
+    """`merge_keys` for lists of up to MAX_LARGE_K keys (tavb_merge_topk_host): uint64 [n_lists <= 64, nq, k] sorted, zero-padded lists with
+    unique keys -> uint64 [nq, k]; a query one of whose lists leads with the failure key comes back as that key in every slot.  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    a = np.ascontiguousarray(lists).view(np.uint64)
+    if a.ndim != 3:
+        raise ValueError("lists must be [n_lists, nq, k]")
+    n_lists, nq, k = a.shape
+    out = np.empty((nq, k), dtype=np.uint64)
+    _check(lib, lib.tavb_merge_topk_host(_addr(a), n_lists, nq, k, _addr(out)))
     return out
 
 

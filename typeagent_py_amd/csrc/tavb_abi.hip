@@ -144,9 +144,19 @@ int tavb_destroy(tavb_ctx* c) {
 int tavb_synchronize(tavb_ctx* c) {
   if (int rc = check_ctx(c)) return rc;
   DeviceGuard guard(c->device);
-  if (c->comm && c->comm_inflight && c->comm_timeout_ms > 0) return comm_wait_or_abort(c);
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  c->comm_inflight = false;
+  if (c->comm && c->comm_inflight && c->comm_timeout_ms > 0) {
+    if (int rc = comm_wait_or_abort(c)) return rc;
+  } else {
+    TAVB_HIP(hipStreamSynchronize(c->stream));
+    c->comm_inflight = false;
+  }
+  if (c->topk_rounds_pending > 0) {  // an asynchronous large-k lookup has finished: its refinement rounds
+    const int32_t* rounds = reinterpret_cast<const int32_t*>(c->h_topk_rounds.ptr);
+    int64_t most = 0;
+    for (int q = 0; q < c->topk_rounds_pending; ++q) most = std::max<int64_t>(most, rounds[q]);
+    c->last_topk_refine = most;
+    c->topk_rounds_pending = 0;
+  }
   return TAVB_OK;
 }
 
@@ -409,6 +419,20 @@ int tavb_merge_device(tavb_ctx* c, const tavb_key* dev_lists, int32_t n_lists, i
   Timed t(c, TAVB_KERNEL_MERGE);
   hipError_t e = tavb::launch_merge(reinterpret_cast<const u64_t*>(dev_lists), n_lists, nq, k, /*query_major=*/false,
                                     reinterpret_cast<u64_t*>(dev_out_keys), c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "merge launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+int tavb_merge_topk_device(tavb_ctx* c, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  const bool query_major = n_lists < 0;
+  if (query_major) n_lists = -n_lists;
+  if (n_lists < 1 || n_lists > 64 || nq < 1 || nq > 65535 || k < 1 || k > TAVB_MAX_LARGE_K)
+    return fail(TAVB_E_INVALID, "bad merge shape (1 .. 64 lists of 1 .. %d keys, 1 .. 65535 queries)", TAVB_MAX_LARGE_K);
+  if (!dev_lists || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  Timed t(c, TAVB_KERNEL_MERGE);
+  hipError_t e = tavb::launch_merge_topk(reinterpret_cast<const u64_t*>(dev_lists), n_lists, nq, k, query_major, reinterpret_cast<u64_t*>(out_keys), c->stream);
   if (e != hipSuccess) return fail(TAVB_E_HIP, "merge launch failed: %s", hipGetErrorString(e));
   return TAVB_OK;
 }

@@ -1,4 +1,5 @@
-// Row-sharded corpora: the RCCL binding of libtavb.so -- tavb_comm_*, tavb_search_allgather, tavb_allgather_merge.  The only file that
+// Row-sharded corpora: the RCCL binding of libtavb.so -- tavb_comm_*, tavb_search_allgather, tavb_allgather_merge and their large-k
+// forms tavb_search_topk_allgather, tavb_allgather_merge_topk.  The only file that
 // includes RCCL's header (the context holds the communicator as an opaque pointer).  Host code only.
 
 #include <dlfcn.h>
@@ -122,6 +123,7 @@ int tavb_comm_init(tavb_ctx* c, const void* id_bytes, int32_t rank, int32_t worl
   c->comm = comm;
   c->comm_rank = rank;
   c->comm_world = world;
+  c->comm_chunk_keys = c->comm_reserve_keys;
   c->comm_inflight = false;
   return TAVB_OK;
 }
@@ -138,12 +140,15 @@ int tavb_comm_destroy(tavb_ctx* c) {
   return TAVB_OK;
 }
 
+}  // extern "C"
+
 // local [nq, k] lists (device; nullptr = this rank FAILED: it sends TAVB_KEY_PEER_FAILED in every slot) -> ncclAllGather on the context's
 // stream -> merge kernel -> out_keys [nq, k].  Nothing here allocates: the lists travel through the buffers tavb_comm_init reserved, in chunks
-// of whole queries when they hold more than comm_reserve_keys keys (every rank makes the same call, so every rank cuts the same chunks).
-static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32_t k, tavb_key* out_keys) {
-  const int64_t reserve_keys = (int64_t)(c->d_xlocal.cap / sizeof(u64_t));
-  const int qc = (int)std::min<int64_t>(nq, std::max<int64_t>(1, reserve_keys / k));  // queries per chunk
+// of whole queries when they hold more than comm_reserve_keys keys.  Every rank makes the same call and cuts by the value tavb_comm_init
+// stored (comm_chunk_keys), so every rank cuts the same chunks.  long_lists: the merge of tavb_topk.hip (any k up to TAVB_MAX_LARGE_K, up to
+// 64 ranks) instead of the register merge (k up to TAVB_MAX_FUSED_K) -- the one difference between the two families of collective calls.
+static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys) {
+  const int qc = (int)std::min<int64_t>(nq, std::max<int64_t>(1, c->comm_chunk_keys / k));  // queries per chunk
   if ((size_t)qc * k * sizeof(u64_t) * c->comm_world > c->d_gather.cap || (size_t)qc * k * sizeof(u64_t) > c->d_xlocal.cap)
     return fail(TAVB_E_INVALID, "the exchange buffers of this communicator are gone (tavb_comm_init reserves them)");
   u64_t* gathered = reinterpret_cast<u64_t*>(c->d_gather.ptr);
@@ -161,11 +166,65 @@ static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32
       TAVB_RCCL(g_rccl.AllGather(src, gathered, (size_t)qn * k, ncclUint64, comm_of(c), c->stream));
     }
     Timed t(c, TAVB_KERNEL_MERGE);
-    hipError_t e = tavb::launch_merge(gathered, c->comm_world, qn, k, /*query_major=*/false, reinterpret_cast<u64_t*>(out_keys) + (size_t)q0 * k, c->stream);
+    u64_t* out = reinterpret_cast<u64_t*>(out_keys) + (size_t)q0 * k;
+    hipError_t e = long_lists ? tavb::launch_merge_topk(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream)
+                              : tavb::launch_merge(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "merge launch failed: %s", hipGetErrorString(e));
   }
   return TAVB_OK;
 }
+
+// The collective lookups after their argument checks: everything that can fail on ONE rank -- the state of its shard, an allocation, a
+// launch -- still joins the collectives, with TAVB_KEY_PEER_FAILED lists, so that the peers are never left waiting in ncclAllGather for a
+// rank that has returned an error to its caller.  Lists of up to comm_reserve_keys keys live in the buffer tavb_comm_init reserved: no
+// allocation between here and the all-gather.  `search(local)` enqueues this shard's lookup into local [nq, k] and returns its status -- the
+// workspaces it reserves on the way are part of it: a failure there joins the exchange like any other.
+template <class Search>
+static int search_exchange_merge(tavb_ctx* c, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys, Search&& search) {
+  DeviceGuard guard(c->device);
+  const size_t list_keys = (size_t)nq * k;
+  int rc_local = TAVB_OK;
+  u64_t* local = nullptr;
+  if ((rc_local = require_corpus(c)) != TAVB_OK) {
+  } else if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    rc_local = fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  else if (list_keys <= (size_t)c->comm_chunk_keys && list_keys * sizeof(u64_t) <= c->d_xlocal.cap) local = reinterpret_cast<u64_t*>(c->d_xlocal.ptr);
+  else if (c->comm_fail_alloc) rc_local = fail(TAVB_E_NOMEM, "injected failure of the list allocation (option comm_fail_alloc)");
+  else if ((rc_local = c->d_local.reserve(list_keys * sizeof(u64_t))) == TAVB_OK) local = reinterpret_cast<u64_t*>(c->d_local.ptr);
+  if (rc_local != TAVB_OK) {
+  } else if (c->comm_fail_rank >= 0 && c->comm_fail_rank == c->comm_rank) {  // fault injection (option "comm_fail_rank"): what a failed launch / allocation inside the local search looks like
+    rc_local = fail(TAVB_E_HIP, "injected failure of the local search on rank %d (option comm_fail_rank)", c->comm_rank);
+  } else if (c->rows == 0) {  // an empty shard still takes part in the collectives
+    const hipError_t e = hipMemsetAsync(local, 0, list_keys * sizeof(u64_t), c->stream);
+    if (e != hipSuccess) rc_local = fail(TAVB_E_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+  } else {
+    rc_local = search(local);
+  }
+  // a failed rank's lists = TAVB_KEY_PEER_FAILED (all bits set) in every slot: it sorts above every real key, so it leads every merged list on
+  // EVERY rank -- the peers' answers would silently miss this shard otherwise; tavb_decode_keys turns it into TAVB_E_PEER
+  const std::string local_error = rc_local != TAVB_OK ? g_last_error : std::string();
+  const int rc_x = exchange_and_merge(c, rc_local == TAVB_OK ? local : nullptr, nq, k, long_lists, out_keys);
+  if (rc_local != TAVB_OK) {
+    g_last_error = local_error;
+    return rc_local;
+  }
+  return rc_x;
+}
+
+static bool collective(const tavb_ctx* c) { return c->comm && !(c->comm_world == 1 && !c->comm_force); }
+
+// argument errors of the large-k collectives that every rank makes alike
+static int check_long_lists(const tavb_ctx* c, int32_t nq, int32_t k) {
+  if (k < 1 || k > TAVB_MAX_LARGE_K) return fail(TAVB_E_INVALID, "k must be 1 .. %d (got %d)", TAVB_MAX_LARGE_K, k);
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (collective(c) && k > c->comm_chunk_keys)
+    return fail(TAVB_E_INVALID, "one list of k=%d keys does not fit the exchange buffers (option comm_reserve_keys = %lld, read by tavb_comm_init)", k,
+                (long long)c->comm_chunk_keys);
+  if (collective(c) && c->comm_world > 64) return fail(TAVB_E_UNSUPPORTED, "the merge of lists beyond %d keys takes up to 64 ranks", TAVB_MAX_FUSED_K);
+  return TAVB_OK;
+}
+
+extern "C" {
 
 int tavb_search_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, float min_score, tavb_key* out_keys) {
   // argument errors every rank makes alike (the ranks make the same call) return at once ...
@@ -175,52 +234,45 @@ int tavb_search_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int
     return fail(TAVB_E_UNSUPPORTED, "k=%d exceeds the fused-select limit %d; page with tavb_search_after / tavb_search_subset_after", k, TAVB_MAX_FUSED_K);
   if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
   if (!dev_queries || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (!c->comm || (c->comm_world == 1 && !c->comm_force)) return tavb_search_device(c, dev_queries, nq, k, min_score, out_keys);
+  if (!collective(c)) return tavb_search_device(c, dev_queries, nq, k, min_score, out_keys);
+  // ... everything else joins the exchange (search_exchange_merge)
+  const std::vector<float> ms((size_t)nq, min_score);
+  return search_exchange_merge(c, nq, k, /*long_lists=*/false, out_keys, [&](u64_t* local) {
+    return tavb_search_device_dispatch(c, dev_queries, nq, k, ms.data(), (uint32_t)c->ordinal_base, local);
+  });
+}
+
+int tavb_search_topk_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = check_long_lists(c, nq, k)) return rc;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (!collective(c)) return tavb_search_topk_device(c, dev_queries, nq, k, min_scores, nullptr, 0, out_keys);
+  return search_exchange_merge(c, nq, k, /*long_lists=*/true, out_keys, [&](u64_t* local) {
+    return search_topk_async(c, dev_queries, nq, k, min_scores, nullptr, c->rows, (uint32_t)c->ordinal_base, local);
+  });
+}
+
+static int allgather_merge_impl(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys) {
+  if (!dev_local_keys || !out_keys) return fail(TAVB_E_INVALID, "null argument");
   DeviceGuard guard(c->device);
-  // ... everything that can fail on ONE rank -- the state of its shard, an allocation, a launch -- still joins the collectives, with
-  // TAVB_KEY_PEER_FAILED lists, so that the peers are never left waiting in ncclAllGather for a rank that has returned an error to its caller.
-  // Lists of up to comm_reserve_keys keys live in the buffer tavb_comm_init reserved: no allocation between here and the all-gather.
-  const size_t list_keys = (size_t)nq * k;
-  int rc_local = TAVB_OK;
-  u64_t* local = nullptr;
-  if ((rc_local = require_corpus(c)) != TAVB_OK) {
-  } else if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    rc_local = fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  else if (list_keys * sizeof(u64_t) <= c->d_xlocal.cap) local = reinterpret_cast<u64_t*>(c->d_xlocal.ptr);
-  else if (c->comm_fail_alloc) rc_local = fail(TAVB_E_NOMEM, "injected failure of the list allocation (option comm_fail_alloc)");
-  else if ((rc_local = c->d_local.reserve(list_keys * sizeof(u64_t))) == TAVB_OK) local = reinterpret_cast<u64_t*>(c->d_local.ptr);
-  std::vector<float> ms((size_t)nq, min_score);
-  if (rc_local != TAVB_OK) {
-  } else if (c->comm_fail_rank >= 0 && c->comm_fail_rank == c->comm_rank) {  // fault injection (option "comm_fail_rank"): what a failed launch / allocation inside the local search looks like
-    rc_local = fail(TAVB_E_HIP, "injected failure of the local search on rank %d (option comm_fail_rank)", c->comm_rank);
-  } else if (c->rows == 0) {  // an empty shard still takes part in the collectives
-    const hipError_t e = hipMemsetAsync(local, 0, list_keys * sizeof(u64_t), c->stream);
-    if (e != hipSuccess) rc_local = fail(TAVB_E_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-  } else {
-    rc_local = tavb_search_device_dispatch(c, dev_queries, nq, k, ms.data(), (uint32_t)c->ordinal_base, local);
+  if (!collective(c)) {
+    if (reinterpret_cast<const void*>(dev_local_keys) != reinterpret_cast<const void*>(out_keys))
+      TAVB_HIP(hipMemcpyAsync(out_keys, dev_local_keys, (size_t)nq * k * sizeof(u64_t), hipMemcpyDefault, c->stream));
+    return TAVB_OK;
   }
-  // a failed rank's lists = TAVB_KEY_PEER_FAILED (all bits set) in every slot: it sorts above every real key, so it leads every merged list on
-  // EVERY rank -- the peers' answers would silently miss this shard otherwise; tavb_decode_keys turns it into TAVB_E_PEER
-  const std::string local_error = rc_local != TAVB_OK ? g_last_error : std::string();
-  const int rc_x = exchange_and_merge(c, rc_local == TAVB_OK ? local : nullptr, nq, k, out_keys);
-  if (rc_local != TAVB_OK) {
-    g_last_error = local_error;
-    return rc_local;
-  }
-  return rc_x;
+  return exchange_and_merge(c, reinterpret_cast<const u64_t*>(dev_local_keys), nq, k, long_lists, out_keys);
 }
 
 int tavb_allgather_merge(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
   if (int rc = check_ctx(c)) return rc;
   if (nq < 1 || k < 1 || k > TAVB_MAX_FUSED_K) return fail(TAVB_E_INVALID, "bad list shape");
-  if (!dev_local_keys || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  DeviceGuard guard(c->device);
-  if (!c->comm || (c->comm_world == 1 && !c->comm_force)) {
-    if (reinterpret_cast<const void*>(dev_local_keys) != reinterpret_cast<const void*>(out_keys))
-      TAVB_HIP(hipMemcpyAsync(out_keys, dev_local_keys, (size_t)nq * k * sizeof(u64_t), hipMemcpyDefault, c->stream));
-    return TAVB_OK;
-  }
-  return exchange_and_merge(c, reinterpret_cast<const u64_t*>(dev_local_keys), nq, k, out_keys);
+  return allgather_merge_impl(c, dev_local_keys, nq, k, /*long_lists=*/false, out_keys);
+}
+
+int tavb_allgather_merge_topk(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = check_long_lists(c, nq, k)) return rc;
+  return allgather_merge_impl(c, dev_local_keys, nq, k, /*long_lists=*/true, out_keys);
 }
 
 }  // extern "C"

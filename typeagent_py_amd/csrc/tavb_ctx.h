@@ -155,6 +155,10 @@ struct tavb_ctx {
   int64_t topk_boundary_keys = 16384;        // option: capacity of a query's boundary list (more keys in the boundary bucket: refinement)
   int64_t topk_scores_bytes = (int64_t)1 << 30;  // option: most bytes of one group's score array (queries per corpus pass are cut to fit)
   int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
+  // the asynchronous forms (tavb_search_topk_device, tavb_search_topk_allgather): the finish kernel writes every query's rounds here, and
+  // the next tavb_synchronize folds the first topk_rounds_pending of them into last_topk_refine
+  Buffer h_topk_rounds{nullptr, 0, true};
+  int topk_rounds_pending = 0;
   // sorted lookups (tavb_search_sorted: every survivor, or any k): the keys of one query at or above its boundary, then their sort
   // (tavb_sort.hip); the decoded results leave through h_out in pieces of at most sort_stage_keys
   Buffer d_sort_keys, d_sort_ws;
@@ -230,6 +234,8 @@ struct tavb_ctx {
   // keys of the exchange buffers reserved by tavb_comm_init (d_xlocal: that many, d_gather: x world): an exchange of up to that many keys per
   // rank allocates NOTHING between entering the call and ncclAllGather; a bigger one goes through the same buffers in chunks of whole queries
   int64_t comm_reserve_keys = (int64_t)1 << 20;
+  int64_t comm_chunk_keys = 0;  // comm_reserve_keys as tavb_comm_init found it: what the chunks of a big exchange are cut by (not Buffer::cap, which
+                                // depends on this context's allocation history -- every rank must cut the same chunks)
   bool comm_inflight = false;   // an exchange was enqueued since the last successful tavb_synchronize
   Buffer d_local;   // this shard's [nq, k] lists when they do not fit d_xlocal
   Buffer d_xlocal;  // this shard's lists of an exchange up to comm_reserve_keys keys; the TAVB_KEY_PEER_FAILED lists of a rank that failed
@@ -242,7 +248,7 @@ struct tavb_ctx {
   void for_each_buffer(F&& f) {
     for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
                       &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk,
-                      &d_sort_keys, &d_sort_ws, &h_sort_info, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
+                      &d_sort_keys, &d_sort_ws, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
                       &d_local, &d_xlocal, &d_gather})
       f(*b);
   }
@@ -337,6 +343,12 @@ DirectGroupPlan plan_direct_group(const tavb_ctx* c, int nq, int k, int full_blo
 // Core: queries on device (f32 [nq, dim]) -> sorted key lists d_out [nq, k] (async on the stream).
 int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_row_ids, int64_t n_pos,
                        uint32_t index_base, u64_t* d_out, u64_t key_bound = ~0ull);
+
+// ---- tavb_lookup.hip
+// The large-k lookup (tavb_search_topk's passes) with the queries on the device and nothing waited for: nq sorted, zero-padded lists of k keys
+// carrying index_base + position -> out_keys (device or device-writable pinned memory); d_rows: a subset's rows (nq == 1), or null.
+int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
+                      uint32_t index_base, u64_t* out_keys);
 
 // ---- tavb_comm.hip
 int comm_wait_or_abort(tavb_ctx* c);

@@ -73,6 +73,7 @@ struct TopkLaunch {
   float lo[TAVB_MAX_STREAM_QUERIES], scale[TAVB_MAX_STREAM_QUERIES];
   unsigned long long* out_keys;
   int32_t* out_rounds;
+  uint32_t index_base;  // added to the position packed into every key that leaves (0: positions; the device-resident forms: ordinal_base)
 };
 constexpr int kTopkRefineBuckets = 4096;  // sub-buckets of one refinement round
 size_t topk_workspace_bytes(int nq, int k, int buckets, int cap, int rounds);
@@ -82,6 +83,15 @@ int topk_refine_rounds(int64_t n_pos, int cap);
 hipError_t launch_topk_refine(const TopkLaunch& t, int round, hipStream_t stream);
 hipError_t launch_topk_compact(const TopkLaunch& t, hipStream_t stream);
 hipError_t launch_topk_finish(const TopkLaunch& t, hipStream_t stream);
+
+// Merge of LONG sorted lists (any k up to TAVB_MAX_LARGE_K; launch_merge stops at TAVB_MAX_FUSED_K): n_lists (1 .. 64) lists of k keys per
+// query, sorted descending and zero-padded, [n_lists, nq, k] or query-major [nq, n_lists, k] -> out [nq, k], the best k of their union,
+// sorted and zero-padded (device or device-writable pinned memory).  Real keys must be unique.  A query one of whose lists leads with
+// TAVB_KEY_PEER_FAILED gets that key in every slot.  tavb_topk.hip
+hipError_t launch_merge_topk(const unsigned long long* lists, int n_lists, int nq, int k, bool query_major, unsigned long long* out,
+                             hipStream_t stream);
+// out[0 .. n) = value, with vector stores (out: device or device-writable pinned memory)
+hipError_t launch_fill_keys(unsigned long long* out, int64_t n, unsigned long long value, hipStream_t stream);
 
 // The sorted route (tavb_search_sorted) over the same score pass and workspace head, after the refinement rounds (t.k: any 1 .. n_pos,
 // n_pos = every survivor; t.out_keys / t.out_rounds unused): sorted_count writes, per query and block of positions, how many keys lie at

@@ -320,6 +320,30 @@ int tavb_search_end(tavb_ctx* c, int32_t nq, int32_t k, tavb_key* out_keys_host)
   return TAVB_OK;
 }
 
+// lists [n_lists, nq, k] sorted best first -> out [nq, k], any k.  Every list's j-th key bounds j of its keys from below.  With
+// j = ceil(k / n_lists) and t = the m-th largest of the lists' j-th keys, m = ceil(k / j), at least m * j >= k keys are >= t: the k best
+// overall all are, and they sit in the prefixes (down to t) of the lists whose head is >= t.  One pass over n_lists keys, a selection among
+// them, a sort of the keys that are left.
+static void merge_pruned(const tavb_key* lists, int n_lists, int nq, int k, tavb_key* out) {
+  static thread_local std::vector<u64_t> pool;
+  const int j = (k + n_lists - 1) / n_lists;
+  const int m = (k + j - 1) / j;  // <= n_lists
+  for (int q = 0; q < nq; ++q) {
+    pool.resize((size_t)n_lists);
+    for (int l = 0; l < n_lists; ++l) pool[l] = lists[((size_t)l * nq + q) * k + (j - 1)];
+    std::nth_element(pool.begin(), pool.begin() + (m - 1), pool.end(), std::greater<u64_t>());
+    const u64_t t = std::max<u64_t>(pool[m - 1], 1);  // (0 = an empty slot, never a result: fewer than k keys in all, take whatever there is)
+    pool.clear();
+    for (int l = 0; l < n_lists; ++l) {
+      const tavb_key* list = lists + ((size_t)l * nq + q) * k;
+      for (int i = 0; i < k && list[i] >= t; ++i) pool.push_back(list[i]);
+    }
+    const size_t take = std::min<size_t>((size_t)k, pool.size());
+    std::partial_sort(pool.begin(), pool.begin() + take, pool.end(), std::greater<u64_t>());
+    for (size_t i = 0; i < (size_t)k; ++i) out[(size_t)q * k + i] = i < take ? pool[i] : 0;  // 0 once every list is exhausted
+  }
+}
+
 int tavb_merge_keys_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out) {
   if (n_lists < 1 || nq < 0 || k < 1) return fail(TAVB_E_INVALID, "bad merge shape");
   if (nq == 0) return TAVB_OK;
@@ -355,23 +379,23 @@ int tavb_merge_keys_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int
     }
     return TAVB_OK;
   }
-  static thread_local std::vector<u64_t> pool;
-  const int j = (k + n_lists - 1) / n_lists;
-  const int m = (k + j - 1) / j;  // <= n_lists
-  for (int q = 0; q < nq; ++q) {
-    pool.resize((size_t)n_lists);
-    for (int l = 0; l < n_lists; ++l) pool[l] = lists[((size_t)l * nq + q) * k + (j - 1)];
-    std::nth_element(pool.begin(), pool.begin() + (m - 1), pool.end(), std::greater<u64_t>());
-    const u64_t t = std::max<u64_t>(pool[m - 1], 1);  // (0 = an empty slot, never a result: fewer than k keys in all, take whatever there is)
-    pool.clear();
-    for (int l = 0; l < n_lists; ++l) {
-      const tavb_key* list = lists + ((size_t)l * nq + q) * k;
-      for (int i = 0; i < k && list[i] >= t; ++i) pool.push_back(list[i]);
-    }
-    const size_t take = std::min<size_t>((size_t)k, pool.size());
-    std::partial_sort(pool.begin(), pool.begin() + take, pool.end(), std::greater<u64_t>());
-    for (size_t i = 0; i < (size_t)k; ++i) out[(size_t)q * k + i] = i < take ? pool[i] : 0;  // 0 once every list is exhausted
-  }
+  merge_pruned(lists, n_lists, nq, k, out);
+  return TAVB_OK;
+}
+
+int tavb_merge_topk_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out) {
+  if (n_lists < 1 || n_lists > 64 || nq < 0 || k < 1 || k > TAVB_MAX_LARGE_K)
+    return fail(TAVB_E_INVALID, "bad merge shape (1 .. 64 lists of 1 .. %d keys)", TAVB_MAX_LARGE_K);
+  if (nq == 0) return TAVB_OK;
+  if (!lists || !out) return fail(TAVB_E_INVALID, "null argument");
+  merge_pruned(lists, n_lists, nq, k, out);
+  // the rule of the device merge (launch_merge_topk): a query one of whose lists leads with the failure key is that key in every slot
+  for (int q = 0; q < nq; ++q)
+    for (int l = 0; l < n_lists; ++l)
+      if (lists[((size_t)l * nq + q) * k] == TAVB_KEY_PEER_FAILED) {
+        std::fill(out + (size_t)q * k, out + (size_t)(q + 1) * k, TAVB_KEY_PEER_FAILED);
+        break;
+      }
   return TAVB_OK;
 }
 
@@ -469,7 +493,7 @@ int tavb_search_subset_all(tavb_ctx* c, const float* query_host, const int64_t* 
 // a memset, ONE score pass, the refinement rounds topk_refine_rounds asks for, the compaction and the finish -- every launch's grid is
 // fixed on the host, nothing is read back before the caller's one synchronise.
 static int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
-                            u64_t* out_keys, int32_t* out_rounds) {
+                            uint32_t index_base, u64_t* out_keys, int32_t* out_rounds) {
   const int nb = (int)c->topk_buckets, cap = (int)c->topk_boundary_keys;
   int64_t per = tavb::topk_queries_per_pass(c->dim, c->dtype, nb);
   per = std::min<int64_t>(per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
@@ -512,6 +536,7 @@ static int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const 
     t.blocks = sel_blocks;
     t.out_keys = out_keys + (size_t)q0 * k;
     t.out_rounds = out_rounds + q0;
+    t.index_base = index_base;
     Timed tm(c, TAVB_KERNEL_TOPK);
     for (int r = 0; r < rounds; ++r) {
       hipError_t e = tavb::launch_topk_refine(t, r, c->stream);
@@ -553,6 +578,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
   if (c->rows == 0) {
     for (int q = 0; q < nq; ++q) out_counts[q] = 0;
     return TAVB_OK;
@@ -563,7 +589,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   int32_t* rounds;
   if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, keys, rounds)) return rc;
+  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, 0u, keys, rounds)) return rc;
   TAVB_HIP(hipStreamSynchronize(c->stream));
   decode(keys, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
   note_rounds(c, rounds, nq);
@@ -576,6 +602,7 @@ int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t*
   if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
   if (!query_host || !out_positions || !out_scores || !out_count) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
   if (n_subset == 0 || c->rows == 0) {
     *out_count = 0;
     return TAVB_OK;
@@ -589,11 +616,47 @@ int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t*
   int32_t* rounds;
   if (int rc = reserve_topk_out(c, 1, k, &keys, &rounds)) return rc;
   if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
-  if (int rc = search_topk_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, keys, rounds)) return rc;
+  if (int rc = search_topk_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, 0u, keys, rounds)) return rc;
   TAVB_HIP(hipStreamSynchronize(c->stream));
   decode(keys, 1, k, 0, out_positions, out_scores, out_count);
   note_rounds(c, rounds, 1);
   return TAVB_OK;
+}
+
+}  // extern "C"
+
+// queries already on the device, keys to device (or device-writable pinned) memory, nothing waited for: the refinement rounds of the queries
+// land in the context's own pinned words and become "last_topk_refine" at the next tavb_synchronize
+int tavb::host::search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const int32_t* d_rows, int64_t n_pos,
+                                  uint32_t index_base, u64_t* out_keys) {
+  c->topk_rounds_pending = 0;
+  c->last_topk_refine = 0;
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (n_pos == 0 || c->rows == 0) {  // nothing to scan: empty lists
+    const hipError_t e = tavb::launch_fill_keys(out_keys, (int64_t)nq * k, 0ull, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
+    return TAVB_OK;
+  }
+  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, d_rows, n_pos, index_base, out_keys, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+extern "C" {
+
+int tavb_search_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                            int64_t n_subset, tavb_key* out_keys) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (dev_rows && nq != 1) return fail(TAVB_E_INVALID, "a subset goes with exactly one query");
+  if (!dev_rows && n_subset != 0) return fail(TAVB_E_INVALID, "null dev_rows");
+  if (!dev_rows && c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  DeviceGuard guard(c->device);
+  return dev_rows ? search_topk_async(c, dev_queries, 1, k, min_scores, dev_rows, n_subset, 0u, reinterpret_cast<u64_t*>(out_keys))
+                  : search_topk_async(c, dev_queries, nq, k, min_scores, nullptr, c->rows, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
 }
 
 // ---- sorted lookups: every survivor (k = 0) or the best k for any k, sorted on the device.  Per group of queries (sized as for
@@ -755,6 +818,7 @@ int tavb_search_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, int64
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
   for (int q = 0; q < nq; ++q) out_counts[q] = 0;
   if (c->rows == 0) return TAVB_OK;
   DeviceGuard guard(c->device);
@@ -771,6 +835,7 @@ int tavb_search_subset_sorted(tavb_ctx* c, const float* query_host, const int64_
   *out_count = 0;
   if (!query_host || (max_total > 0 && (!out_positions || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
   if (n_subset == 0 || c->rows == 0) return TAVB_OK;
   if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
   if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");

@@ -15,6 +15,9 @@
 //              same way: every boundary key ranks below every sure key), written straight into the caller's pinned [nq, k] keys.
 // Keys are (score bits << 32) | (0xFFFFFFFF - position): unique, so the boundary search always ends and equal scores order by
 // ascending position, as everywhere in this library.
+//
+// Also here: the merge of long sorted lists (merge_topk_kernel), which puts the lists of several shards -- each the output of the passes
+// above -- together for k beyond what the register merge of tavb_misc.hip holds.
 
 #include "tavb_device.h"
 #include "tavb_internal.h"
@@ -225,8 +228,9 @@ __global__ void __launch_bounds__(256) topk_compact_kernel(const TopkLaunch t) {
     const uint32_t v = pos < t.n_pos ? sc[pos] : kScoreNone;
     const u64 key = row_key(v, pos);
     const bool live = v != kScoreNone;
-    wave_append(live && key > s.kb, key, &l.cnt[q * 4 + 0], sure, (unsigned)t.k, lane);
-    wave_append(live && key >= s.ka && key <= s.kb, key, &l.cnt[q * 4 + 1], bnd, (unsigned)t.cap, lane);
+    // (keys leave with index_base added to their position: the same amount off the low half of every key, no borrow -- the order stays)
+    wave_append(live && key > s.kb, key - t.index_base, &l.cnt[q * 4 + 0], sure, (unsigned)t.k, lane);
+    wave_append(live && key >= s.ka && key <= s.kb, key - t.index_base, &l.cnt[q * 4 + 1], bnd, (unsigned)t.cap, lane);
   }
 }
 
@@ -343,6 +347,94 @@ __global__ void __launch_bounds__(1024) topk_finish_kernel(const TopkLaunch t) {
   if (threadIdx.x == 0) t.out_rounds[q] = l.meta[q * 4 + 1];
 }
 
+// ---- merge of long sorted lists (launch_merge_topk): every key of the n_lists x k input finds its own place.  Real keys are unique (their
+// low half is a global ordinal or position), so the final rank of a key is its position in its own list plus, for every other list, the
+// number of keys greater than it -- a binary search of at most 15 steps in an L2-resident list -- and a key of rank < k is stored at
+// out[rank]: no sort, no atomics, no waiting between workgroups, and one query spreads over as many workgroups as its keys ask for.
+// Most keys never search: with j = ceil(k / n_lists) and m = ceil(k / j), the m-th largest of the lists' j-th keys has at least k keys at or
+// above it (the bound of tavb_merge_keys_host), so whatever is smaller cannot rank.  The first wave of every workgroup works that bound out
+// again (n_lists loads and a count over the lanes), together with the number of real keys in all (slots past it are zeroed: zeros are
+// padding and never rank) and whether a list leads with TAVB_KEY_PEER_FAILED (then the whole output row is that key: duplicates of it would
+// break the rank arithmetic, and no rank may take such a row for an answer).
+constexpr u64 kPeerFailed = ~0ull;
+constexpr int kMergeTopkPerThread = 4;
+
+// keys greater than x among L[0 .. hi), L sorted descending
+__device__ __forceinline__ int count_greater(const u64* __restrict__ L, int hi, u64 x) {
+  int lo = 0;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (L[mid] > x)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(256) merge_topk_kernel(const u64* __restrict__ lists, int n_lists, int nq, int k, int query_major,
+                                                         u64* __restrict__ out) {
+  __shared__ u64 floor_sh;
+  __shared__ int total_sh, failed_sh;
+  const int q = blockIdx.y;
+  const size_t stride = query_major ? (size_t)k : (size_t)nq * k;  // from one list of this query to the next
+  const u64* __restrict__ base = lists + (query_major ? (size_t)q * n_lists * k : (size_t)q * k);
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const int j = (k + n_lists - 1) / n_lists;
+    const int m = (k + j - 1) / j;  // <= n_lists
+    const bool live = lane < n_lists;
+    const u64* __restrict__ L = base + (size_t)(live ? lane : 0) * stride;
+    const u64 head = live ? L[0] : 0ull;
+    const u64 jth = live ? L[j - 1] : 0ull;
+    int total = live ? count_greater(L, k, 0ull) : 0;  // real keys of this lane's list
+    int at_least = 0;
+    for (int d = 0; d < n_lists; ++d) at_least += __shfl(jth, d, 64) >= jth ? 1 : 0;
+    u64 t = (live && at_least >= m) ? jth : 0ull;  // the largest of these is the m-th largest j-th key
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const u64 o = __shfl_xor(t, d, 64);
+      t = o > t ? o : t;
+      total += __shfl_xor(total, d, 64);
+    }
+    const unsigned long long failed = __ballot(head == kPeerFailed);
+    if (lane == 0) {
+      floor_sh = t > 1ull ? t : 1ull;  // (0 = fewer than k real keys: every real key ranks)
+      total_sh = total < k ? total : k;
+      failed_sh = failed != 0ull;
+    }
+  }
+  __syncthreads();
+  const u64 floor = floor_sh;
+  const int total = total_sh;
+  const bool failed = failed_sh != 0;
+  const int n_keys = n_lists * k;
+  u64* __restrict__ o = out + (size_t)q * k;
+#pragma unroll
+  for (int r = 0; r < kMergeTopkPerThread; ++r) {
+    const int e = (blockIdx.x * kMergeTopkPerThread + r) * 256 + threadIdx.x;
+    if (e >= n_keys) break;
+    if (e < k) {  // the slots no key will claim
+      if (failed)
+        o[e] = kPeerFailed;
+      else if (e >= total)
+        o[e] = 0ull;
+    }
+    if (failed) continue;
+    const int l = e / k, i = e - l * k;
+    const u64 key = base[(size_t)l * stride + i];
+    if (key < floor) continue;
+    int rank = i;
+    for (int other = 0; other < n_lists && rank < k; ++other)
+      if (other != l) rank += count_greater(base + (size_t)other * stride, k - rank, key);  // (searching k - rank keys is enough to learn rank >= k)
+    if (rank < k) o[rank] = key;
+  }
+}
+
+__global__ void __launch_bounds__(256) fill_keys_kernel(u64* __restrict__ out, int64_t n, u64 value) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = value;
+}
+
 int pow2_at_least(int n) {
   int p = 2;
   while (p < n) p <<= 1;
@@ -395,6 +487,22 @@ hipError_t launch_topk_finish(const TopkLaunch& t, hipStream_t stream) {
   const size_t lds = (size_t)pow2_at_least(t.k > t.cap ? t.k : t.cap) * sizeof(u64);  // <= 16384 keys: 128 KiB
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(topk_finish_kernel), (int)lds)) return e;
   hipLaunchKernelGGL(topk_finish_kernel, dim3(t.nq), dim3(1024), lds, stream, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_topk(const unsigned long long* lists, int n_lists, int nq, int k, bool query_major, unsigned long long* out,
+                             hipStream_t stream) {
+  if (!lists || !out || n_lists < 1 || n_lists > 64 || nq < 1 || nq > 65535 || k < 1 || k > TAVB_MAX_LARGE_K) return hipErrorInvalidValue;
+  const int per_block = 256 * kMergeTopkPerThread;
+  const int blocks = (n_lists * k + per_block - 1) / per_block;
+  hipLaunchKernelGGL(merge_topk_kernel, dim3(blocks, nq), dim3(256), 0, stream, lists, n_lists, nq, k, query_major ? 1 : 0, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_keys(unsigned long long* out, int64_t n, unsigned long long value, hipStream_t stream) {
+  if (!out || n < 1) return hipErrorInvalidValue;
+  const int blocks = n > 1024 * 256 ? 1024 : (int)((n + 255) / 256);
+  hipLaunchKernelGGL(fill_keys_kernel, dim3(blocks), dim3(256), 0, stream, out, n, value);
   return hipGetLastError();
 }
 

@@ -11,6 +11,9 @@ to back (`tavb_search_begin`: nothing blocks), then collects the per-shard key l
 on the host (`tavb_merge_keys_host`: G x k keys per query -- cheaper than any collective) and
 decodes.  Keys carry global ordinals and order by (score desc, ordinal asc), so the merged answer is the whole-corpus
 answer, ties included.
+
+max_hits 257 .. 16384 (`search_topk`, `search_subset_topk`): the exact device top-k of every shard (`tavb_search_topk_device`, enqueued
+on all shards before anything is waited for) into one reused pinned buffer, merged on the host by `tavb_merge_topk_host`.
 """
 
 from __future__ import annotations
@@ -50,6 +53,8 @@ class DeviceGroup:
         self.dtype = _native.TAVB_F32
         self.ordinal_base = 0
         self.corpus = None  # truthy once rows are resident (VectorBase only tests it against None)
+        self._topk_out: dict = {}  # (shards, nq, k) -> pinned int64 [shards, nq, k]: where the shards' large-k lists land
+        self._topk_q: dict = {}  # ("pinned" or shard, nq, dim) -> the pinned staging buffer / that device's copy of the queries
 
     # -- lifecycle / options -------------------------------------------------------------------------------------
     def close(self) -> None:
@@ -184,6 +189,99 @@ class DeviceGroup:
             raise ValueError(f"queries must be [nq, {self.dim}]")
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (a.shape[0],)))
         return _native.decode_keys(self._gather(a, k, t))
+
+    # -- exact top-k past the fused selection (tavb_search_topk_device per shard + tavb_merge_topk_host) -------------------------
+    def large_k_capable(self) -> bool:
+        """Every engine is a real `_native.Engine` (has the device-resident large-k call) with the "large_k" option on."""
+        return all(hasattr(e, "search_topk_device") and e.get_option("large_k") != 0 for e in self.engines)
+
+    def _topk_lists(self, shards: int, nq: int, k: int):
+        import torch
+
+        key = (shards, nq, k)
+        buf = self._topk_out.get(key)
+        if buf is None:
+            if len(self._topk_out) >= 8:
+                self._topk_out.clear()
+            buf = self._topk_out[key] = torch.empty(key, dtype=torch.int64).pin_memory()
+        return buf
+
+    def _device_queries(self, shards, a: np.ndarray):
+        """The queries on every shard's device: `a` goes into ONE reused pinned buffer, the copies to the devices are enqueued back to back
+        on torch's streams and each device is waited for once -- the engines run on streams of their own, so the rows must be there
+        before their scans are enqueued.  shards: [(slot, engine)] -> one device tensor per shard."""
+        import torch
+
+        key = ("pinned",) + a.shape
+        pinned = self._topk_q.get(key)
+        if pinned is None:
+            if len(self._topk_q) >= 32:
+                self._topk_q.clear()
+            pinned = self._topk_q[key] = torch.empty(a.shape, dtype=torch.float32).pin_memory()
+        pinned.numpy()[...] = a
+        out = []
+        for g, e in shards:
+            dq = self._topk_q.get((g,) + a.shape)
+            if dq is None or dq.device.index != e.device:
+                dq = self._topk_q[(g,) + a.shape] = torch.empty(a.shape, dtype=torch.float32, device=torch.device("cuda", e.device))
+            dq.copy_(pinned, non_blocking=True)
+            out.append(dq)
+        for d in {e.device for g, e in shards}:
+            torch.cuda.current_stream(d).synchronize()
+        return out
+
+    @_locked
+    def search_topk(self, queries, k: int, thrs):
+        """`Engine.search_topk` over the shards: queries f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K ->
+        (ordinals [nq,k], scores [nq,k], counts [nq])."""
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        act = self._active()
+        if not act or nq == 0:
+            return np.zeros((nq, k), np.int64), np.zeros((nq, k), np.float32), np.zeros(nq, np.int32)
+        lists = self._topk_lists(len(act), nq, k)
+        dqs = self._device_queries([(g, e) for g, (e, lo, hi) in enumerate(act)], a)
+        for g, (e, lo, hi) in enumerate(act):  # enqueue everywhere first: the devices scan concurrently
+            e.search_topk_device(dqs[g], k, t, out_keys=lists[g])
+        for e, lo, hi in act:
+            e.synchronize()
+        keys = lists.numpy().view(np.uint64)
+        return _native.decode_keys(keys[0] if len(act) == 1 else _native.merge_topk_keys(keys))
+
+    @_locked
+    def search_subset_topk(self, q, rows: np.ndarray, k: int, thr: np.float32):
+        """`Engine.search_subset_topk` over the shards: rows: int64 global corpus row per subset position -> (positions int64[m], scores
+        float32[m]), ordered (score desc, position asc) like one device's."""
+        import torch
+
+        a = self._query(q)[None, :]
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        parts = []
+        for g, (e, lo, hi) in enumerate(self._active()):
+            idx = np.flatnonzero((rows >= lo) & (rows < hi))  # ascending positions: the remapped lists stay sorted among equal scores
+            if idx.size:
+                parts.append((g, e, idx, torch.from_numpy((rows[idx] - lo).astype(np.int32)).to(torch.device("cuda", e.device))))
+        if not parts:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
+        lists = self._topk_lists(len(parts), 1, k)
+        dqs = self._device_queries([(g, e) for g, e, idx, dev_rows in parts], a)
+        for i, (g, e, idx, dev_rows) in enumerate(parts):
+            e.search_topk_device(dqs[i], k, thr, out_keys=lists[i], dev_rows=dev_rows)
+        for g, e, idx, dev_rows in parts:
+            e.synchronize()
+        keys = lists.numpy().view(np.uint64).copy()
+        low = np.uint64(0xFFFFFFFF)
+        for i, (g, e, idx, dev_rows) in enumerate(parts):  # positions in the shard's part of the subset -> positions in the caller's list
+            row = keys[i, 0]
+            live = row != 0
+            local = (low - (row[live] & low)).astype(np.int64)
+            row[live] = (row[live] & ~low) | (low - idx[local].astype(np.uint64))
+        ords, scs, cnts = _native.decode_keys(keys[0] if len(parts) == 1 else _native.merge_topk_keys(keys))
+        m = int(cnts[0])
+        return ords[0, :m], scs[0, :m]
 
     @_locked
     def search_all(self, q, thr: np.float32, max_out: int | None = None, subset_rows=None):

@@ -25,6 +25,11 @@ on CPU with `gloo` (tests/test_sharded_gloo.py supplies a host backend: for such
 backends the searcher falls back to `torch.distributed.all_gather_into_tensor`);
 the product backend below is the only one this package ships and it runs the HIP
 kernels.  There is no CPU fallback in the product path.
+
+max_hits 257 .. 16384 take the same steps with the large-k calls of the library: `tavb_search_topk_allgather` (the exact device top-k of
+the shard, the all-gather in chunks of whole queries, the merge of long lists), `tavb_search_topk_device` + `tavb_allgather_merge_topk`
+for the subset form.  max_hits = 0 (every survivor) and max_hits above 16384 have no bounded list to exchange and raise ValueError here;
+a `VectorBase(devices=[...])` device group serves them through its emit-all route.
 """
 
 from __future__ import annotations
@@ -80,6 +85,12 @@ class ShardBackend(Protocol):
 
     def rows_to_host(self) -> np.ndarray:  # this rank's rows as float32 [n, dim]
         ...
+
+
+def _check_k(k: int, what: str) -> None:
+    if not (1 <= k <= _native.MAX_LARGE_K):
+        raise ValueError(f"{what} must be in 1..{_native.MAX_LARGE_K} for a row-sharded lookup (0 = every survivor and larger values have no bounded "
+                         "per-rank list to exchange: a VectorBase(devices=[...]) device group serves them)")
 
 
 PEER_FAILED_KEY = -1  # TAVB_KEY_PEER_FAILED (all bits set) seen as int64: what a rank whose local search failed contributes to the exchange
@@ -193,10 +204,17 @@ class DeviceShardBackend:
             dq = torch.from_numpy(np.ascontiguousarray(query, dtype=np.float32)).to(dev)
             rows = torch.from_numpy(np.ascontiguousarray(local_rows, dtype=np.int32)).to(dev)
             pmap = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.int32)).to(dev)
-            keys = self.engine.search_subset_device(dq, rows, k, thr)
+            keys = self._subset_keys(dq, rows, k, thr)
             self.engine.remap_key_positions(keys, pmap)
             self._keep = (dq, rows, pmap)  # alive until the next call (the kernels run asynchronously)
             return keys
+
+    def _subset_keys(self, dq, dev_rows, k: int, thr: float):
+        """this shard's part of a subset -> keys [1, k] carrying positions in that part: the fused selection up to MAX_FUSED_K, the exact
+        device top-k beyond"""
+        if k <= _native.MAX_FUSED_K:
+            return self.engine.search_subset_device(dq, dev_rows, k, thr)
+        return self.engine.search_topk_device(dq.reshape(1, -1), k, thr, dev_rows=dev_rows)
 
     def subset_to_device(self, local_rows: np.ndarray, positions: np.ndarray):
         """This shard's part of a caller's subset as device tensors (rows int32 [S], positions int32 [S]) -- a handle for
@@ -217,7 +235,7 @@ class DeviceShardBackend:
             if handle is None:
                 return torch.zeros((1, k), dtype=torch.int64, device=dev)
             dq = torch.from_numpy(np.ascontiguousarray(query, dtype=np.float32)).to(dev)
-            keys = self.engine.search_subset_device(dq, handle[0], k, thr)
+            keys = self._subset_keys(dq, handle[0], k, thr)
             self.engine.remap_key_positions(keys, handle[1])
             self._keep = (dq, handle)  # alive until the next call (the kernels run asynchronously)
             return keys
@@ -238,17 +256,24 @@ class DeviceShardBackend:
         pinned = self._pinned.get(shape)
         if pinned is None:
             pinned = self._pinned[shape] = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
-        self.engine.search_allgather(queries, k, thr, out_keys=pinned)
+        if k <= _native.MAX_FUSED_K:
+            self.engine.search_allgather(queries, k, thr, out_keys=pinned)
+        else:
+            self.engine.search_topk_allgather(queries, k, thr, out_keys=pinned)
         self.engine.synchronize()
         return pinned.numpy()
 
     def local_search(self, queries, k: int, thr: float):
         with self.torch.cuda.stream(self.stream):
-            return self.engine.search_device(queries, k, thr)
+            if k <= _native.MAX_FUSED_K:
+                return self.engine.search_device(queries, k, thr)
+            return self.engine.search_topk_device(queries, k, thr)
 
     def merge(self, gathered):
         with self.torch.cuda.stream(self.stream):
-            return self.engine.merge_device(gathered)
+            if gathered.shape[2] <= _native.MAX_FUSED_K:
+                return self.engine.merge_device(gathered)
+            return self.engine.merge_topk_device(gathered)
 
     def to_host(self, keys) -> np.ndarray:
         # pinned staging buffer, reused: one async copy + one stream sync, no allocation per lookup
@@ -308,8 +333,7 @@ class ShardedSearcher:
 
     def search_keys(self, queries, k: int, min_score: float = 0.0):
         """-> backend tensor int64 [nq, k] of merged keys (still on the device, async)."""
-        if not (1 <= k <= _native.MAX_FUSED_K):
-            raise ValueError(f"k must be in 1..{_native.MAX_FUSED_K}")
+        _check_k(k, "k")
         thr = float(_native.f32_threshold(min_score))
         collective = not (self.world == 1 and not (self.always_collective and self.dist.is_initialized()))
         failure = None
@@ -343,7 +367,9 @@ class ShardedSearcher:
     def exchange(self, local_keys):
         """this rank's sorted lists [nq, k] (global ordinals / positions) -> the lists merged over all ranks, on every rank."""
         if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
-            return self.backend.engine.allgather_merge(local_keys)
+            if local_keys.shape[1] <= _native.MAX_FUSED_K:
+                return self.backend.engine.allgather_merge(local_keys)
+            return self.backend.engine.allgather_merge_topk(local_keys)
         if self.gather_fn is not None:
             return self.backend.merge(self.gather_fn(local_keys))
         if self.world == 1 and not (self.always_collective and self.dist.is_initialized()):
@@ -356,8 +382,7 @@ class ShardedSearcher:
     def search(self, queries, k: int, min_score: float = 0.0) -> ShardedResult:
         if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
             # the product path: one C-ABI call (no torch.distributed, no torch op), results land in pinned host memory
-            if not (1 <= k <= _native.MAX_FUSED_K):
-                raise ValueError(f"k must be in 1..{_native.MAX_FUSED_K}")
+            _check_k(k, "k")
             keys = self.backend.search_allgather(queries, k, float(_native.f32_threshold(min_score)))
         else:
             keys = self.backend.to_host(self.search_keys(queries, k, min_score))
@@ -511,7 +536,8 @@ class ShardedVectorBase:
             raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
         if self.total_rows == 0 or len(q) == 0:
             return [[] for _ in range(len(q))]
-        res = self.searcher.search(self._queries(q), max_hits, min_score)
+        _check_k(int(max_hits), "max_hits")  # (before anything collective: every rank makes the same call)
+        res = self.searcher.search(self._queries(q), int(max_hits), min_score)
         from .vectorbase import _scored_lists  # (the lists are built in C: csrc/tavb_pyhits.c)
 
         return _scored_lists(res.ordinals, res.scores, res.counts, int(max_hits))
@@ -573,8 +599,7 @@ class ShardedVectorBase:
         from .vectorbase import ScoredInt
 
         k = 10 if max_hits is None else int(max_hits)
-        if not (1 <= k <= _native.MAX_FUSED_K):
-            raise ValueError(f"max_hits must be in 1..{_native.MAX_FUSED_K} for a sharded subset lookup")
+        _check_k(k, "max_hits")
         thr = float(_native.f32_threshold(0.0 if min_score is None else min_score))
         if len(ordinals_of_subset) == 0 or self.total_rows == 0:
             return []

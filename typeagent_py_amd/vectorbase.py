@@ -582,8 +582,13 @@ class VectorBase:
     @staticmethod
     def _large_k(eng, max_hits: int) -> bool:
         """max_hits past the fused selection that the exact device top-k takes (tavb_search_topk): a single-GPU engine with the
-        "large_k" option on (the default); device groups and test doubles keep the emit-all route."""
-        return _PAGE < max_hits <= _native.MAX_LARGE_K and isinstance(eng, _native.Engine) and eng.get_option("large_k") != 0
+        "large_k" option on (the default), or a device group all of whose engines are such engines (tavb_search_topk_device per shard,
+        merged on the host); test doubles and "large_k" = 0 keep the emit-all route."""
+        if not (_PAGE < max_hits <= _native.MAX_LARGE_K):
+            return False
+        if hasattr(eng, "large_k_capable"):  # multidevice.DeviceGroup
+            return eng.large_k_capable()
+        return isinstance(eng, _native.Engine) and eng.get_option("large_k") != 0
 
     @staticmethod
     def _sort_all(eng, max_hits: int) -> bool:
