@@ -1,5 +1,5 @@
 """The case table of tests/test_gpu_wide256_shapes.py and of its CPU twin tests/test_wide256_cases_host.py: the 256-query filter tile
-(`mfma_scan_kernel<..., NI = 4>`, csrc/tavb_mfma.hip) at every width, row tail and query tail, in both MFMA shapes.
+(`mfma_scan_kernel<..., NI = 4>`, csrc/tavb_mfma_wide.hip) at every width, row tail and query tail, in both MFMA shapes.
 
 Why small corpora and k = 256.  Every key that leaves the engine is rescored exactly, so a filter bug shows only as a MISSING row, and only when
 the row it mis-scores belongs to some query's true top k.  A tile is 320 rows x 256 queries; its epilogue has a 4-row lane group, a 16-row
@@ -86,7 +86,7 @@ LADDER_OPTS = {64: (("mfma_sample_rows", 1536), ("mfma_ladder", 4)), 192: (("mfm
 CASES = [
     *_widths(),
     *_tails(),
-    # one workgroup walks five tiles and appends 1283 keys per query at threshold 0: more than CAPW - TILE_ROWS = 704, so compact_to_band runs
+    # one workgroup walks five tiles and appends 1283 keys per query at threshold 0: more than CAPW - TILE_ROWS = 704, so the band compaction (compact_buffer<CAPW, true>) runs
     # between tiles; the answer must be that of the library's own row ranges
     *[Case(f"compact-d{d}", "compact", "fp16", 1283, d, splits=(1, 0), seed=2000 + d) for d in (64, 192)],
     *[Case(f"qtail-nq{nq}-k{k}", "qtail", "fp16", 643, 192, nq=nq, k=k, seed=3000) for k in (32, 256) for nq in (65, 129, 143, 255, 256, 257, 513)],

@@ -155,7 +155,7 @@ hipError_t launch_corpus_max_norm(const void* rows_f16, int64_t n, int dim, floa
 // The prologue of the wide path in one launch (tavb_rescore.hip::query_prepare_kernel): nq live queries, slots up to nq_pad zeroed.
 // q16 may be null (rows_only: the filter uses the exact queries, only the rows' rounding enters the bound)
 // band (optional, [nq_pad]): 2 * delta, the width of the band selection
-// frag_major: q16 in MFMA-fragment-major order for 256-query tiles (tavb_mfma.hip, BD) instead of row-major
+// frag_major: q16 in MFMA-fragment-major order for 256-query tiles (tavb_mfma_wide.hip, BD) instead of row-major
 // min_scores: device [nq], the callers' thresholds per query (float32 values, NaN allowed) -- or, ms_fill: ONE threshold for the whole batch,
 //   written to ms_out / ms_floor_out [nq_pad] (+inf for the padding) by this launch
 // aux (optional): [3][nq_pad] ints zeroed (band counts, lost levels, verdicts); flag64 (optional): 64 ints zeroed (the work list's header)
@@ -231,7 +231,7 @@ size_t mfma_workspace_bytes(int n_splits, int nq_padded, bool wide);
 // the BAND of every query (all keys within band[q] of its k-th best; at most kc_max, else the strict best k) over the 128/256-query tile's
 // candidate buffers (+ an optional carried-over band [nq, kc_max] / carried_cnt [nq]) -> out [nq, kc_max] unsorted, out_cnt [nq];
 // thr_out[q] = just below the band's cut (or floor[q]); lost [nq]: highest score level (bits) at which band rows were dropped so far
-// (in/out); verdict (optional, last phase) [nq]: 1 = the band handed over is not provably complete; tavb_mfma.hip
+// (in/out); verdict (optional, last phase) [nq]: 1 = the band handed over is not provably complete; tavb_select.hip
 constexpr int kBandMax = 2048;  // most candidates per query the rescoring accepts (kc_max <= kBandMax: the context's "band_max" option; also the most the select
                                 // kernel's cache keeps when it cuts mid-stream).  1024 until round 6: a band of 1500 near-duplicates cost a 2x exact pass
 hipError_t launch_select_band(const unsigned long long* cand, const int* counts, int n_splits, int nq, int nq_padded, int k, int kc_max,

@@ -1,0 +1,827 @@
+// Batched lookup on fp16 corpora: S = X . Q^T as a dense (rows x D) . (D x queries)
+// contraction on the matrix cores (v_mfma_f32_32x32x16_f16, fp32 accumulate), with the
+// score map, threshold and per-query top-k selection fused into the epilogue so that
+// the [queries x rows] score matrix (41 GB at 1024 x 10M) never exists.
+//
+// This is the batch the reference leaves as a TODO (storage/sqlite/reltermsindex.py:259-271);
+// its semantics are Q independent `fuzzy_lookup_embedding` calls (vectorbase.py:163-190).
+// Products of two fp16 values are exact in fp32, so against an oracle fed the same
+// fp16-rounded values only the accumulation order differs (fp32 noise ~5e-8).
+//
+// Decomposition (256-query tile, `mfma_scan_kernel`)
+//   * operand roles: A = corpus tile (M = 320 rows), B = query tile (N = 256 queries).  With this orientation the MFMA
+//     result layout puts ONE query in each lane (col = lane & 31) and 16 corpus rows in its 16 accumulator registers,
+//     so the epilogue's "does this score beat the query's current k-th best" test needs one threshold register per
+//     lane and one max3 chain + compare per 32 x 32 block.
+//   * workgroup = 4 waves (2 along rows x 2 along queries), one per SIMD with the whole 512-register budget: a
+//     160 x 128 sub-tile = 5 x 4 MFMA tiles each.  K advances in steps of 64 halves (whole 128-byte lines); both operand
+//     slabs are staged into a two-slot LDS ring by LDS-DMA (`buffer_load ... lds`, 16 B per lane) that runs ahead of the
+//     MFMAs across tile boundaries, with raw `s_barrier` and explicit `s_waitcnt`.  Details in the kernel's header.
+//   * a workgroup owns one query tile and one contiguous range of corpus rows and walks that range tile by tile
+//     (persistent); the workgroups that share a row range (one per query tile) get block ids congruent mod 8 so they
+//     run on the same XCD at the same time and the corpus tile is fetched from HBM once and re-read from that XCD's L2.
+//   * selection: per (workgroup, query) a candidate buffer of CAPW keys in global memory plus, in LDS, its fill count
+//     and the current admission threshold.  A score that beats the threshold is clipped, packed into a key and
+//     appended (one LDS atomic per lane per block).  A buffer that could overflow on the next tile is compacted to its
+//     BAND (`compact_buffer<CAPW, true>`: the k-th best score by bisection on the score bits, no sort; everything within 2 delta_q below it
+//     stays) and the threshold rises to the band's cut.  At the end of a launch the buffers are left as they are;
+//     `select_band_kernel` (one workgroup per QUERY) picks the band over all row ranges and derives the next admission threshold.
+//   * the host scans the corpus in phases of growing size (threshold ladder, tavb_route.hip): the k-th best score after a
+//     phase seeds the admission thresholds of the next (`thr_in`).
+//
+// Two kernel families share the parameter block and the compaction of tavb_tile.h: the 256-query fp16 tile described
+// above (this file) and a 32/64-query tile (`skinny_scan_kernel`, tavb_mfma_skinny.hip) for fp32 and fp16 corpora that carries small
+// batches -- and every batch on the reference's fp32 layout -- at HBM speed; `select_band_kernel` is in tavb_select.hip.  On fp16
+// corpora the 256-query tile multiplies fp16-ROUNDED queries: it is used as an exact filter, its candidates are rescored with the
+// fp32 queries (tavb_rescore.hip).
+
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "tavb_tile.h"
+
+namespace tavb {
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// The 256-query tile: four waves with the whole register file each, K steps of whole cache lines.
+// (Round 1 shipped an 8-wave 256 x 256 tile with K steps of 32 halves -- "variant 3" -- and a 4-wave 384 x 256 one --
+// "variant 5"; this kernel, "variant 6" in the profiles, replaced both: profiles/r02_cfg3_ablation.md.)
+//
+// Why four waves: an 8-wave 256 x 256 tile sits on the machine balance between the L2 -> CU operand path and the
+// matrix pipe (32 KiB of operands per 256 x 256 x 32 step).  Fewer operand bytes per flop needs a bigger tile per CU,
+// and the biggest one the register file allows is held by FOUR waves (2 x 2), one per SIMD, each with the full
+// 512-register budget.  hipcc picks the AGPR or the VGPR form of an MFMA builtin per FUNCTION, so > 256 accumulators
+// cannot be split over the two files through the builtin (hundreds of spills); the MFMAs are therefore inline asm with
+// explicit register classes ("+a" / "+v").  A volatile asm is ordered against memory operations, so the program order
+// -- MFMA, LDS read, MFMA, ..., MFMA, LDS-DMA -- IS the schedule (no sched_group_barrier).  The asm MFMAs are invisible
+// to the compiler's hazard recognizer: the epilogue opens with the wait states an MFMA result needs.
+//
+// Why whole lines: with K steps of 32 halves a staging piece is sixteen 64-byte HALF lines; the CU's
+// texture-address path serves a 1 KiB piece of that shape in ~14 ns from L2 against ~7.7 ns for eight whole 128-byte
+// lines (tools/microbench/load_paths.hip, all CUs pulling; profiles/r02_operand_path.md).  A round-1 four-wave kernel
+// with 32-half steps kept that path ~90 % busy and its waves stalled at the ISSUE of their staging loads.  Here a K
+// step is 64 halves = one 128-byte line per row:
+//   * tile = 320 corpus rows x 256 queries; a wave owns 160 x 128 = 5 x 4 MFMA tiles (320 accumulator registers: 15
+//     tiles in AGPRs, 5 in VGPRs; the spare AGPRs are where the register allocator parks VGPR values during the
+//     epilogue -- with all 256 taken it parks them in scratch, and a scratch reload is a VMEM load queued behind the
+//     whole in-flight LDS-DMA).  (384 rows at K = 64 need 2 x 80 KiB of LDS: all 160 KiB, nothing left for the
+//     selection state.)
+//   * LDS: two slots per operand (A 40 KiB, B 32 KiB each) = 144 KiB.  Rows are 128 bytes; 16-byte slot j of row r
+//     sits at physical slot j ^ ((r >> 1) & 7) (applied to the global SOURCE address of the staging loads, because
+//     LDS-DMA writes lane-linear, and to the fragment reads), which spreads the 16 lanes of every ds_read_b128 group
+//     over the 16 bank slots: SQ_LDS_BANK_CONFLICT = 0 measured.
+//   * staging goes through buffer descriptors (`buffer_load_dwordx4 ... lds`): the per-lane part of an address is one
+//     of two persistent 32-bit VGPR offsets (even / odd piece: the swizzle term has a piece-parity bit), the piece and the
+//     K step are the scalar offset, the tile is the descriptor base, and rows past the end of the corpus are cut off by
+//     the descriptor's size (they read as zero; the epilogue masks them anyway).  A piece = 8 rows x 128 bytes; per
+//     step 40 A + 32 B pieces = 18 per wave (the 32-half form needed 40 per wave for the same K range).
+//   * a step is four quarters (k16 slices) of 20 MFMAs.  Quarter q multiplies fragment set q & 1 while the 9
+//     fragment reads of the next quarter fill the other set; one barrier per step, in front of quarter 3:
+//       q0, q1, q2: multiply slices 0-2 of slot P; fetch slices 1-3 of slot P
+//       ---- vmcnt(0): this wave's pieces of step S+1 landed; lgkmcnt(0): slot P read out; s_barrier ----
+//       q3: multiply slice 3; fetch slice 0 of slot P^1 (step S+1, across tile boundaries too)
+//     Slot P is then free: the pieces of step S+2 are issued behind the MFMAs of q3 (N3 of them), of the next q0 (N0)
+//     and q1 (N1) -- corpus pieces first, they have the longest way -- and have until the next barrier to land.
+//   * the first quarter of a tile multiplies into a ZERO C operand instead of clearing 320 registers.
+//   * NI = 2 (the 128-query width, WideGeom<2>): a wave owns 160 x 64 = 10 accumulator blocks, all in AGPRs; half the MFMAs per
+//     step no longer cover the loaded HBM latency with one corpus slab in flight, and this width has the LDS for a THIRD
+//     corpus slot (3 x 40 + 2 x 16 KiB): a round then stages query slab S + 1 first and corpus slab S + 2 behind it, and the
+//     wait in front of quarter 3 is counted (`vmcnt(10)`: everything but the ten corpus pieces of slab S + 2 has landed).
+//     HBM-bound: 5.8 TB/s at 128 queries (profiles/r02_mid_batch.md).
+//   * M16 (the default of the 256-query filter tile, option mfma_shape = 16; profiles/r09_mfma_shape.md): the same tile, ring, barrier and
+//     epilogue on v_mfma_f32_16x16x32_f16.  The kernel runs at the board's power limit; in bare MFMA loops on random data the chip held a
+//     higher clock on this shape at the same cycles per flop, which is the expected source of the gain (profiles/r09_mfma_shape.md).  A wave's 160 x 128 is 10 x 8 blocks of 16 x 16 (f32x4: the same 320 registers, 60 blocks in AGPRs, 20 in
+//     VGPRs); a quarter is one k32 slice x one 80-row half x the 8 query fragments = 40 MFMAs, the four quarters of a step (rows 0-79, k32 #0)
+//     (80-159, #0) (0-79, #1) | barrier | (80-159, #1).  Row fragments double-buffer (5 + 5); the 8 query fragments serve two quarters and are
+//     reloaded in place in quarters 1 and 3, so the operands stay at 72 registers.  Per k32 slice a wave still reads 10 row and 8 query
+//     fragments of 1 KiB: LDS bytes per flop are unchanged.  The SPLIT and BD forms and the 128-query tile stay on 32x32x16.
+// Measured and rejected (profiles/r02_cfg3_ablation.md): touching the corpus lines of the step 1 / 2 / 4 steps ahead
+// into L2 with one 4-byte load per line (-3 .. -6 %); other piece-per-quarter schedules (no difference).
+// ---------------------------------------------------------------------------------------------
+constexpr int SLOT_A6 = BM6 * 128;  // 40 KiB
+constexpr int PIECES_A6 = BM6 / 8 / 4;  // per wave per step: 10
+
+// NI = 32-query MFMA blocks per wave along the query axis: 4 (256-query workgroup tile) or 2 (128-query tile, for batches of
+// 65 .. 128 queries: half the MFMAs and half the query-operand traffic per corpus byte -- HBM-bound instead of padding-bound)
+template <int NI>
+struct WideGeom {
+  static constexpr int QT = 64 * NI;           // queries per workgroup tile
+  static constexpr int WQ = 32 * NI;           // ... per wave
+  static constexpr int NT = 5 * NI;            // 32 x 32 accumulator blocks per wave: 20 or 10
+  static constexpr int NA = NI == 4 ? 15 : NT; // blocks 0 .. NA-1 accumulate in AGPRs, the rest in VGPRs (the spare AGPRs are where the allocator parks VGPR values in the epilogue: no scratch)
+  static constexpr int SLOT_B = QT * 128;      // 32 or 16 KiB
+  // corpus ring: the 128-query tile is HBM-bound and has the LDS for a third slot (3 x 40 + 2 x 16 KiB): the corpus slab of
+  // step S + 2 is in flight while step S is multiplied (one slab in flight left the tile latency-bound at 5.2 TB/s)
+  static constexpr int RA = NI == 2 ? 3 : 2;
+  static constexpr int B_RING = RA * SLOT_A6;  // the query ring (always two slots) sits behind the corpus ring
+  static constexpr int CTRL = B_RING + 2 * SLOT_B;
+  static constexpr int LDS = CTRL + QT * 8 + 16;
+  static constexpr int PIECES_B = QT / 8 / 4;  // per wave per step: 8 or 4
+  static constexpr int PIECES = PIECES_A6 + PIECES_B;
+};
+
+// index of the staging piece issued behind MFMA `i` of quarter `q` (-1: none): n pieces spread evenly over the NT MFMAs
+template <int NT, int N3, int N0, int N1>
+constexpr int staging_piece_at(int q, int i) {
+  const int n = q == 3 ? N3 : q == 0 ? N0 : q == 1 ? N1 : 0;
+  const int base = q == 3 ? 0 : q == 0 ? N3 : N3 + N0;
+  for (int j = 0; j < n; ++j)
+    if ((j * NT + NT / 2) / n == i) return base + j;
+  return -1;
+}
+
+// M16 issue order of a 40-MFMA quarter: MFMA i multiplies row fragment m16_row_frag(i) by query fragment m16_query_frag(i) (query fragment
+// outermost); m16_last_reader: the last MFMA of a quarter that reads a given query (or row) fragment as an operand
+constexpr int m16_query_frag(int i) { return i / 5; }
+constexpr int m16_row_frag(int i) { return i % 5; }
+constexpr int m16_last_reader(bool query, int f) {
+  int last = -1;
+  for (int i = 0; i < 40; ++i)
+    if ((query ? m16_query_frag(i) : m16_row_frag(i)) == f) last = i;
+  return last;
+}
+
+// One MFMA of the K loop as inline asm with an explicit register class for the accumulator (see "Why four waves"): the 16x16x32 or the 32x32x16
+// shape, C / D in AGPRs or VGPRs, accumulating or -- the first quarter of a tile -- multiplying into a zero C operand.
+template <bool M16, bool AGPR, bool ZERO_C, typename Acc>
+__device__ __forceinline__ void mfma_f16(Acc& acc, const f16x8& a, const f16x8& b) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+#define TAVB_MFMA_ASM(OP)                                                                                                                          \
+  if constexpr (ZERO_C && AGPR) asm volatile(OP " %0, %1, %2, 0" : "=a"(acc) : "v"(__builtin_bit_cast(i32x4, a)), "v"(__builtin_bit_cast(i32x4, b)));    \
+  else if constexpr (ZERO_C) asm volatile(OP " %0, %1, %2, 0" : "=&v"(acc) : "v"(__builtin_bit_cast(i32x4, a)), "v"(__builtin_bit_cast(i32x4, b)));      \
+  else if constexpr (AGPR) asm volatile(OP " %0, %1, %2, %0" : "+a"(acc) : "v"(__builtin_bit_cast(i32x4, a)), "v"(__builtin_bit_cast(i32x4, b)));        \
+  else asm volatile(OP " %0, %1, %2, %0" : "+v"(acc) : "v"(__builtin_bit_cast(i32x4, a)), "v"(__builtin_bit_cast(i32x4, b)))
+  if constexpr (M16) {
+    TAVB_MFMA_ASM("v_mfma_f32_16x16x32_f16");
+  } else {
+    TAVB_MFMA_ASM("v_mfma_f32_32x32x16_f16");
+  }
+#undef TAVB_MFMA_ASM
+}
+
+// SPLIT: the queries arrive as TWO fp16 planes (q = hi + lo to 2^-22) and a tile runs its K loop twice over the corpus rows, once per plane, into
+// the same accumulators: fp32 query x fp16 row like the 64-query exact tile, at the wide tile's rate -- the bounded fallback for batches in which
+// MANY queries have more near-duplicates than a band holds (tavb_rescore.hip).  Twice the MFMAs; only this instantiation pays for it.
+// BD ("B direct"): the query operand does not go through LDS at all.  The library lays the fp16 queries out in MFMA-FRAGMENT-MAJOR order (1 KiB per
+// (K step, k16 slice, 32-query block): lane l = query l & 31, halves 8 (l >> 5) .. + 7 of the slice -- query_prepare_kernel), so a fragment is ONE
+// coalesced 16 B-per-lane load out of L2 straight into the registers the MFMA reads; four register sets rotate, the loads run three quarters
+// (~1.2 us) ahead.  Per K step the LDS then moves 120 KiB instead of 216 (no query slab written, no query fragments read); the price is that
+// both row halves of the workgroup load the same fragments (L2 -> CU traffic 104 KiB per step instead of 72).
+template <int ABL, int NI, int N3, int N0, int N1, bool SPLIT = false, bool BD = false, bool M16 = false>
+__global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p) {
+  using G = WideGeom<NI>;
+  constexpr int BN = G::QT, NT = G::NT, SLOT_B6 = G::SLOT_B, PIECES_B6 = G::PIECES_B, B_RING6 = G::B_RING;
+  // BD: the 64 KiB the query ring occupied pay for a THIRD corpus slot -- a corpus piece then has more than a whole K step (~2 us) to land instead
+  // of 0.4 .. 1 step (the last pieces of a slab are issued in quarter 1 and needed behind quarter 2: an HBM round trip does not fit)
+  constexpr int RA = BD ? 3 : G::RA;
+  constexpr int CTRL6 = BD ? 3 * SLOT_A6 : G::CTRL;
+  constexpr int PIECES6 = BD ? PIECES_A6 : G::PIECES;
+  static_assert(!BD || (NI == 4 && !SPLIT), "the direct query operand is built for the 256-query tile");
+  static_assert(!M16 || (NI == 4 && !SPLIT && !BD), "the 16x16x32 form is built for the 256-query filter tile");
+  constexpr int QM = M16 ? 40 : NT;  // MFMAs per quarter
+  static_assert(N3 + N0 + N1 == PIECES6, "every piece of a step is issued exactly once");
+  static_assert(N3 <= QM && N0 <= QM && N1 <= QM && NI + 5 <= NT, "one piece / one fragment read behind an MFMA at most");
+  // ABL: what a measurement variant leaves out or changes (launch_mfma_scan; results are garbage unless only the issue order changes)
+  constexpr bool NO_MFMA = (ABL & 1) != 0;            // no MFMAs
+  constexpr bool NO_STAGING = (ABL & 2) != 0;         // no LDS-DMA
+  constexpr bool CORPUS_RESIDENT = (ABL & 4) != 0;    // corpus tile 0 re-read by every block (L2 resident)
+  constexpr bool QUERY_RESIDENT = (ABL & 8) != 0;     // the query operand's K step 0 every time (cache resident)
+  constexpr bool NO_FRAG_READS = (ABL & 32) != 0;     // no fragment reads
+  constexpr bool QUERY_MAJOR = (ABL & 1024) != 0;     // MFMA issue order: query fragment outermost
+  constexpr bool SERPENTINE = (ABL & 2048) != 0;      // ... either order walked boustrophedon
+  constexpr bool NO_ADMIT = (ABL & ~(1024 | 2048)) != 0;  // no admissions (bit 256 alone, and with every other ablation; the issue order is no ablation)
+  extern __shared__ __align__(16) unsigned char smem[];
+  float* thr_lds = reinterpret_cast<float*>(smem + CTRL6);
+  int* cnt_lds = reinterpret_cast<int*>(smem + CTRL6 + BN * 4);
+  lds_flag* need_compact = (lds_flag*)(smem + CTRL6 + BN * 8);
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1;  // rows wm * 160 ..
+  const int wn = wave & 1;   // queries wn * 32 * NI ..
+
+  const int b = blockIdx.x;
+  const int xcd = b & 7;
+  const int t = b >> 3;
+  const int qtile = t % p.n_qtiles;
+  const int split = (t / p.n_qtiles) * 8 + xcd;
+  if (split >= p.n_splits) return;
+  if (p.gate != nullptr && *p.gate > p.gate_max) return;  // most of the batch is going to the exact form anyway: this filter phase would be wasted work
+  int live_q = p.nq;  // queries that exist: the batch, or -- for a fixed-shape launch over a device-side work list (tavb_rescore.hip) -- the slots in use
+  if (p.active != nullptr) {  // nothing to do, or not this kernel's share
+    const int live = *p.active;
+    if (live <= p.active_min || live > p.active_max || qtile * BN >= live) return;
+    live_q = live < live_q ? live : live_q;
+  }
+  const int64_t r_begin = (int64_t)split * p.rows_per_split;
+  const int64_t r_end = (r_begin + p.rows_per_split < p.rows) ? r_begin + p.rows_per_split : p.rows;
+  const int logical_block = split * p.n_qtiles + qtile;
+  u64* my_cand = p.cand + (size_t)logical_block * BN * CAPW;
+  int* my_counts = p.counts + (size_t)logical_block * BN;
+
+  const float thr0 = (p.min_score > 0.0f) ? __uint_as_float(__float_as_uint(p.min_score) - 1u) : -__builtin_inff();
+  for (int i = tid; i < BN; i += NT6) {
+    // NaN threshold admits nothing; neither does one above 1 (scores are clipped to [0, 1]) -- with that, `score > thr` alone implies
+    // `clip(score) >= min_score` (thr >= the float below min_score), and the epilogue needs no second test per row
+    float t0 = (p.min_score != p.min_score || p.min_score > 1.0f) ? __builtin_inff() : thr0;
+    const int qg0 = qtile * BN + i;
+    // padding queries -- and the unused slots of the last live tile of a work list: zero queries, every row scores 0.5, and from the second
+    // ladder phase on their thr_in is NaN (the select kernel skips them), so without this they would admit every row of the big phases --
+    // admit nothing
+    if (qg0 >= live_q) t0 = __builtin_inff();
+    else if (p.thr_in && p.thr_in[qg0] > t0) t0 = p.thr_in[qg0];  // k-th best so far: a valid lower bound
+    thr_lds[i] = t0;
+    cnt_lds[i] = 0;
+  }
+  if (tid == 0) *need_compact = 0;
+
+  const int D = p.dim;
+  const int steps_per_plane = D / 64;
+  const int steps_per_tile = SPLIT ? 2 * steps_per_plane : steps_per_plane;
+  const uint32_t row_bytes = (uint32_t)D * 2u;
+  const char* corpus = reinterpret_cast<const char*>(p.corpus);
+  const char* qbase = reinterpret_cast<const char*>(p.queries) + (size_t)qtile * BN * row_bytes;
+  const int n_tiles = (r_end > r_begin) ? (int)((r_end - r_begin + BM6 - 1) / BM6) : 0;
+  if (n_tiles == 0) {
+    for (int i = tid; i < BN; i += NT6) my_counts[i] = 0;  // empty row range: empty buffers
+    return;
+  }
+
+  // ---- per-lane constants of the K loop: two staging offsets (even / odd piece), three fragment-address terms.
+  //      Staging: lane l = row l >> 3 of an 8-row piece, PHYSICAL 16-byte slot l & 7, which holds logical slot
+  //      (l & 7) ^ ((row >> 1) & 7); with row = 8 * piece + (l >> 3) that is (l & 7) ^ (4 * (piece & 1) + (l >> 4)).
+  int st_even, st_odd;
+  uint32_t frag_x, a_lane, b_lane;
+  uint32_t frag_x16, a_lane16, b_lane16;  // M16: lane l = row / query l & 15 of a 16-row fragment, halves 8 (l >> 4) .. + 7 of a k32 slice
+  {
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
+    const uint32_t lane_row = (uint32_t)(ln >> 3);
+    st_even = (int)(lane_row * row_bytes + (uint32_t)(((ln & 7) ^ (ln >> 4)) * 16));
+    st_odd = (int)(lane_row * row_bytes + (uint32_t)(((ln & 7) ^ (4 + (ln >> 4))) * 16));
+    const int frag_row = ln & 31;
+    frag_x = (uint32_t)(((ln >> 5) ^ ((frag_row >> 1) & 7)) << 4);  // byte (k16 << 5) ^ frag_x within the 128-byte row
+    a_lane = (uint32_t)((wm * 160 + frag_row) * 128);              // + mi * 4096
+    b_lane = (uint32_t)(B_RING6 + (wn * G::WQ + frag_row) * 128);    // + ni * 4096
+    const int frag_row16 = ln & 15;
+    frag_x16 = (uint32_t)(((ln >> 4) ^ ((frag_row16 >> 1) & 7)) << 4);  // byte (k32 << 6) ^ frag_x16 within the 128-byte row
+    a_lane16 = (uint32_t)((wm * 160 + frag_row16) * 128);              // + row fragment * 2048
+    b_lane16 = (uint32_t)(B_RING6 + (wn * G::WQ + frag_row16) * 128);    // + query fragment * 2048
+  }
+  const __amdgpu_buffer_rsrc_t rsrc_b =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sgpr_ptr(qbase)), 0, (int)(BN * row_bytes) + (SPLIT ? (int)p.split_plane : 0), 0x00020000);
+  const int plane_jump = SPLIT ? (int)p.split_plane - steps_per_plane * 128 : 0;  // K step s >= steps_per_plane reads step s - steps_per_plane of the low plane
+
+  // ---- stager.  A "round" is what one K step issues: two slots deep (256-query tile) round S = corpus slab S + 1 then query
+  //      slab S + 1; three corpus slots deep (128-query tile) round S = query slab S + 1 FIRST, then corpus slab S + 2, so that
+  //      the counted wait of step S ("everything but the newest PIECES_A6 loads has landed") covers query slab S + 1 and corpus
+  //      slab S + 1 while corpus slab S + 2 stays in flight.  Piece IDX of a round: its position in that order.
+  int sa_kt = 0, sa_tile = 0, sa_slot = 0;  // corpus slab being staged
+  int sb_kt = 0, sb_slot = 0;               // query slab being staged
+  auto stage_a = [&](auto j_tag) {
+    constexpr int J = decltype(j_tag)::value;
+    const int tile = sa_tile < n_tiles ? sa_tile : n_tiles - 1;  // past the end: harmless reloads of the last tile
+    const int64_t row0 = CORPUS_RESIDENT ? 0 : r_begin + (int64_t)tile * BM6;
+    const int64_t left = p.rows - row0;
+    const int valid = (int)(left < BM6 ? left : BM6);  // rows past the end of the corpus read as zero (masked in the epilogue)
+    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(sgpr_ptr(corpus + (size_t)row0 * row_bytes)), 0, __builtin_amdgcn_readfirstlane(valid * (int)row_bytes), 0x00020000);
+    const int pc = wave * PIECES_A6 + J;
+    unsigned char* la = smem + sa_slot * SLOT_A6 + pc * 1024;
+    const int a_kt = (SPLIT && sa_kt >= steps_per_plane) ? sa_kt - steps_per_plane : sa_kt;  // second plane: the same corpus columns again
+    const int soff = __builtin_amdgcn_readfirstlane(a_kt * 128 + pc * 8 * (int)row_bytes);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_void*)la, 16, (J & 1) ? st_odd : st_even, soff, 0, 0);
+    if constexpr (J == PIECES_A6 - 1) {
+      sa_slot = (sa_slot + 1 == RA) ? 0 : sa_slot + 1;
+      const bool wrap = (sa_kt + 1 == steps_per_tile);
+      sa_kt = wrap ? 0 : sa_kt + 1;
+      sa_tile += wrap ? 1 : 0;
+    }
+  };
+  auto stage_b = [&](auto j_tag) {
+    constexpr int BJ = decltype(j_tag)::value;
+    const int pc = wave * PIECES_B6 + BJ;
+    unsigned char* lb = smem + B_RING6 + sb_slot * SLOT_B6 + pc * 1024;
+    const int soff = __builtin_amdgcn_readfirstlane((QUERY_RESIDENT ? 0 : sb_kt * 128 + ((SPLIT && sb_kt >= steps_per_plane) ? plane_jump : 0)) +
+                                                    pc * 8 * (int)row_bytes);  // ablation 8: the query operand's K step 0 every time (cache resident)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void*)lb, 16, (BJ & 1) ? st_odd : st_even, soff, 0, 0);
+    if constexpr (BJ == PIECES_B6 - 1) {
+      sb_slot ^= 1;
+      sb_kt = (sb_kt + 1 == steps_per_tile) ? 0 : sb_kt + 1;
+    }
+  };
+  auto stage_piece = [&](auto idx_tag) {
+    constexpr int IDX = decltype(idx_tag)::value;
+    if constexpr (BD) {
+      stage_a(std::integral_constant<int, IDX>{});
+    } else if constexpr (RA == 2) {
+      if constexpr (IDX < PIECES_A6) stage_a(std::integral_constant<int, IDX>{});
+      else stage_b(std::integral_constant<int, IDX - PIECES_A6>{});
+    } else {
+      if constexpr (IDX < PIECES_B6) stage_b(std::integral_constant<int, IDX>{});
+      else stage_a(std::integral_constant<int, IDX - PIECES_B6>{});
+    }
+  };
+  auto stage_range = [&]<int... I>(std::integer_sequence<int, I...>) { (stage_piece(std::integral_constant<int, I>{}), ...); };
+  auto stage_a_all = [&]<int... I>(std::integer_sequence<int, I...>) { (stage_a(std::integral_constant<int, I>{}), ...); };
+
+  // ---- prologue: step 0 whole (three slots: and corpus slab 1), then the first N3 pieces of round 0 (what quarter 3 of a
+  //      step "-1" would have issued)
+  if constexpr (RA == 2) {
+    stage_range(std::make_integer_sequence<int, PIECES6>{});
+    stage_range(std::make_integer_sequence<int, N3>{});
+    wait_vmcnt<N3>();
+  } else {
+    stage_a_all(std::make_integer_sequence<int, PIECES_A6>{});  // corpus slab 0
+    stage_range(std::make_integer_sequence<int, PIECES6>{});    // "round -1": query slab 0, corpus slab 1
+    stage_range(std::make_integer_sequence<int, N3>{});
+    wait_vmcnt<PIECES_A6 + N3>();
+  }
+  __syncthreads();  // step 0 landed everywhere, thresholds initialised (the waits above are counted: nothing is drained)
+
+  // M16: 10 x 8 blocks of 16 x 16 (f32x4) per wave, the same 320 registers; the 20 blocks of rows 80 .. 159 x queries 64 .. 127 of the wave
+  // accumulate in VGPRs, the other 60 in AGPRs (the 32 x 32 form's 15 / 5 split)
+  using Acc = std::conditional_t<M16, f32x4, f32x16>;
+  constexpr int NACC = M16 ? 80 : NT;
+  constexpr int NA_TILES = M16 ? 60 : G::NA;
+  Acc acc_a[NA_TILES];
+  Acc acc_v[NACC - NA_TILES > 0 ? NACC - NA_TILES : 1];
+
+  f16x8 a0[5], b0[M16 ? 2 * NI : NI], a1[5], b1[M16 ? 1 : NI];  // M16: b0 = the wave's 8 query fragments of a k32 slice (b1 unused)
+  f16x8 b2[BD ? NI : 1], b3[BD ? NI : 1];  // BD: four rotating sets of query fragments (quarter q multiplies set q, the loads for quarter q + 3 fill set (q + 3) & 3)
+  constexpr int BQ_SLICE = (BN / 32) * 1024;  // bytes of one k16 slice of the tile's queries in fragment-major order
+  int bq_soff = 0;                            // BD: byte offset (from the tile's queries) of the slice to load next; wraps with the tile
+  const int bq_tile_bytes = BN * (int)row_bytes;
+  int bq_voff = 0;
+  auto bq_load = [&](f16x8(&dst)[BD ? NI : 1]) {  // one slice: this wave's NI fragments (its half of the tile's query blocks)
+    if constexpr (BD) {
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+        dst[ni] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, bq_voff + ni * 1024, bq_soff, 0));
+      bq_soff = (bq_soff + BQ_SLICE == bq_tile_bytes) ? 0 : bq_soff + BQ_SLICE;
+    }
+  };
+  {
+    const unsigned char* abase = smem + (a_lane + frag_x);
+    const unsigned char* bbase = smem + (b_lane + frag_x);
+    if constexpr (BD) {
+      int zero_b = 0;
+      asm volatile("" : "+v"(zero_b));
+      const int ln_b = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero_b));
+      bq_voff = ln_b * 16 + wn * NI * 1024;
+      bq_load(b0);
+      bq_load(b1);
+      bq_load(b2);
+    } else if constexpr (M16) {
+      const unsigned char* abase16 = smem + (a_lane16 + frag_x16);
+      const unsigned char* bbase16 = smem + (b_lane16 + frag_x16);
+#pragma unroll
+      for (int n = 0; n < 2 * NI; ++n) b0[n] = *reinterpret_cast<const f16x8*>(bbase16 + n * 2048);
+#pragma unroll
+      for (int m = 0; m < 5; ++m) a0[m] = *reinterpret_cast<const f16x8*>(abase16 + m * 2048);
+    } else {
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) b0[ni] = *reinterpret_cast<const f16x8*>(bbase + ni * 4096);
+    }
+    if constexpr (!M16) {
+#pragma unroll
+      for (int mi = 0; mi < 5; ++mi) a0[mi] = *reinterpret_cast<const f16x8*>(abase + mi * 4096);
+    }
+  }
+  int rd = 0, rd_a = 0;  // ring slots (query, corpus) of the step being multiplied
+
+  // One quarter: the NT MFMAs of one k16 slice on (fa, fb); behind them, in program order, the NI + 5 fragment reads of the
+  // next quarter (slot `nslot`, slice NKK) into (na, nb) and the staging pieces the schedule puts into quarter Q.
+  auto quarter = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&fb)[NI], f16x8(&na)[5], f16x8(&nb)[NI], int nslot_a, int nslot, auto nkk_tag) {
+    constexpr int Q = decltype(q_tag)::value;
+    constexpr bool FIRST = decltype(first_tag)::value;  // first quarter of a tile: C = 0
+    constexpr int NKK = decltype(nkk_tag)::value;
+    const uint32_t kx = (uint32_t)(NKK << 5) ^ frag_x;
+    const unsigned char* abase = smem + nslot_a * SLOT_A6 + (a_lane + kx);
+    const unsigned char* bbase = smem + nslot * SLOT_B6 + (b_lane + kx);
+    auto mfma_at = [&](auto i_tag) {
+      constexpr int I = decltype(i_tag)::value;
+      // issue order of the NT MFMAs of a slice (measurement, profiles/r06_mfma_power.md): corpus fragment outermost (ships), query fragment
+      // outermost (QUERY_MAJOR: the operand whose bits the board's power follows more closely stays put for five MFMAs), and either walked
+      // boustrophedon (SERPENTINE: exactly one operand changes between any two consecutive MFMAs)
+      constexpr int outer = QUERY_MAJOR ? I / 5 : I / NI;
+      constexpr int inner0 = QUERY_MAJOR ? I % 5 : I % NI;
+      constexpr int inner = (SERPENTINE && (outer & 1)) ? (QUERY_MAJOR ? 4 : NI - 1) - inner0 : inner0;
+      constexpr int mi = QUERY_MAJOR ? inner : outer, ni = QUERY_MAJOR ? outer : inner;
+      constexpr int J = mi * NI + ni;  // the accumulator block
+      if constexpr (!NO_MFMA) {
+        if constexpr (J < NA_TILES)
+          mfma_f16<false, true, FIRST>(acc_a[J], fa[mi], fb[ni]);
+        else
+          mfma_f16<false, false, FIRST>(acc_v[J - NA_TILES], fa[mi], fb[ni]);
+      }
+      if constexpr (!NO_FRAG_READS) {
+        if constexpr (BD) {  // the slice three quarters ahead, straight from L2 into the set the previous quarter has just finished with
+          if constexpr (I < NI) nb[I] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, bq_voff + I * 1024, bq_soff, 0));
+        } else {
+          if constexpr (I < NI) nb[I] = *reinterpret_cast<const f16x8*>(bbase + I * 4096);
+        }
+        if constexpr (I >= NI && I < NI + 5) na[I - NI] = *reinterpret_cast<const f16x8*>(abase + (I - NI) * 4096);
+      }
+      if constexpr (!NO_STAGING) {
+        constexpr int PC = staging_piece_at<NT, N3, N0, N1>(Q, I);
+        if constexpr (PC >= 0) stage_piece(std::integral_constant<int, PC>{});
+      }
+    };
+    [&]<int... I>(std::integer_sequence<int, I...>) { (mfma_at(std::integral_constant<int, I>{}), ...); }
+    (std::make_integer_sequence<int, NT>{});
+    if constexpr (BD) bq_soff = (bq_soff + BQ_SLICE == bq_tile_bytes) ? 0 : bq_soff + BQ_SLICE;
+    if constexpr (NO_MFMA) asm volatile("" ::"v"(fa[0]), "v"(fa[4]), "v"(fb[0]), "v"(fb[NI - 1]));
+  };
+  // M16 quarter Q: the 5 row fragments of rows 80 H .. 80 H + 79 (H = Q & 1) of k32 slice Q >> 1 (fa) x the 8 query fragments of that slice (b0),
+  // query fragment outermost: MFMA i = 5 n + m multiplies row fragment m by query fragment n.  Behind them, in program order: the 5 row fragments of
+  // the next quarter (the other row half; slot `nslot_a`, k32 slice NKK) into na, and the query fragments IN PLACE -- in quarters 1 and 3 all
+  // eight, of slice NKK (the next quarter's), b0[n] behind MFMA 5 n + 9, the last one, b0[7], behind MFMA 5 of the next quarter.  Every fragment
+  // read thus sits at least five MFMAs behind the last MFMA that reads its register as SrcA / SrcB (the row fragments: a0[m] / a1[m] is last read
+  // by MFMA 35 + m and reloaded behind MFMA m of the next quarter).  The ISA's table of required wait states for XDL (MFMA) operations has a
+  // write-after-read row for SrcC only ("XDL read VGPR SrcC, VALU write of the same VGPR": 3 wait states at four passes); SrcA / SrcB are read
+  // when the MFMA issues.  Five MFMA issues cover even the SrcC figure, so no s_nop is needed anywhere in the loop (the static_asserts below
+  // measure each distance from the issue order, m16_query_frag / m16_row_frag).
+  auto quarter16 = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&na)[5], int nslot_a, int nslot, auto nkk_tag) {
+    constexpr int Q = decltype(q_tag)::value;
+    constexpr bool FIRST = decltype(first_tag)::value;  // first quarter of a tile for these accumulators: C = 0
+    constexpr int NKK = decltype(nkk_tag)::value;
+    constexpr int H = Q & 1;
+    const uint32_t kx = (uint32_t)(NKK << 6) ^ frag_x16;
+    const unsigned char* abase = smem + nslot_a * SLOT_A6 + (a_lane16 + (H ^ 1) * 5 * 2048 + kx);
+    const unsigned char* bbase = smem + nslot * SLOT_B6 + (b_lane16 + kx);
+    auto mfma_at = [&](auto i_tag) {
+      constexpr int I = decltype(i_tag)::value;
+      constexpr int n = m16_query_frag(I), m = m16_row_frag(I), mr = 5 * H + m;
+      constexpr bool VB = mr >= 5 && n >= 4;  // accumulator block in VGPRs
+      constexpr int J = VB ? (mr - 5) * 4 + (n - 4) : (mr < 5 ? mr * 8 + n : 40 + (mr - 5) * 4 + n);
+      if constexpr (!NO_MFMA) {
+        if constexpr (VB)
+          mfma_f16<true, false, FIRST>(acc_v[J], fa[m], b0[n]);
+        else
+          mfma_f16<true, true, FIRST>(acc_a[J], fa[m], b0[n]);
+      }
+      if constexpr (!NO_FRAG_READS) {
+        // a reload sits behind MFMA I of this quarter; its register was last read by MFMA m16_last_reader(...) of the previous quarter (row
+        // fragments, b0[7]) or of this one (b0[0 .. 6]): the distance counts the MFMAs issued in between, from the issue order itself
+        if constexpr (I < 5) {
+          static_assert(I + QM - m16_last_reader(false, I) >= 5, "five MFMAs between the last read of a row fragment and its reload");
+          na[I] = *reinterpret_cast<const f16x8*>(abase + I * 2048);
+        }
+        if constexpr ((Q & 1) == 1 && I >= 9 && (I - 9) % 5 == 0) {
+          static_assert(I - m16_last_reader(true, (I - 9) / 5) >= 5, "five MFMAs between the last read of a query fragment and its reload");
+          b0[(I - 9) / 5] = *reinterpret_cast<const f16x8*>(bbase + ((I - 9) / 5) * 2048);
+        }
+        if constexpr ((Q & 1) == 0 && I == 5) {
+          static_assert(I + QM - m16_last_reader(true, 7) >= 5, "five MFMAs between the last read of a query fragment and its reload");
+          b0[7] = *reinterpret_cast<const f16x8*>(bbase + 7 * 2048);
+        }
+      }
+      if constexpr (!NO_STAGING) {
+        constexpr int PC = staging_piece_at<QM, N3, N0, N1>(Q, I);
+        if constexpr (PC >= 0) stage_piece(std::integral_constant<int, PC>{});
+      }
+    };
+    [&]<int... I>(std::integer_sequence<int, I...>) { (mfma_at(std::integral_constant<int, I>{}), ...); }
+    (std::make_integer_sequence<int, QM>{});
+    if constexpr (NO_MFMA) asm volatile("" ::"v"(fa[0]), "v"(fa[4]), "v"(b0[0]), "v"(b0[7]));
+  };
+  using Q0 = std::integral_constant<int, 0>;
+  using Q1 = std::integral_constant<int, 1>;
+  using Q2 = std::integral_constant<int, 2>;
+  using Q3 = std::integral_constant<int, 3>;
+  auto step = [&](auto first_tag) {
+    if constexpr (M16) {
+      // (rows 0-79, k32 #0) (rows 80-159, #0) (rows 0-79, #1) | barrier | (rows 80-159, #1): the first two quarters of a tile start the accumulators
+      quarter16(Q0{}, first_tag, a0, a1, rd_a, rd, Q0{});
+      quarter16(Q1{}, first_tag, a1, a0, rd_a, rd, Q1{});
+      quarter16(Q2{}, std::false_type{}, a0, a1, rd_a, rd, Q1{});
+      if constexpr (!NO_STAGING) wait_vmcnt<0>();
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      TAVB_BARRIER();
+      const int nxt_a = rd_a ^ 1;
+      quarter16(Q3{}, std::false_type{}, a1, a0, nxt_a, rd ^ 1, Q0{});
+      rd ^= 1;
+      rd_a = nxt_a;
+    } else if constexpr (BD) {
+      quarter(Q0{}, first_tag, a0, b0, a1, b3, rd_a, rd, Q1{});
+      quarter(Q1{}, std::false_type{}, a1, b1, a0, b0, rd_a, rd, Q2{});
+      quarter(Q2{}, std::false_type{}, a0, b2, a1, b1, rd_a, rd, Q3{});
+      // corpus slab S+1 has landed in this wave: behind its last piece (quarter 1 of the PREVIOUS step) came five quarters' query-fragment loads
+      // (5 NI) and the ten pieces of slab S+2, which may all still be in flight (loads return in order: the count is exact)
+      if constexpr (!NO_STAGING) wait_vmcnt<5 * NI + PIECES_A6>();
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      TAVB_BARRIER();
+      const int nxt_a = rd_a + 1 == RA ? 0 : rd_a + 1;
+      quarter(Q3{}, std::false_type{}, a1, b3, a0, b2, nxt_a, rd, Q0{});
+      rd_a = nxt_a;
+    } else {
+      quarter(Q0{}, first_tag, a0, b0, a1, b1, rd_a, rd, Q1{});
+      quarter(Q1{}, std::false_type{}, a1, b1, a0, b0, rd_a, rd, Q2{});
+      quarter(Q2{}, std::false_type{}, a0, b0, a1, b1, rd_a, rd, Q3{});
+      // ---- step S+1 has landed in this wave (two slots: nothing newer is in flight; three: only corpus slab S+2 is); the
+      //      slots of step S are read out; meet
+      if constexpr (!NO_STAGING) wait_vmcnt<(RA == 2 ? 0 : PIECES_A6)>();
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) through the builtin: visible to the compiler's wait-count pass
+      TAVB_BARRIER();
+      const int nxt_a = (RA == 2) ? (rd_a ^ 1) : (rd_a + 1 == RA ? 0 : rd_a + 1);
+      quarter(Q3{}, std::false_type{}, a1, b1, a0, b0, nxt_a, rd ^ 1, Q0{});
+      rd ^= 1;
+      rd_a = nxt_a;
+    }
+  };
+
+  for (int tile = 0; tile < n_tiles; ++tile) {
+    const int64_t row0 = r_begin + (int64_t)tile * BM6;
+    const bool tile_full = row0 + BM6 <= r_end;  // wave-uniform: every row of this tile belongs to the row range
+    if constexpr (NO_MFMA) {  // MFMAs ablated: give the accumulators a value
+#pragma unroll
+      for (int i = 0; i < NA_TILES; ++i) acc_a[i] = Acc{};
+#pragma unroll
+      for (int i = 0; i < NACC - NA_TILES; ++i) acc_v[i] = Acc{};
+    }
+    step(std::true_type{});
+#pragma unroll 1
+    for (int kt = 1; kt < steps_per_tile; ++kt) step(std::false_type{});
+
+    // ---- epilogue: admission test on the raw dot products, append .  The asm MFMAs are invisible
+    //      to the compiler's hazard recognizer: a 32x32x16 MFMA needs 18 wait states before its result may be read (a 16x16x32 one fewer).
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    int zero_e = 0;
+    asm volatile("" : "+v"(zero_e));
+    const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero_e));
+    if constexpr (M16) {
+      // 16 x 16 blocks: lane l holds query l & 15 of its block, rows 4 (l >> 4) + r, r = 0 .. 3.  One test per (query fragment n, row half h): the
+      // 20 scores a lane holds there, 1280 per wave, all against the lane's one threshold.  Pass 0: the VGPR blocks (h = 1, n >= 4), pass 1: the rest.
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+          const int ql = wn * G::WQ + n * 16 + (lane_e & 15);
+          const float thr = thr_lds[ql];
+          const float thr_pre = fmaf(thr, 2.0f, -1.0f) - 4.8e-7f;  // score > thr implies dot > thr_pre (as in the 32 x 32 form)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            constexpr int VT = NACC - NA_TILES;
+            const bool vb = h == 1 && n >= 4;
+            if (vb != (pass == 0)) continue;
+            f32x4 dots[5];
+#pragma unroll
+            for (int m = 0; m < 5; ++m) {
+              const int mr = 5 * h + m;
+              dots[m] = vb ? acc_v[((mr - 5) * 4 + (n - 4) + VT) % VT] : acc_a[(mr < 5 ? mr * 8 + n : 40 + (mr - 5) * 4 + n) % NA_TILES];
+            }
+            float top = dots[0][0];
+#pragma unroll
+            for (int m = 0; m < 5; ++m)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) top = __builtin_fmaxf(top, dots[m][r]);
+            TAVB_SB();  // one group at a time
+            const bool any = !NO_ADMIT && (top > thr_pre);
+            if constexpr (NO_ADMIT) asm volatile("" ::"v"(top));
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+              // as in the 32 x 32 form: one v_cmp per accumulator register gives a wave mask of four rows x 16 queries in an SGPR pair
+              const int64_t row_base = row0 + wm * 160 + h * 80 + 4 * (lane_e >> 4);  // + 16 m + r
+              const int64_t left64 = r_end - row_base;
+              const int rows_left = tile_full ? 80 : (int)(left64 < 80 ? left64 : 80);
+#pragma unroll
+              for (int m = 0; m < 5; ++m) {
+                float sc[4];
+                u64 mk[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  sc[j] = fmaf(dots[m][j], 0.5f, 0.5f);
+                  asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(mk[j]) : "v"(sc[j]), "v"(thr));
+                }
+                if ((mk[0] | mk[1] | mk[2] | mk[3]) == 0ull) continue;  // wave-uniform
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  const int r_off = 16 * m + j;
+                  if (mk[j] == 0ull) continue;
+                  if (((mk[j] >> lane_e) & 1ull) != 0ull && r_off < rows_left) {
+                    const int pos = lds_add_rtn(&cnt_lds[ql], 1);
+                    if (pos + 1 > CAPW - BM6) lds_store_i32(need_compact, 1);
+                    float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
+                    s1 = (s1 > 1.0f) ? 1.0f : s1;
+                    if (pos < CAPW) my_cand[(size_t)ql * CAPW + pos] = make_key(s1, (uint32_t)(row_base + r_off) + p.index_base);
+                  }
+                }
+              }
+            }
+          }
+        }
+    } else {
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) {
+        const int ql = wn * G::WQ + ni * 32 + (lane_e & 31);
+        const float thr = thr_lds[ql];
+        const float thr_pre = fmaf(thr, 2.0f, -1.0f) - 4.8e-7f;  // score > thr implies dot > thr_pre: fma(dot, 0.5, 0.5) is monotone, the margin covers both roundings
+#pragma unroll
+        for (int mi = 0; mi < 5; ++mi) {
+          constexpr int VT = NT - NA_TILES > 0 ? NT - NA_TILES : 1;
+          if ((mi * NI + ni >= NA_TILES) != (pass == 0)) continue;  // pass 0: VGPR tiles, pass 1: AGPR tiles
+          const f32x16 dots = (mi * NI + ni < NA_TILES) ? acc_a[mi * NI + ni] : acc_v[(mi * NI + ni - NA_TILES + VT) % VT];
+          float top = dots[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) top = __builtin_fmaxf(top, dots[r]);
+          TAVB_SB();  // one block at a time
+          const bool any = !NO_ADMIT && (top > thr_pre);
+          if constexpr (NO_ADMIT) asm volatile("" ::"v"(top));
+          if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+            // (rare: ~1 % of the blocks once the ladder's thresholds are in -- but each costs the workgroup ~0.3 us, and a batch has a few hundred
+            //  thousand of them.)  One compare per row whose result is a WAVE mask in scalar registers (v_cmp into an SGPR pair: no per-lane
+            //  bit twiddling); a row nobody admits -- 15 of 16 in the usual case -- costs one scalar test.  An admitted row takes its slot
+            //  with one LDS atomic per admitting lane.  Rows past the end of the row range exist only in a range's last tile (wave-uniform).
+            const int64_t row_base = row0 + wm * 160 + mi * 32 + 4 * (lane_e >> 5);
+            // rows of this block that belong to the row range, seen from this lane's first row (>= 32: all of them)
+            const int64_t left64 = r_end - row_base;
+            const int rows_left = tile_full ? 64 : (int)(left64 < 64 ? left64 : 64);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {  // four rows at a time: their masks stay in scalar registers
+              float sc[4];
+              u64 m[4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                sc[j] = fmaf(dots[4 * g + j], 0.5f, 0.5f);
+                asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(m[j]) : "v"(sc[j]), "v"(thr));  // (the builtin ballot goes through a 0/1 VGPR and back)
+              }
+              if ((m[0] | m[1] | m[2] | m[3]) == 0ull) continue;  // wave-uniform: nobody admits any of the four
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const int r_off = j + 8 * g;  // row 4 g + j of the accumulator = tile row (r & 3) + 8 (r >> 2) from row_base
+                if (m[j] == 0ull) continue;
+                if (((m[j] >> lane_e) & 1ull) != 0ull && r_off < rows_left) {
+                  const int pos = lds_add_rtn(&cnt_lds[ql], 1);
+                  if (pos + 1 > CAPW - BM6) lds_store_i32(need_compact, 1);  // this buffer could overflow on the next tile
+                  float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
+                  s1 = (s1 > 1.0f) ? 1.0f : s1;
+                  if (pos < CAPW) my_cand[(size_t)ql * CAPW + pos] = make_key(s1, (uint32_t)(row_base + r_off) + p.index_base);
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    TAVB_BARRIER();
+    if (*need_compact != 0) {  // workgroup-uniform: read after the barrier
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      TAVB_BARRIER();
+      for (int q = wave; q < BN; q += NT6 / 64) {
+        const int n = cnt_lds[q];
+        if (n > CAPW - BM6) {
+          u64* buf = my_cand + (size_t)q * CAPW;
+          const int qg = qtile * BN + q;  // (a padding query admits nothing: never here)
+          const float band = p.band ? p.band[qg] : 0.0f;
+          float thr_excl;
+          uint32_t lost;
+          const int kept = compact_buffer<CAPW, true>(buf, n < CAPW ? n : CAPW, p.k, lane_e, band, CAPW - BM6 - 64, &thr_excl, &lost);
+          if (lane_e == 0) {
+            cnt_lds[q] = kept;
+            if (thr_excl > thr_lds[q]) thr_lds[q] = thr_excl;
+            if (lost != 0u && p.lost) atomicMax(&p.lost[qg], lost);  // (n > CAPW cannot happen: a tile appends at most BM6 keys)
+          }
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      TAVB_BARRIER();
+      if (tid == 0) *need_compact = 0;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      TAVB_BARRIER();
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the run-ahead LDS-DMA before the block retires
+  __syncthreads();
+
+  // the buffers stay unsorted: tavb::select_band_kernel picks the band over all workgroups' buffers of a query
+  for (int i = tid; i < BN; i += NT6) my_counts[i] = cnt_lds[i] < CAPW ? cnt_lds[i] : CAPW;
+}
+
+}  // namespace
+
+// 128-query tiles when they leave less padding than 256-query tiles (up to 128 queries: one HBM-bound pass instead of a
+// half-empty 256-query tile; 257 .. 384 and 513 .. 640: measured 6 % and 3.5 % faster, profiles/r02_mid_batch.md)
+int mfma_query_tile(int nq) {
+  const int n128 = (nq + 127) / 128;
+  return ((n128 & 1) && n128 <= 5) ? 128 : BN;
+}
+
+// ... and 128-query tiles on a corpus so small that 256-query tiles would give a CU fewer than four tiles to walk (query tiles x corpus
+// tiles <= 4 n_cu): twice the workgroups or half the tile, half the all-admitted epilogue of a workgroup's first tile -- 256 queries over
+// 1000 / 5000 / 20000 / 50000 fp16 rows 0.131 / 0.157 / 0.181 / 0.238 -> 0.090 / 0.116 / 0.141 / 0.197 ms (257 queries took three 128-query
+// tiles all along and were faster than 256), 1024 queries over 30720 / 50000 rows 0.317 / 0.380 -> 0.264 / 0.342 ms, 512 over 120000 rows
+// 0.392 -> 0.367; beyond that the wider tile's operand reuse wins (1024 queries over 250k rows: 0.910 against 0.927 ms).  tools/regime_sweep.py,
+// profiles/r06_regime_sweep.md
+int mfma_query_tile_for(int nq, int64_t rows, int n_cu) {
+  const int qt = mfma_query_tile(nq);
+  if (qt == 128) return qt;
+  const int64_t corpus_tiles = (rows + BM6 - 1) / BM6;
+  const int64_t wgs = (int64_t)((nq + BN - 1) / BN) * corpus_tiles;
+  return wgs <= 4 * (int64_t)n_cu ? 128 : qt;
+}
+
+// k: the band selection holds any k the fused selections serve (a band of k + its 2-delta neighbourhood has to fit the 640 keys a candidate
+// buffer keeps between compactions and the 1024 of the select kernel: k = 256 leaves the same slack as k = 32 on isotropic data)
+bool mfma_supported(int dim, int k) { return dim % BK == 0 && dim >= BK && dim <= 16384 && k >= 1 && k <= TAVB_MAX_FUSED_K; }
+
+int mfma_pick_splits(int64_t rows, int nq_padded, int tile, int n_cu) {
+  // One workgroup per CU and all of them resident at once: the grid is (groups of 8 row ranges) x query tiles x 8, so the
+  // number of row ranges is a multiple of 8 with groups * n_qtiles * 8 <= n_cu.  (85 ranges for 3 query tiles made 264
+  // workgroups on 256 CUs: a second scheduling round for the last 8, and a 768-query batch slower than a 1024-query one.)
+  const int n_qtiles = nq_padded / tile > 0 ? nq_padded / tile : 1;
+  int splits = (n_cu / (8 * n_qtiles)) * 8;
+  if (splits < 8) splits = 8;
+  const int64_t tiles = (rows + BM - 1) / BM;
+  if (splits > tiles) splits = (int)tiles;
+  return splits;
+}
+
+// candidate buffers of a launch: nq_padded = tiles x queries per tile; the 256-query tile has the deeper buffers
+size_t mfma_workspace_bytes(int n_splits, int nq_padded, bool wide) {
+  return (size_t)n_splits * (size_t)nq_padded * (wide ? CAPW : CAP) * sizeof(u64);
+}
+
+int mfma_tile_shape(const MfmaParams& p) {
+  // the 16x16x32 form exists for the 256-query filter tile (not SPLIT, not BD) and its two like-for-like ablations; everything else is 32x32x16
+  if (p.shape != 16 || p.wide_tile == 128 || p.split_plane > 0) return 32;
+  if (p.ablate != 0) return (p.ablate == 256 || p.ablate == 258) ? 16 : 32;
+  return (p.bdirect || p.sched != 0) ? 32 : 16;
+}
+
+hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream) {
+  const int tile = p.wide_tile == 128 ? 128 : BN;
+  if (!mfma_supported(p.dim, p.k) || p.nq_padded % tile != 0 || p.n_splits < 1) return hipErrorInvalidValue;
+  if (!p.workspace || !p.counts) return hipErrorInvalidValue;
+  MfmaDeviceParams d = fill_device_params(p, tile, BM6);
+  d.counts = p.counts;
+  d.band = p.band;
+  d.lost = p.lost;
+  d.split_plane = p.split_plane;
+  d.gate = p.gate;
+  d.gate_max = p.gate_max;
+  // grid: groups of 8 consecutive block ids = 8 different row ranges (one per XCD)
+  const int groups = (p.n_splits + 7) / 8;
+  const int grid = groups * d.n_qtiles * 8;
+  auto go = [&](auto kern, int threads, int lds) -> hipError_t {
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, d);
+    return hipGetLastError();
+  };
+  // `ablate` modes exist to time parts of a kernel (results are garbage): see profiles/r02_cfg3_ablation.md
+  {
+    if (p.dim % 64 != 0) return hipErrorInvalidValue;
+    constexpr int LDS256 = WideGeom<4>::LDS, LDS128 = WideGeom<2>::LDS;
+    if (p.split_plane > 0) {
+      if (tile != BN) return hipErrorInvalidValue;
+      return go(mfma_scan_kernel<0, 4, 8, 6, 4, true>, NT6, LDS256);
+    }
+    if (tile == 128) {
+      switch (p.ablate) {  // (measurement: what bounds the 128-query width, profiles/r05_mid_batch.md)
+        case 1: return go(mfma_scan_kernel<1, 2, 6, 4, 4>, NT6, LDS128);      // no MFMAs
+        case 256: return go(mfma_scan_kernel<256, 2, 6, 4, 4>, NT6, LDS128);  // no admissions
+        case 257: return go(mfma_scan_kernel<257, 2, 6, 4, 4>, NT6, LDS128);  // neither: staging, fragment reads, barriers
+        case 264: return go(mfma_scan_kernel<264, 2, 6, 4, 4>, NT6, LDS128);  // no admissions, query operand cache resident
+        default: return go(mfma_scan_kernel<0, 2, 6, 4, 4>, NT6, LDS128);
+      }
+    }
+    if (mfma_tile_shape(p) == 16) {  // v_mfma_f32_16x16x32_f16: the default
+      switch (p.ablate) {
+        case 256: return go(mfma_scan_kernel<256, 4, 8, 6, 4, false, false, true>, NT6, LDS256);  // everything except admissions
+        case 258: return go(mfma_scan_kernel<258, 4, 8, 6, 4, false, false, true>, NT6, LDS256);  // no LDS-DMA, no admissions
+        default: return go(mfma_scan_kernel<0, 4, 8, 6, 4, false, false, true>, NT6, LDS256);
+      }
+    }
+    if (p.bdirect && p.ablate == 0) return go(mfma_scan_kernel<0, 4, 4, 3, 3, false, true>, NT6, 3 * SLOT_A6 + BN * 8 + 16);  // queries in fragment-major order (query_prepare_kernel)
+    switch (p.ablate) {
+      case 256: return go(mfma_scan_kernel<256, 4, 8, 6, 4>, NT6, LDS256);  // everything except admissions
+      case 260: return go(mfma_scan_kernel<260, 4, 8, 6, 4>, NT6, LDS256);  // same, corpus tile 0 re-read by every block (L2 resident)
+      case 264: return go(mfma_scan_kernel<264, 4, 8, 6, 4>, NT6, LDS256);  // same as 256, query operand K step 0 re-read (cache resident)
+      case 268: return go(mfma_scan_kernel<268, 4, 8, 6, 4>, NT6, LDS256);  // both operands cache resident
+      case 258: return go(mfma_scan_kernel<258, 4, 8, 6, 4>, NT6, LDS256);  // no LDS-DMA, no admissions
+      case 1282: return go(mfma_scan_kernel<1282, 4, 8, 6, 4>, NT6, LDS256);  // the same in the other MFMA issue orders (sched 3 / 4 / 5)
+      case 2306: return go(mfma_scan_kernel<2306, 4, 8, 6, 4>, NT6, LDS256);
+      case 3330: return go(mfma_scan_kernel<3330, 4, 8, 6, 4>, NT6, LDS256);
+      default: break;
+    }
+    switch (p.sched) {  // staging pieces per quarter (q3, q0, q1), MFMA issue order: measurement
+      case 1: return go(mfma_scan_kernel<0, 4, 10, 8, 0>, NT6, LDS256);
+      case 2: return go(mfma_scan_kernel<0, 4, 6, 6, 6>, NT6, LDS256);
+      case 3: return go(mfma_scan_kernel<1024, 4, 8, 6, 4>, NT6, LDS256);  // query fragment outermost
+      case 4: return go(mfma_scan_kernel<2048, 4, 8, 6, 4>, NT6, LDS256);  // corpus fragment outermost, boustrophedon
+      case 5: return go(mfma_scan_kernel<3072, 4, 8, 6, 4>, NT6, LDS256);  // query fragment outermost, boustrophedon
+      default: return go(mfma_scan_kernel<0, 4, 8, 6, 4>, NT6, LDS256);
+    }
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace tavb

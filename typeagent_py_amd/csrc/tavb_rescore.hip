@@ -8,7 +8,7 @@
 //   1. query_prepare_kernel: q16 = fp16(q); delta_q = a rigorous bound on |score_fp16query(x) - score_fp32query(x)| over
 //      every corpus row x:   |x.(q - q16)| <= ||x|| ||q - q16||   (Cauchy-Schwarz), ||x|| <= R = the largest row norm of
 //      the corpus (corpus_max_norm_kernel, cached per corpus), plus the fp32 summation slack of the two dot products.
-//   2. the tile + select_band_kernel (tavb_mfma.hip) keep, per query, the BAND: every row whose approximate score is within
+//   2. the tile + select_band_kernel (tavb_mfma_wide.hip, tavb_select.hip) keep, per query, the BAND: every row whose approximate score is within
 //      2 delta_q of the approximate k-th best a_k (and above min_score - 2 delta_q) -- as many rows as the data puts there
 //      (k + 2..3 on isotropic corpora, a whole cluster of near-duplicates on clustered ones), up to kBandMax.
 //   3. rescore_kernel: the band is scored exactly (fp32 query, fp16 row widened, fp32 accumulate -- the arithmetic of the
@@ -20,7 +20,7 @@
 //   4. only a band that did not fit (more than kBandMax rows, or more than a candidate buffer holds inside one row range, at
 //      a level the final band reaches: select_band_kernel's verdict) makes a query incomplete; it is appended to a
 //      device-side list; one fixed-shape launch of the 64-query tile with split hi/lo query planes (exact by construction,
-//      tavb_mfma.hip) serves the list and returns at once when it is empty.  No host round trip anywhere: the asynchronous
+//      tavb_mfma_skinny.hip) serves the list and returns at once when it is empty.  No host round trip anywhere: the asynchronous
 //      device-resident form stays asynchronous.
 //   The 32/64-query tile over an fp16 shadow (f32_shadow = 2) still hands over its best 64 by approximate score; there the
 //   set is complete when it was not cut, or when rank 63 + delta is below the exact k-th best (rescore_kernel, cut mode).

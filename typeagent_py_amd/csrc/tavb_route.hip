@@ -1,5 +1,5 @@
 // Routing of a device-resident query batch (tavb_search_device_dispatch): the grouped one-launch form and its cost model, the streaming
-// passes, the tile kernels (tavb_mfma.hip) behind the threshold ladder, the wide tile as an exact filter with its rescoring and fallbacks
+// passes, the tile kernels (tavb_mfma_wide.hip, tavb_mfma_skinny.hip) behind the threshold ladder, the wide tile as an exact filter with its rescoring and fallbacks
 // (tavb_rescore.hip) -- and the two pure planning functions of the C ABI that expose its decisions.  Host code only.
 
 #include "tavb_ctx.h"
@@ -151,7 +151,7 @@ int search_device_grouped(tavb_ctx* c, const float* d_q, int nq, int k, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Tile kernels (tavb_mfma.hip) behind the threshold ladder.
+// Tile kernels (tavb_mfma_wide.hip, tavb_mfma_skinny.hip) behind the threshold ladder.
 // ---------------------------------------------------------------------------------------------------------------
 struct TileRun {
   bool skinny;            // 32/64-query tile (fp32 or split-fp16 queries) instead of the 256-query fp16 tile
@@ -169,7 +169,7 @@ struct TileRun {
   bool bdirect;           // 256-query tile: `queries` are in fragment-major order (straight from L2 into registers)
   int64_t split_plane;    // 128/256-query tile: > 0 = exact form, `queries` = [2][nq_pad][dim] fp16 planes this many bytes apart (final scores, no band)
   bool ladder;            // scan in phases of growing size (else one phase)
-  // 128/256-query tile only: band selection (tavb_mfma.hip::select_band_kernel).  d_out then receives [nq, kBandMax] unsorted keys,
+  // 128/256-query tile only: band selection (tavb_select.hip::select_band_kernel).  d_out then receives [nq, kBandMax] unsorted keys,
   const float* band;      // device [nq_pad]: width of the band below the k-th best
   int* band_cnt;          // device [nq]: out, keys per query in d_out
   unsigned* lost;         // device [nq_pad]: scratch (zeroed by the caller), score level below which a query lost band rows
@@ -199,7 +199,7 @@ std::vector<int64_t> ladder_bounds(int64_t rows, int splits, int nq_pad, bool sk
   // first phase: `mfma_sample_rows`, or (0 = auto) part of ONE tile per workgroup of the 128/256-query kernel -- nothing compacts while
   // everything is still being admitted, and every unfiltered row of this phase is a key the select kernel has to stream (one workgroup per
   // QUERY).  Round 2 used two tiles per workgroup (40960 rows), round 3 one (20480: 4 % faster on a 1.25M-row shard, the same on 10M rows;
-  // profiles/r03_shard_ladder.md).  Round 4: with one LDS atomic per admitted row (tavb_mfma.hip) the all-admitted first phase is best kept
+  // profiles/r03_shard_ladder.md).  Round 4: with one LDS atomic per admitted row (tavb_mfma_wide.hip) the all-admitted first phase is best kept
   // to 32 ranges' worth, 10240 rows -- 1 % faster on the shard, the same on 10M rows, half the keys for the select kernel
   // (profiles/r04_cfg3_kernel.md).  (The 32/64-query tile keeps round 2's 40960 rows.)
   // One or two query tiles (up to 256 queries: 128 .. 256 row ranges) keep 64 ranges' worth: 1 - 2 % faster there (profiles/r04_raw/mid_batch.txt).
