@@ -57,6 +57,8 @@ extern "C" {
 #define TAVB_MAX_LARGE_K 16384
 /* Largest number of queries one streaming pass serves (bigger batches are split). */
 #define TAVB_MAX_STREAM_QUERIES 8
+/* Rows of a mask one workgroup of tavb_mask_expand covers (its two launches have ceil(rows / this) workgroups each). */
+#define TAVB_MASK_ROWS_PER_WORKGROUP 16384
 
 typedef struct tavb_ctx tavb_ctx;
 
@@ -356,6 +358,34 @@ int tavb_search_subset_device(tavb_ctx* ctx, const float* dev_query, const int32
  * a 1536-wide query rides in the kernel arguments), like tavb_search on small corpora: 21 us against 28 for the 1000-of-10k case. */
 int tavb_search_subset_resident(tavb_ctx* ctx, const float* query_host, const int32_t* dev_rows, int64_t n_subset, int32_t k, float min_score,
                                 int64_t* out_positions, float* out_scores, int32_t* out_count);
+
+/* ---- row masks: "search only among the rows I allow" ---------------------------------------------------------------------
+ * An allow-mask is one bit per corpus row in device memory, held as uint32 words: row r is bit (r & 31) of word (r >> 5), `rows` valid
+ * bits, (rows + 31) / 32 words; bits at or beyond `rows` in the last word may hold anything and are ignored.  A time range or a thread
+ * scope over 10M rows is 1.25 MB as a mask against 40 - 80 MB as ordinals, and a mask computed on the device never visits the host.
+ *
+ * tavb_mask_expand: the set rows in ASCENDING order -> dev_rows_out (device int32 [cap]), their number -> *out_count (host).  Ascending
+ * rows keep "equal scores order by ascending ordinal" when the list is searched (keys carry list positions), and are what
+ * np.flatnonzero gives.  Two launches on the context's stream (a popcount per chunk of TAVB_MASK_ROWS_PER_WORKGROUP rows; a write pass
+ * in which every workgroup starts at the sum of the counts before it -- no atomics on the output order, nothing read back in between),
+ * then ONE synchronise.  cap < count: TAVB_E_INVALID, *out_count is still the count and nothing is written at or beyond dev_rows_out
+ * [cap]; dev_rows_out == NULL with cap == 0 asks for the count alone (the write pass then only sums the counts) and is no error.  rows == 0: count 0, no launch.
+ * tavb_mask_pack: device bytes [rows] (non-zero = allowed; the storage of a torch.bool tensor) -> the bit form at dev_bits_out
+ * ((rows + 31) / 32 words, tail bits zero).  Asynchronous on the context's stream. */
+int tavb_mask_expand(tavb_ctx* ctx, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap, int64_t* out_count);
+int tavb_mask_pack(tavb_ctx* ctx, const uint8_t* dev_bytes, int64_t rows, uint32_t* dev_bits_out);
+
+/* tavb_search_subset_resident for nq queries over ONE resident row list (the output of tavb_mask_expand, or any wrapped, range-checked
+ * device int32 [n_subset]): what nq calls of tavb_search_subset_resident (k <= TAVB_MAX_FUSED_K) or tavb_search_subset_topk (up to
+ * TAVB_MAX_LARGE_K) return, bit for bit, in one submission -- a consumer with T scope-restricted term lookups
+ * (storage/memory/messageindex.py:173-183) makes one call instead of T.  queries_host float32 [nq, dim]; min_scores [nq]; the
+ * queries go over the list in groups of at most TAVB_MAX_STREAM_QUERIES per pass (4 for 64 < k <= TAVB_MAX_FUSED_K, as everywhere).
+ * remap = 0: out holds POSITIONS into dev_rows (like tavb_search_subset).  remap = 1: the keys' positions are turned into corpus rows on
+ * the device (dev_rows[position]) before they come back and `ordinal_base` is added at decode: out holds corpus ORDINALS and the caller
+ * needs no host copy of the list; dev_rows must then be ascending for equal scores to stay in ascending-ordinal order.  Outputs
+ * [nq, k] / [nq] as tavb_search_batch.  n_subset == 0, nq == 0 or an empty corpus: zero counts, nothing launched.  One synchronise. */
+int tavb_search_subset_batch_resident(tavb_ctx* ctx, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                      const float* min_scores, int32_t remap, int64_t* out, float* out_scores, int32_t* out_counts);
 
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */

@@ -17,6 +17,7 @@ from .embeddings import CachingEmbeddingModel, IEmbedder, IEmbeddingModel, Norma
 from .vectorbase import (
     DEFAULT_MIN_SCORE,
     MODEL_DEFAULT_MIN_SCORES,
+    RowMask,
     ScoredInt,
     TextEmbeddingIndexSettings,
     VectorBase,
@@ -33,6 +34,7 @@ __all__ = [
     "MODEL_DEFAULT_MIN_SCORES",
     "NormalizedEmbedding",
     "NormalizedEmbeddings",
+    "RowMask",
     "ScoredInt",
     "TextEmbeddingIndexSettings",
     "VectorBase",

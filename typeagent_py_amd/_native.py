@@ -22,6 +22,7 @@ TAVB_F16 = 1
 MAX_FUSED_K = 256
 MAX_LARGE_K = 16384  # TAVB_MAX_LARGE_K: largest k of tavb_search_topk (exact top-k after one corpus pass)
 MAX_STREAM_QUERIES = 8
+MASK_ROWS_PER_WORKGROUP = 16384  # TAVB_MASK_ROWS_PER_WORKGROUP: rows of a mask one workgroup of tavb_mask_expand covers
 
 KERNEL_SCAN, KERNEL_MERGE, KERNEL_MFMA, KERNEL_NORMALIZE, KERNEL_CONVERT, KERNEL_MFMA_SAMPLE, KERNEL_SKINNY, KERNEL_RESCORE, KERNEL_EXCHANGE, KERNEL_TOPK = range(10)
 COMM_ID_BYTES = 128
@@ -74,6 +75,10 @@ _SIGNATURES = [
     ("tavb_search_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_search_subset_device", c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
     ("tavb_search_subset_resident", c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    ("tavb_mask_expand", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
+    ("tavb_mask_pack", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_search_subset_batch_resident", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -104,6 +109,18 @@ def _addr(arr: np.ndarray):
         return _AS_POINTER.from_buffer(arr)
     except (TypeError, ValueError, BufferError):  # read-only (or otherwise not exportable) buffer
         return arr.ctypes.data_as(c_void_p)
+
+
+def pack_mask_bits(mask: np.ndarray) -> np.ndarray:
+    """bool [rows] -> the bit form tavb_mask_expand reads: uint32 [(rows + 31) // 32], row r = bit (r & 31) of word (r >> 5), the bits
+    past `rows` zero.  Needs no GPU."""
+    m = np.ascontiguousarray(mask)
+    if m.dtype != np.bool_ or m.ndim != 1:
+        raise TypeError("mask must be a 1-D bool array")
+    packed = np.packbits(m, bitorder="little")
+    words = np.zeros(((m.shape[0] + 31) // 32) * 4, dtype=np.uint8)
+    words[: packed.shape[0]] = packed
+    return words.view("<u4")
 
 
 def plan_ladder(rows: int, nq: int, n_cu: int = 256) -> list[int]:
@@ -460,6 +477,76 @@ class Engine:
         _check(self.lib, rc)
         m = int(cnt.value)
         return pos[:m], scs[:m]
+
+    # row masks ---------------------------------------------------------------
+    def expand_mask_bits(self, dev_bits, rows: int, cap: int | None = None):
+        """Mask words on the device (torch int32 [(rows + 31) // 32], see `pack_mask_bits`) -> (torch int32 [count] on the device: the set
+        rows below `rows` in ascending order, count) by tavb_mask_expand.  `cap`: the length of the output when the count is known (a
+        smaller one raises ValueError); None asks the library for the count first -- a second call and synchronise, whose count pass reads
+        the mask once more and whose write pass only sums the per-chunk counts."""
+        torch = self._torch
+        assert dev_bits.dtype == torch.int32 and dev_bits.is_contiguous() and dev_bits.numel() * 32 >= rows
+        dev = torch.device("cuda", self.device)
+        cnt = c_int64(0)
+        with self._lock:
+            if cap is None:
+                rc = self.lib.tavb_mask_expand(self._h, c_void_p(dev_bits.data_ptr()), int(rows), None, 0, byref(cnt))
+                _check(self.lib, rc)
+                cap = int(cnt.value)
+            out = torch.empty(max(int(cap), 0), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(self.device).synchronize()
+            rc = self.lib.tavb_mask_expand(self._h, c_void_p(dev_bits.data_ptr()), int(rows), c_void_p(out.data_ptr()) if cap else None, int(cap),
+                                           byref(cnt))
+        _check(self.lib, rc)
+        n = int(cnt.value)
+        return out[:n], n
+
+    def mask_to_rows(self, mask):
+        """An allow-mask -- a numpy bool array [rows], or a torch bool tensor [rows] on this engine's device -- -> (torch int32 [count] on
+        the device: the allowed rows in ascending order, i.e. np.flatnonzero(mask); count).  A numpy mask is packed to bits on the host
+        (rows / 8 bytes travel) and its count is known there; a device tensor is packed by tavb_mask_pack and never visits the host -- its
+        count is not known, so the expansion is two calls (pack, count + sum, count + write: five launches, two synchronises)."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(mask, torch.Tensor):
+            if mask.dtype != torch.bool or mask.dim() != 1:
+                raise TypeError("mask must be a 1-D bool tensor")
+            if mask.device.type != "cuda" or (mask.device.index or 0) != self.device:
+                raise ValueError(f"a tensor mask must live on cuda:{self.device}")
+            rows = int(mask.shape[0])
+            m = mask.contiguous()
+            bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(self.device).synchronize()  # whatever produced the mask ran on torch's stream
+            with self._lock:
+                rc = self.lib.tavb_mask_pack(self._h, c_void_p(m.data_ptr()), rows, c_void_p(bits.data_ptr()))
+            _check(self.lib, rc)
+            return self.expand_mask_bits(bits, rows)
+        words = pack_mask_bits(np.asarray(mask))
+        rows = int(np.shape(mask)[0])
+        bits = torch.from_numpy(words.view(np.int32)).to(dev)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.expand_mask_bits(bits, rows, cap=int(np.count_nonzero(mask)))
+
+    def search_subset_batch_resident(self, queries, dev_rows, k: int, thrs, remap: bool = True):
+        """`search_subset_resident` for a batch: queries f32 [nq, dim] over ONE resident row list (torch int32 [S]: `mask_to_rows`, or
+        wrapped, range-checked rows) in one submission, 1 <= k <= MAX_LARGE_K; thrs float32 [nq] (or one for all) -> (ordinals [nq, k],
+        scores [nq, k], counts [nq]), the layout of `search_batch`.  remap=True: corpus ordinals (dev_rows ascending); False: positions."""
+        torch = self._torch
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        ords = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        cnts = np.zeros(nq, dtype=np.int32)
+        n = int(dev_rows.shape[0])
+        with self._lock:
+            rc = self.lib.tavb_search_subset_batch_resident(self._h, _addr(a), nq, c_void_p(dev_rows.data_ptr()) if n else None, n, k, _addr(t),
+                                                            1 if remap else 0, _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
 
     def search_all(self, q, thr: np.float32, max_out: int | None = None, subset_rows=None):
         """Every row (or subset position) with score >= thr, best first, in one corpus pass; the first `max_out` of them

@@ -138,6 +138,14 @@ hipError_t launch_merge_scatter(const unsigned long long* lists, int n_lists, in
 // keys carrying list positions -> keys carrying map[position] (tavb_misc.hip)
 hipError_t launch_remap_positions(unsigned long long* keys, int64_t n, const int32_t* map, int64_t map_len, hipStream_t stream);
 
+// Row masks (tavb_mask.hip).  mask_expand: bits (uint32 words, row r = bit r & 31 of word r >> 5; bits at or beyond `rows` ignored) -> out
+// [0 .. min(total, cap)) = the set rows ascending, *total_out = their number (device-writable memory, e.g. pinned); counts: workspace of
+// mask_blocks(rows) words.  Two launches, grids fixed by `rows`.  mask_pack: bytes [rows] (non-zero = set) -> those words.
+int mask_blocks(int64_t rows);
+hipError_t launch_mask_expand(const uint32_t* bits, int64_t rows, unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
+                              hipStream_t stream);
+hipError_t launch_mask_pack(const uint8_t* bytes, int64_t rows, uint32_t* bits, hipStream_t stream);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (device, kernel) (tavb_misc.hip)
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);
 

@@ -1,6 +1,6 @@
 // The lookups of the C ABI (include/tavb.h): every host-synchronous and device-resident tavb_search_* entry point, the message re-rank, the
-// large-k and sorted forms, and the staging they share.  Host code only -- a device-resident batch is routed by tavb_route.hip, the kernels
-// live in tavb_scan.hip / tavb_misc.hip / tavb_topk.hip / tavb_sort.hip.
+// large-k and sorted forms, the batched resident subset, the row masks, and the staging they share.  Host code only -- a device-resident
+// batch is routed by tavb_route.hip, the kernels live in tavb_scan.hip / tavb_misc.hip / tavb_topk.hip / tavb_sort.hip / tavb_mask.hip.
 
 #include <functional>
 
@@ -1018,6 +1018,91 @@ int tavb_search_subset_resident(tavb_ctx* c, const float* query_host, const int3
   if (int rc = search_device_impl(c, d_q, 1, k, &min_score, dev_rows, n_subset, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr))) return rc;
   TAVB_HIP(hipStreamSynchronize(c->stream));
   decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), 1, k, 0, out_positions, out_scores, out_count);
+  return TAVB_OK;
+}
+
+// nq queries over one resident row list: the passes of search_device_impl (k <= TAVB_MAX_FUSED_K: a scan + a merge per group of queries) or of
+// search_topk_impl (beyond), both of which take a row list with any number of queries.  Up to kRemapPinnedKeys keys land in pinned host
+// memory as in the single-query form, and the remap (a few KiB) runs on them in place; more keys are merged (and remapped) in device
+// memory and copied out once.
+int tavb_search_subset_batch_resident(tavb_ctx* c, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                      const float* min_scores, int32_t remap, int64_t* out, float* out_scores, int32_t* out_counts) {
+  constexpr size_t kRemapPinnedKeys = 4096;
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (corpus ordinals)");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  if (n_subset == 0 || c->rows == 0) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  u64_t* target = keys;
+  const bool via_device = n_keys > kRemapPinnedKeys;  // (with or without the remap: no merge writes megabytes over PCIe)
+  if (via_device) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (k <= TAVB_MAX_FUSED_K) {
+    if (int rc = search_device_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  } else {
+    if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target, rounds)) return rc;
+  }
+  if (remap) {
+    hipError_t e = tavb::launch_remap_positions(target, (int64_t)n_keys, dev_rows, n_subset, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  }
+  if (via_device) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  decode(keys, nq, k, remap ? c->ordinal_base : 0, out, out_scores, out_counts);
+  if (k > TAVB_MAX_FUSED_K) note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+// ---- row masks (tavb_mask.hip)
+int tavb_mask_expand(tavb_ctx* c, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap, int64_t* out_count) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!out_count) return fail(TAVB_E_INVALID, "null argument");
+  *out_count = 0;
+  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (cap < 0 || (cap > 0 && !dev_rows_out)) return fail(TAVB_E_INVALID, "bad capacity");
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
+  DeviceGuard guard(c->device);
+  if (int rc = c->d_mask_counts.reserve((size_t)tavb::mask_blocks(rows) * sizeof(unsigned))) return rc;
+  if (int rc = c->h_out.reserve(sizeof(long long))) return rc;
+  long long* total = reinterpret_cast<long long*>(c->h_out.ptr);
+  *total = -1;
+  hipError_t e = tavb::launch_mask_expand(dev_bits, rows, reinterpret_cast<unsigned*>(c->d_mask_counts.ptr), dev_rows_out, cap, total, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask expansion launch failed: %s", hipGetErrorString(e));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  if (*total < 0) return fail(TAVB_E_HIP, "mask expansion wrote no count (internal error)");
+  *out_count = (int64_t)*total;
+  if (dev_rows_out && *total > cap)
+    return fail(TAVB_E_INVALID, "the mask has %lld rows set, dev_rows_out holds %lld", *total, (long long)cap);
+  return TAVB_OK;
+}
+
+int tavb_mask_pack(tavb_ctx* c, const uint8_t* dev_bytes, int64_t rows, uint32_t* dev_bits_out) {
+  if (int rc = check_ctx(c)) return rc;
+  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bytes || !dev_bits_out) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  hipError_t e = tavb::launch_mask_pack(dev_bytes, rows, dev_bits_out, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask pack launch failed: %s", hipGetErrorString(e));
   return TAVB_OK;
 }
 

@@ -1,0 +1,144 @@
+// Row masks (tavb_mask_expand, tavb_mask_pack): an allow-mask of one bit per corpus row -> the int32 row list the subset lookups
+// gather by, in ascending row order, without a trip to the host.
+//
+// The mask is uint32 words, row r = bit (r & 31) of word (r >> 5).  Two launches, both grids fixed on the host:
+//   mask_count_kernel   workgroup b popcounts its kMaskWordsPerBlock words -> counts[b]
+//   mask_write_kernel   workgroup b starts at the sum of the counts before it (as sorted_compact_kernel in tavb_topk.hip does); a lane
+//                       takes one word, an inclusive scan of the popcounts over the wave (cross-lane shuffles) and the waves' totals
+//                       through LDS give the lane's first slot, and the lane writes the rows of its set bits from there.
+// N / 8 bytes read twice, 4 bytes written per set row, no atomics on the output order: the list is deterministic and ascending, which
+// is what keeps "equal scores order by ascending ordinal" once the keys carry list positions.
+
+#include <algorithm>
+
+#include "tavb_internal.h"
+
+namespace tavb {
+
+namespace {
+
+constexpr int kMaskThreads = 256;
+constexpr int kMaskWordsPerBlock = TAVB_MASK_ROWS_PER_WORKGROUP / 32;
+static_assert(kMaskWordsPerBlock % kMaskThreads == 0, "a workgroup takes its words in whole rounds of its threads");
+
+// word w of the mask with the bits at or beyond `rows` cleared (they may hold anything); 0 past the last word
+__device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ bits, int64_t w, int64_t n_words, int64_t rows) {
+  if (w >= n_words) return 0u;
+  uint32_t v = bits[w];
+  const int tail = (int)(rows & 31);
+  if (w == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+  return v;
+}
+
+__global__ void __launch_bounds__(kMaskThreads) mask_count_kernel(const uint32_t* __restrict__ bits, int64_t rows, int64_t n_words,
+                                                                  unsigned* __restrict__ counts) {
+  __shared__ unsigned wc[kMaskThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock;
+  unsigned n = 0;
+  for (int i = threadIdx.x; i < kMaskWordsPerBlock; i += kMaskThreads) n += (unsigned)__popc(mask_word(bits, w0 + i, n_words, rows));
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_down(n, d, 64);
+  if (lane == 0) wc[wave] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned all = 0;
+    for (int w = 0; w < kMaskThreads / 64; ++w) all += wc[w];
+    counts[blockIdx.x] = all;
+  }
+}
+
+// out [0 .. min(total, cap)) = the set rows in ascending order; *total_out = total (written by the last workgroup; device-writable memory).
+// cap == 0: only the total, from the counts.
+__global__ void __launch_bounds__(kMaskThreads) mask_write_kernel(const uint32_t* __restrict__ bits, int64_t rows, int64_t n_words,
+                                                                  const unsigned* __restrict__ counts, int32_t* __restrict__ out, int64_t cap,
+                                                                  long long* __restrict__ total_out) {
+  __shared__ unsigned start_sh;
+  __shared__ unsigned wc[kMaskThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) start_sh = 0u;
+  __syncthreads();
+  {  // where this workgroup's rows start: the counts of the workgroups before it
+    unsigned part = 0;
+    for (unsigned b = threadIdx.x; b < blockIdx.x; b += kMaskThreads) part += counts[b];
+    if (part) atomicAdd(&start_sh, part);
+  }
+  __syncthreads();
+  unsigned base = start_sh;
+  if (cap == 0) {  // the count alone (block-uniform): nothing to write, the mask is not read again
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = (long long)base + counts[blockIdx.x];
+    return;
+  }
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock;
+  for (int i = 0; i < kMaskWordsPerBlock; i += kMaskThreads) {  // (block-uniform trip count)
+    const int64_t w = w0 + i + threadIdx.x;
+    uint32_t v = mask_word(bits, w, n_words, rows);
+    const unsigned mine = (unsigned)__popc(v);
+    unsigned incl = mine;  // inclusive scan over the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) wc[wave] = incl;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+    for (int x = 0; x < kMaskThreads / 64; ++x) {
+      before += x < wave ? wc[x] : 0u;
+      all += wc[x];
+    }
+    int64_t slot = (int64_t)base + before + (incl - mine);
+    const int32_t row0 = (int32_t)(w << 5);  // (w < n_words <= 2^26 wherever v != 0)
+    while (v) {
+      const int bit = __ffs((int)v) - 1;
+      if (slot < cap) out[slot] = row0 + bit;
+      ++slot;
+      v &= v - 1u;
+    }
+    base += all;
+    __syncthreads();  // wc is rewritten by the next round
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = (long long)base;
+}
+
+// bytes [rows] (non-zero = allowed: a torch.bool tensor) -> mask words: a wave takes 64 rows per round, one byte per lane, and its ballot IS
+// the two words
+__global__ void __launch_bounds__(kMaskThreads) mask_pack_kernel(const uint8_t* __restrict__ bytes, int64_t rows, int64_t n_words,
+                                                                 uint32_t* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * kMaskThreads + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * kMaskThreads) >> 6;
+  const int64_t groups = (rows + 63) >> 6;
+  for (int64_t g = wave; g < groups; g += n_waves) {  // (wave-uniform trip count)
+    const int64_t r = (g << 6) + lane;
+    const bool on = r < rows && bytes[r] != 0;
+    const unsigned long long m = __ballot(on);
+    const int64_t w = (g << 1) + lane;
+    if (lane < 2 && w < n_words) bits[w] = (uint32_t)(m >> (32 * lane));
+  }
+}
+
+}  // namespace
+
+int mask_blocks(int64_t rows) { return (int)((rows + TAVB_MASK_ROWS_PER_WORKGROUP - 1) / TAVB_MASK_ROWS_PER_WORKGROUP); }
+
+hipError_t launch_mask_expand(const uint32_t* bits, int64_t rows, unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
+                              hipStream_t stream) {
+  if (!bits || !counts || !total_out || rows < 1 || rows >= 0x7FFFFFFFll || cap < 0 || (cap > 0 && !out)) return hipErrorInvalidValue;
+  const int64_t n_words = (rows + 31) >> 5;
+  const int blocks = mask_blocks(rows);
+  hipLaunchKernelGGL(mask_count_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, bits, rows, n_words, counts);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mask_write_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, bits, rows, n_words, counts, out, cap, total_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_pack(const uint8_t* bytes, int64_t rows, uint32_t* bits, hipStream_t stream) {
+  if (!bytes || !bits || rows < 1 || rows >= 0x7FFFFFFFll) return hipErrorInvalidValue;
+  const int64_t n_words = (rows + 31) >> 5;
+  const int64_t groups = (rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((groups + kMaskThreads / 64 - 1) / (kMaskThreads / 64), 2048);
+  hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)blocks), dim3(kMaskThreads), 0, stream, bytes, rows, n_words, bits);
+  return hipGetLastError();
+}
+
+}  // namespace tavb

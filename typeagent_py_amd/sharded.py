@@ -641,6 +641,53 @@ class ShardedVectorBase:
         pos, sc, cnt = self._exchange_or_fail(local_lists, 1, k)
         return [ScoredInt(int(subset[p]), float(s_)) for p, s_ in zip(pos[0, : cnt[0]].tolist(), sc[0, : cnt[0]].tolist())]
 
+    # ---- masked lookups: no route of their own over shards -- the subset lookup per query over np.flatnonzero(mask), collective like it
+    def row_mask(self, allowed):
+        """An allow-mask (bool array / sequence / torch bool tensor of length len(self), the same on every rank) -> a `RowMask` holding
+        np.flatnonzero of it; tied to this index at this length."""
+        from .vectorbase import RowMask
+
+        if hasattr(allowed, "is_cuda") and hasattr(allowed, "dtype"):  # a torch tensor
+            if "bool" not in str(allowed.dtype):
+                raise TypeError(f"a mask must be bool, got {allowed.dtype}")
+            allowed = allowed.cpu().numpy()
+        a = np.asarray(allowed)
+        if a.dtype != np.bool_:
+            raise TypeError(f"a mask must be bool, got {a.dtype}")
+        if a.ndim != 1 or a.shape[0] != self.total_rows:
+            raise ValueError(f"mask covers {a.shape[0] if a.ndim else 0} rows, the index has {self.total_rows}")
+        flat = np.flatnonzero(a)
+        return RowMask(self, self.total_rows, len(flat), flat=flat)
+
+    def _resolve_mask(self, allowed):
+        from .vectorbase import RowMask
+
+        if not isinstance(allowed, RowMask):
+            return self.row_mask(allowed)
+        if allowed._owner() is not self:
+            raise ValueError("this RowMask was built by another index")
+        if allowed.rows != self.total_rows:
+            raise ValueError(f"mask covers {allowed.rows} rows, the index has {self.total_rows}")
+        return allowed
+
+    def fuzzy_lookup_embeddings_masked(self, embeddings, allowed, max_hits: int | None = None, min_score=None):
+        """≡ [fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(allowed), max_hits, min_score) for e in embeddings] (`min_score`: one
+        threshold, or one per query); `allowed`: a mask or the `RowMask` made from one."""
+        q = np.asarray(embeddings, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
+        per_query = min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1
+        if per_query and len(min_score) != len(q):
+            raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(q)}")
+        flat = self._resolve_mask(allowed).flat()
+        return [self.fuzzy_lookup_embedding_in_subset(e, flat, max_hits, min_score[i] if per_query else min_score) for i, e in enumerate(q)]
+
+    def fuzzy_lookup_embedding_masked(self, embedding, allowed, max_hits: int | None = None, min_score: float | None = None):
+        e = np.asarray(embedding, dtype=np.float32)
+        if e.ndim != 1:
+            raise ValueError(f"Expected 1D embedding, got {e.ndim}D")
+        return self.fuzzy_lookup_embeddings_masked(e[None, :], allowed, max_hits, min_score)[0]
+
     def lookup_messages_by_embedding(self, embedding, row_to_message, max_matches: int | None = None, threshold_score: float | None = None, accept=None):
         """`SqliteMessageTextIndex.lookup_by_embedding` / `lookup_in_subset_by_embedding` (storage/sqlite/messageindex.py:296-326, 182-257)
         over the sharded corpus: the whole-corpus top-`max_matches` chunk rows (collective), THEN the provider's message filter and

@@ -12,9 +12,10 @@ API mirror of the reference's `src/typeagent/aitools/vectorbase.py`
 
 Same names, arguments, defaults, return types and exceptions.  What differs is
 where the arithmetic runs: `fuzzy_lookup_embedding*` launch HIP kernels (fused
-dot + score + threshold + top-k) instead of np.dot/argpartition, and there is
-one additive method, `fuzzy_lookup_embeddings` (a batch of queries in one
-submission).  The host ndarray `_vectors` stays the authoritative copy for
+dot + score + threshold + top-k) instead of np.dot/argpartition, and there are
+additive methods: `fuzzy_lookup_embeddings` (a batch of queries in one
+submission) and the masked lookups (`row_mask`, `fuzzy_lookup_embedding_masked`,
+`fuzzy_lookup_embeddings_masked`: search only among the rows an allow-mask names).  The host ndarray `_vectors` stays the authoritative copy for
 serialize()/deserialize(); the device buffer mirrors it and is synced lazily,
 appends moving only the new rows.
 
@@ -33,6 +34,7 @@ from __future__ import annotations
 import gc
 import os
 import time
+import weakref
 from collections.abc import Callable
 from dataclasses import dataclass
 
@@ -261,6 +263,34 @@ def _sorted_lists(ords: np.ndarray, scs: np.ndarray, cnts: np.ndarray) -> list[l
         out.append(_scored_lists(ords[None, off:off + m], scs[None, off:off + m], np.array([m], np.int32), m)[0] if m else [])
         off += m
     return out
+
+
+class RowMask:
+    """What `VectorBase.row_mask(allowed)` returns: the allowed rows of ONE index at ONE length, expanded once and kept where the lookups
+    read them -- on a single-GPU engine an int32 row list in device memory (`dev_rows`, ascending; `count` of them), so that a masked
+    lookup sends only its queries.  `rows` is the index length the mask was built for: a handle used after the index grew or shrank
+    raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it."""
+
+    __slots__ = ("rows", "count", "dev_rows", "_flat", "_owner")
+
+    def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None):
+        self.rows = int(rows)
+        self.count = int(count)
+        self.dev_rows = dev_rows
+        self._flat = flat
+        self._owner = weakref.ref(owner)
+
+    def __len__(self) -> int:
+        return self.count
+
+    def flat(self) -> np.ndarray:
+        if self._flat is None:
+            self._flat = np.zeros(0, np.int64) if self.dev_rows is None else self.dev_rows.cpu().numpy().astype(np.int64)
+        return self._flat
+
+
+def _is_tensor(x) -> bool:
+    return hasattr(x, "is_cuda") and hasattr(x, "dtype")  # a torch tensor, without importing torch for callers that never pass one
 
 
 class VectorBase:
@@ -731,6 +761,118 @@ class VectorBase:
         if as_arrays:
             return ords, scs, cnts
         return _scored_lists(ords, scs, cnts, max_hits)
+
+    # ------------------------------------------------------------------ masked lookups (additive)
+    def row_mask(self, allowed) -> RowMask:
+        """An allow-mask -- a bool array or sequence of length len(self), or a torch bool tensor (on the engine's device it never visits the
+        host) -- expanded once into a `RowMask` that the masked lookups take in place of the mask.  The handle is tied to this index at this
+        length."""
+        n = self._count
+        if _is_tensor(allowed):
+            if "bool" not in str(allowed.dtype):
+                raise TypeError(f"a mask must be bool, got {allowed.dtype}")
+            if allowed.dim() != 1 or allowed.shape[0] != n:
+                raise ValueError(f"mask covers {allowed.shape[0] if allowed.dim() else 0} rows, the index has {n}")
+            eng = self._sync_device() if n else None
+            if self._masked_native(eng) and allowed.is_cuda and (allowed.device.index or 0) == eng.device:
+                dev_rows, count = eng.mask_to_rows(allowed)
+                return RowMask(self, n, count, dev_rows=dev_rows)
+            allowed = allowed.cpu().numpy()
+        a = np.asarray(allowed)
+        if a.dtype != np.bool_:
+            raise TypeError(f"a mask must be bool, got {a.dtype}")
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"mask covers {a.shape[0] if a.ndim else 0} rows, the index has {n}")
+        if n == 0:
+            return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
+        eng = self._sync_device()
+        if self._masked_native(eng):
+            dev_rows, count = eng.mask_to_rows(a)
+            return RowMask(self, n, count, dev_rows=dev_rows)
+        flat = np.flatnonzero(a)  # device groups, test doubles: the fallback's ordinal list
+        return RowMask(self, n, len(flat), flat=flat)
+
+    @staticmethod
+    def _masked_native(eng) -> bool:
+        """A single-GPU engine that expands masks and searches their row list itself (tavb_mask_expand, tavb_search_subset_batch_resident);
+        device groups and test doubles take the fallback."""
+        return isinstance(eng, _native.Engine) and hasattr(eng, "mask_to_rows") and hasattr(eng, "search_subset_batch_resident")
+
+    def _resolve_mask(self, allowed) -> RowMask:
+        if not isinstance(allowed, RowMask):
+            return self.row_mask(allowed)
+        if allowed._owner() is not self:
+            raise ValueError("this RowMask was built by another index")
+        if allowed.rows != self._count:
+            raise ValueError(f"mask covers {allowed.rows} rows, the index has {self._count}")
+        return allowed
+
+    def fuzzy_lookup_embedding_masked(
+        self,
+        embedding: NormalizedEmbedding,
+        allowed,
+        max_hits: int | None = None,
+        min_score: float | None = None,
+    ) -> list[ScoredInt]:
+        """`fuzzy_lookup_embedding` among the rows `allowed` names (a mask, see `row_mask`, or a `RowMask`): equals
+        fuzzy_lookup_embedding_in_subset(embedding, np.flatnonzero(allowed).tolist(), max_hits, min_score)."""
+        q = np.asarray(embedding, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"Expected 1D embedding, got {q.ndim}D")
+        return self.fuzzy_lookup_embeddings_masked(q.reshape(1, -1), allowed, max_hits, min_score)[0]
+
+    def fuzzy_lookup_embeddings_masked(
+        self,
+        embeddings: NormalizedEmbeddings,
+        allowed,
+        max_hits: int | None = None,
+        min_score: float | None = None,
+        as_arrays: bool = False,
+    ):
+        """Batch form over ONE mask: equals [fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(allowed).tolist(), max_hits, min_score)
+        for e in embeddings].  On a single-GPU engine with 1 <= max_hits <= 16384 (beyond 256: while the "large_k" option is on, as for
+        every other lookup) it is one submission -- the queries go over the
+        mask's resident row list eight per pass -- and with a `RowMask` only the queries travel; everything else (max_hits == 0 or
+        beyond 16384, device groups, test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
+        threshold per query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings`."""
+        queries = np.asarray(embeddings, dtype=np.float32)
+        if queries.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
+        if min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1:
+            if len(min_score) != len(queries):
+                raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(queries)}")
+            per_query = list(min_score)
+            max_hits, _ = self._limits(max_hits, 0.0)
+            thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32)
+        else:
+            per_query = None
+            max_hits, thr = self._limits(max_hits, min_score)
+        if as_arrays and not (1 <= max_hits <= _PAGE):
+            raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
+        mask = self._resolve_mask(allowed)
+        nq = len(queries)
+        if self._count == 0 or mask.count == 0 or nq == 0:
+            if as_arrays:
+                return np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+            return [[] for _ in range(nq)]
+        eng = self._sync_device()
+        if self._masked_native(eng) and mask.dev_rows is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
+            ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
+            if eng.ordinal_base:
+                ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
+            if as_arrays:
+                return ords, scs, cnts
+            return _scored_lists(ords, scs, cnts, max_hits)
+        flat = mask.flat()
+        lists = [self.fuzzy_lookup_embedding_in_subset(q, flat, max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
+        if not as_arrays:
+            return lists
+        ords, scs = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32)
+        cnts = np.array([len(hits) for hits in lists], dtype=np.int32)
+        for i, hits in enumerate(lists):
+            ords[i, : len(hits)] = [h.item for h in hits]
+            scs[i, : len(hits)] = [h.score for h in hits]
+        return ords, scs, cnts
 
     # ------------------------------------------------------------------ message re-rank (additive)
     def set_row_messages(self, row_to_message) -> None:
