@@ -274,44 +274,71 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   }
   const __amdgpu_buffer_rsrc_t rsrc_b =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sgpr_ptr(qbase)), 0, (int)(BN * row_bytes) + (SPLIT ? (int)p.split_plane : 0), 0x00020000);
-  const int plane_jump = SPLIT ? (int)p.split_plane - steps_per_plane * 128 : 0;  // K step s >= steps_per_plane reads step s - steps_per_plane of the low plane
 
   // ---- stager.  A "round" is what one K step issues: two slots deep (256-query tile) round S = corpus slab S + 1 then query
   //      slab S + 1; three corpus slots deep (128-query tile) round S = query slab S + 1 FIRST, then corpus slab S + 2, so that
   //      the counted wait of step S ("everything but the newest PIECES_A6 loads has landed") covers query slab S + 1 and corpus
   //      slab S + 1 while corpus slab S + 2 stays in flight.  Piece IDX of a round: its position in that order.
-  int sa_kt = 0, sa_tile = 0, sa_slot = 0;  // corpus slab being staged
-  int sb_kt = 0, sb_slot = 0;               // query slab being staged
+  //      What a piece needs is kept as RUNNING scalar state, advanced once per slab behind its last piece, so that a piece costs its load and
+  //      two scalar adds (profiles/r12_kloop_issue.md: recomputed per use, the corpus descriptor alone stood as two clumps of 33 and 27
+  //      instructions in front of an MFMA in every K step):
+  //        * the corpus descriptor of the tile being staged -- base = its first row, size = its rows that exist (rows past the end of the corpus
+  //          read as zero; the epilogue masks them anyway) -- moves on only where the slab wraps to the next tile; past the last tile of the row
+  //          range it stays there (harmless reloads of the last tile);
+  //        * the scalar offset of a wave's piece 0 (K step x 128 bytes + the wave's first row of the slab) and its LDS address (ring slot + the
+  //          wave's first piece); piece J adds J x 8 rows and J KiB.
+  const int piece_stride = 8 * (int)row_bytes;                 // global bytes from a piece to the next: 8 rows
+  const int sa_soff0 = wave * PIECES_A6 * piece_stride;        // K step 0
+  const int sb_soff0 = wave * PIECES_B6 * piece_stride;
+  const int sa_lds0 = wave * PIECES_A6 * 1024;                 // ring slot 0
+  const int sb_lds0 = B_RING6 + wave * PIECES_B6 * 1024;
+  const int tile_bytes = BM6 * (int)row_bytes;
+  int sa_kt = 0, sa_tiles_left = n_tiles - 1;  // corpus slab being staged: its K step, tiles of the row range behind its tile
+  int sb_kt = 0;                               // query slab being staged
+  int sa_soff = sa_soff0, sa_lds = sa_lds0, sb_soff = sb_soff0, sb_lds = sb_lds0;
+  const char* sa_base = sgpr_ptr(corpus + (size_t)(CORPUS_RESIDENT ? 0 : r_begin) * row_bytes);
+  int64_t sa_left = p.rows - (CORPUS_RESIDENT ? 0 : r_begin);  // rows of the corpus from the staged tile's first row on (> 0)
+  auto corpus_rsrc = [&]() {
+    // min(sa_left, BM6) on the two halves: there is no scalar 64-bit ordered compare, and the vector one costs a VALU slot and a readfirstlane
+    const uint32_t lo = (uint32_t)sa_left, hi = (uint32_t)((uint64_t)sa_left >> 32);
+    const int valid = (hi != 0u || lo >= (uint32_t)BM6) ? BM6 : (int)lo;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sa_base), 0, valid * (int)row_bytes, 0x00020000);
+  };
+  __amdgpu_buffer_rsrc_t rsrc_a = corpus_rsrc();
   auto stage_a = [&](auto j_tag) {
     constexpr int J = decltype(j_tag)::value;
-    const int tile = sa_tile < n_tiles ? sa_tile : n_tiles - 1;  // past the end: harmless reloads of the last tile
-    const int64_t row0 = CORPUS_RESIDENT ? 0 : r_begin + (int64_t)tile * BM6;
-    const int64_t left = p.rows - row0;
-    const int valid = (int)(left < BM6 ? left : BM6);  // rows past the end of the corpus read as zero (masked in the epilogue)
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(sgpr_ptr(corpus + (size_t)row0 * row_bytes)), 0, __builtin_amdgcn_readfirstlane(valid * (int)row_bytes), 0x00020000);
-    const int pc = wave * PIECES_A6 + J;
-    unsigned char* la = smem + sa_slot * SLOT_A6 + pc * 1024;
-    const int a_kt = (SPLIT && sa_kt >= steps_per_plane) ? sa_kt - steps_per_plane : sa_kt;  // second plane: the same corpus columns again
-    const int soff = __builtin_amdgcn_readfirstlane(a_kt * 128 + pc * 8 * (int)row_bytes);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_void*)la, 16, (J & 1) ? st_odd : st_even, soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_void*)(smem + sa_lds + J * 1024), 16, (J & 1) ? st_odd : st_even, sa_soff + J * piece_stride, 0, 0);
     if constexpr (J == PIECES_A6 - 1) {
-      sa_slot = (sa_slot + 1 == RA) ? 0 : sa_slot + 1;
-      const bool wrap = (sa_kt + 1 == steps_per_tile);
-      sa_kt = wrap ? 0 : sa_kt + 1;
-      sa_tile += wrap ? 1 : 0;
+      sa_lds = (sa_lds + SLOT_A6 == sa_lds0 + RA * SLOT_A6) ? sa_lds0 : sa_lds + SLOT_A6;
+      ++sa_kt;
+      sa_soff += 128;
+      if constexpr (SPLIT) sa_soff = (sa_kt == steps_per_plane) ? sa_soff0 : sa_soff;  // second plane: the same corpus columns again
+      if (sa_kt == steps_per_tile) {  // the slab wraps to the next tile (once in dim / 64 steps)
+        sa_kt = 0;
+        sa_soff = sa_soff0;
+        if (!CORPUS_RESIDENT && sa_tiles_left > 0) {
+          --sa_tiles_left;
+          sa_base += tile_bytes;
+          sa_left -= BM6;
+          rsrc_a = corpus_rsrc();
+        }
+      }
     }
   };
   auto stage_b = [&](auto j_tag) {
     constexpr int BJ = decltype(j_tag)::value;
-    const int pc = wave * PIECES_B6 + BJ;
-    unsigned char* lb = smem + B_RING6 + sb_slot * SLOT_B6 + pc * 1024;
-    const int soff = __builtin_amdgcn_readfirstlane((QUERY_RESIDENT ? 0 : sb_kt * 128 + ((SPLIT && sb_kt >= steps_per_plane) ? plane_jump : 0)) +
-                                                    pc * 8 * (int)row_bytes);  // ablation 8: the query operand's K step 0 every time (cache resident)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void*)lb, 16, (BJ & 1) ? st_odd : st_even, soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void*)(smem + sb_lds + BJ * 1024), 16, (BJ & 1) ? st_odd : st_even, sb_soff + BJ * piece_stride, 0, 0);
     if constexpr (BJ == PIECES_B6 - 1) {
-      sb_slot ^= 1;
-      sb_kt = (sb_kt + 1 == steps_per_tile) ? 0 : sb_kt + 1;
+      sb_lds = (sb_lds == sb_lds0) ? sb_lds0 + SLOT_B6 : sb_lds0;
+      if constexpr (!QUERY_RESIDENT) {  // ablation 8: the query operand's K step 0 every time (cache resident)
+        ++sb_kt;
+        sb_soff += 128;
+        if constexpr (SPLIT) sb_soff = (sb_kt == steps_per_plane) ? sb_soff0 + (int)p.split_plane : sb_soff;  // on to the low plane
+        if (sb_kt == steps_per_tile) {
+          sb_kt = 0;
+          sb_soff = sb_soff0;
+        }
+      }
     }
   };
   auto stage_piece = [&](auto idx_tag) {
@@ -392,17 +419,17 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
       for (int mi = 0; mi < 5; ++mi) a0[mi] = *reinterpret_cast<const f16x8*>(abase + mi * 4096);
     }
   }
-  int rd = 0, rd_a = 0;  // ring slots (query, corpus) of the step being multiplied
+  int rd = 0, rd_a = 0;  // ring slots (query, corpus) of the step being multiplied, as byte offsets into their rings
 
   // One quarter: the NT MFMAs of one k16 slice on (fa, fb); behind them, in program order, the NI + 5 fragment reads of the
-  // next quarter (slot `nslot`, slice NKK) into (na, nb) and the staging pieces the schedule puts into quarter Q.
-  auto quarter = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&fb)[NI], f16x8(&na)[5], f16x8(&nb)[NI], int nslot_a, int nslot, auto nkk_tag) {
+  // next quarter (ring offsets `noff_a` / `noff_b`, slice NKK) into (na, nb) and the staging pieces the schedule puts into quarter Q.
+  auto quarter = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&fb)[NI], f16x8(&na)[5], f16x8(&nb)[NI], int noff_a, int noff_b, auto nkk_tag) {
     constexpr int Q = decltype(q_tag)::value;
     constexpr bool FIRST = decltype(first_tag)::value;  // first quarter of a tile: C = 0
     constexpr int NKK = decltype(nkk_tag)::value;
     const uint32_t kx = (uint32_t)(NKK << 5) ^ frag_x;
-    const unsigned char* abase = smem + nslot_a * SLOT_A6 + (a_lane + kx);
-    const unsigned char* bbase = smem + nslot * SLOT_B6 + (b_lane + kx);
+    const unsigned char* abase = smem + noff_a + (a_lane + kx);
+    const unsigned char* bbase = smem + noff_b + (b_lane + kx);
     auto mfma_at = [&](auto i_tag) {
       constexpr int I = decltype(i_tag)::value;
       // issue order of the NT MFMAs of a slice (measurement, profiles/r06_mfma_power.md): corpus fragment outermost (ships), query fragment
@@ -439,21 +466,21 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
   };
   // M16 quarter Q: the 5 row fragments of rows 80 H .. 80 H + 79 (H = Q & 1) of k32 slice Q >> 1 (fa) x the 8 query fragments of that slice (b0),
   // query fragment outermost: MFMA i = 5 n + m multiplies row fragment m by query fragment n.  Behind them, in program order: the 5 row fragments of
-  // the next quarter (the other row half; slot `nslot_a`, k32 slice NKK) into na, and the query fragments IN PLACE -- in quarters 1 and 3 all
+  // the next quarter (the other row half; ring offset `noff_a`, k32 slice NKK) into na, and the query fragments IN PLACE -- in quarters 1 and 3 all
   // eight, of slice NKK (the next quarter's), b0[n] behind MFMA 5 n + 9, the last one, b0[7], behind MFMA 5 of the next quarter.  Every fragment
   // read thus sits at least five MFMAs behind the last MFMA that reads its register as SrcA / SrcB (the row fragments: a0[m] / a1[m] is last read
   // by MFMA 35 + m and reloaded behind MFMA m of the next quarter).  The ISA's table of required wait states for XDL (MFMA) operations has a
   // write-after-read row for SrcC only ("XDL read VGPR SrcC, VALU write of the same VGPR": 3 wait states at four passes); SrcA / SrcB are read
   // when the MFMA issues.  Five MFMA issues cover even the SrcC figure, so no s_nop is needed anywhere in the loop (the static_asserts below
   // measure each distance from the issue order, m16_query_frag / m16_row_frag).
-  auto quarter16 = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&na)[5], int nslot_a, int nslot, auto nkk_tag) {
+  auto quarter16 = [&](auto q_tag, auto first_tag, f16x8(&fa)[5], f16x8(&na)[5], int noff_a, int noff_b, auto nkk_tag) {
     constexpr int Q = decltype(q_tag)::value;
     constexpr bool FIRST = decltype(first_tag)::value;  // first quarter of a tile for these accumulators: C = 0
     constexpr int NKK = decltype(nkk_tag)::value;
     constexpr int H = Q & 1;
     const uint32_t kx = (uint32_t)(NKK << 6) ^ frag_x16;
-    const unsigned char* abase = smem + nslot_a * SLOT_A6 + (a_lane16 + (H ^ 1) * 5 * 2048 + kx);
-    const unsigned char* bbase = smem + nslot * SLOT_B6 + (b_lane16 + kx);
+    const unsigned char* abase = smem + noff_a + (a_lane16 + (H ^ 1) * 5 * 2048 + kx);
+    const unsigned char* bbase = smem + noff_b + (b_lane16 + kx);
     auto mfma_at = [&](auto i_tag) {
       constexpr int I = decltype(i_tag)::value;
       constexpr int n = m16_query_frag(I), m = m16_row_frag(I), mr = 5 * H + m;
@@ -503,9 +530,9 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
       if constexpr (!NO_STAGING) wait_vmcnt<0>();
       __builtin_amdgcn_s_waitcnt(0xC07F);
       TAVB_BARRIER();
-      const int nxt_a = rd_a ^ 1;
-      quarter16(Q3{}, std::false_type{}, a1, a0, nxt_a, rd ^ 1, Q0{});
-      rd ^= 1;
+      const int nxt_a = rd_a ^ SLOT_A6;
+      quarter16(Q3{}, std::false_type{}, a1, a0, nxt_a, rd ^ SLOT_B6, Q0{});
+      rd ^= SLOT_B6;
       rd_a = nxt_a;
     } else if constexpr (BD) {
       quarter(Q0{}, first_tag, a0, b0, a1, b3, rd_a, rd, Q1{});
@@ -516,7 +543,7 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
       if constexpr (!NO_STAGING) wait_vmcnt<5 * NI + PIECES_A6>();
       __builtin_amdgcn_s_waitcnt(0xC07F);
       TAVB_BARRIER();
-      const int nxt_a = rd_a + 1 == RA ? 0 : rd_a + 1;
+      const int nxt_a = rd_a + SLOT_A6 == RA * SLOT_A6 ? 0 : rd_a + SLOT_A6;
       quarter(Q3{}, std::false_type{}, a1, b3, a0, b2, nxt_a, rd, Q0{});
       rd_a = nxt_a;
     } else {
@@ -528,9 +555,9 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
       if constexpr (!NO_STAGING) wait_vmcnt<(RA == 2 ? 0 : PIECES_A6)>();
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) through the builtin: visible to the compiler's wait-count pass
       TAVB_BARRIER();
-      const int nxt_a = (RA == 2) ? (rd_a ^ 1) : (rd_a + 1 == RA ? 0 : rd_a + 1);
-      quarter(Q3{}, std::false_type{}, a1, b1, a0, b0, nxt_a, rd ^ 1, Q0{});
-      rd ^= 1;
+      const int nxt_a = (RA == 2) ? (rd_a ^ SLOT_A6) : (rd_a + SLOT_A6 == RA * SLOT_A6 ? 0 : rd_a + SLOT_A6);
+      quarter(Q3{}, std::false_type{}, a1, b1, a0, b0, nxt_a, rd ^ SLOT_B6, Q0{});
+      rd ^= SLOT_B6;
       rd_a = nxt_a;
     }
   };
