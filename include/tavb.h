@@ -387,6 +387,20 @@ int tavb_mask_pack(tavb_ctx* ctx, const uint8_t* dev_bytes, int64_t rows, uint32
 int tavb_search_subset_batch_resident(tavb_ctx* ctx, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
                                       const float* min_scores, int32_t remap, int64_t* out, float* out_scores, int32_t* out_counts);
 
+/* The no-wait twin of tavb_search_subset_batch_resident (what tavb_search_topk_device is to tavb_search_topk): dev_queries device float32
+ * [nq, dim], nq >= 1 queries over ONE resident row list -- tavb_search_topk_device takes a row list with one query only -- 1 <= k <=
+ * TAVB_MAX_LARGE_K: the same passes (the fused selection up to TAVB_MAX_FUSED_K, the exact top-k beyond; "last_topk_refine" is then valid
+ * after the next tavb_synchronize), so the keys are those of the host-synchronous call bit for bit.  min_scores: nq thresholds on the HOST,
+ * read before the call returns.  out_keys [nq, k]: sorted, zero-padded lists in device memory or device-writable pinned memory, written on
+ * the context's stream; nothing is waited for.  remap = 0: keys carry POSITIONS into dev_rows.  remap = 1: keys carry GLOBAL ordinals,
+ * ordinal_base + dev_rows[position] -- the form every key merge takes (tavb_merge_keys_host, tavb_merge_topk_host, tavb_merge_device,
+ * tavb_merge_topk_device, tavb_allgather_merge, tavb_allgather_merge_topk): a shard of a device group or a rank of a row-sharded index
+ * searches ITS slice of a row mask and hands the lists on as they are; ordinal_base + rows must stay below 2^32 - 1 (TAVB_E_UNSUPPORTED
+ * otherwise), and dev_rows must be ascending for equal scores to stay in ascending-ordinal order.  n_subset == 0 (dev_rows may then be
+ * NULL) or an empty corpus: all-zero keys are enqueued, no error. */
+int tavb_search_subset_batch_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                    const float* min_scores, int32_t remap, tavb_key* out_keys);
+
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */
 int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k,

@@ -79,6 +79,7 @@ _SIGNATURES = [
     ("tavb_mask_pack", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_search_subset_batch_resident", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_subset_batch_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -501,6 +502,25 @@ class Engine:
         n = int(cnt.value)
         return out[:n], n
 
+    def pack_mask_tensor(self, mask, wait: bool = True):
+        """A torch bool tensor [rows] on this engine's device -> its bit form on the device (torch int32 [(rows + 31) // 32], the layout of
+        `pack_mask_bits`, tail bits zero) by tavb_mask_pack: rows / 8 bytes to expand here or -- after the synchronise of `wait` -- to copy out."""
+        torch = self._torch
+        if mask.dtype != torch.bool or mask.dim() != 1:
+            raise TypeError("mask must be a 1-D bool tensor")
+        if mask.device.type != "cuda" or (mask.device.index or 0) != self.device:
+            raise ValueError(f"a tensor mask must live on cuda:{self.device}")
+        rows = int(mask.shape[0])
+        m = mask.contiguous()
+        bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()  # whatever produced the mask ran on torch's CURRENT stream (a caller inside another stream context waits for the producer itself)
+        with self._lock:
+            rc = self.lib.tavb_mask_pack(self._h, c_void_p(m.data_ptr()), rows, c_void_p(bits.data_ptr()))
+        _check(self.lib, rc)
+        if wait:
+            self.synchronize()
+        return bits
+
     def mask_to_rows(self, mask):
         """An allow-mask -- a numpy bool array [rows], or a torch bool tensor [rows] on this engine's device -- -> (torch int32 [count] on
         the device: the allowed rows in ascending order, i.e. np.flatnonzero(mask); count).  A numpy mask is packed to bits on the host
@@ -509,18 +529,7 @@ class Engine:
         torch = self._torch
         dev = torch.device("cuda", self.device)
         if isinstance(mask, torch.Tensor):
-            if mask.dtype != torch.bool or mask.dim() != 1:
-                raise TypeError("mask must be a 1-D bool tensor")
-            if mask.device.type != "cuda" or (mask.device.index or 0) != self.device:
-                raise ValueError(f"a tensor mask must live on cuda:{self.device}")
-            rows = int(mask.shape[0])
-            m = mask.contiguous()
-            bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(self.device).synchronize()  # whatever produced the mask ran on torch's stream
-            with self._lock:
-                rc = self.lib.tavb_mask_pack(self._h, c_void_p(m.data_ptr()), rows, c_void_p(bits.data_ptr()))
-            _check(self.lib, rc)
-            return self.expand_mask_bits(bits, rows)
+            return self.expand_mask_bits(self.pack_mask_tensor(mask, wait=False), int(mask.shape[0]))  # (same stream: nothing to wait for)
         words = pack_mask_bits(np.asarray(mask))
         rows = int(np.shape(mask)[0])
         bits = torch.from_numpy(words.view(np.int32)).to(dev)
@@ -762,6 +771,27 @@ class Engine:
             rc = self.lib.tavb_search_topk_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t),
                                                   None if dev_rows is None else c_void_p(dev_rows.data_ptr()),
                                                   0 if dev_rows is None else int(dev_rows.shape[0]), c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def search_subset_batch_device(self, dev_queries, dev_rows, k: int, thrs, out_keys=None, remap: bool = True):
+        """`search_subset_batch_resident` with the queries on the device and nothing waited for (tavb_search_subset_batch_device):
+        dev_queries torch f32 [nq, dim], nq >= 1, over ONE resident row list (torch int32 [S]: `mask_to_rows`, or wrapped, range-checked
+        rows); thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> torch int64 [nq, k] sorted, zero-padded keys.  remap=True:
+        the keys carry global ordinals (ordinal_base + row: what the key merges take; dev_rows ascending); False: positions in dev_rows.
+        `out_keys`: a device tensor or a PINNED host tensor.  Async: `synchronize()` before reading."""
+        torch = self._torch
+        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
+        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
+        nq = int(dev_queries.shape[0])
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
+        n = int(dev_rows.shape[0])
+        with self._lock:  # (an empty tensor has no address to name "a subset" by: length 0 and no pointer -- the library enqueues zero keys)
+            rc = self.lib.tavb_search_subset_batch_device(self._h, c_void_p(dev_queries.data_ptr()), nq, c_void_p(dev_rows.data_ptr()) if n else None, n,
+                                                          k, _addr(t), 1 if remap else 0, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 

@@ -459,7 +459,7 @@ int tavb_remap_key_positions(tavb_ctx* c, tavb_key* dev_keys, int64_t count, con
   if (count == 0) return TAVB_OK;
   if (!dev_keys || (map_len > 0 && !dev_map)) return fail(TAVB_E_INVALID, "null argument");
   DeviceGuard guard(c->device);
-  hipError_t e = tavb::launch_remap_positions(reinterpret_cast<u64_t*>(dev_keys), count, dev_map, map_len, c->stream);
+  hipError_t e = tavb::launch_remap_positions(reinterpret_cast<u64_t*>(dev_keys), reinterpret_cast<u64_t*>(dev_keys), count, dev_map, map_len, 0u, c->stream);
   if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
   return TAVB_OK;
 }

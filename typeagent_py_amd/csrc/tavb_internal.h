@@ -135,8 +135,9 @@ hipError_t launch_merge(const unsigned long long* lists, int n_lists, int nq, in
 hipError_t launch_merge_scatter(const unsigned long long* lists, int n_lists, int nq, int k, const int* active, const int* scatter,
                                 unsigned long long* out, hipStream_t stream);
 
-// keys carrying list positions -> keys carrying map[position] (tavb_misc.hip)
-hipError_t launch_remap_positions(unsigned long long* keys, int64_t n, const int32_t* map, int64_t map_len, hipStream_t stream);
+// keys carrying list positions -> keys carrying base + map[position], src -> dst (the same array: in place) (tavb_misc.hip)
+hipError_t launch_remap_positions(const unsigned long long* src, unsigned long long* dst, int64_t n, const int32_t* map, int64_t map_len, uint32_t base,
+                                  hipStream_t stream);
 
 // Row masks (tavb_mask.hip).  mask_expand: bits (uint32 words, row r = bit r & 31 of word r >> 5; bits at or beyond `rows` ignored) -> out
 // [0 .. min(total, cap)) = the set rows ascending, *total_out = their number (device-writable memory, e.g. pinned); counts: workspace of

@@ -1061,13 +1061,54 @@ int tavb_search_subset_batch_resident(tavb_ctx* c, const float* queries_host, in
     if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target, rounds)) return rc;
   }
   if (remap) {
-    hipError_t e = tavb::launch_remap_positions(target, (int64_t)n_keys, dev_rows, n_subset, c->stream);
+    hipError_t e = tavb::launch_remap_positions(target, target, (int64_t)n_keys, dev_rows, n_subset, 0u, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
   }
   if (via_device) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
   TAVB_HIP(hipStreamSynchronize(c->stream));
   decode(keys, nq, k, remap ? c->ordinal_base : 0, out, out_scores, out_counts);
   if (k > TAVB_MAX_FUSED_K) note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+// The no-wait twin of the call above: queries already on the device, keys to device (or device-writable pinned) memory.  remap = 1: the passes
+// write their positions into d_out and the remap kernel turns them into ordinal_base + dev_rows[position] on the way to out_keys -- one
+// launch either way, and a pinned out_keys is written once and never read over PCIe.
+int tavb_search_subset_batch_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                    const float* min_scores, int32_t remap, tavb_key* out_keys) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (global ordinals)");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (remap && c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  const size_t n_keys = (size_t)nq * k;
+  if (n_subset == 0 || c->rows == 0) {  // nothing to scan: empty lists (dev_rows may be null)
+    const hipError_t e = tavb::launch_fill_keys(out, (int64_t)n_keys, 0ull, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
+    return TAVB_OK;
+  }
+  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  u64_t* target = out;
+  if (remap) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  if (k <= TAVB_MAX_FUSED_K) {
+    if (int rc = search_device_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  } else {
+    if (int rc = search_topk_async(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  }
+  if (remap) {
+    hipError_t e = tavb::launch_remap_positions(target, out, (int64_t)n_keys, dev_rows, n_subset, (uint32_t)c->ordinal_base, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  }
   return TAVB_OK;
 }
 

@@ -281,15 +281,21 @@ __global__ void __launch_bounds__(256) message_rerank_kernel(const u64* __restri
   if (first && pos < max_messages && pos < k) o[pos] = (key & 0xFFFFFFFF00000000ull) | (u64)(0xFFFFFFFFu - (uint32_t)msg);
 }
 
-// keys that carry POSITIONS of a list (0xFFFFFFFF - position in the low word) -> keys that carry map[position]: a shard's subset search
-// returns positions into ITS part of the caller's subset; the exchange needs positions into the caller's whole list
-__global__ void __launch_bounds__(256) remap_positions_kernel(u64* __restrict__ keys, int64_t n, const int32_t* __restrict__ map, int64_t map_len) {
+// keys that carry POSITIONS of a list (0xFFFFFFFF - position in the low word) -> keys that carry base + map[position]: a shard's subset search
+// returns positions into ITS part of the caller's subset; the exchange needs positions into the caller's whole list (base 0), the key merges
+// of a masked lookup over shards need global ordinals (base = the shard's ordinal_base, map = its allowed rows).  src -> dst, which may be
+// the same array (every thread reads and writes its own keys only).  A zero key stays zero; a position behind the map becomes the
+// out-of-range ordinal 0xFFFFFFFE whatever the base.
+__global__ void __launch_bounds__(256) remap_positions_kernel(const u64* src, u64* dst, int64_t n, const int32_t* __restrict__ map, int64_t map_len, uint32_t base) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const u64 key = keys[i];
-    if (key == 0ull) continue;
+    const u64 key = src[i];
+    if (key == 0ull) {
+      if (dst != src) dst[i] = 0ull;
+      continue;
+    }
     const int64_t pos = (int64_t)(0xFFFFFFFFu - (uint32_t)key);
-    const uint32_t to = (pos < map_len) ? (uint32_t)map[pos] : 0xFFFFFFFEu;
-    keys[i] = (key & 0xFFFFFFFF00000000ull) | (u64)(0xFFFFFFFFu - to);
+    const uint32_t to = (pos < map_len) ? base + (uint32_t)map[pos] : 0xFFFFFFFEu;
+    dst[i] = (key & 0xFFFFFFFF00000000ull) | (u64)(0xFFFFFFFFu - to);
   }
 }
 
@@ -305,11 +311,12 @@ hipError_t launch_stall(int ms, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_remap_positions(unsigned long long* keys, int64_t n, const int32_t* map, int64_t map_len, hipStream_t stream) {
+hipError_t launch_remap_positions(const unsigned long long* src, unsigned long long* dst, int64_t n, const int32_t* map, int64_t map_len, uint32_t base,
+                                  hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(remap_positions_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, keys, n, map, map_len);
+  hipLaunchKernelGGL(remap_positions_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, dst, n, map, map_len, base);
   return hipGetLastError();
 }
 

@@ -14,6 +14,10 @@ answer, ties included.
 
 max_hits 257 .. 16384 (`search_topk`, `search_subset_topk`): the exact device top-k of every shard (`tavb_search_topk_device`, enqueued
 on all shards before anything is waited for) into one reused pinned buffer, merged on the host by `tavb_merge_topk_host`.
+
+Masked lookups (`mask_to_rows`, `search_masked`): the mask is cut at the shard bounds, every slice is expanded on its shard's device
+(`tavb_mask_expand`) into shard-local rows that stay there, and a batch of queries is ONE `tavb_search_subset_batch_device` per shard --
+keys carrying global ordinals into the same pinned buffer, enqueued everywhere before anything is waited for -- merged on the host.
 """
 
 from __future__ import annotations
@@ -282,6 +286,70 @@ class DeviceGroup:
         ords, scs, cnts = _native.decode_keys(keys[0] if len(parts) == 1 else _native.merge_topk_keys(keys))
         m = int(cnts[0])
         return ords[0, :m], scs[0, :m]
+
+    # -- masked lookups (tavb_mask_expand + tavb_search_subset_batch_device per shard, merged on the host) ------------------------------
+    def masked_capable(self) -> bool:
+        """Every engine expands masks and searches their row list without waiting (`_native.Engine`); test doubles lack the methods."""
+        return all(hasattr(e, "mask_to_rows") and hasattr(e, "search_subset_batch_device") for e in self.engines)
+
+    @_locked
+    def mask_to_rows(self, mask):
+        """An allow-mask over the whole index -- a numpy bool array [rows] or a torch bool tensor [rows] on any device -- cut at the
+        current `bounds` and expanded shard by shard on the shard's own device -> (handles: one per engine, torch int32 shard-local rows
+        in ascending order, None where the shard has no allowed row; the total count; the bounds the mask was cut by)."""
+        is_tensor = hasattr(mask, "is_cuda") and hasattr(mask, "dtype")
+        handles, total = [None] * len(self.engines), 0
+        for g, e in enumerate(self.engines):
+            lo, hi = self.bounds[g], self.bounds[g + 1]
+            if hi <= lo:
+                continue
+            part = mask[lo:hi]  # (one byte per row in either form: every cut is on a byte boundary, the shard packs its own bits)
+            if is_tensor:
+                import torch
+
+                part = part.to(torch.device("cuda", e.device)).contiguous()
+            dev_rows, count = e.mask_to_rows(part)
+            if count:
+                handles[g] = dev_rows
+                total += int(count)
+        return handles, total, tuple(self.bounds)
+
+    @_locked
+    def _rows_to_handles(self, flat: np.ndarray):
+        """Ascending global rows (np.flatnonzero of a mask) -> what `mask_to_rows` returns for that mask under the current `bounds`."""
+        flat = np.ascontiguousarray(flat, dtype=np.int64)
+        cuts = np.searchsorted(flat, np.asarray(self.bounds, dtype=np.int64))
+        handles = [None] * len(self.engines)
+        for g, e in enumerate(self.engines):
+            if cuts[g + 1] > cuts[g]:
+                handles[g] = e.rows_to_device(flat[cuts[g] : cuts[g + 1]] - self.bounds[g])
+        return handles, int(len(flat)), tuple(self.bounds)
+
+    @_locked
+    def search_masked(self, queries, handles, k: int, thrs):
+        """`search_topk` among the rows of a mask (handles: `mask_to_rows` under the current bounds): queries f32 [nq, dim]; thrs float32
+        [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> (ordinals [nq,k], scores [nq,k], counts [nq]).  One batched call per shard that
+        has a handle, all of them enqueued before any is waited for; shards without allowed rows are not visited."""
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        if len(handles) != len(self.engines):
+            raise ValueError("one handle (or None) per device")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        parts = [(g, e, handles[g]) for g, e in enumerate(self.engines) if handles[g] is not None and self.bounds[g + 1] > self.bounds[g]]
+        if not parts or nq == 0:
+            return np.zeros((nq, k), np.int64), np.zeros((nq, k), np.float32), np.zeros(nq, np.int32)
+        lists = self._topk_lists(len(parts), nq, k)
+        dqs = self._device_queries([(g, e) for g, e, rows in parts], a)
+        for i, (g, e, rows) in enumerate(parts):  # enqueue everywhere first: the devices scan concurrently
+            e.search_subset_batch_device(dqs[i], rows, k, t, out_keys=lists[i], remap=True)
+        for g, e, rows in parts:
+            e.synchronize()
+        keys = lists.numpy().view(np.uint64)
+        if len(parts) == 1:
+            return _native.decode_keys(keys[0])
+        return _native.decode_keys(_native.merge_keys(keys) if k <= _native.MAX_FUSED_K else _native.merge_topk_keys(keys))
 
     @_locked
     def search_all(self, q, thr: np.float32, max_out: int | None = None, subset_rows=None):

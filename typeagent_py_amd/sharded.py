@@ -30,6 +30,9 @@ max_hits 257 .. 16384 take the same steps with the large-k calls of the library:
 the shard, the all-gather in chunks of whole queries, the merge of long lists), `tavb_search_topk_device` + `tavb_allgather_merge_topk`
 for the subset form.  max_hits = 0 (every survivor) and max_hits above 16384 have no bounded list to exchange and raise ValueError here;
 a `VectorBase(devices=[...])` device group serves them through its emit-all route.
+
+Masked lookups: every rank expands ITS slice of the mask on its device once (`DeviceShardBackend.mask_to_device`, tavb_mask_expand), a
+batch of queries is one `tavb_search_subset_batch_device` per rank -- keys carrying global ordinals -- and ONE exchange of the [nq, k] lists.
 """
 
 from __future__ import annotations
@@ -91,6 +94,14 @@ def _check_k(k: int, what: str) -> None:
     if not (1 <= k <= _native.MAX_LARGE_K):
         raise ValueError(f"{what} must be in 1..{_native.MAX_LARGE_K} for a row-sharded lookup (0 = every survivor and larger values have no bounded "
                          "per-rank list to exchange: a VectorBase(devices=[...]) device group serves them)")
+
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint8)
+
+
+def _popcount(words: np.ndarray) -> int:
+    """set bits of a packed mask (uint32 words, tail bits zero)"""
+    return int(_POP8[words.view(np.uint8)].sum(dtype=np.int64))
 
 
 PEER_FAILED_KEY = -1  # TAVB_KEY_PEER_FAILED (all bits set) seen as int64: what a rank whose local search failed contributes to the exchange
@@ -239,6 +250,35 @@ class DeviceShardBackend:
             self.engine.remap_key_positions(keys, handle[1])
             self._keep = (dq, handle)  # alive until the next call (the kernels run asynchronously)
             return keys
+
+    # -- masked lookups: this rank's slice of a mask, expanded once and kept on the device ------------------------------------------------
+    def mask_to_device(self, local_mask):
+        """This rank's slice of an allow-mask (numpy bool [local_rows], or a torch bool tensor on this device) -> the allowed local rows
+        as a device tensor (int32, ascending; tavb_mask_expand) -- a handle for `local_search_masked`; None when the slice allows no row."""
+        if len(local_mask) == 0:
+            return None
+        if hasattr(local_mask, "is_cuda"):
+            # whatever produced a tensor mask ran on the CALLER's stream; inside the context below the current stream is the backend's own
+            # (the engine's), so the synchronise of Engine.pack_mask_tensor would wait for the wrong one
+            self.torch.cuda.current_stream(self.device).synchronize()
+        with self.torch.cuda.stream(self.stream):
+            dev_rows, count = self.engine.mask_to_rows(local_mask)
+        return dev_rows if count else None
+
+    def local_search_masked(self, queries: np.ndarray, handle, k: int, thrs):
+        """A batch of queries (host float32 [nq, dim]; thrs: one threshold per query) over a handle of `mask_to_device`: ONE
+        tavb_search_subset_batch_device on the backend's stream -> keys [nq, k] carrying GLOBAL ordinals (the engine's ordinal_base is this
+        rank's row_offset).  Asynchronous; an empty part (handle None) gives zero keys."""
+        torch = self.torch
+        nq = int(np.shape(queries)[0])
+        if handle is None:
+            with torch.cuda.stream(self.stream):
+                return torch.zeros((nq, k), dtype=torch.int64, device=torch.device("cuda", self.device))
+        dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
+        with torch.cuda.stream(self.stream):
+            keys = self.engine.search_subset_batch_device(dq, handle, k, thrs, remap=True)
+        self._keep = (dq, handle, keys)  # alive until the next call (the kernels run asynchronously)
+        return keys
 
     def local_survivors(self, query: np.ndarray, thr: float):
         """every row of this shard with score >= thr -> (global ordinals int64, scores float32), unsorted (one emit-all pass)."""
@@ -641,21 +681,47 @@ class ShardedVectorBase:
         pos, sc, cnt = self._exchange_or_fail(local_lists, 1, k)
         return [ScoredInt(int(subset[p]), float(s_)) for p, s_ in zip(pos[0, : cnt[0]].tolist(), sc[0, : cnt[0]].tolist())]
 
-    # ---- masked lookups: no route of their own over shards -- the subset lookup per query over np.flatnonzero(mask), collective like it
+    # ---- masked lookups: with a backend that offers `mask_to_device` / `local_search_masked`, this rank's slice of the mask stays on its
+    # device and a batch is ONE exchange; any other backend: the subset lookup per query over np.flatnonzero(mask), collective like it
+    def _masked_backend(self):
+        backend = getattr(self, "backend", None)
+        return backend if hasattr(backend, "mask_to_device") and hasattr(backend, "local_search_masked") else None
+
     def row_mask(self, allowed):
-        """An allow-mask (bool array / sequence / torch bool tensor of length len(self), the same on every rank) -> a `RowMask` holding
-        np.flatnonzero of it; tied to this index at this length."""
+        """An allow-mask (bool array / sequence / torch bool tensor of length len(self), the same on every rank) -> a `RowMask` tied to
+        this index at this length.  With a backend that expands masks itself it holds this rank's allowed rows on the device, the GLOBAL
+        count, the layout they were cut under and the whole mask packed to bits on the host (rows / 8 bytes; a tensor on the backend's
+        device is packed there and only its bits are copied out); otherwise np.flatnonzero of the mask.  No collective."""
         from .vectorbase import RowMask
 
+        backend = self._masked_backend()
+        bits = None
         if hasattr(allowed, "is_cuda") and hasattr(allowed, "dtype"):  # a torch tensor
             if "bool" not in str(allowed.dtype):
                 raise TypeError(f"a mask must be bool, got {allowed.dtype}")
+            on_device = (backend is not None and allowed.is_cuda and hasattr(backend, "engine") and (allowed.device.index or 0) == getattr(backend, "device", None)
+                         and allowed.dim() == 1 and allowed.shape[0] == self.total_rows and self.total_rows > 0)
+            if on_device:
+                # the mask was made on the caller's stream: wait for it BEFORE entering the backend's stream (the engine's own), where
+                # Engine.pack_mask_tensor's synchronise of the "current" stream no longer means the caller's.  Every rank must pack the
+                # finished mask: the global count decides whether a rank joins the exchange.
+                backend.torch.cuda.current_stream(backend.device).synchronize()
+                with backend.torch.cuda.stream(backend.stream):
+                    bits = backend.engine.pack_mask_tensor(allowed).cpu().numpy().view(np.uint32)
+                local = allowed[self.row_offset : self.row_offset + self.local_rows]
+                return RowMask(self, self.total_rows, _popcount(bits), dev_rows=backend.mask_to_device(local),
+                               layout=(self.total_rows, self.row_offset, self.local_rows), bits=bits)
             allowed = allowed.cpu().numpy()
         a = np.asarray(allowed)
         if a.dtype != np.bool_:
             raise TypeError(f"a mask must be bool, got {a.dtype}")
         if a.ndim != 1 or a.shape[0] != self.total_rows:
             raise ValueError(f"mask covers {a.shape[0] if a.ndim else 0} rows, the index has {self.total_rows}")
+        if backend is not None:
+            bits = _native.pack_mask_bits(a)
+            local = a[self.row_offset : self.row_offset + self.local_rows]
+            return RowMask(self, self.total_rows, int(np.count_nonzero(a)), dev_rows=backend.mask_to_device(local),
+                           layout=(self.total_rows, self.row_offset, self.local_rows), bits=bits)
         flat = np.flatnonzero(a)
         return RowMask(self, self.total_rows, len(flat), flat=flat)
 
@@ -672,13 +738,40 @@ class ShardedVectorBase:
 
     def fuzzy_lookup_embeddings_masked(self, embeddings, allowed, max_hits: int | None = None, min_score=None):
         """≡ [fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(allowed), max_hits, min_score) for e in embeddings] (`min_score`: one
-        threshold, or one per query); `allowed`: a mask or the `RowMask` made from one."""
+        threshold, or one per query); `allowed`: a mask or the `RowMask` made from one.  With a backend that offers the masked route the
+        whole batch is one local call per rank and ONE exchange (a rank whose part of the mask is empty still joins); a handle cut under
+        another layout (`rebalance()`) is cut again from its packed bits, on every rank alike and without a collective."""
         q = np.asarray(embeddings, dtype=np.float32)
         if q.ndim != 2:
             raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
         per_query = min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1
         if per_query and len(min_score) != len(q):
             raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(q)}")
+        backend = self._masked_backend()
+        if backend is not None:
+            k = 10 if max_hits is None else int(max_hits)
+            _check_k(k, "max_hits")  # (before anything collective: every rank makes the same call)
+            nq = len(q)
+            each = list(min_score) if per_query else [min_score] * nq
+            thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in each], dtype=np.float32)
+            mask = self._resolve_mask(allowed)
+            if mask.bits is not None:
+                if mask.count == 0 or nq == 0 or self.total_rows == 0:
+                    return [[] for _ in range(nq)]  # (the global count is the same on every rank: nobody waits in an exchange)
+                layout = (self.total_rows, self.row_offset, self.local_rows)
+
+                def local_lists():
+                    if mask.layout != layout:  # the rows were re-dealt since: this rank's slice of the packed mask, expanded again
+                        lo, n = self.row_offset, self.local_rows
+                        part = np.unpackbits(mask.bits.view(np.uint8)[lo // 8 : (lo + n + 7) // 8], bitorder="little")[lo % 8 : lo % 8 + n]
+                        mask.dev_rows = backend.mask_to_device(part.astype(np.bool_))
+                        mask.layout = layout
+                    return backend.local_search_masked(q, mask.dev_rows, k, thr)
+
+                from .vectorbase import _scored_lists
+
+                ords, scs, cnts = self._exchange_or_fail(local_lists, nq, k)
+                return _scored_lists(ords, scs, cnts, k)
         flat = self._resolve_mask(allowed).flat()
         return [self.fuzzy_lookup_embedding_in_subset(e, flat, max_hits, min_score[i] if per_query else min_score) for i, e in enumerate(q)]
 

@@ -269,14 +269,23 @@ class RowMask:
     """What `VectorBase.row_mask(allowed)` returns: the allowed rows of ONE index at ONE length, expanded once and kept where the lookups
     read them -- on a single-GPU engine an int32 row list in device memory (`dev_rows`, ascending; `count` of them), so that a masked
     lookup sends only its queries.  `rows` is the index length the mask was built for: a handle used after the index grew or shrank
-    raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it."""
+    raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it.  On a device group the
+    handle holds one shard-local list per device (`shards`, cut by `bounds`), on a row-sharded index this rank's list and the packed mask."""
 
-    __slots__ = ("rows", "count", "dev_rows", "_flat", "_owner")
+    __slots__ = ("rows", "count", "dev_rows", "shards", "bounds", "layout", "bits", "_flat", "_owner")
 
-    def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None):
+    def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None, shards=None, bounds=None, layout=None, bits=None):
         self.rows = int(rows)
         self.count = int(count)
         self.dev_rows = dev_rows
+        # a device group (multidevice.DeviceGroup.mask_to_rows): one shard-local int32 row list per device (None: no allowed row there)
+        # and the shard bounds the mask was cut by
+        self.shards = shards
+        self.bounds = None if bounds is None else tuple(bounds)
+        # a row-sharded index (sharded.ShardedVectorBase): dev_rows = THIS rank's local rows, `count` the global count, `layout` =
+        # (total_rows, row_offset, local_rows) they were cut under, `bits` the whole mask packed on the host (rows / 8 bytes, pack_mask_bits)
+        self.layout = layout
+        self.bits = bits
         self._flat = flat
         self._owner = weakref.ref(owner)
 
@@ -285,7 +294,13 @@ class RowMask:
 
     def flat(self) -> np.ndarray:
         if self._flat is None:
-            self._flat = np.zeros(0, np.int64) if self.dev_rows is None else self.dev_rows.cpu().numpy().astype(np.int64)
+            if self.bits is not None:
+                self._flat = np.flatnonzero(np.unpackbits(self.bits.view(np.uint8), bitorder="little")[: self.rows]).astype(np.int64)
+            elif self.shards is not None:
+                parts = [r.cpu().numpy().astype(np.int64) + lo for r, lo in zip(self.shards, self.bounds) if r is not None]
+                self._flat = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+            else:
+                self._flat = np.zeros(0, np.int64) if self.dev_rows is None else self.dev_rows.cpu().numpy().astype(np.int64)
         return self._flat
 
 
@@ -777,6 +792,9 @@ class VectorBase:
             if self._masked_native(eng) and allowed.is_cuda and (allowed.device.index or 0) == eng.device:
                 dev_rows, count = eng.mask_to_rows(allowed)
                 return RowMask(self, n, count, dev_rows=dev_rows)
+            if self._masked_group(eng):  # a tensor on any device: every shard's slice goes to that shard's device
+                shards, count, bounds = eng.mask_to_rows(allowed)
+                return RowMask(self, n, count, shards=shards, bounds=bounds)
             allowed = allowed.cpu().numpy()
         a = np.asarray(allowed)
         if a.dtype != np.bool_:
@@ -789,7 +807,10 @@ class VectorBase:
         if self._masked_native(eng):
             dev_rows, count = eng.mask_to_rows(a)
             return RowMask(self, n, count, dev_rows=dev_rows)
-        flat = np.flatnonzero(a)  # device groups, test doubles: the fallback's ordinal list
+        if self._masked_group(eng):
+            shards, count, bounds = eng.mask_to_rows(a)
+            return RowMask(self, n, count, shards=shards, bounds=bounds)
+        flat = np.flatnonzero(a)  # groups of test doubles, test doubles: the fallback's ordinal list
         return RowMask(self, n, len(flat), flat=flat)
 
     @staticmethod
@@ -797,6 +818,12 @@ class VectorBase:
         """A single-GPU engine that expands masks and searches their row list itself (tavb_mask_expand, tavb_search_subset_batch_resident);
         device groups and test doubles take the fallback."""
         return isinstance(eng, _native.Engine) and hasattr(eng, "mask_to_rows") and hasattr(eng, "search_subset_batch_resident")
+
+    @staticmethod
+    def _masked_group(eng) -> bool:
+        """A device group all of whose engines expand masks and search their row list themselves (multidevice.DeviceGroup.search_masked:
+        tavb_mask_expand and tavb_search_subset_batch_device per shard); groups of test doubles take the fallback."""
+        return eng is not None and hasattr(eng, "masked_capable") and eng.masked_capable()
 
     def _resolve_mask(self, allowed) -> RowMask:
         if not isinstance(allowed, RowMask):
@@ -832,8 +859,9 @@ class VectorBase:
         """Batch form over ONE mask: equals [fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(allowed).tolist(), max_hits, min_score)
         for e in embeddings].  On a single-GPU engine with 1 <= max_hits <= 16384 (beyond 256: while the "large_k" option is on, as for
         every other lookup) it is one submission -- the queries go over the
-        mask's resident row list eight per pass -- and with a `RowMask` only the queries travel; everything else (max_hits == 0 or
-        beyond 16384, device groups, test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
+        mask's resident row list eight per pass -- and with a `RowMask` only the queries travel; a device group does the same on every
+        shard that has allowed rows (one batched call per shard, merged on the host); everything else (max_hits == 0 or
+        beyond 16384, "large_k" off beyond 256, test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
         threshold per query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings`."""
         queries = np.asarray(embeddings, dtype=np.float32)
         if queries.ndim != 2:
@@ -858,6 +886,17 @@ class VectorBase:
         eng = self._sync_device()
         if self._masked_native(eng) and mask.dev_rows is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
             ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
+            if eng.ordinal_base:
+                ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
+            if as_arrays:
+                return ords, scs, cnts
+            return _scored_lists(ords, scs, cnts, max_hits)
+        if self._masked_group(eng) and mask.shards is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
+            if mask.bounds != tuple(eng.bounds):
+                # the same index at the same length under other shard bounds (grown row by row, then re-uploaded from row 0): the
+                # caller has done nothing wrong -- the handle is cut again, once
+                mask.shards, _, mask.bounds = eng._rows_to_handles(mask.flat())
+            ords, scs, cnts = eng.search_masked(queries, mask.shards, max_hits, thr)
             if eng.ordinal_base:
                 ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
             if as_arrays:
