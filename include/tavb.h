@@ -143,6 +143,10 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   answers bit for bit; 16 is faster on cfg3, measured in profiles/r09_mfma_shape.md).  The routing: tavb_plan_filter_shape.  The SPLIT exact form, the 128-query
  *                   tile, "mfma_bdirect", "mfma_sched" and the ablations other than 256 / 258 always run 32x32x16.  "last_mfma_shape" (read only) = the
  *                   shape the last filter launch of the 128/256-query tile ran on (0 before the first)
+ *   "last_skinny_kernel" (read only) what the last launch of the 32/64-query tile instantiated (0 before the first): variant * 10000 + bytes per K
+ *                   step * 100 + queries per tile.  Variant 0 = the LDS-DMA ring (ships); under "mfma_sched" 8 / 6 / 5 on whole-line widths and 32 queries
+ *                   1 = deep ring, 2 = half tiles of 128 rows, 4 = register staging (K steps a multiple of 4; else the ring).  The step is 128 bytes
+ *                   when a row is a multiple of that and "mfma_sched" is not 9, else 64: 12832, 12864, 6432, 6464, 22832, 32832, 52832
  *   "mfma_bdirect"  0 (default) / 1: the 256-query tile takes its query operand in MFMA-fragment-major order straight from L2 into registers
  *                   (no LDS staging; three corpus slots instead of two): measured +0.8 %, kept as an option (profiles/r04_cfg3_kernel.md section 10)
  *   "small_direct_bytes" host-synchronous lookups of one query (tavb_search) or a few (tavb_search_batch with nq <= 8; <= 4 for k > 64) on corpora up

@@ -83,6 +83,7 @@ SET_NOT_READ_BEFORE = ("mfma_sched", "mfma_ablate")  # settable, and not readabl
 READ_ONLY = {
     "last_shadow": 0,
     "last_mfma_shape": 0,
+    "last_skinny_kernel": 0,
     "last_direct": 0,
     "last_graph": 0,
     "last_topk_refine": 0,

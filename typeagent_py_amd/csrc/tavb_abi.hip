@@ -248,6 +248,7 @@ const Option kOptions[] = {
     RANGE("sort_small_keys", sort_small_keys, 0, tavb::kSortSmallMax),
     READ_ONLY("last_shadow", last_shadow),
     READ_ONLY("last_mfma_shape", last_mfma_shape),
+    READ_ONLY("last_skinny_kernel", last_skinny_kernel),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),
     READ_ONLY("last_topk_refine", last_topk_refine),

@@ -250,6 +250,7 @@ hipError_t launch_select_band(const unsigned long long* cand, const int* counts,
                               int doom_limit = 0);
 // 32-query tiles at HBM speed, fp32 or fp16 corpora (same parameter block; `queries` in the corpus dtype)
 hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream);
+int skinny_kernel_id(const MfmaParams& p);  // the instantiation launch_skinny_scan picks for p: variant * 10000 + K step in bytes * 100 + queries per tile
 int skinny_query_tile(int nq);  // 32, or 64 for batches of 33 and more
 int skinny_pick_splits(int64_t rows, int nq_padded, int tile, int n_cu, int dim, bool f32, int sched);
 bool skinny_supported(int dim, int k, bool f32);

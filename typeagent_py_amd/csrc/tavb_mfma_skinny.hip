@@ -475,6 +475,15 @@ static int skinny_variant(int dim, bool f32, int tile, int sched) {
   return v;
 }
 
+// What launch_skinny_scan instantiates for p (option "last_skinny_kernel"): variant * 10000 + bytes per K step * 100 + queries per tile --
+// 12832 = the ring at whole-line steps on 32 queries, 6464 = 64-byte steps on 64 queries, 52832 = register staging.  The launcher switches on it.
+int skinny_kernel_id(const MfmaParams& p) {
+  const bool f32 = p.f32 != 0;
+  const int tile = p.skinny_tile == 64 ? 64 : 32;
+  const int step = (skinny_line_steps(p.dim, f32) && p.sched != 9) ? 128 : 64;  // (sched 9: force the 64-byte steps, measurement)
+  return skinny_variant(p.dim, f32, tile, p.sched) * 10000 + step * 100 + tile;
+}
+
 static int skinny_wg_per_cu(int dim, bool f32, int tile, int sched) {
   const bool line = skinny_line_steps(dim, f32);
   const int v = skinny_variant(dim, f32, tile, sched);
@@ -514,26 +523,21 @@ hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(S_THREADS), lds, stream, d);
     return hipGetLastError();
   };
-  const bool line = skinny_line_steps(p.dim, f32) && p.sched != 9;  // (sched 9: force the 64-byte steps, measurement)
-  switch (skinny_variant(p.dim, f32, tile, p.sched)) {
-    case 1:
-      return f32 ? go(skinny_scan_kernel<float, 1, 128, true>, SkinnyGeom<float, 1, 128, true>::LDS)
-                 : go(skinny_scan_kernel<_Float16, 1, 128, true>, SkinnyGeom<_Float16, 1, 128, true>::LDS);
-    case 2:
-      return f32 ? go(skinny_scan_kernel<float, 1, 128, false, 0, true>, SkinnyGeom<float, 1, 128, false, 0, true>::LDS)
-                 : go(skinny_scan_kernel<_Float16, 1, 128, false, 0, true>, SkinnyGeom<_Float16, 1, 128, false, 0, true>::LDS);
-    case 4:
-      return f32 ? go(skinny_scan_kernel<float, 1, 128, false, 4>, SkinnyGeom<float, 1, 128, false, 4>::LDS)
-                 : go(skinny_scan_kernel<_Float16, 1, 128, false, 4>, SkinnyGeom<_Float16, 1, 128, false, 4>::LDS);
-    default: break;
+  // (one case per instantiation, keyed by the value the "last_skinny_kernel" getter reports: the getter cannot drift from the dispatch)
+#define TAVB_SKINNY(NI, STEP, ...)                                                                                   \
+  (f32 ? go(skinny_scan_kernel<float, NI, STEP, ##__VA_ARGS__>, SkinnyGeom<float, NI, STEP, ##__VA_ARGS__>::LDS) \
+       : go(skinny_scan_kernel<_Float16, NI, STEP, ##__VA_ARGS__>, SkinnyGeom<_Float16, NI, STEP, ##__VA_ARGS__>::LDS))
+  switch (skinny_kernel_id(p)) {
+    case 12832: return TAVB_SKINNY(1, 128);
+    case 12864: return TAVB_SKINNY(2, 128);
+    case 6432: return TAVB_SKINNY(1, 64);
+    case 6464: return TAVB_SKINNY(2, 64);
+    case 22832: return TAVB_SKINNY(1, 128, true);            // deep ring
+    case 32832: return TAVB_SKINNY(1, 128, false, 0, true);  // half tiles
+    case 52832: return TAVB_SKINNY(1, 128, false, 4);        // register staging
+    default: return hipErrorInvalidValue;
   }
-  if (f32) {
-    if (tile == 64) return line ? go(skinny_scan_kernel<float, 2, 128>, SkinnyGeom<float, 2, 128>::LDS) : go(skinny_scan_kernel<float, 2, 64>, SkinnyGeom<float, 2, 64>::LDS);
-    return line ? go(skinny_scan_kernel<float, 1, 128>, SkinnyGeom<float, 1, 128>::LDS) : go(skinny_scan_kernel<float, 1, 64>, SkinnyGeom<float, 1, 64>::LDS);
-  }
-  if (tile == 64)
-    return line ? go(skinny_scan_kernel<_Float16, 2, 128>, SkinnyGeom<_Float16, 2, 128>::LDS) : go(skinny_scan_kernel<_Float16, 2, 64>, SkinnyGeom<_Float16, 2, 64>::LDS);
-  return line ? go(skinny_scan_kernel<_Float16, 1, 128>, SkinnyGeom<_Float16, 1, 128>::LDS) : go(skinny_scan_kernel<_Float16, 1, 64>, SkinnyGeom<_Float16, 1, 64>::LDS);
+#undef TAVB_SKINNY
 }
 
 }  // namespace tavb
