@@ -177,6 +177,14 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   and a host sort as before (the library itself reads it nowhere else)
  *   "sort_stage_keys" 1 .. 2^30 (default 2^21): most results of a sorted lookup decoded into pinned memory (12 bytes each) before they
  *                   are copied into the caller's arrays; more results take several such pieces, one synchronise each
+ *   "mask_tile"     masked batches (the binding reads it; the rule is tavb_plan_masked): 1 (default) = a batch takes the 32/64-query tile with the bit test in
+ *                   its admission path (tavb_search_masked_batch) where tavb_plan_masked says so, else the gather route (the mask expanded to a row list,
+ *                   the queries over it eight per pass); 0 = never the tile; 2 = the tile wherever it serves the shape (tests)
+ *   "mask_tile_min_bytes"  (default 128 MiB, the default of "small_direct_bytes") allowed rows x row bytes below which a masked batch keeps the gather
+ *                   route -- one launch there -- and everything behaves as before the tile route existed
+ *   "mask_tile_pct" (default 100 = byte parity) the tile is taken when the gather route's bytes (allowed rows once per 8 queries) are at least this
+ *                   many per cent of the tile's (the mask's span once per 64 queries)
+ *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the tile
  *   "sort_small_keys" 0 .. 16384 (default 16384): a sort of up to this many keys (tavb_search_sorted, tavb_sort_keys_device) runs in ONE
  *                   workgroup in LDS; bigger ones take the multi-pass radix sort (3 launches per 8-bit digit that is not the same for
  *                   every key, + 2)
@@ -405,6 +413,22 @@ int tavb_search_subset_batch_resident(tavb_ctx* ctx, const float* queries_host, 
 int tavb_search_subset_batch_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
                                     const float* min_scores, int32_t remap, tavb_key* out_keys);
 
+/* A masked batch on the 32/64-query MFMA tile: nq queries over the rows an allow-mask names, the corpus read ONCE per 64 queries with the bit
+ * test in the tile's admission path, instead of the allowed rows gathered once per TAVB_MAX_STREAM_QUERIES queries -- the route for a DENSE mask
+ * under a real batch (a time range, a thread scope).  dev_bits: the mask over the whole corpus in the bit form above, `rows` == the corpus' rows;
+ * [first_row, last_row] must contain every set bit (0, rows - 1 is always valid): the tile scans rows [first_row rounded down to a multiple of
+ * 256, last_row] only, so a contiguous range costs its own bytes.  Serves 1 <= k <= 64 and rows of a multiple of 64 bytes; anything else returns
+ * TAVB_E_UNSUPPORTED and the caller keeps the gather route (tavb_search_subset_batch_resident / _device over tavb_mask_expand's list).  The
+ * corpus' own rows are multiplied -- fp32 x fp32, or the fp32 queries as split fp16 planes x fp16 rows, as on the unmasked tile route; no
+ * shadow -- and the scores are final.  Outputs and ordering: tavb_search_batch / tavb_search_device (min_scores: nq thresholds on the HOST;
+ * the device form's keys carry ordinal_base + row and nothing is waited for).  Against the gather route the answers agree the way the tile
+ * agrees with the streaming kernels everywhere: the same ordinals except among float32 near-ties, scores within 1e-5 -- not bit for bit.  An
+ * empty corpus, nq == 0 or first_row > last_row: zero counts / zero keys, no tile launch. */
+int tavb_search_masked_batch(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
+                             int64_t last_row, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_masked_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
+                              int64_t last_row, int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
+
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */
 int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k,
@@ -503,6 +527,14 @@ int tavb_plan_ladder(int64_t rows, int32_t nq, int32_t n_cu, int64_t* out_bounds
  * measurement options "mfma_sched" and "mfma_ablate".  Returns 16 or 32, or a negative error code for a shape or tile out of range (the
  * rule "mfma_shape" is validated by).  A pure function, needs no context and no GPU. */
 int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate);
+
+/* Which route a masked batch takes under option "mask_tile" = 1: 1 = the 32/64-query tile (tavb_search_masked_batch), 0 = the gather route.
+ * nq queries, k, the corpus' dim and dtype (TAVB_F32 / TAVB_F16), `allowed` set rows inside a span of `span` rows (last allowed row + 1 - the
+ * first allowed row rounded down to a multiple of 256), and the options "mask_tile_min_bytes" / "mask_tile_pct".  The tile when it serves the shape
+ * (1 <= k <= 64, rows of a multiple of 64 bytes), nq is at least the unmasked tile's own lower bound (the defaults of "skinny_min_batch_f32" /
+ * "skinny_min_batch_f16"), allowed x row bytes >= min_bytes, and ceil(nq / 8) x allowed x 100 >= ceil(nq / 64) x span x pct -- the gather
+ * route's bytes are at least pct % of the tile's.  Negative: an argument out of range.  A pure function, needs no context and no GPU. */
+int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct);
 
 #ifdef __cplusplus
 }

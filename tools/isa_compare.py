@@ -18,6 +18,10 @@ import sys
 DESCRIPTOR = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "group_segment_fixed_size", "private_segment_fixed_size")
 # template arguments of the OLD side that the new side no longer has: kernel name -> argument index (skinny_scan_kernel lost ABL, always 0)
 DROPPED_ARGS = {"skinny_scan_kernel": 3}
+# template arguments the NEW side gained at the end of the list, and the value that names the old kernel: kernel name -> (arguments the old side
+# has, value).  skinny_scan_kernel gained MASKED: <..., false> is the kernel the old side has, <..., true> exists on the new side only.
+# (Comparing a parent that still had ABL needs DROPPED_ARGS alone: such a parent has seven arguments too, and its index 3 is dropped first.)
+ADDED_ARGS = {"skinny_scan_kernel": (6, "false")}
 
 
 def kernel_id(symbol):
@@ -32,6 +36,10 @@ def kernel_id(symbol):
     if symbol[pos] == "I":
         pos += 1
         while symbol[pos] != "E":
+            pack = re.match(r"J(PKj)?E", symbol[pos:])  # a trailing parameter pack (the mask argument of skinny_scan_kernel): says nothing MASKED does not
+            if pack is not None:
+                pos += pack.end()
+                continue
             m = re.match(r"Li(\d+)E|Ln(\d+)E|Lb([01])E|(f)|(DF16_)", symbol[pos:])
             if m is None:
                 raise ValueError(f"template argument not understood at {symbol[pos:]!r}")
@@ -65,8 +73,10 @@ def kernels(path, old_side):
             line = line.replace(symbol, "KERNEL")
             body.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
         name, args = kernel_id(symbol)
-        if old_side and name in DROPPED_ARGS:
+        if old_side and name in DROPPED_ARGS and len(args) > ADDED_ARGS.get(name, (len(args),))[0]:
             del args[DROPPED_ARGS[name]]
+        if not old_side and name in ADDED_ARGS and len(args) == ADDED_ARGS[name][0] + 1 and args[-1] == ADDED_ARGS[name][1]:
+            del args[-1]
         out[name + ("<" + ",".join(args) + ">" if args else "")] = (body, desc)
     return out
 

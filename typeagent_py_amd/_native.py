@@ -80,6 +80,9 @@ _SIGNATURES = [
     ("tavb_search_subset_batch_resident", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_subset_batch_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
+    ("tavb_search_masked_batch", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_masked_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -96,6 +99,7 @@ _SIGNATURES = [
     ("tavb_profile_read", c_int, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int64)]),
     ("tavb_plan_ladder", c_int, [c_int64, c_int32, c_int32, POINTER(c_int64), c_int32]),
     ("tavb_plan_filter_shape", c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    ("tavb_plan_masked", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
 ]
 
 ABI_SYMBOLS = [name for name, _, _ in _SIGNATURES]
@@ -141,6 +145,19 @@ def plan_filter_shape(shape: int, query_tile: int = 256, split: bool = False, bd
     r = lib.tavb_plan_filter_shape(int(shape), int(query_tile), int(bool(split)), int(bool(bdirect)), int(sched), int(ablate))
     _check(lib, r if r < 0 else 0)
     return int(r)
+
+
+MASK_TILE_MIN_BYTES = 128 << 20  # the defaults of the options "mask_tile_min_bytes" / "mask_tile_pct"
+MASK_TILE_PCT = 100
+
+
+def plan_masked(nq: int, k: int, dim: int, dtype: int, allowed: int, span: int, min_bytes: int = MASK_TILE_MIN_BYTES, pct: int = MASK_TILE_PCT) -> bool:
+    """True: a masked batch of `nq` queries with `allowed` set rows inside a span of `span` rows takes the 32/64-query tile under option
+    "mask_tile" = 1, False: the gather route (tavb_plan_masked; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_masked(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
 
 
 def library_path() -> str:
@@ -291,6 +308,15 @@ class Engine:
     # -- options / profiling ----------------------------------------------
     def set_option(self, name: str, value: int) -> None:
         _check(self.lib, self.lib.tavb_set_option(self._h, name.encode(), int(value)))
+        self.__dict__.pop("_mask_tile_opts", None)
+
+    def mask_tile_options(self) -> tuple[int, int, int]:
+        """("mask_tile", "mask_tile_min_bytes", "mask_tile_pct") as the library holds them, read once and again after any `set_option`: a
+        masked batch asks on every call, and three option reads are 3 - 4 us of a 90 us lookup."""
+        opts = self.__dict__.get("_mask_tile_opts")
+        if opts is None:
+            opts = self._mask_tile_opts = tuple(self.get_option(n) for n in ("mask_tile", "mask_tile_min_bytes", "mask_tile_pct"))
+        return opts
 
     def get_option(self, name: str) -> int:
         out = c_int64(0)
@@ -522,19 +548,71 @@ class Engine:
         return bits
 
     def mask_to_rows(self, mask):
+        """`mask_to_rows_bits` without the packed bits: (dev_rows, count)."""
+        return self.mask_to_rows_bits(mask)[:2]
+
+    def mask_to_rows_bits(self, mask):
         """An allow-mask -- a numpy bool array [rows], or a torch bool tensor [rows] on this engine's device -- -> (torch int32 [count] on
         the device: the allowed rows in ascending order, i.e. np.flatnonzero(mask); count).  A numpy mask is packed to bits on the host
         (rows / 8 bytes travel) and its count is known there; a device tensor is packed by tavb_mask_pack and never visits the host -- its
-        count is not known, so the expansion is two calls (pack, count + sum, count + write: five launches, two synchronises)."""
+        count is not known, so the expansion is two calls (pack, count + sum, count + write: five launches, two synchronises).  Third: the packed mask on the device (torch int32 [(rows + 31) // 32]), what
+        `search_masked_batch` reads."""
         torch = self._torch
         dev = torch.device("cuda", self.device)
         if isinstance(mask, torch.Tensor):
-            return self.expand_mask_bits(self.pack_mask_tensor(mask, wait=False), int(mask.shape[0]))  # (same stream: nothing to wait for)
+            bits = self.pack_mask_tensor(mask, wait=False)
+            return (*self.expand_mask_bits(bits, int(mask.shape[0])), bits)  # (same stream: nothing to wait for)
         words = pack_mask_bits(np.asarray(mask))
         rows = int(np.shape(mask)[0])
         bits = torch.from_numpy(words.view(np.int32)).to(dev)
         torch.cuda.current_stream(self.device).synchronize()
-        return self.expand_mask_bits(bits, rows, cap=int(np.count_nonzero(mask)))
+        return (*self.expand_mask_bits(bits, rows, cap=int(np.count_nonzero(mask))), bits)
+
+    # masked batches on the 32/64-query tile ------------------------------------------
+    plan_masked = staticmethod(plan_masked)
+
+    def _masked_args(self, dev_bits, span):
+        torch = self._torch
+        assert dev_bits.dtype == torch.int32 and dev_bits.is_contiguous() and dev_bits.dim() == 1 and dev_bits.numel() * 32 >= self.rows
+        first, last = (0, self.rows - 1) if span is None else (int(span[0]), int(span[1]))
+        return (c_void_p(dev_bits.data_ptr()) if dev_bits.numel() else None), first, last
+
+    def search_masked_batch(self, queries, dev_bits, k: int, thrs, span=None):
+        """A masked batch on the 32/64-query tile (tavb_search_masked_batch): queries f32 [nq, dim]; dev_bits torch int32 [(rows + 31) // 32]
+        on this device, the mask over the whole corpus (`mask_to_rows_bits`, `pack_mask_tensor`); span = (first, last) allowed row (None:
+        the whole corpus); 1 <= k <= 64; thrs float32 [nq] (or one for all) -> (ordinals [nq, k], scores [nq, k], counts [nq]), the layout
+        of `search_batch`.  Raises TavbError (TAVB_E_UNSUPPORTED) for a shape the tile does not serve."""
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        ords = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        cnts = np.zeros(nq, dtype=np.int32)
+        bits, first, last = self._masked_args(dev_bits, span)
+        with self._lock:
+            rc = self.lib.tavb_search_masked_batch(self._h, _addr(a), nq, bits, int(self.rows), first, last, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_masked_device(self, dev_queries, dev_bits, k: int, thrs, span=None, out_keys=None):
+        """`search_masked_batch` with the queries on the device and nothing waited for (tavb_search_masked_device): dev_queries torch f32
+        [nq, dim] -> torch int64 [nq, k] sorted, zero-padded keys carrying ordinal_base + row.  `out_keys`: a device tensor or a PINNED
+        host tensor.  Async: `synchronize()` before reading."""
+        torch = self._torch
+        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
+        nq = int(dev_queries.shape[0])
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
+        bits, first, last = self._masked_args(dev_bits, span)
+        with self._lock:
+            rc = self.lib.tavb_search_masked_device(self._h, c_void_p(dev_queries.data_ptr()), nq, bits, int(self.rows), first, last, k, _addr(t),
+                                                    c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
 
     def search_subset_batch_resident(self, queries, dev_rows, k: int, thrs, remap: bool = True):
         """`search_subset_resident` for a batch: queries f32 [nq, dim] over ONE resident row list (torch int32 [S]: `mask_to_rows`, or

@@ -249,6 +249,10 @@ const Option kOptions[] = {
     READ_ONLY("last_shadow", last_shadow),
     READ_ONLY("last_mfma_shape", last_mfma_shape),
     READ_ONLY("last_skinny_kernel", last_skinny_kernel),
+    RANGE("mask_tile", mask_tile, 0, 2),
+    AT_LEAST("mask_tile_min_bytes", mask_tile_min_bytes, 0),
+    RANGE("mask_tile_pct", mask_tile_pct, 0, 1000000),
+    READ_ONLY("masked_route", masked_route),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),
     READ_ONLY("last_topk_refine", last_topk_refine),

@@ -77,6 +77,10 @@ struct Buffer {
   }
 };
 
+// the defaults of skinny_min_batch_f32 / skinny_min_batch_f16 (the measured break-even of the 32/64-query tile against the streaming tiers);
+// tavb_plan_masked, which has no context, uses them as they ship
+constexpr int64_t kSkinnyMinBatchF32 = 5, kSkinnyMinBatchF16 = 3;
+
 struct PendingTiming {
   int kernel;
   hipEvent_t start, stop;
@@ -130,8 +134,8 @@ struct tavb_ctx {
   int64_t mfma_sched = 0;
   int64_t mfma_tile = 0;  // 0 = auto (128 queries per tile up to 128 queries, else 256)
   int64_t mfma_sample_rows = 0;  // rows of the first (threshold-seeding) phase: 0 = auto (two tiles per workgroup), -1 = one phase, no seeding
-  int64_t skinny_min_batch_f32 = 5;   // fp32 corpus: batches from this size up use the 32-query MFMA tile
-  int64_t skinny_min_batch_f16 = 3;   // fp16 corpus: batches from this size up to mfma_min_batch - 1 use it
+  int64_t skinny_min_batch_f32 = tavb::host::kSkinnyMinBatchF32;   // fp32 corpus: batches from this size up use the 32-query MFMA tile
+  int64_t skinny_min_batch_f16 = tavb::host::kSkinnyMinBatchF16;   // fp16 corpus: batches from this size up to mfma_min_batch - 1 use it
   int64_t mfma_ladder = 4;            // each further phase scans this many times the rows scanned so far (0 = seed once)
 
   Buffer d_queries, d_queries_f16, d_lists, d_out, d_rows, d_cand, d_thr, d_sample_keys;
@@ -181,6 +185,12 @@ struct tavb_ctx {
   Buffer h_flag{nullptr, 0, true};   // pinned: the work list of flagged queries read back by the one route that needs a host round trip (fp32 corpus, k > 64)
   int64_t mfma_shape = 16;      // option: MFMA of the 256-query filter tile, 16 = v_mfma_f32_16x16x32_f16, 32 = v_mfma_f32_32x32x16_f16 (profiles/r09_mfma_shape.md)
   int64_t last_mfma_shape = 0;  // option "last_mfma_shape" (get): the MFMA shape the last filter launch of the 128/256-query tile ran on (0: none yet)
+  // masked batches (tavb_search_masked_batch / _device): the binding's choice between the gather route (tavb_search_subset_batch_resident over the
+  // expanded row list) and the 32/64-query tile with the bit test in its admission path; the rule is tavb_plan_masked
+  int64_t mask_tile = 1;                            // option: 1 = follow tavb_plan_masked, 0 = never the tile, 2 = always where supported
+  int64_t mask_tile_min_bytes = (int64_t)128 << 20;  // option: allowed rows x row bytes below which the gather route (one launch there) is kept; the default of small_direct_bytes
+  int64_t mask_tile_pct = 100;                      // option: the tile when the gather route's bytes are at least this many % of the tile's (100 = byte parity)
+  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile
   int64_t last_skinny_kernel = 0;  // option "last_skinny_kernel" (get): what the last launch of the 32/64-query tile instantiated, tavb::skinny_kernel_id (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
   int64_t band_max = tavb::kBandMax;  // option: keys of a query's band the wide tile's selection hands to the rescoring (256 .. kBandMax); a band that does not fit flags the query
@@ -345,6 +355,11 @@ DirectGroupPlan plan_direct_group(const tavb_ctx* c, int nq, int k, int full_blo
 // Core: queries on device (f32 [nq, dim]) -> sorted key lists d_out [nq, k] (async on the stream).
 int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_row_ids, int64_t n_pos,
                        uint32_t index_base, u64_t* d_out, u64_t key_bound = ~0ull);
+
+// Masked batch on the 32/64-query tile: dev_bits = the allow-mask over the corpus rows, [first_row, last_row] holds every set bit; keys carry
+// index_base + row -> d_out [nq, k] (async on the stream).  The caller has checked skinny_supported and the bounds.
+int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits, int64_t first_row,
+                       int64_t last_row, uint32_t index_base, u64_t* d_out);
 
 // ---- tavb_lookup.hip
 // The large-k lookup (tavb_search_topk's passes) with the queries on the device and nothing waited for: nq sorted, zero-padded lists of k keys

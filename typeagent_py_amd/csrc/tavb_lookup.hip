@@ -1037,6 +1037,7 @@ int tavb_search_subset_batch_resident(tavb_ctx* c, const float* queries_host, in
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
   c->last_direct = 0;
+  c->masked_route = 1;  // the gather route of a masked batch
   if (n_subset == 0 || c->rows == 0) {
     for (int q = 0; q < nq; ++q) out_counts[q] = 0;
     return TAVB_OK;
@@ -1086,6 +1087,7 @@ int tavb_search_subset_batch_device(tavb_ctx* c, const float* dev_queries, int32
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
   c->last_direct = 0;
+  c->masked_route = 1;  // the gather route of a masked batch
   DeviceGuard guard(c->device);
   u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
   const size_t n_keys = (size_t)nq * k;
@@ -1110,6 +1112,62 @@ int tavb_search_subset_batch_device(tavb_ctx* c, const float* dev_queries, int32
     if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
   }
   return TAVB_OK;
+}
+
+// ---- masked batches on the 32/64-query tile (tavb_route.hip::search_masked_tile)
+// What both entry points check alike; *empty: nothing to scan (an empty corpus, no query, an empty span).
+static int check_masked_args(tavb_ctx* c, int32_t nq, int32_t min_nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, int32_t k,
+                             bool* empty) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
+  if (nq < min_nq) return fail(TAVB_E_INVALID, "nq must be >= %d", min_nq);
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  *empty = rows == 0 || nq == 0 || first_row > last_row;
+  if (!*empty && (first_row < 0 || last_row >= rows)) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
+  if (!*empty && !dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
+  if (!tavb::skinny_supported(c->dim, k, c->dtype != TAVB_F16))
+    return fail(TAVB_E_UNSUPPORTED, "the masked tile serves 1 <= k <= 64 and rows of a multiple of 64 bytes (k = %d, %d bytes): use the gather route", k,
+                c->dim * (c->dtype == TAVB_F16 ? 2 : 4));
+  return TAVB_OK;
+}
+
+int tavb_search_masked_batch(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                             int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_masked_args(c, nq, 0, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = c->h_out.reserve((size_t)nq * k * sizeof(u64_t))) return rc;
+  c->last_graph = 0;
+  if (int rc = search_masked_tile(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr))) return rc;
+  TAVB_HIP(hipStreamSynchronize(c->stream));  // (no D2H copy: the merge kernel wrote the keys into pinned host memory)
+  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+  return TAVB_OK;
+}
+
+int tavb_search_masked_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                              int32_t k, const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_masked_args(c, nq, 0, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  DeviceGuard guard(c->device);
+  if (empty) {  // zero keys; no tile launch
+    const hipError_t e = tavb::launch_fill_keys(reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k, 0ull, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
+    return TAVB_OK;
+  }
+  return search_masked_tile(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
 }
 
 // ---- row masks (tavb_mask.hip)

@@ -88,8 +88,17 @@ struct SkinnyGeom {
   static_assert(DR == 0 || STEP == 128, "register staging is built for whole-line steps");
 };
 
-template <typename T, int NI, int STEP, bool DEEP = false, int DR = 0, bool HALF = false>
-__global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) == 2)) ? 1 : 2)) skinny_scan_kernel(const MfmaDeviceParams p) {
+// MASKED: a row is a candidate only if its bit is set in an allow-mask (tavb.h "row masks": uint32 words, row r = bit r & 31 of word r >> 5).  The
+// mask is the ONE extra kernel argument of the masked instantiations (`mask_arg`: empty, or one `const uint32_t*`) -- MfmaDeviceParams, which the
+// 128/256-query tile shares, does not know about it, and MASKED = false compiles to what it compiled to before the parameter existed.  The
+// pointer names the word of the launch's first row (a multiple of 32: the launcher checks), so a 32-row block of the epilogue is exactly one
+// word.  The word is wave-uniform and comes in through the SCALAR data path (a constant-address-space load: it counts in lgkmcnt, which every
+// K step waits out anyway) -- a vector or flat load the compiler can see among the staging loads would make its wait-count pass drain the whole
+// staging queue (see `need_compact` and the candidate store).
+typedef const __attribute__((address_space(4))) uint32_t const_u32;
+template <typename T, int NI, int STEP, bool DEEP = false, int DR = 0, bool HALF = false, bool MASKED = false, typename... MaskArg>
+__global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) == 2)) ? 1 : 2)) skinny_scan_kernel(const MfmaDeviceParams p, MaskArg... mask_arg) {
+  static_assert(sizeof...(MaskArg) == (MASKED ? 1 : 0), "the mask is an argument of the masked instantiations only");
   using G = SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>;
   constexpr int BMT = G::BMT, RW = G::RW, MI = G::MI;
   constexpr int SQ = G::SQ;
@@ -373,6 +382,14 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
         for (int r = 1; r < 16; ++r) top = __builtin_fmaxf(top, acc[mi][ni][r]);
         const bool any = top > thr_pre;
         if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+          [[maybe_unused]] uint32_t allow = ~0u;  // MASKED: the word of this 32-row block; bit r_off + 4 * (lane >> 5) is the row a lane tests
+          if constexpr (MASKED) {
+            const int64_t block_row = row0 + wave * RW + mi * 32;  // (a multiple of 32, as r_begin and the tile are)
+            if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no word (and admits nothing either way)
+            const char* word = sgpr_ptr(reinterpret_cast<const char*>((mask_arg, ...)) + (size_t)(block_row >> 5) * sizeof(uint32_t));
+            allow = *(const const_u32*)(uintptr_t)word;  // s_load_dword: lgkmcnt, not vmcnt
+            if (allow == 0u) continue;  // nothing of this block is allowed
+          }
           // (the admission path of the 256-query tile: wave masks in scalar registers, four rows at a time, one LDS atomic per admitted row)
           const int64_t row_base = row0 + wave * RW + mi * 32 + 4 * (lane >> 5);
           const int64_t left64 = r_end - row_base;
@@ -391,7 +408,8 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
             for (int j = 0; j < 4; ++j) {
               const int r_off = j + 8 * g;
               if (m[j] == 0ull) continue;
-              if (((m[j] >> lane) & 1ull) != 0ull && r_off < rows_left) {
+              // (MASKED: bits at or beyond `rows` in the last word may hold anything -- rows_left cuts those rows)
+              if (((m[j] >> lane) & 1ull) != 0ull && r_off < rows_left && (!MASKED || ((allow >> (r_off + 4 * (lane >> 5))) & 1u) != 0u)) {
                 const int pos = lds_add_rtn(&cnt_lds[ql], 1);
                 if (pos + 1 > CAP - BMT) lds_store_i32(need_compact, 1);  // this buffer could overflow on the next tile
                 float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
@@ -514,30 +532,34 @@ hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
   const bool f32 = p.f32 != 0;
   const int tile = p.skinny_tile == 64 ? 64 : 32;
   if (!skinny_supported(p.dim, p.k, f32) || p.nq_padded % tile != 0 || p.n_splits < 1 || !p.workspace) return hipErrorInvalidValue;
+  if (p.mask && (p.active || (reinterpret_cast<uintptr_t>(p.mask) & 3) != 0)) return hipErrorInvalidValue;  // (no work-list form of the masked tile)
   const MfmaDeviceParams d = fill_device_params(p, tile, BM);
   const int groups = (p.n_splits + 7) / 8;
   const int grid = groups * d.n_qtiles * 8;
-  auto go = [&](auto kern, int lds) -> hipError_t {
+  auto go = [&](auto kern, int lds, auto... mask) -> hipError_t {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(S_THREADS), lds, stream, d);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(S_THREADS), lds, stream, d, mask...);
     return hipGetLastError();
   };
   // (one case per instantiation, keyed by the value the "last_skinny_kernel" getter reports: the getter cannot drift from the dispatch)
-#define TAVB_SKINNY(NI, STEP, ...)                                                                                   \
-  (f32 ? go(skinny_scan_kernel<float, NI, STEP, ##__VA_ARGS__>, SkinnyGeom<float, NI, STEP, ##__VA_ARGS__>::LDS) \
-       : go(skinny_scan_kernel<_Float16, NI, STEP, ##__VA_ARGS__>, SkinnyGeom<_Float16, NI, STEP, ##__VA_ARGS__>::LDS))
+  // (p.mask: the same seven variants in their MASKED form, the mask as their second argument)
+#define TAVB_SKINNY_T(T, NI, STEP, DEEP, DR, HALF)                                                                                   \
+  (p.mask ? go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF, true, const uint32_t*>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS, p.mask) \
+          : go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS))
+#define TAVB_SKINNY(NI, STEP, DEEP, DR, HALF) (f32 ? TAVB_SKINNY_T(float, NI, STEP, DEEP, DR, HALF) : TAVB_SKINNY_T(_Float16, NI, STEP, DEEP, DR, HALF))
   switch (skinny_kernel_id(p)) {
-    case 12832: return TAVB_SKINNY(1, 128);
-    case 12864: return TAVB_SKINNY(2, 128);
-    case 6432: return TAVB_SKINNY(1, 64);
-    case 6464: return TAVB_SKINNY(2, 64);
-    case 22832: return TAVB_SKINNY(1, 128, true);            // deep ring
-    case 32832: return TAVB_SKINNY(1, 128, false, 0, true);  // half tiles
-    case 52832: return TAVB_SKINNY(1, 128, false, 4);        // register staging
+    case 12832: return TAVB_SKINNY(1, 128, false, 0, false);
+    case 12864: return TAVB_SKINNY(2, 128, false, 0, false);
+    case 6432: return TAVB_SKINNY(1, 64, false, 0, false);
+    case 6464: return TAVB_SKINNY(2, 64, false, 0, false);
+    case 22832: return TAVB_SKINNY(1, 128, true, 0, false);   // deep ring
+    case 32832: return TAVB_SKINNY(1, 128, false, 0, true);   // half tiles
+    case 52832: return TAVB_SKINNY(1, 128, false, 4, false);  // register staging
     default: return hipErrorInvalidValue;
   }
 #undef TAVB_SKINNY
+#undef TAVB_SKINNY_T
 }
 
 }  // namespace tavb

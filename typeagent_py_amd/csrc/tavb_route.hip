@@ -182,6 +182,11 @@ struct TileRun {
   // (tavb_rescore.hip, slot mode): the callers' fp32 queries [*, dim], their thresholds [*] (device), indexed by scatter[slot]
   const float* rs_queries;
   const float* rs_min_scores;
+  // 32/64-query tile only: an allow-mask over the corpus rows (tavb.h "row masks"; word 0 = rows 0 .. 31) and the row span [span_begin, span_end)
+  // that holds every set bit, span_begin a multiple of 256: the phases run over the span instead of [0, rows) -- a contiguous time range costs its
+  // own bytes -- and only rows whose bit is set are candidates.  nullptr: no mask, the whole corpus.
+  const uint32_t* mask;
+  int64_t span_begin, span_end;
 };
 
 // Width (in score) of the band the exact fallbacks keep below their k-th best before the candidates are scored again with the streaming
@@ -256,8 +261,11 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   };
   auto launch = [&](const tavb::MfmaParams& q) { return r.skinny ? tavb::launch_skinny_scan(q, c->stream) : tavb::launch_mfma_scan(q, c->stream); };
   const int nq = r.nq, k = r.k;
-  const int splits = c->mfma_splits > 0 ? (int)c->mfma_splits : pick_splits(c->rows);
   const bool wide = !r.skinny;  // the 256-query tile leaves unsorted buffers + counts, one select kernel picks the best k over them
+  const int64_t row_first = r.mask ? r.span_begin : 0;  // the rows the phases cover: the mask's span, or the corpus
+  const int64_t n_rows = (r.mask ? r.span_end : c->rows) - row_first;
+  if (r.mask && (wide || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
+  const int splits = c->mfma_splits > 0 ? (int)c->mfma_splits : pick_splits(n_rows);
   if (!wide)
     if (int rc = c->d_lists.reserve((size_t)nq * (splits + 1) * k * sizeof(u64_t))) return rc;  // + the carried-over top-k
   if (int rc = c->d_cand.reserve(tavb::mfma_workspace_bytes(splits, r.nq_pad, wide))) return rc;
@@ -269,7 +277,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   p.lists = reinterpret_cast<u64_t*>(c->d_lists.ptr);
   p.workspace = reinterpret_cast<u64_t*>(c->d_cand.ptr);
   p.counts = reinterpret_cast<int*>(c->d_counts.ptr);
-  p.rows = c->rows;
+  p.rows = n_rows;
   p.dim = dim;
   p.nq = nq;
   p.nq_padded = r.nq_pad;
@@ -288,7 +296,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   p.split_plane = r.split_plane;
   p.bdirect = r.bdirect ? 1 : 0;
   p.shape = (int)c->mfma_shape;
-  const std::vector<int64_t> bounds = ladder_bounds(c->rows, splits, r.nq_pad, r.skinny, r.ladder, c->mfma_sample_rows, c->mfma_ladder);  // phase i scans rows [bounds[i], bounds[i+1])
+  const std::vector<int64_t> bounds = ladder_bounds(n_rows, splits, r.nq_pad, r.skinny, r.ladder, c->mfma_sample_rows, c->mfma_ladder);  // phase i scans rows row_first + [bounds[i], bounds[i+1])
   const int n_phases = (int)bounds.size() - 1;
   const int kc = wide ? (int)c->band_max : k;  // keys per query of the running selection between phases
   if (wide)  // (every phase's selection leaves its cut here -- the last one's seeds the exact fallbacks' admission thresholds, search_wide_exact)
@@ -304,9 +312,14 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   for (int ph = 0; ph < n_phases; ++ph) {
     const bool last = (ph == n_phases - 1);
     tavb::MfmaParams pp = p;
-    pp.corpus = reinterpret_cast<const char*>(p.corpus) + (size_t)bounds[ph] * row_bytes;
+    const int64_t ph_first = row_first + bounds[ph];
+    pp.corpus = reinterpret_cast<const char*>(p.corpus) + (size_t)ph_first * row_bytes;
     pp.rows = bounds[ph + 1] - bounds[ph];
-    pp.index_base = r.index_base + (uint32_t)bounds[ph];
+    pp.index_base = r.index_base + (uint32_t)ph_first;
+    if (r.mask) {  // whole words: a 32-row block of the tile's epilogue is one word of the mask (ladder_bounds gives multiples of 640 or 256)
+      if (ph_first % 32 != 0) return fail(TAVB_E_INVALID, "masked tile phase %d starts at row %lld, not a multiple of 32 (internal error)", ph, (long long)ph_first);
+      pp.mask = r.mask + (ph_first >> 5);
+    }
     pp.n_splits = pick_splits(pp.rows);
     if (c->mfma_splits > 0 || pp.n_splits > splits) pp.n_splits = splits;  // lists / candidate buffers are sized for `splits`
     const int carried = ph > 0 ? 1 : 0;  // the running top-k of the earlier phases occupies one more list slot
@@ -318,7 +331,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
     // a band of c keys over `seen` of `rows` rows grows to about c * rows / seen when its rows are spread evenly (a cluster of near-duplicates around
     // the k-th best; on ordinary data the band is k plus a key or two whatever the row count): counted when that is 1.25 x the band buffer,
     // and only with at least 16 keys beyond k in hand
-    const int doom_limit = std::max(k + 15, (int)std::min<int64_t>(1 << 30, (int64_t)(1.25 * kc * (double)bounds[ph + 1] / (double)c->rows)));
+    const int doom_limit = std::max(k + 15, (int)std::min<int64_t>(1 << 30, (int64_t)(1.25 * kc * (double)bounds[ph + 1] / (double)n_rows)));
     if (doom_gate) {
       pp.gate = r.doomed;
       pp.gate_max = r.doomed_max;
@@ -759,6 +772,72 @@ int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, co
     return run_tile_ladder(c, r, d_out, nullptr);
   }
   return search_device_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, index_base, d_out);
+}
+
+// Masked batch on the 32/64-query tile (tavb_search_masked_batch / tavb_search_masked_device; the callers have checked the arguments and that
+// skinny_supported holds): the queries as the unmasked tile route takes them -- fp32 on an fp32 corpus, split into an fp16 high and low plane on
+// an fp16 one, the corpus' own rows, no shadow -- over the span of the mask, the bit test in the tile's admission path.  Scores are final.
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* dev_bits, int64_t first_row, int64_t last_row,
+                       uint32_t index_base, u64_t* d_out) {
+  const bool q32 = c->dtype != TAVB_F16;
+  const int qt = tavb::skinny_query_tile(nq);
+  const int nq_pad = ((nq + qt - 1) / qt) * qt;
+  const size_t plane = (size_t)nq_pad * c->dim * (q32 ? 4 : 2);
+  const size_t qbytes = plane * (q32 ? 1 : 2);
+  if (int rc = c->d_queries_f16.reserve(qbytes)) return rc;
+  bool uniform_thr = true;
+  for (int i = 1; i < nq; ++i) uniform_thr = uniform_thr && (memcmp(&min_scores[i], &min_scores[0], sizeof(float)) == 0);
+  float *d_ms = nullptr, *d_ms_floor = nullptr;
+  if (!uniform_thr) {
+    bool uni = false;
+    if (int rc = upload_min_scores(c, min_scores, nq, nq_pad, &d_ms, &d_ms_floor, &uni)) return rc;
+  }
+  TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, qbytes, c->stream));
+  if (q32) {
+    TAVB_HIP(hipMemcpyAsync(c->d_queries_f16.ptr, d_q, (size_t)nq * c->dim * 4, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    hipError_t e = tavb::launch_f32_split_f16(d_q, c->d_queries_f16.ptr, reinterpret_cast<char*>(c->d_queries_f16.ptr) + plane, (int64_t)nq * c->dim, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "query split launch failed: %s", hipGetErrorString(e));
+  }
+  c->last_tier = 5;
+  c->last_shadow = 0;
+  c->last_direct = 0;
+  c->masked_route = 2;
+  TileRun r{};
+  r.skinny = true;
+  r.q32 = q32;
+  r.qt = qt;
+  r.nq = nq;
+  r.nq_pad = nq_pad;
+  r.k = k;
+  r.index_base = index_base;
+  r.kernel_min_score = uniform_thr ? min_scores[0] : lowest_min_score(min_scores, nq);
+  r.floor = d_ms_floor;
+  r.queries = c->d_queries_f16.ptr;
+  r.ladder = true;
+  r.mask = dev_bits;
+  r.span_begin = first_row / 256 * 256;
+  r.span_end = last_row + 1;
+  return run_tile_ladder(c, r, d_out, nullptr);
+}
+}  // namespace host
+}  // namespace tavb
+
+extern "C" int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct) {
+  if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");
+  if (nq < 0 || allowed < 0 || span < allowed || min_bytes < 0 || pct < 0) return fail(TAVB_E_INVALID, "bad shape");
+  const bool f32 = dtype == TAVB_F32;
+  if (dim <= 0 || !tavb::skinny_supported(dim, k, f32)) return 0;
+  if (nq < (f32 ? kSkinnyMinBatchF32 : kSkinnyMinBatchF16)) return 0;  // (the unmasked tile's own lower bounds, as they ship)
+  const __int128 row_bytes = (__int128)dim * (f32 ? 4 : 2);
+  if ((__int128)allowed * row_bytes < (__int128)min_bytes) return 0;
+  // the gather route reads the allowed rows once per 8 queries, the tile the span once per 64: the tile when the gather's bytes are at least
+  // pct % of the tile's
+  const __int128 gather = (__int128)((nq + 7) / 8) * allowed * 100;
+  const __int128 tile = (__int128)((nq + 63) / 64) * span * pct;
+  return gather >= tile ? 1 : 0;
 }
 
 extern "C" int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate) {

@@ -270,14 +270,20 @@ class RowMask:
     read them -- on a single-GPU engine an int32 row list in device memory (`dev_rows`, ascending; `count` of them), so that a masked
     lookup sends only its queries.  `rows` is the index length the mask was built for: a handle used after the index grew or shrank
     raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it.  On a device group the
-    handle holds one shard-local list per device (`shards`, cut by `bounds`), on a row-sharded index this rank's list and the packed mask."""
+    handle holds one shard-local list per device (`shards`, cut by `bounds`), on a row-sharded index this rank's list and the packed mask.
+    A single-GPU engine also keeps the packed mask on the device (`dev_bits`, int32 words: row r = bit r & 31 of word r >> 5) and
+    `span` = (first, last) allowed row, read once when the handle is built: what a batch on the 32/64-query tile reads instead of the list."""
 
-    __slots__ = ("rows", "count", "dev_rows", "shards", "bounds", "layout", "bits", "_flat", "_owner")
+    __slots__ = ("rows", "count", "dev_rows", "dev_bits", "span", "shards", "bounds", "layout", "bits", "_flat", "_owner", "_plans")
 
-    def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None, shards=None, bounds=None, layout=None, bits=None):
+    def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None, shards=None, bounds=None, layout=None, bits=None,
+                 dev_bits=None):
         self.rows = int(rows)
         self.count = int(count)
         self.dev_rows = dev_rows
+        self.dev_bits = dev_bits
+        self.span = (int(dev_rows[0]), int(dev_rows[-1])) if dev_bits is not None and dev_rows is not None and self.count > 0 else None
+        self._plans: dict = {}  # (queries, max_hits, the engine's mask_tile options) -> tile route or not: a handle is searched again and again
         # a device group (multidevice.DeviceGroup.mask_to_rows): one shard-local int32 row list per device (None: no allowed row there)
         # and the shard bounds the mask was cut by
         self.shards = shards
@@ -790,8 +796,7 @@ class VectorBase:
                 raise ValueError(f"mask covers {allowed.shape[0] if allowed.dim() else 0} rows, the index has {n}")
             eng = self._sync_device() if n else None
             if self._masked_native(eng) and allowed.is_cuda and (allowed.device.index or 0) == eng.device:
-                dev_rows, count = eng.mask_to_rows(allowed)
-                return RowMask(self, n, count, dev_rows=dev_rows)
+                return self._native_row_mask(eng, allowed, n)
             if self._masked_group(eng):  # a tensor on any device: every shard's slice goes to that shard's device
                 shards, count, bounds = eng.mask_to_rows(allowed)
                 return RowMask(self, n, count, shards=shards, bounds=bounds)
@@ -805,13 +810,40 @@ class VectorBase:
             return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
         eng = self._sync_device()
         if self._masked_native(eng):
-            dev_rows, count = eng.mask_to_rows(a)
-            return RowMask(self, n, count, dev_rows=dev_rows)
+            return self._native_row_mask(eng, a, n)
         if self._masked_group(eng):
             shards, count, bounds = eng.mask_to_rows(a)
             return RowMask(self, n, count, shards=shards, bounds=bounds)
         flat = np.flatnonzero(a)  # groups of test doubles, test doubles: the fallback's ordinal list
         return RowMask(self, n, len(flat), flat=flat)
+
+    def _native_row_mask(self, eng, allowed, n: int) -> RowMask:
+        if hasattr(eng, "mask_to_rows_bits"):  # the packed mask stays on the device next to the row list: the tile route reads it
+            dev_rows, count, dev_bits = eng.mask_to_rows_bits(allowed)
+            return RowMask(self, n, count, dev_rows=dev_rows, dev_bits=dev_bits)
+        dev_rows, count = eng.mask_to_rows(allowed)
+        return RowMask(self, n, count, dev_rows=dev_rows)
+
+    @staticmethod
+    def _mask_tile(eng, mask: RowMask, nq: int, k: int) -> bool:
+        """Whether a masked batch takes the 32/64-query tile (Engine.search_masked_batch) instead of the gather route: the engine has the
+        call, the handle the packed mask, and the option "mask_tile" (0 = never, 2 = wherever the tile serves the shape, 1 = where
+        tavb_plan_masked expects it to win: a dense mask under a real batch) says so."""
+        if mask.dev_bits is None or mask.span is None or not (hasattr(eng, "search_masked_batch") and hasattr(eng, "plan_masked")):
+            return False
+        opts = eng.mask_tile_options() if hasattr(eng, "mask_tile_options") else tuple(eng.get_option(n) for n in ("mask_tile", "mask_tile_min_bytes", "mask_tile_pct"))
+        mode, min_bytes, pct = opts
+        if mode == 0:
+            return False
+        key = (nq, k, eng.dim, eng.dtype, opts)
+        tile = mask._plans.get(key)
+        if tile is None:
+            if mode == 2:  # (64 queries, one allowed row in a span of one, no floors: the rule says yes exactly when the tile serves k and the width)
+                tile = bool(eng.plan_masked(64, k, eng.dim, eng.dtype, 1, 1, 0, 0))
+            else:
+                tile = bool(eng.plan_masked(nq, k, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_bytes, pct))
+            mask._plans[key] = tile
+        return tile
 
     @staticmethod
     def _masked_native(eng) -> bool:
@@ -862,7 +894,14 @@ class VectorBase:
         mask's resident row list eight per pass -- and with a `RowMask` only the queries travel; a device group does the same on every
         shard that has allowed rows (one batched call per shard, merged on the host); everything else (max_hits == 0 or
         beyond 16384, "large_k" off beyond 256, test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
-        threshold per query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings`."""
+        threshold per query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings`.
+
+        A DENSE mask under a real batch (1 <= max_hits <= 64, rows of a multiple of 64 bytes; engine option "mask_tile": by default from
+        128 MiB of allowed rows, where eight queries per pass over them move at least the bytes of 64 queries per pass over the mask's
+        span) runs on the 32/64-query matrix-core tile instead: the span of the mask is read once per 64 queries and the mask's bit is
+        tested where a row is admitted.  There a batch equals the sequential subset lookups the way `fuzzy_lookup_embeddings` on the same
+        tile equals `fuzzy_lookup_embedding`: the ordinals are identical except among float32 near-ties and the scores agree within
+        1e-5 -- it is not bit for bit.  `engine.get_option("masked_route")` tells which ran (1 = row list, 2 = tile)."""
         queries = np.asarray(embeddings, dtype=np.float32)
         if queries.ndim != 2:
             raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
@@ -885,7 +924,10 @@ class VectorBase:
             return [[] for _ in range(nq)]
         eng = self._sync_device()
         if self._masked_native(eng) and mask.dev_rows is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
-            ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
+            if 1 <= max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
+                ords, scs, cnts = eng.search_masked_batch(queries, mask.dev_bits, max_hits, thr, span=mask.span)
+            else:
+                ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
             if eng.ordinal_base:
                 ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
             if as_arrays:
