@@ -184,7 +184,13 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   route -- one launch there -- and everything behaves as before the tile route existed
  *   "mask_tile_pct" (default 100 = byte parity) the tile is taken when the gather route's bytes (allowed rows once per 8 queries) are at least this
  *                   many per cent of the tile's (the mask's span once per 64 queries)
- *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the tile
+ *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the
+ *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide)
+ *   "mask_wide"     masked batches on fp16 corpora (the binding reads it; the rule is tavb_plan_masked_wide, with "mask_tile_min_bytes" / "mask_tile_pct"):
+ *                   1 (default) = a batch takes the 128/256-query filter tile with the bit test in its admission path + exact rescoring
+ *                   (tavb_search_masked_wide) where tavb_plan_masked_wide says so -- it then wins over "mask_tile"; 0 = never; 2 = wherever that route
+ *                   serves the shape (tests).  It never changes what "mask_tile" does for the batches this route does not take.
+ *                   "last_flagged" after such a lookup: its queries that were re-run on the gather route
  *   "sort_small_keys" 0 .. 16384 (default 16384): a sort of up to this many keys (tavb_search_sorted, tavb_sort_keys_device) runs in ONE
  *                   workgroup in LDS; bigger ones take the multi-pass radix sort (3 launches per 8-bit digit that is not the same for
  *                   every key, + 2)
@@ -429,6 +435,24 @@ int tavb_search_masked_batch(tavb_ctx* ctx, const float* queries_host, int32_t n
 int tavb_search_masked_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
                               int64_t last_row, int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
 
+/* A masked batch on the 128/256-query filter tile + exact rescoring -- the route every large unmasked batch on an fp16 corpus takes, with the
+ * mask's bit tested in the filter's admission path: the mask's span is read once per 128 or 256 queries.  dev_bits (4-byte aligned), rows,
+ * [first_row, last_row]: as for tavb_search_masked_batch.  dev_rows / n_allowed: the mask's resident row list (tavb_mask_expand: the set rows in
+ * ascending order, device memory) -- a query whose band of candidates does not provably fit (more near-duplicates around its k-th best than
+ * option "band_max" holds: rare) is re-run over it on the gather route; the list of such queries is read back, so BOTH forms synchronise the
+ * stream once per call ("last_flagged" counts them).  Serves fp16 corpora of any width up to 16384 and 1 <= k <= TAVB_MAX_FUSED_K; an fp32
+ * corpus and any other k return TAVB_E_UNSUPPORTED.  The filter multiplies fp16-rounded queries (an odd width: over a zero-padded copy of the
+ * rows), every candidate is scored again with the fp32 queries in the streaming kernels' arithmetic: ordinals, float32 scores and counts EQUAL
+ * those of the gather route (tavb_search_subset_batch_resident over dev_rows, remap = 1) bit for bit.  Outputs and ordering as
+ * tavb_search_masked_batch / tavb_search_masked_device (min_scores: nq thresholds on the HOST; the device form's keys carry ordinal_base + row).
+ * An empty corpus, nq == 0, first_row > last_row or n_allowed == 0: zero counts / zero keys, no tile launch. */
+int tavb_search_masked_wide(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
+                            int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, int64_t* out_ordinals,
+                            float* out_scores, int32_t* out_counts);
+int tavb_search_masked_wide_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
+                                   int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores /*host*/,
+                                   tavb_key* out_keys);
+
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */
 int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k,
@@ -535,6 +559,14 @@ int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int
  * "skinny_min_batch_f16"), allowed x row bytes >= min_bytes, and ceil(nq / 8) x allowed x 100 >= ceil(nq / 64) x span x pct -- the gather
  * route's bytes are at least pct % of the tile's.  Negative: an argument out of range.  A pure function, needs no context and no GPU. */
 int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct);
+
+/* Whether a masked batch takes the 128/256-query filter tile + rescoring (tavb_search_masked_wide) under option "mask_wide" = 1; the arguments
+ * of tavb_plan_masked.  1 when the corpus is fp16 and the route serves the shape (dim <= 16384, 1 <= k <= TAVB_MAX_FUSED_K), nq is at least the
+ * shipped default of "mfma_min_batch" (65: the unmasked dispatcher's own bound for that tile), allowed x row bytes >= min_bytes, and
+ * ceil(nq / 8) x allowed x 100 >= ceil(nq / qt) x span x pct, qt = the query tile (128 or 256) the filter picks for nq queries over `span` rows
+ * on 256 compute units.  0 otherwise (an fp32 corpus: always); negative: an argument out of range.  Where this and tavb_plan_masked both say
+ * 1 the binding takes this route.  A pure function, needs no context and no GPU. */
+int tavb_plan_masked_wide(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct);
 
 #ifdef __cplusplus
 }

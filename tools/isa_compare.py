@@ -16,13 +16,13 @@ import re
 import sys
 
 DESCRIPTOR = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "group_segment_fixed_size", "private_segment_fixed_size")
-# template arguments of the OLD side that the new side no longer has: kernel name -> argument index (skinny_scan_kernel lost ABL, always 0)
-DROPPED_ARGS = {"skinny_scan_kernel": 3}
+# template arguments of the OLD side that the new side no longer has: kernel name -> argument index.  (skinny_scan_kernel lost ABL two
+# changes ago: {"skinny_scan_kernel": 3} compares against a parent that still has it.)
+DROPPED_ARGS = {}
 # template arguments the NEW side gained at the end of the list, and the value that names the old kernel: kernel name -> (arguments the old side
-# has, value).  skinny_scan_kernel gained MASKED: <..., false> is the kernel the old side has, <..., true> exists on the new side only.
-# (Comparing a parent that still had ABL needs DROPPED_ARGS alone: such a parent has seven arguments too, and its index 3 is dropped first.)
-ADDED_ARGS = {"skinny_scan_kernel": (6, "false")}
-
+# has, value).  (skinny_scan_kernel gained MASKED in the last change: {"skinny_scan_kernel": (6, "false")} compares against a parent without it.
+# The 128/256-query kernel's masked form is a kernel of its own, mfma_scan_masked_kernel: mfma_scan_kernel's names did not change.)
+ADDED_ARGS = {}
 
 def kernel_id(symbol):
     """'_ZN4tavb12_GLOBAL__N_116mfma_scan_kernelILi0ELi4E...EEvNS0_...' -> ('mfma_scan_kernel', ['0', '4', ...])"""

@@ -83,6 +83,10 @@ _SIGNATURES = [
     ("tavb_search_masked_batch", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_masked_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_masked_wide", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_masked_wide_device", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -100,6 +104,7 @@ _SIGNATURES = [
     ("tavb_plan_ladder", c_int, [c_int64, c_int32, c_int32, POINTER(c_int64), c_int32]),
     ("tavb_plan_filter_shape", c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     ("tavb_plan_masked", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
+    ("tavb_plan_masked_wide", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
 ]
 
 ABI_SYMBOLS = [name for name, _, _ in _SIGNATURES]
@@ -156,6 +161,18 @@ def plan_masked(nq: int, k: int, dim: int, dtype: int, allowed: int, span: int, 
     "mask_tile" = 1, False: the gather route (tavb_plan_masked; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
     lib = load_library(preload_torch=False)
     r = lib.tavb_plan_masked(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
+
+
+MFMA_MIN_BATCH = 65  # the default of the option "mfma_min_batch": the fewest queries tavb_plan_masked_wide says yes to
+
+
+def plan_masked_wide(nq: int, k: int, dim: int, dtype: int, allowed: int, span: int, min_bytes: int = MASK_TILE_MIN_BYTES, pct: int = MASK_TILE_PCT) -> bool:
+    """True: a masked batch of `nq` queries with `allowed` set rows inside a span of `span` rows takes the 128/256-query filter tile +
+    rescoring under option "mask_wide" = 1 (tavb_plan_masked_wide; fp16 corpora only).  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_masked_wide(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
     _check(lib, r if r < 0 else 0)
     return bool(r)
 
@@ -309,6 +326,7 @@ class Engine:
     def set_option(self, name: str, value: int) -> None:
         _check(self.lib, self.lib.tavb_set_option(self._h, name.encode(), int(value)))
         self.__dict__.pop("_mask_tile_opts", None)
+        self.__dict__.pop("_mask_wide_opts", None)
 
     def mask_tile_options(self) -> tuple[int, int, int]:
         """("mask_tile", "mask_tile_min_bytes", "mask_tile_pct") as the library holds them, read once and again after any `set_option`: a
@@ -316,6 +334,13 @@ class Engine:
         opts = self.__dict__.get("_mask_tile_opts")
         if opts is None:
             opts = self._mask_tile_opts = tuple(self.get_option(n) for n in ("mask_tile", "mask_tile_min_bytes", "mask_tile_pct"))
+        return opts
+
+    def mask_wide_options(self) -> tuple[int, int, int]:
+        """("mask_wide", "mask_tile_min_bytes", "mask_tile_pct"), cached like `mask_tile_options`."""
+        opts = self.__dict__.get("_mask_wide_opts")
+        if opts is None:
+            opts = self._mask_wide_opts = tuple(self.get_option(n) for n in ("mask_wide", "mask_tile_min_bytes", "mask_tile_pct"))
         return opts
 
     def get_option(self, name: str) -> int:
@@ -611,6 +636,55 @@ class Engine:
         with self._lock:
             rc = self.lib.tavb_search_masked_device(self._h, c_void_p(dev_queries.data_ptr()), nq, bits, int(self.rows), first, last, k, _addr(t),
                                                     c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    # masked batches on the 128/256-query filter tile + rescoring --------------------------
+    plan_masked_wide = staticmethod(plan_masked_wide)
+
+    def _masked_wide_rows(self, dev_rows):
+        torch = self._torch
+        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
+        return (c_void_p(dev_rows.data_ptr()) if dev_rows.numel() else None), int(dev_rows.numel())
+
+    def search_masked_wide(self, queries, dev_bits, dev_rows, k: int, thrs, span=None):
+        """A masked batch on the 128/256-query filter tile with exact rescoring (tavb_search_masked_wide; fp16 corpora, 1 <= k <= 256): the
+        arguments of `search_masked_batch` plus dev_rows, the mask's resident row list (torch int32 [count], ascending: `mask_to_rows_bits`),
+        over which a query whose candidate band did not fit is re-run -> (ordinals [nq, k], scores [nq, k], counts [nq]), equal to
+        `search_subset_batch_resident(queries, dev_rows, k, thrs)` bit for bit.  Raises TavbError (TAVB_E_UNSUPPORTED) for an fp32 corpus or a
+        k the route does not serve."""
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        ords = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        cnts = np.zeros(nq, dtype=np.int32)
+        bits, first, last = self._masked_args(dev_bits, span)
+        rows_ptr, n_allowed = self._masked_wide_rows(dev_rows)
+        with self._lock:
+            rc = self.lib.tavb_search_masked_wide(self._h, _addr(a), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k, _addr(t), _addr(ords),
+                                                  _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_masked_wide_device(self, dev_queries, dev_bits, dev_rows, k: int, thrs, span=None, out_keys=None):
+        """`search_masked_wide` with the queries on the device and the keys left there (tavb_search_masked_wide_device): torch int64 [nq, k]
+        sorted, zero-padded keys carrying ordinal_base + row.  The call synchronises the stream once (the list of flagged queries is read
+        back); `synchronize()` before reading the keys all the same."""
+        torch = self._torch
+        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
+        nq = int(dev_queries.shape[0])
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        if out_keys is None:
+            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
+        self._check_out_keys(out_keys, nq, k)
+        bits, first, last = self._masked_args(dev_bits, span)
+        rows_ptr, n_allowed = self._masked_wide_rows(dev_rows)
+        with self._lock:
+            rc = self.lib.tavb_search_masked_wide_device(self._h, c_void_p(dev_queries.data_ptr()), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k,
+                                                         _addr(t), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 

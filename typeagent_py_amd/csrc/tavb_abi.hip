@@ -253,6 +253,7 @@ const Option kOptions[] = {
     AT_LEAST("mask_tile_min_bytes", mask_tile_min_bytes, 0),
     RANGE("mask_tile_pct", mask_tile_pct, 0, 1000000),
     READ_ONLY("masked_route", masked_route),
+    RANGE("mask_wide", mask_wide, 0, 2),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),
     READ_ONLY("last_topk_refine", last_topk_refine),

@@ -80,6 +80,10 @@ struct Buffer {
 // the defaults of skinny_min_batch_f32 / skinny_min_batch_f16 (the measured break-even of the 32/64-query tile against the streaming tiers);
 // tavb_plan_masked, which has no context, uses them as they ship
 constexpr int64_t kSkinnyMinBatchF32 = 5, kSkinnyMinBatchF16 = 3;
+// the default of mfma_min_batch (the unmasked dispatcher's own bound for the 128/256-query tile on fp16 corpora) and the compute units the
+// planning functions that have no context assume (MI355X); tavb_plan_masked_wide uses both as they ship
+constexpr int64_t kMfmaMinBatch = 65;
+constexpr int kPlanComputeUnits = 256;
 
 struct PendingTiming {
   int kernel;
@@ -105,7 +109,7 @@ struct tavb_ctx {
   int64_t ordinal_base = 0;
 
   tavb::ScanGeometry geom{0, 16, 2, 1, 0, 0};
-  int64_t mfma_min_batch = 65;  // batches from this size up use the 128/256-query tile + rescoring (smaller ones the 32/64-query tile) ...
+  int64_t mfma_min_batch = tavb::host::kMfmaMinBatch;  // batches from this size up use the 128/256-query tile + rescoring (smaller ones the 32/64-query tile) ...
   // ... and on corpora of `mfma_big_bytes` (256 MiB) or more already from `mfma_min_batch_big` = 33 queries (round 5): padded to 128 queries the wide
   // tile serves 33 / 48 / 64 queries over 10M fp16 rows in 5.42 / 5.48 / 5.46 ms against 5.54 / 5.81 / 5.91 ms on the 64-query split-plane tile,
   // and 64 queries over 1M fp32 rows (through the fp16 shadow) in 0.85 ms against 2.17 ms (profiles/r05_raw/b64.txt).  On small corpora its ~40
@@ -190,7 +194,8 @@ struct tavb_ctx {
   int64_t mask_tile = 1;                            // option: 1 = follow tavb_plan_masked, 0 = never the tile, 2 = always where supported
   int64_t mask_tile_min_bytes = (int64_t)128 << 20;  // option: allowed rows x row bytes below which the gather route (one launch there) is kept; the default of small_direct_bytes
   int64_t mask_tile_pct = 100;                      // option: the tile when the gather route's bytes are at least this many % of the tile's (100 = byte parity)
-  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile
+  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring
+  int64_t mask_wide = 1;                            // option: masked batches on the 128/256-query filter tile (tavb_search_masked_wide): 1 = follow tavb_plan_masked_wide, 0 = never, 2 = always where supported
   int64_t last_skinny_kernel = 0;  // option "last_skinny_kernel" (get): what the last launch of the 32/64-query tile instantiated, tavb::skinny_kernel_id (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
   int64_t band_max = tavb::kBandMax;  // option: keys of a query's band the wide tile's selection hands to the rescoring (256 .. kBandMax); a band that does not fit flags the query
@@ -360,6 +365,12 @@ int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float
 // index_base + row -> d_out [nq, k] (async on the stream).  The caller has checked skinny_supported and the bounds.
 int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits, int64_t first_row,
                        int64_t last_row, uint32_t index_base, u64_t* d_out);
+// Masked batch on the 128/256-query filter tile + exact rescoring (fp16 corpora; masked_wide_supported): the same mask and span, plus the mask's
+// resident row list (dev_rows, n_allowed: tavb_mask_expand) for the re-run of flagged queries on the gather route -- the one host round trip,
+// taken by every call (the flag list is read back).  Scores are the streaming kernels' float32 scores: the gather route's answers bit for bit.
+bool masked_wide_supported(const tavb_ctx* c, int k);
+int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits, int64_t first_row,
+                       int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, uint32_t index_base, u64_t* d_out);
 
 // ---- tavb_lookup.hip
 // The large-k lookup (tavb_search_topk's passes) with the queries on the device and nothing waited for: nq sorted, zero-padded lists of k keys

@@ -228,7 +228,7 @@ struct MfmaParams {
   const float* band;    // 128/256-query kernel only, optional [nq_padded]: band selection (keep every key within band[q] of the k-th best)
   unsigned* lost;       // ... [nq_padded]: atomicMax of the score level (bits) below which a query lost band rows to a buffer that could not hold its band
   int32_t shape;        // 256-query filter tile: 16 = v_mfma_f32_16x16x32_f16, anything else = v_mfma_f32_32x32x16_f16 (see mfma_tile_shape)
-  // skinny kernel only, optional: allow-mask (tavb.h "row masks"), the word that holds the bit of row 0 of `corpus` -- the launch's first row must
+  // optional (the skinny kernel; the shipping filter variants of the 128/256-query kernel): allow-mask (tavb.h "row masks"), the word that holds the bit of row 0 of `corpus` -- the launch's first row must
   // be a multiple of 32 in the mask's numbering, so that bit 0 of that word IS row 0.  Rows whose bit is clear are never candidates.
   const uint32_t* mask;
 };

@@ -1170,6 +1170,72 @@ int tavb_search_masked_device(tavb_ctx* c, const float* dev_queries, int32_t nq,
   return search_masked_tile(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
 }
 
+// ---- masked batches on the 128/256-query filter tile + rescoring (tavb_route.hip::search_masked_wide)
+static int check_masked_wide_args(tavb_ctx* c, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, const int32_t* dev_rows,
+                                  int64_t n_allowed, int32_t k, bool* empty) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  if (n_allowed < 0 || n_allowed > rows) return fail(TAVB_E_INVALID, "bad row list length");
+  *empty = rows == 0 || nq == 0 || first_row > last_row || n_allowed == 0;
+  if (!*empty && (first_row < 0 || last_row >= rows)) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
+  if (!*empty && (!dev_bits || !dev_rows)) return fail(TAVB_E_INVALID, "null dev_bits / dev_rows");
+  if ((reinterpret_cast<uintptr_t>(dev_bits) & 3) != 0) return fail(TAVB_E_INVALID, "dev_bits must be 4-byte aligned");
+  if (!masked_wide_supported(c, k))
+    return fail(TAVB_E_UNSUPPORTED, "the masked wide route serves fp16 corpora of up to 16384 halves per row and 1 <= k <= %d (k = %d): use another masked route",
+                TAVB_MAX_FUSED_K, k);
+  return TAVB_OK;
+}
+
+int tavb_search_masked_wide(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                            const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
+                            int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  // up to 4096 keys land in pinned host memory as the other batched forms' do; more are written in device memory and copied out once
+  const size_t n_keys = (size_t)nq * k;
+  const bool via_device = n_keys > 4096;
+  if (int rc = c->h_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  if (via_device)
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  u64_t* const target = reinterpret_cast<u64_t*>(via_device ? c->d_out.ptr : c->h_out.ptr);
+  c->last_graph = 0;
+  if (int rc = search_masked_wide(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, 0u, target)) return rc;
+  if (via_device) TAVB_HIP(hipMemcpyAsync(c->h_out.ptr, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+  return TAVB_OK;
+}
+
+int tavb_search_masked_wide_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                                   const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
+    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  DeviceGuard guard(c->device);
+  if (empty) {  // zero keys; no tile launch
+    const hipError_t e = tavb::launch_fill_keys(reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k, 0ull, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
+    return TAVB_OK;
+  }
+  return search_masked_wide(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, (uint32_t)c->ordinal_base,
+                            reinterpret_cast<u64_t*>(out_keys));
+}
+
 // ---- row masks (tavb_mask.hip)
 int tavb_mask_expand(tavb_ctx* c, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap, int64_t* out_count) {
   if (int rc = check_ctx(c)) return rc;

@@ -182,7 +182,7 @@ struct TileRun {
   // (tavb_rescore.hip, slot mode): the callers' fp32 queries [*, dim], their thresholds [*] (device), indexed by scatter[slot]
   const float* rs_queries;
   const float* rs_min_scores;
-  // 32/64-query tile only: an allow-mask over the corpus rows (tavb.h "row masks"; word 0 = rows 0 .. 31) and the row span [span_begin, span_end)
+  // the 32/64-query tile and the filter pass of the 128/256-query tile (no work-list run): an allow-mask over the corpus rows (tavb.h "row masks"; word 0 = rows 0 .. 31) and the row span [span_begin, span_end)
   // that holds every set bit, span_begin a multiple of 256: the phases run over the span instead of [0, rows) -- a contiguous time range costs its
   // own bytes -- and only rows whose bit is set are candidates.  nullptr: no mask, the whole corpus.
   const uint32_t* mask;
@@ -264,7 +264,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   const bool wide = !r.skinny;  // the 256-query tile leaves unsorted buffers + counts, one select kernel picks the best k over them
   const int64_t row_first = r.mask ? r.span_begin : 0;  // the rows the phases cover: the mask's span, or the corpus
   const int64_t n_rows = (r.mask ? r.span_end : c->rows) - row_first;
-  if (r.mask && (wide || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
+  if (r.mask && ((wide && (r.active || r.split_plane > 0)) || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
   const int splits = c->mfma_splits > 0 ? (int)c->mfma_splits : pick_splits(n_rows);
   if (!wide)
     if (int rc = c->d_lists.reserve((size_t)nq * (splits + 1) * k * sizeof(u64_t))) return rc;  // + the carried-over top-k
@@ -316,7 +316,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
     pp.corpus = reinterpret_cast<const char*>(p.corpus) + (size_t)ph_first * row_bytes;
     pp.rows = bounds[ph + 1] - bounds[ph];
     pp.index_base = r.index_base + (uint32_t)ph_first;
-    if (r.mask) {  // whole words: a 32-row block of the tile's epilogue is one word of the mask (ladder_bounds gives multiples of 640 or 256)
+    if (r.mask) {  // whole words: a 32-row block of the tile's epilogue is one word of the mask (ladder_bounds gives multiples of 640 or 256; the wide tile's: of 320 or 256)
       if (ph_first % 32 != 0) return fail(TAVB_E_INVALID, "masked tile phase %d starts at row %lld, not a multiple of 32 (internal error)", ph, (long long)ph_first);
       pp.mask = r.mask + (ph_first >> 5);
     }
@@ -438,7 +438,17 @@ int upload_min_scores(tavb_ctx* c, const float* min_scores, int nq, int nq_pad, 
 // `small` (fp32 corpora only): the filter is the 32/64-query tile over the shadow with the EXACT queries (split fp16 planes), for batches
 // below the wide tile's range -- half the bytes of an fp32 pass.
 // min_scores: host [nq], one threshold per query (the reference takes `min_score` per call, vectorbase.py:163-173: a batch of Q calls has Q of them).
-int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, uint32_t index_base, u64_t* d_out, bool small = false) {
+// `mw` (fp16 corpora, not `small`): a MASKED batch -- the filter pass runs over the mask's span with the bit test in its admission path (the corpus
+// max-norm bound stays valid for any subset of the rows), the rescoring as ever; neither exact fallback has a masked form, so there is no early
+// verdict, and the flagged queries -- read back, one round trip -- are re-run on the gather route over the mask's resident row list.
+struct MaskedWide {
+  const uint32_t* bits;           // the mask over the corpus rows
+  int64_t span_begin, span_end;   // rows [span_begin, span_end) hold every set bit; span_begin a multiple of 256
+  const int32_t* dev_rows;        // the allowed rows in ascending order (device), n_allowed of them
+  int64_t n_allowed;
+};
+int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, uint32_t index_base, u64_t* d_out, bool small = false,
+                      const MaskedWide* mw = nullptr) {
   // candidates per query handed to the rescoring: the wide tile selects a BAND (every row within 2 delta of the approximate k-th best: as many
   // as the data makes it, up to kBandMax), the 32/64-query tile (`small`) the best 64 by approximate score
   const int KC = small ? 64 : (int)c->band_max;
@@ -451,7 +461,8 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   const int fdim = padded ? ((c->dim + 63) / 64) * 64 : c->dim;
   const bool shadow_ops = f32c || padded;  // the filter's corpus operand is d_shadow
   const bool big_k = k > 64;  // beyond what the 64-query exact tile ranks: every flagged query goes to the wide split-plane form (fp16 corpora only: the caller checked)
-  const int qt = small ? tavb::skinny_query_tile(nq) : (c->mfma_tile > 0 ? (int)c->mfma_tile : tavb::mfma_query_tile_for(nq, c->rows, c->n_cu));
+  const int64_t scan_rows = mw ? mw->span_end - mw->span_begin : c->rows;  // the rows the filter walks
+  const int qt = small ? tavb::skinny_query_tile(nq) : (c->mfma_tile > 0 ? (int)c->mfma_tile : tavb::mfma_query_tile_for(nq, scan_rows, c->n_cu));
   const int nq_pad = ((nq + qt - 1) / qt) * qt;
   const bool bdirect = !small && qt == 256 && c->mfma_bdirect && c->mfma_ablate == 0;
   // Work list of queries that need an exact pass (a band that did not fit).  Few of them (<= 64): ONE pass of the 64-query exact tile.  Many: the
@@ -459,13 +470,13 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   // 16 passes of the 64-query tile per 1024 flagged queries otherwise (round 2-3: "stated, not solved").  Both are fixed-shape
   // launches over the same device-side list and return at once when it is empty or is the other one's share.  Either one hands its best rows
   // (and a small band below them) to the rescoring kernel in slot mode: a query served by a fallback gets the streaming kernels' float32 scores.
-  const bool wide_fallback = !small && !f32c && c->wide_fallback && (nq >= 256 || big_k);
+  const bool wide_fallback = !mw && !small && !f32c && c->wide_fallback && (nq >= 256 || big_k);
   // k > 64 on an FP32 corpus (end of round 6): the filter, the band and the rescoring serve any k up to TAVB_MAX_FUSED_K, but no exact tile ranks
   // more than 64 fp32 rows per query.  A flagged query -- more than band_max near-duplicates around its k-th best: rare -- is therefore re-run on
   // the streaming kernels, which takes the one host round trip of this file (the work list is read back; nothing flagged: nothing more to do).
   // Until then such batches took the streaming kernels four queries per corpus pass: 128 queries over 2M x 1536 fp32 rows, k = 65: 66 ms against 1.3.
   const bool f32_big_k = !small && f32c && big_k;
-  if (big_k && !wide_fallback && !f32_big_k) return fail(TAVB_E_UNSUPPORTED, "k > 64 on the batched tile of an fp16 corpus needs the wide_fallback option");
+  if (big_k && !wide_fallback && !f32_big_k && !mw) return fail(TAVB_E_UNSUPPORTED, "k > 64 on the batched tile of an fp16 corpus needs the wide_fallback option");
   const int cap = wide_fallback ? ((nq + 255) / 256) * 256 : ((nq + 63) / 64) * 64;  // slots of the work list
   const size_t q16_bytes = (size_t)nq_pad * fdim * 2 * (small ? 2 : 1);  // small: high and low plane
   if (int rc = c->d_queries_f16.reserve(q16_bytes)) return rc;
@@ -483,8 +494,10 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   }
   if (!big_k || f32_big_k)
     if (int rc = c->d_fb_cand.reserve((size_t)cap * (f32_big_k ? k : 64) * sizeof(u64_t))) return rc;
-  if (f32_big_k)
+  if (f32_big_k || mw)
     if (int rc = c->h_flag.reserve((size_t)(64 + cap) * sizeof(int))) return rc;
+  if (mw)  // the re-run's lists
+    if (int rc = c->d_fb_cand.reserve((size_t)cap * k * sizeof(u64_t))) return rc;
   if (int rc = c->d_norm.reserve(256)) return rc;
   float *d_ms = nullptr, *d_ms_floor = nullptr;
   bool ms_uniform = false;
@@ -559,6 +572,11 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   filt.corpus = shadow_ops ? c->d_shadow.ptr : nullptr;
   filt.dim = fdim;
   filt.ladder = true;
+  if (mw) {
+    filt.mask = mw->bits;
+    filt.span_begin = mw->span_begin;
+    filt.span_end = mw->span_end;
+  }
   // a batch MOST of whose bands are not going to fit (every query next to more near-duplicates than a band holds) is found out before the last --
   // the big -- filter phase and goes straight to the exact split-plane form: the filter's last phase, its selection and the rescoring return at once
   const bool early = wide_fallback && c->early_exact;
@@ -581,10 +599,35 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
     // the exact fallbacks start from what the filter has proven: the cut its last selection left in d_thr (the one before it when the early
     // verdict skipped the last phase) less the filter's error bound is a valid admission threshold on exact scores, so ONE phase each
     const float* seed = small ? nullptr : reinterpret_cast<const float*>(c->d_thr.ptr);
-    e = f32c ? tavb::launch_gather_flagged_f32(d_q, c->dim, d_ms, d_nflag, d_flagged, cap, reinterpret_cast<float*>(fb), fb_thr, seed, d_delta, c->stream)
-             : tavb::launch_gather_flagged(fq, fdim, d_ms, d_nflag, d_flagged, cap, fb, fb + (size_t)cap * fdim * 2, fb_thr, seed, d_delta,
-                                           wide_fallback ? fb_band : nullptr, kExactBand, c->stream);
+    if (!mw)  // (a masked batch re-runs its flagged queries from their fp32 rows in d_q: nothing to gather)
+      e = f32c ? tavb::launch_gather_flagged_f32(d_q, c->dim, d_ms, d_nflag, d_flagged, cap, reinterpret_cast<float*>(fb), fb_thr, seed, d_delta, c->stream)
+               : tavb::launch_gather_flagged(fq, fdim, d_ms, d_nflag, d_flagged, cap, fb, fb + (size_t)cap * fdim * 2, fb_thr, seed, d_delta,
+                                             wide_fallback ? fb_band : nullptr, kExactBand, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
+  }
+  if (mw) {
+    int* h = reinterpret_cast<int*>(c->h_flag.ptr);
+    TAVB_HIP(hipMemcpyAsync(h, d_nflag, (size_t)(64 + cap) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    TAVB_HIP(hipStreamSynchronize(c->stream));
+    const int n_flagged = h[0] < cap ? h[0] : cap;
+    if (n_flagged > 0) {  // their fp32 queries side by side in fb (cap x fdim x 4 bytes and more), their lists by position, then as index_base + row
+      std::vector<float> ms_f((size_t)n_flagged);
+      float* fq32 = reinterpret_cast<float*>(fb);
+      for (int i = 0; i < n_flagged; ++i) {
+        ms_f[i] = min_scores[h[64 + i]];
+        TAVB_HIP(hipMemcpyAsync(fq32 + (size_t)i * c->dim, d_q + (size_t)h[64 + i] * c->dim, (size_t)c->dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      }
+      u64_t* d_redo = reinterpret_cast<u64_t*>(c->d_fb_cand.ptr);
+      const int tier = c->last_tier;  // (the batch's route stays what "last_tier" reports: the re-run is a detail of it)
+      const int rc_redo = search_device_impl(c, fq32, n_flagged, k, ms_f.data(), mw->dev_rows, mw->n_allowed, 0u, d_redo);
+      c->last_tier = tier;
+      if (rc_redo) return rc_redo;
+      const hipError_t e = tavb::launch_remap_positions(d_redo, d_redo, (int64_t)n_flagged * k, mw->dev_rows, mw->n_allowed, index_base, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+      for (int i = 0; i < n_flagged; ++i)
+        TAVB_HIP(hipMemcpyAsync(d_out + (size_t)h[64 + i] * k, d_redo + (size_t)i * k, (size_t)k * sizeof(u64_t), hipMemcpyDefault, c->stream));
+    }
+    return TAVB_OK;
   }
   if (f32_big_k) {
     int* h = reinterpret_cast<int*>(c->h_flag.ptr);
@@ -824,6 +867,47 @@ int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
 }
 }  // namespace host
 }  // namespace tavb
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+// fp16 corpora of any width (one that is no multiple of 64 filters on the zero-padded copy of the rows, as the unmasked route does), every k the
+// filter's band and the rescoring serve
+bool masked_wide_supported(const tavb_ctx* c, int k) {
+  return c->dtype == TAVB_F16 && c->dim > 0 && c->dim <= 16384 && tavb::mfma_supported(((c->dim + 63) / 64) * 64, k);
+}
+
+int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* dev_bits, int64_t first_row, int64_t last_row,
+                       const int32_t* dev_rows, int64_t n_allowed, uint32_t index_base, u64_t* d_out) {
+  if (c->dim % 64 != 0) {  // the filter reads the padded copy (search_wide_exact fills it in; the unmasked dispatcher reserves it the same way)
+    const size_t need = (size_t)c->rows * (((size_t)c->dim + 63) / 64 * 64) * 2;
+    if (c->d_shadow.cap < need) {
+      c->norm_rows = 0;  // reserve() does not keep the old contents
+      if (int rc = c->d_shadow.reserve(need)) return rc;
+    }
+  }
+  c->last_tier = 4;
+  c->last_direct = 0;
+  c->masked_route = 3;
+  const MaskedWide mw{dev_bits, first_row / 256 * 256, last_row + 1, dev_rows, n_allowed};
+  return search_wide_exact(c, d_q, nq, k, min_scores, index_base, d_out, /*small=*/false, &mw);
+}
+}  // namespace host
+}  // namespace tavb
+
+extern "C" int tavb_plan_masked_wide(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct) {
+  if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");
+  if (nq < 0 || allowed < 0 || span < allowed || min_bytes < 0 || pct < 0) return fail(TAVB_E_INVALID, "bad shape");
+  if (dtype != TAVB_F16) return 0;  // (an fp32 corpus would filter on its shadow: not built)
+  if (dim <= 0 || dim > 16384 || !tavb::mfma_supported(((dim + 63) / 64) * 64, k)) return 0;
+  if (nq < kMfmaMinBatch) return 0;  // (the unmasked dispatcher's own lower bound for the wide tile, as it ships)
+  if ((__int128)allowed * dim * 2 < (__int128)min_bytes) return 0;
+  // the gather route reads the allowed rows once per 8 queries, the wide tile the span once per query tile (128 or 256 queries: what the filter
+  // pass picks for this batch over `span` rows): the tile when the gather's bytes are at least pct % of the tile's
+  const int qt = tavb::mfma_query_tile_for(nq, span, kPlanComputeUnits);
+  const __int128 gather = (__int128)((nq + 7) / 8) * allowed * 100;
+  const __int128 tile = (__int128)((nq + qt - 1) / qt) * span * pct;
+  return gather >= tile ? 1 : 0;
+}
 
 extern "C" int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct) {
   if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");

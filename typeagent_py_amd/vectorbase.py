@@ -846,6 +846,27 @@ class VectorBase:
         return tile
 
     @staticmethod
+    def _mask_wide(eng, mask: RowMask, nq: int, k: int) -> bool:
+        """Whether a masked batch takes the 128/256-query filter tile + rescoring (Engine.search_masked_wide): the engine has the call, the
+        handle the packed mask and the row list, and the option "mask_wide" (0 = never, 2 = wherever the route serves the shape, 1 = where
+        tavb_plan_masked_wide expects it to win) says so.  The plan is kept on the handle like `_mask_tile`'s."""
+        if mask.dev_bits is None or mask.span is None or mask.dev_rows is None or not (hasattr(eng, "search_masked_wide") and hasattr(eng, "plan_masked_wide")):
+            return False
+        opts = eng.mask_wide_options() if hasattr(eng, "mask_wide_options") else tuple(eng.get_option(n) for n in ("mask_wide", "mask_tile_min_bytes", "mask_tile_pct"))
+        mode, min_bytes, pct = opts
+        if mode == 0:
+            return False
+        key = ("wide", nq, k, eng.dim, eng.dtype, opts)
+        wide = mask._plans.get(key)
+        if wide is None:
+            if mode == 2:  # (the fewest queries the rule takes, one allowed row in a span of one, no floors: yes exactly when the route serves the corpus and k)
+                wide = bool(eng.plan_masked_wide(_native.MFMA_MIN_BATCH, k, eng.dim, eng.dtype, 1, 1, 0, 0))
+            else:
+                wide = bool(eng.plan_masked_wide(nq, k, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_bytes, pct))
+            mask._plans[key] = wide
+        return wide
+
+    @staticmethod
     def _masked_native(eng) -> bool:
         """A single-GPU engine that expands masks and searches their row list itself (tavb_mask_expand, tavb_search_subset_batch_resident);
         device groups and test doubles take the fallback."""
@@ -901,7 +922,14 @@ class VectorBase:
         span) runs on the 32/64-query matrix-core tile instead: the span of the mask is read once per 64 queries and the mask's bit is
         tested where a row is admitted.  There a batch equals the sequential subset lookups the way `fuzzy_lookup_embeddings` on the same
         tile equals `fuzzy_lookup_embedding`: the ordinals are identical except among float32 near-ties and the scores agree within
-        1e-5 -- it is not bit for bit.  `engine.get_option("masked_route")` tells which ran (1 = row list, 2 = tile)."""
+        1e-5 -- it is not bit for bit.
+
+        From 65 queries on an fp16 corpus (1 <= max_hits <= 256, any width; engine option "mask_wide": by default under the same 128 MiB
+        and byte-parity rule, with the 128 or 256 queries per pass of that tile) a dense mask runs where every large unmasked batch runs: the
+        128/256-query filter tile, the mask's bit tested where a row is admitted, and exact rescoring of its candidates.  It is tried before
+        the 32/64-query tile, and its answers EQUAL the row list's bit for bit -- ordinals, float32 scores and counts -- because the
+        rescoring is the streaming kernels' arithmetic; a query with more near-duplicates around its last hit than a candidate band holds is
+        re-run over the row list.  `engine.get_option("masked_route")` tells which ran (1 = row list, 2 = 32/64-query tile, 3 = wide)."""
         queries = np.asarray(embeddings, dtype=np.float32)
         if queries.ndim != 2:
             raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
@@ -924,7 +952,9 @@ class VectorBase:
             return [[] for _ in range(nq)]
         eng = self._sync_device()
         if self._masked_native(eng) and mask.dev_rows is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
-            if 1 <= max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
+            if 1 <= max_hits <= _PAGE and self._mask_wide(eng, mask, nq, max_hits):
+                ords, scs, cnts = eng.search_masked_wide(queries, mask.dev_bits, mask.dev_rows, max_hits, thr, span=mask.span)
+            elif 1 <= max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
                 ords, scs, cnts = eng.search_masked_batch(queries, mask.dev_bits, max_hits, thr, span=mask.span)
             else:
                 ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
