@@ -141,6 +141,28 @@ def test_device_form_ordinal_base_and_untouched_rows():
     eng.close()
 
 
+def test_device_form_with_nothing_to_scan_fills_zero_keys():
+    """An empty span or an empty row list: the device form writes nq x k zero keys (no tile launch), as the 32/64-query tile's device form does
+    for an empty span, and leaves the rows behind them alone."""
+    torch = _torch()
+    case = next(c for c in mw.CASES if c.name == "mask-rand50")
+    _, _, qs = mw.case_inputs(case)
+    eng, dev, bits, dev_rows, flat = _setup(case, "t128")
+    dq = torch.from_numpy(np.ascontiguousarray(qs[:5])).cuda()
+    no_rows = torch.zeros(0, dtype=torch.int32, device="cuda")
+    want = eng.search_masked_device(dq, bits, 10, 0.0, span=(5, 4))
+    eng.synchronize()
+    assert (want.cpu().numpy() == 0).all()
+    for rows, span in ((dev_rows, (5, 4)), (no_rows, (0, case.rows - 1))):
+        out = torch.full((6, 10), SENTINEL, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        eng.search_masked_wide_device(dq, bits, rows, 10, 0.0, span=span, out_keys=out)
+        eng.synchronize()
+        host = out.cpu().numpy()
+        assert np.array_equal(host[:5], want.cpu().numpy()) and (host[5] == SENTINEL).all(), (len(rows), span)
+    eng.close()
+
+
 def test_argument_errors_and_empty_shapes():
     torch = _torch()
     case = next(c for c in mw.CASES if c.name == "mask-rand50")

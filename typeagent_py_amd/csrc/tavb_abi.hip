@@ -1,5 +1,5 @@
 // C ABI of libtavb.so (declared in include/tavb.h), the part that is not a lookup: version and error string, the context and its options,
-// corpus, load path, normalise / convert / merge / remap, profiling.  Host code only -- the lookups are in tavb_lookup.hip, their routing
+// corpus, load path, normalise / convert / merge / remap, profiling.  Host code only -- the lookups are in tavb_lookup.hip / tavb_lookup_topk.hip / tavb_lookup_masked.hip, their routing
 // in tavb_route.hip, the RCCL binding in tavb_comm.hip, the kernels in tavb_scan.hip / tavb_misc.hip / tavb_mfma_wide.hip / ...
 
 #include <cstdarg>

@@ -186,9 +186,8 @@ static int search_exchange_merge(tavb_ctx* c, int32_t nq, int32_t k, bool long_l
   int rc_local = TAVB_OK;
   u64_t* local = nullptr;
   if ((rc_local = require_corpus(c)) != TAVB_OK) {
-  } else if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    rc_local = fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  else if (list_keys <= (size_t)c->comm_chunk_keys && list_keys * sizeof(u64_t) <= c->d_xlocal.cap) local = reinterpret_cast<u64_t*>(c->d_xlocal.ptr);
+  } else if ((rc_local = check_key_ordinals(c, /*device_resident=*/true)) != TAVB_OK) {
+  } else if (list_keys <= (size_t)c->comm_chunk_keys && list_keys * sizeof(u64_t) <= c->d_xlocal.cap) local = reinterpret_cast<u64_t*>(c->d_xlocal.ptr);
   else if (c->comm_fail_alloc) rc_local = fail(TAVB_E_NOMEM, "injected failure of the list allocation (option comm_fail_alloc)");
   else if ((rc_local = c->d_local.reserve(list_keys * sizeof(u64_t))) == TAVB_OK) local = reinterpret_cast<u64_t*>(c->d_local.ptr);
   if (rc_local != TAVB_OK) {

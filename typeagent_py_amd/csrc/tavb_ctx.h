@@ -1,6 +1,7 @@
-// What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the lookups), tavb_route.hip
-// (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the context itself and the internal
-// functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
+// What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the fused-k lookups and the
+// staging), tavb_lookup_topk.hip (the large-k and sorted lookups), tavb_lookup_masked.hip (the batched resident subset, the masked batches,
+// the row masks), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
+// context itself and the internal functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
 // tavb_search_device_dispatch lives in tavb::host, whose symbols stay inside the library.
 #pragma once
 
@@ -373,6 +374,29 @@ int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
                        int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, uint32_t index_base, u64_t* d_out);
 
 // ---- tavb_lookup.hip
+// Staging: [nq, dim] queries of the caller -> pinned h_stage (stage_queries_host; *d_q = where submit_queries then copies them) -- stage_queries
+// does both.  stage_subset: one query and a subset's rows (int64 on the host, checked against the corpus; int32 at *d_rows), both copies enqueued;
+// the caller has checked 0 < n_subset < 2^31 - 1.
+int stage_queries_host(tavb_ctx* c, const float* queries_host, int nq, const float** d_q);
+hipError_t submit_queries(tavb_ctx* c, int nq);
+int stage_queries(tavb_ctx* c, const float* queries_host, int nq, const float** d_q);
+int stage_subset(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, const float** d_q, const int32_t** d_rows);
+// keys carry ordinal_base + row in 32 bits: TAVB_E_UNSUPPORTED where the corpus does not fit (the message names device-resident keys or not)
+int check_key_ordinals(const tavb_ctx* c, bool device_resident);
+// the empty result of a device-resident lookup that has nothing to scan: n zero keys at `out` (async on the stream)
+int fill_empty_keys(tavb_ctx* c, u64_t* out, int64_t n);
+// the tail of a host-synchronous lookup whose last kernel wrote [nq, k] keys into h_out: ONE synchronise, the keys decoded into the caller's arrays
+int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts);
+
+// ---- tavb_lookup_topk.hip
+int check_topk_args(tavb_ctx* c, int k);  // context, corpus, 1 <= k <= TAVB_MAX_LARGE_K
+// the pinned keys [nq][k] + rounds [nq] of a large-k lookup (h_out), and what tavb_search_topk reports of the rounds ("last_topk_refine")
+int reserve_topk_out(tavb_ctx* c, int nq, int k, u64_t** keys, int32_t** rounds);
+void note_rounds(tavb_ctx* c, const int32_t* rounds, int nq);
+// Exact top-k beyond the fused selection: queries on the device over n_pos positions (d_rows: a subset's rows, or null) -> out_keys [nq][k]
+// sorted, zero-filled, + out_rounds [nq], both device-writable; nothing is read back before the caller's one synchronise.
+int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
+                     uint32_t index_base, u64_t* out_keys, int32_t* out_rounds);
 // The large-k lookup (tavb_search_topk's passes) with the queries on the device and nothing waited for: nq sorted, zero-padded lists of k keys
 // carrying index_base + position -> out_keys (device or device-writable pinned memory); d_rows: a subset's rows (nq == 1), or null.
 int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,

@@ -1,6 +1,8 @@
-// The lookups of the C ABI (include/tavb.h): every host-synchronous and device-resident tavb_search_* entry point, the message re-rank, the
-// large-k and sorted forms, the batched resident subset, the row masks, and the staging they share.  Host code only -- a device-resident
-// batch is routed by tavb_route.hip, the kernels live in tavb_scan.hip / tavb_misc.hip / tavb_topk.hip / tavb_sort.hip / tavb_mask.hip.
+// The fused-k lookups of the C ABI (include/tavb.h): the host-synchronous and device-resident tavb_search_* entry points up to
+// TAVB_MAX_FUSED_K keys per query, the one-launch form and the captured graph of a small corpus, the host merges, the message re-rank -- and
+// the staging and the small helpers every lookup file shares (declared in tavb_ctx.h).  The large-k and sorted forms are in
+// tavb_lookup_topk.hip, the batched resident subset, the masked batches and the row masks in tavb_lookup_masked.hip.  Host code only -- a
+// device-resident batch is routed by tavb_route.hip, the kernels live in tavb_scan.hip / tavb_misc.hip.
 
 #include <functional>
 
@@ -26,6 +28,11 @@ int cursor_key(float after_score, int64_t after_index, int64_t limit, u64_t* out
   *out = host_key(after_score, (uint32_t)after_index);
   return TAVB_OK;
 }
+
+}  // namespace
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
 
 // ---- staging: the caller's queries (and a subset's rows) -> pinned h_stage -> d_queries (d_rows)
 
@@ -74,6 +81,29 @@ int stage_subset(tavb_ctx* c, const float* query_host, const int64_t* rows_host,
   *d_rows = reinterpret_cast<const int32_t*>(c->d_rows.ptr);
   return TAVB_OK;
 }
+
+// ---- what the entry points of every lookup file repeat
+int check_key_ordinals(const tavb_ctx* c, bool device_resident) {
+  if (c->ordinal_base + c->rows < 0xFFFFFFFFll) return TAVB_OK;
+  return fail(TAVB_E_UNSUPPORTED, "%skeys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1", device_resident ? "device-resident " : "");
+}
+
+int fill_empty_keys(tavb_ctx* c, u64_t* out, int64_t n) {
+  const hipError_t e = tavb::launch_fill_keys(out, n, 0ull, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts) {
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, base, ordinals, scores, counts);
+  return TAVB_OK;
+}
+
+}  // namespace host
+}  // namespace tavb
+
+namespace {
 
 // ---- the one-launch lookup of a small corpus or subset (tavb_search_batch, tavb_search_subset_resident; the callers decide whether, and
 // cut the grid): the scan's per-workgroup lists [p.nq][g.blocks][p.k] go straight into pinned host memory and are merged here.  The queries
@@ -221,9 +251,8 @@ int tavb_search_batch(tavb_ctx* c, const float* queries_host, int32_t nq, int32_
     slot = graph_slot(c, k, min_scores[0]);
     if (slot->exec) {
       TAVB_HIP(hipGraphLaunch(slot->exec, c->stream));
-      TAVB_HIP(hipStreamSynchronize(c->stream));
+      if (int rc = sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts)) return rc;
       c->last_graph = 1;
-      decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
       return TAVB_OK;
     }
   }
@@ -277,10 +306,7 @@ int tavb_search_batch(tavb_ctx* c, const float* queries_host, int32_t nq, int32_
     ~NoGroup() { c->dispatch_no_group = false; }
   } no_group(c);
   if (int rc = dispatch_staged(c, slot, d_q, nq, k, min_scores)) return rc;
-  // no D2H copy: the merge kernel wrote the keys into pinned host memory
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
-  return TAVB_OK;
+  return sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);  // (no D2H copy: the merge kernel wrote the keys into pinned host memory)
 }
 
 int tavb_search_begin(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const tavb_key* cursor) {
@@ -288,8 +314,7 @@ int tavb_search_begin(tavb_ctx* c, const float* queries_host, int32_t nq, int32_
   if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
   if (!queries_host || !min_scores) return fail(TAVB_E_INVALID, "null argument");
   if (cursor && nq != 1) return fail(TAVB_E_INVALID, "a cursor goes with exactly one query");
-  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/false)) return rc;
   DeviceGuard guard(c->device);
   const size_t obytes = (size_t)nq * k * sizeof(u64_t);
   if (int rc = c->h_out.reserve(obytes)) return rc;
@@ -323,7 +348,8 @@ int tavb_search_end(tavb_ctx* c, int32_t nq, int32_t k, tavb_key* out_keys_host)
 // lists [n_lists, nq, k] sorted best first -> out [nq, k], any k.  Every list's j-th key bounds j of its keys from below.  With
 // j = ceil(k / n_lists) and t = the m-th largest of the lists' j-th keys, m = ceil(k / j), at least m * j >= k keys are >= t: the k best
 // overall all are, and they sit in the prefixes (down to t) of the lists whose head is >= t.  One pass over n_lists keys, a selection among
-// them, a sort of the keys that are left.
+// them, a sort of the keys that are left: 0.6 us for the 204 lists of a 10k-row lookup and 0.9 us for 40 lists of 50, where picking the
+// maximum head k times took k * n_lists steps (3.1 us of a 30 us call; profiles/r04_latency_small.md).
 static void merge_pruned(const tavb_key* lists, int n_lists, int nq, int k, tavb_key* out) {
   static thread_local std::vector<u64_t> pool;
   const int j = (k + n_lists - 1) / n_lists;
@@ -348,14 +374,9 @@ int tavb_merge_keys_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int
   if (n_lists < 1 || nq < 0 || k < 1) return fail(TAVB_E_INVALID, "bad merge shape");
   if (nq == 0) return TAVB_OK;
   if (!lists || !out) return fail(TAVB_E_INVALID, "null argument");
-  // Every list is sorted best first, so its j-th key bounds j of its keys from below.  With j = ceil(k / n_lists) and t = the m-th largest of the
-  // lists' j-th keys, m = ceil(k / j), at least m * j >= k keys are >= t: the k best overall all are, and they sit in the prefixes (down to t) of
-  // the lists whose head is >= t.  One pass over n_lists keys, a selection among them, a sort of a few dozen keys: 0.6 us for the 204 lists of a
-  // 10k-row lookup and 0.9 us for 40 lists of 50, where picking the maximum head k times took k * n_lists steps (3.1 us of a 30 us call;
-  // profiles/r04_latency_small.md).
   // A FEW lists (the grouped one-launch form leaves 8 .. 32 per query, and there are up to 64 queries to merge): a plain k-way merge, the
-  // largest head k times -- with 8 lists of 50 the selection above keeps most of their 400 keys for the sort (~2 us per query, 64 us for
-  // a 32-term batch of a 91 us call); k * n_lists steps are ~0.3 us.
+  // largest head k times -- with 8 lists of 50 the selection of merge_pruned keeps most of their 400 keys for the sort (~2 us per query, 64 us
+  // for a 32-term batch of a 91 us call); k * n_lists steps are ~0.3 us.
   if (n_lists <= 16 && nq == 1) {
     const tavb_key* head[16];
     int left[16];
@@ -426,9 +447,7 @@ static int search_subset_impl(tavb_ctx* c, const float* query_host, const int64_
   if (int rc = c->h_out.reserve((size_t)k * sizeof(u64_t))) return rc;
   if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
   if (int rc = search_device_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr), bound)) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), 1, k, 0, out_positions, out_scores, out_count);
-  return TAVB_OK;
+  return sync_decode(c, 1, k, 0, out_positions, out_scores, out_count);
 }
 
 // one pass, every survivor: keys on the device -> host, sorted best first, the first max_out decoded
@@ -487,384 +506,6 @@ int tavb_search_subset_all(tavb_ctx* c, const float* query_host, const int64_t* 
   return search_all_impl(c, query_host, rows_host, n_subset, true, min_score, max_out, out_positions, out_scores, out_count, out_total);
 }
 
-// ---- exact top-k beyond the fused selection (tavb_topk.hip): queries on the device (d_q [nq, dim]) over n_pos positions (d_rows: the
-// subset's rows, or null) -> out_keys [nq][k] sorted, zero-filled, + out_rounds [nq], both in pinned host memory.  Per group of up to
-// TAVB_MAX_STREAM_QUERIES queries (fewer where the score array would pass topk_scores_bytes or the vector tier's LDS would overflow):
-// a memset, ONE score pass, the refinement rounds topk_refine_rounds asks for, the compaction and the finish -- every launch's grid is
-// fixed on the host, nothing is read back before the caller's one synchronise.
-static int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
-                            uint32_t index_base, u64_t* out_keys, int32_t* out_rounds) {
-  const int nb = (int)c->topk_buckets, cap = (int)c->topk_boundary_keys;
-  int64_t per = tavb::topk_queries_per_pass(c->dim, c->dtype, nb);
-  per = std::min<int64_t>(per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
-  per = std::min<int64_t>(per, nq);
-  const int rounds = tavb::topk_refine_rounds(n_pos, cap);
-  if (int rc = c->d_topk_scores.reserve((size_t)per * n_pos * sizeof(uint32_t))) return rc;
-  if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)per, k, nb, cap, rounds))) return rc;
-  tavb::ScanGeometry g = clamped_geometry(c);
-  g.blocks = scan_blocks_for(c, n_pos, g.waves, 2);
-  // the passes over the score array: 4 bytes per row and query, ~8 rows per thread and a grid of a few workgroups per CU in all
-  const int sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (n_pos + 2047) / 2048), std::max<int64_t>(1, 2048 / per));
-  for (int q0 = 0; q0 < nq; q0 += (int)per) {
-    const int n = (int)std::min<int64_t>(per, nq - q0);
-    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, nb, rounds), c->stream));
-    tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, n_pos, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
-    p.topk_scores = reinterpret_cast<unsigned*>(c->d_topk_scores.ptr);
-    p.topk_hist = reinterpret_cast<unsigned*>(c->d_topk.ptr);
-    p.topk_buckets = nb;
-    tavb::TopkLaunch t{};
-    for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
-      const float ms = i < n ? min_scores[q0 + i] : INFINITY;
-      float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
-      if (lo > 1.0f) lo = 1.0f;
-      p.topk_lo[i] = t.lo[i] = lo;
-      p.topk_scale[i] = t.scale[i] = lo < 1.0f ? (float)nb / (1.0f - lo) : 0.0f;
-    }
-    {
-      Timed tm(c, TAVB_KERNEL_SCAN);
-      hipError_t e = tavb::launch_scan_topk(p, g, c->stream, &c->last_tier);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k score pass launch failed: %s", hipGetErrorString(e));
-    }
-    t.scores = p.topk_scores;
-    t.workspace = c->d_topk.ptr;
-    t.n_pos = n_pos;
-    t.nq = n;
-    t.k = k;
-    t.buckets = nb;
-    t.cap = cap;
-    t.rounds = rounds;
-    t.blocks = sel_blocks;
-    t.out_keys = out_keys + (size_t)q0 * k;
-    t.out_rounds = out_rounds + q0;
-    t.index_base = index_base;
-    Timed tm(c, TAVB_KERNEL_TOPK);
-    for (int r = 0; r < rounds; ++r) {
-      hipError_t e = tavb::launch_topk_refine(t, r, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k refinement launch failed: %s", hipGetErrorString(e));
-    }
-    hipError_t e = tavb::launch_topk_compact(t, c->stream);
-    if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k selection launch failed: %s", hipGetErrorString(e));
-  }
-  return TAVB_OK;
-}
-
-static int check_topk_args(tavb_ctx* c, int k) {
-  if (int rc = check_ctx(c)) return rc;
-  if (int rc = require_corpus(c)) return rc;
-  if (k < 1 || k > TAVB_MAX_LARGE_K) return fail(TAVB_E_INVALID, "k must be 1 .. %d (got %d)", TAVB_MAX_LARGE_K, k);
-  return TAVB_OK;
-}
-
-// the pinned keys [nq][k] + rounds [nq] of a large-k lookup
-static int reserve_topk_out(tavb_ctx* c, int nq, int k, u64_t** keys, int32_t** rounds) {
-  const size_t kbytes = (size_t)nq * k * sizeof(u64_t);
-  if (int rc = c->h_out.reserve(kbytes + (size_t)nq * sizeof(int32_t))) return rc;
-  *keys = reinterpret_cast<u64_t*>(c->h_out.ptr);
-  *rounds = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->h_out.ptr) + kbytes);
-  return TAVB_OK;
-}
-
-static void note_rounds(tavb_ctx* c, const int32_t* rounds, int nq) {
-  int m = 0;
-  for (int q = 0; q < nq; ++q) m = std::max(m, (int)rounds[q]);
-  c->last_topk_refine = m;
-}
-
-int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
-                     int32_t* out_counts) {
-  if (int rc = check_topk_args(c, k)) return rc;
-  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
-  if (nq == 0) return TAVB_OK;
-  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
-  if (c->rows == 0) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  u64_t* keys;
-  int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, 0u, keys, rounds)) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(keys, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
-}
-
-int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int32_t k, float min_score,
-                            int64_t* out_positions, float* out_scores, int32_t* out_count) {
-  if (int rc = check_topk_args(c, k)) return rc;
-  if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
-  if (!query_host || !out_positions || !out_scores || !out_count) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  if (n_subset == 0 || c->rows == 0) {
-    *out_count = 0;
-    return TAVB_OK;
-  }
-  if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
-  if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  const int32_t* d_rows;
-  u64_t* keys;
-  int32_t* rounds;
-  if (int rc = reserve_topk_out(c, 1, k, &keys, &rounds)) return rc;
-  if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
-  if (int rc = search_topk_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, 0u, keys, rounds)) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(keys, 1, k, 0, out_positions, out_scores, out_count);
-  note_rounds(c, rounds, 1);
-  return TAVB_OK;
-}
-
-}  // extern "C"
-
-// queries already on the device, keys to device (or device-writable pinned) memory, nothing waited for: the refinement rounds of the queries
-// land in the context's own pinned words and become "last_topk_refine" at the next tavb_synchronize
-int tavb::host::search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const int32_t* d_rows, int64_t n_pos,
-                                  uint32_t index_base, u64_t* out_keys) {
-  c->topk_rounds_pending = 0;
-  c->last_topk_refine = 0;
-  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
-  if (n_pos == 0 || c->rows == 0) {  // nothing to scan: empty lists
-    const hipError_t e = tavb::launch_fill_keys(out_keys, (int64_t)nq * k, 0ull, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
-    return TAVB_OK;
-  }
-  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, d_rows, n_pos, index_base, out_keys, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
-  c->topk_rounds_pending = nq;
-  return TAVB_OK;
-}
-
-extern "C" {
-
-int tavb_search_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
-                            int64_t n_subset, tavb_key* out_keys) {
-  if (int rc = check_topk_args(c, k)) return rc;
-  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
-  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
-  if (dev_rows && nq != 1) return fail(TAVB_E_INVALID, "a subset goes with exactly one query");
-  if (!dev_rows && n_subset != 0) return fail(TAVB_E_INVALID, "null dev_rows");
-  if (!dev_rows && c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  DeviceGuard guard(c->device);
-  return dev_rows ? search_topk_async(c, dev_queries, 1, k, min_scores, dev_rows, n_subset, 0u, reinterpret_cast<u64_t*>(out_keys))
-                  : search_topk_async(c, dev_queries, nq, k, min_scores, nullptr, c->rows, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
-}
-
-// ---- sorted lookups: every survivor (k = 0) or the best k for any k, sorted on the device.  Per group of queries (sized as for
-// search_topk_impl): a memset, ONE score pass, the refinement rounds (only when k < n_pos), the per-block key counts -> pinned, ONE
-// synchronise; the host checks max_total and then, query by query: compaction in position order, the sort, and the decode of the
-// best `need` keys into h_out, which is copied to the caller's arrays whenever the next piece would not fit sort_stage_keys.
-namespace {
-struct SortedOut {  // the caller's concatenated results and how far they are filled
-  int64_t* ords;
-  float* scs;
-  int64_t done = 0;    // results copied to the caller
-  int64_t staged = 0;  // results decoded into h_out, not yet copied
-};
-
-int flush_staged(tavb_ctx* c, SortedOut& o, int64_t cap) {
-  if (o.staged == 0) return TAVB_OK;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  const char* base = reinterpret_cast<const char*>(c->h_out.ptr);
-  parallel_copy(o.ords + o.done, base, (size_t)o.staged * sizeof(int64_t));
-  parallel_copy(o.scs + o.done, base + (size_t)cap * sizeof(int64_t), (size_t)o.staged * sizeof(float));
-  o.done += o.staged;
-  o.staged = 0;
-  return TAVB_OK;
-}
-}  // namespace
-
-static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /*1 .. n_pos*/, const float* min_scores /*host, nq*/,
-                              const int32_t* d_rows, int64_t n_pos, int64_t base, int64_t max_total, int64_t* out_ords, float* out_scores,
-                              int64_t* out_counts, int64_t* out_total) {
-  const int nb = (int)c->topk_buckets, cap = (int)c->topk_boundary_keys;
-  int64_t per = tavb::topk_queries_per_pass(c->dim, c->dtype, nb);
-  per = std::min<int64_t>(per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
-  per = std::min<int64_t>(per, nq);
-  const int rounds = k < n_pos ? tavb::topk_refine_rounds(n_pos, cap) : 0;  // (k = n_pos: every survivor, nothing to refine)
-  int64_t chunk;
-  const int cblocks = tavb::sorted_blocks(n_pos, &chunk);
-  const size_t head = tavb::topk_head_bytes((int)per, nb, rounds);
-  if (int rc = c->d_topk_scores.reserve((size_t)per * n_pos * sizeof(uint32_t))) return rc;
-  if (int rc = c->d_topk.reserve(head + (size_t)per * cblocks * sizeof(unsigned))) return rc;
-  if (int rc = c->h_sort_info.reserve((size_t)per * (4 + cblocks) * sizeof(int32_t))) return rc;
-  const int64_t stage = c->sort_stage_keys;
-  if (int rc = c->h_out.reserve((size_t)stage * (sizeof(int64_t) + sizeof(float)))) return rc;
-  tavb::ScanGeometry g = clamped_geometry(c);
-  g.blocks = scan_blocks_for(c, n_pos, g.waves, 2);
-  const int sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (n_pos + 2047) / 2048), std::max<int64_t>(1, 2048 / per));
-  SortedOut o{out_ords, out_scores};
-  int64_t total = 0;
-  int max_rounds = 0;
-  for (int q0 = 0; q0 < nq; q0 += (int)per) {
-    const int n = (int)std::min<int64_t>(per, nq - q0);
-    unsigned* d_counts = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(c->d_topk.ptr) + head);
-    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, nb, rounds), c->stream));
-    tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, n_pos, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
-    p.topk_scores = reinterpret_cast<unsigned*>(c->d_topk_scores.ptr);
-    p.topk_hist = reinterpret_cast<unsigned*>(c->d_topk.ptr);
-    p.topk_buckets = nb;
-    tavb::TopkLaunch t{};
-    for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
-      const float ms = i < n ? min_scores[q0 + i] : INFINITY;
-      float lo = ms > 0.0f ? ms : 0.0f;
-      if (lo > 1.0f) lo = 1.0f;
-      p.topk_lo[i] = t.lo[i] = lo;
-      p.topk_scale[i] = t.scale[i] = lo < 1.0f ? (float)nb / (1.0f - lo) : 0.0f;
-    }
-    {
-      Timed tm(c, TAVB_KERNEL_SCAN);
-      hipError_t e = tavb::launch_scan_topk(p, g, c->stream, &c->last_tier);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted score pass launch failed: %s", hipGetErrorString(e));
-    }
-    t.scores = p.topk_scores;
-    t.workspace = c->d_topk.ptr;
-    t.n_pos = n_pos;
-    t.nq = n;
-    t.k = (int32_t)k;
-    t.buckets = nb;
-    t.cap = cap;
-    t.rounds = rounds;
-    t.blocks = sel_blocks;
-    {
-      Timed tm(c, TAVB_KERNEL_TOPK);
-      for (int r = 0; r < rounds; ++r) {
-        hipError_t e = tavb::launch_topk_refine(t, r, c->stream);
-        if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted refinement launch failed: %s", hipGetErrorString(e));
-      }
-      hipError_t e = tavb::launch_sorted_count(t, d_counts, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted count launch failed: %s", hipGetErrorString(e));
-    }
-    int32_t* meta = reinterpret_cast<int32_t*>(c->h_sort_info.ptr);
-    unsigned* counts = reinterpret_cast<unsigned*>(meta + (size_t)n * 4);
-    TAVB_HIP(hipMemcpyAsync(meta, reinterpret_cast<char*>(c->d_topk.ptr) + tavb::topk_meta_offset(n, nb, rounds), (size_t)n * 4 * sizeof(int32_t),
-                            hipMemcpyDeviceToHost, c->stream));
-    TAVB_HIP(hipMemcpyAsync(counts, d_counts, (size_t)n * cblocks * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    TAVB_HIP(hipStreamSynchronize(c->stream));
-    int64_t group_total = 0, most = 0;
-    for (int q = 0; q < n; ++q) {
-      int64_t kept = 0;
-      for (int b = 0; b < cblocks; ++b) kept += counts[(size_t)q * cblocks + b];
-      group_total += meta[q * 4 + 0];
-      most = std::max(most, kept);
-      max_rounds = std::max(max_rounds, (int)meta[q * 4 + 1]);
-    }
-    if (total + group_total > max_total)
-      return fail(TAVB_E_INVALID, "the lookup has more than max_total = %lld results (%lld so far)", (long long)max_total,
-                  (long long)(total + group_total));
-    if (most > 0) {
-      if (int rc = c->d_sort_keys.reserve((size_t)most * sizeof(u64_t))) return rc;
-      if (int rc = c->d_sort_ws.reserve(tavb::sort_workspace_bytes(most))) return rc;
-    }
-    for (int q = 0; q < n; ++q) {
-      const int64_t need = meta[q * 4 + 0];
-      out_counts[q0 + q] = need;
-      if (need == 0) continue;
-      int64_t kept = 0;
-      for (int b = 0; b < cblocks; ++b) kept += counts[(size_t)q * cblocks + b];
-      if (kept < need) return fail(TAVB_E_HIP, "sorted lookup: %lld keys kept for %lld results (internal error)", (long long)kept, (long long)need);
-      tavb::SortJob j{reinterpret_cast<u64_t*>(c->d_sort_keys.ptr), kept, 4, c->d_sort_ws.ptr, (int)c->sort_small_keys, false};
-      {
-        Timed tm(c, TAVB_KERNEL_TOPK);
-        hipError_t e = tavb::launch_sorted_compact(t, q, d_counts, j.keys, c->stream);
-        if (e == hipSuccess) e = tavb::launch_sort_desc(j, c->stream);
-        if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted compaction / sort launch failed: %s", hipGetErrorString(e));
-      }
-      for (int64_t off = 0; off < need;) {
-        if (o.staged == stage) {
-          if (int rc = flush_staged(c, o, stage)) return rc;
-        }
-        const int64_t len = std::min(need - off, stage - o.staged);
-        char* hb = reinterpret_cast<char*>(c->h_out.ptr);
-        Timed tm(c, TAVB_KERNEL_TOPK);
-        hipError_t e = tavb::launch_sort_decode(j, off, len, base, reinterpret_cast<int64_t*>(hb) + o.staged,
-                                                reinterpret_cast<float*>(hb + (size_t)stage * sizeof(int64_t)) + o.staged, c->stream);
-        if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted decode launch failed: %s", hipGetErrorString(e));
-        o.staged += len;
-        off += len;
-      }
-    }
-    total += group_total;
-  }
-  if (int rc = flush_staged(c, o, stage)) return rc;
-  c->last_topk_refine = max_rounds;
-  *out_total = total;
-  return TAVB_OK;
-}
-
-static int check_sorted_args(tavb_ctx* c, int64_t k, int64_t max_total, const void* out_total) {
-  if (int rc = check_ctx(c)) return rc;
-  if (int rc = require_corpus(c)) return rc;
-  if (k < 0) return fail(TAVB_E_INVALID, "k must be >= 0 (0 = every survivor)");
-  if (max_total < 0) return fail(TAVB_E_INVALID, "max_total must be >= 0");
-  if (!out_total) return fail(TAVB_E_INVALID, "null argument");
-  return TAVB_OK;
-}
-
-int tavb_search_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, int64_t k, const float* min_scores, int64_t max_total, int64_t* out_ordinals,
-                       float* out_scores, int64_t* out_counts, int64_t* out_total) {
-  if (int rc = check_sorted_args(c, k, max_total, out_total)) return rc;
-  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
-  *out_total = 0;
-  if (nq == 0) return TAVB_OK;
-  if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-  if (c->rows == 0) return TAVB_OK;
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  const int64_t kk = (k == 0 || k > c->rows) ? c->rows : k;
-  return search_sorted_impl(c, d_q, nq, kk, min_scores, nullptr, c->rows, c->ordinal_base, max_total, out_ordinals, out_scores, out_counts, out_total);
-}
-
-int tavb_search_subset_sorted(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int64_t k, float min_score,
-                              int64_t max_total, int64_t* out_positions, float* out_scores, int64_t* out_count) {
-  if (int rc = check_sorted_args(c, k, max_total, out_count)) return rc;
-  if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
-  *out_count = 0;
-  if (!query_host || (max_total > 0 && (!out_positions || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  if (n_subset == 0 || c->rows == 0) return TAVB_OK;
-  if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
-  if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  const int32_t* d_rows;
-  if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
-  const int64_t kk = (k == 0 || k > n_subset) ? n_subset : k;
-  int64_t count = 0;
-  return search_sorted_impl(c, d_q, 1, kk, &min_score, d_rows, n_subset, 0, max_total, out_positions, out_scores, &count, out_count);
-}
-
-int tavb_sort_keys_device(tavb_ctx* c, tavb_key* dev_keys, int64_t n) {
-  if (int rc = check_ctx(c)) return rc;
-  if (n < 0 || n >= ((int64_t)1 << 32)) return fail(TAVB_E_INVALID, "n must be 0 .. 2^32 - 1");
-  if (n == 0) return TAVB_OK;
-  if (!dev_keys) return fail(TAVB_E_INVALID, "null dev_keys");
-  DeviceGuard guard(c->device);
-  if (int rc = c->d_sort_ws.reserve(tavb::sort_workspace_bytes(n))) return rc;
-  tavb::SortJob j{reinterpret_cast<u64_t*>(dev_keys), n, 0, c->d_sort_ws.ptr, (int)c->sort_small_keys, false};
-  {
-    Timed tm(c, TAVB_KERNEL_TOPK);
-    hipError_t e = tavb::launch_sort_desc(j, c->stream);
-    if (e == hipSuccess) e = tavb::launch_sort_copy_back(j, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "sort launch failed: %s", hipGetErrorString(e));
-  }
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  return TAVB_OK;
-}
 
 int tavb_set_row_messages(tavb_ctx* c, const int32_t* dev_row_to_msg, int64_t rows, int64_t n_messages) {
   if (int rc = check_ctx(c)) return rc;
@@ -898,9 +539,7 @@ static int rerank_and_return(tavb_ctx* c, const u64_t* d_hits, int k, const int3
   hipError_t e = tavb::launch_message_rerank(d_hits, 1, k, 0u, d_pos_to_row, c->row_to_msg, c->row_to_msg_rows, d_bits, c->n_messages, max_messages,
                                              reinterpret_cast<u64_t*>(c->h_out.ptr), c->stream);
   if (e != hipSuccess) return fail(TAVB_E_HIP, "re-rank launch failed: %s", hipGetErrorString(e));
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), 1, k, 0, out_messages, out_scores, out_count);
-  return TAVB_OK;
+  return sync_decode(c, 1, k, 0, out_messages, out_scores, out_count);
 }
 
 static int check_message_args(tavb_ctx* c, int k, int32_t max_messages) {
@@ -968,8 +607,7 @@ int tavb_search_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_
   if (int rc = check_search_args(c, k)) return rc;
   if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
   if (!dev_queries || !dev_out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
   DeviceGuard guard(c->device);
   std::vector<float> ms((size_t)nq, min_score);
   return tavb_search_device_dispatch(c, dev_queries, nq, k, ms.data(), (uint32_t)c->ordinal_base,
@@ -1016,260 +654,9 @@ int tavb_search_subset_resident(tavb_ctx* c, const float* query_host, const int3
   }
   TAVB_HIP(submit_queries(c, 1));
   if (int rc = search_device_impl(c, d_q, 1, k, &min_score, dev_rows, n_subset, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr))) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), 1, k, 0, out_positions, out_scores, out_count);
-  return TAVB_OK;
+  return sync_decode(c, 1, k, 0, out_positions, out_scores, out_count);
 }
 
-// nq queries over one resident row list: the passes of search_device_impl (k <= TAVB_MAX_FUSED_K: a scan + a merge per group of queries) or of
-// search_topk_impl (beyond), both of which take a row list with any number of queries.  Up to kRemapPinnedKeys keys land in pinned host
-// memory as in the single-query form, and the remap (a few KiB) runs on them in place; more keys are merged (and remapped) in device
-// memory and copied out once.
-int tavb_search_subset_batch_resident(tavb_ctx* c, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
-                                      const float* min_scores, int32_t remap, int64_t* out, float* out_scores, int32_t* out_counts) {
-  constexpr size_t kRemapPinnedKeys = 4096;
-  if (int rc = check_topk_args(c, k)) return rc;
-  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
-  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
-  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (corpus ordinals)");
-  if (nq == 0) return TAVB_OK;
-  if (!queries_host || !min_scores || !out || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  c->last_direct = 0;
-  c->masked_route = 1;  // the gather route of a masked batch
-  if (n_subset == 0 || c->rows == 0) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
-  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
-  DeviceGuard guard(c->device);
-  const size_t n_keys = (size_t)nq * k;
-  u64_t* keys;
-  int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  u64_t* target = keys;
-  const bool via_device = n_keys > kRemapPinnedKeys;  // (with or without the remap: no merge writes megabytes over PCIe)
-  if (via_device) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
-  const float* d_q;
-  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  if (k <= TAVB_MAX_FUSED_K) {
-    if (int rc = search_device_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
-  } else {
-    if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target, rounds)) return rc;
-  }
-  if (remap) {
-    hipError_t e = tavb::launch_remap_positions(target, target, (int64_t)n_keys, dev_rows, n_subset, 0u, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
-  }
-  if (via_device) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(keys, nq, k, remap ? c->ordinal_base : 0, out, out_scores, out_counts);
-  if (k > TAVB_MAX_FUSED_K) note_rounds(c, rounds, nq);
-  return TAVB_OK;
-}
-
-// The no-wait twin of the call above: queries already on the device, keys to device (or device-writable pinned) memory.  remap = 1: the passes
-// write their positions into d_out and the remap kernel turns them into ordinal_base + dev_rows[position] on the way to out_keys -- one
-// launch either way, and a pinned out_keys is written once and never read over PCIe.
-int tavb_search_subset_batch_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
-                                    const float* min_scores, int32_t remap, tavb_key* out_keys) {
-  if (int rc = check_topk_args(c, k)) return rc;
-  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
-  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
-  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (global ordinals)");
-  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (remap && c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  c->last_direct = 0;
-  c->masked_route = 1;  // the gather route of a masked batch
-  DeviceGuard guard(c->device);
-  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
-  const size_t n_keys = (size_t)nq * k;
-  if (n_subset == 0 || c->rows == 0) {  // nothing to scan: empty lists (dev_rows may be null)
-    const hipError_t e = tavb::launch_fill_keys(out, (int64_t)n_keys, 0ull, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
-    return TAVB_OK;
-  }
-  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
-  u64_t* target = out;
-  if (remap) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
-  if (k <= TAVB_MAX_FUSED_K) {
-    if (int rc = search_device_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
-  } else {
-    if (int rc = search_topk_async(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
-  }
-  if (remap) {
-    hipError_t e = tavb::launch_remap_positions(target, out, (int64_t)n_keys, dev_rows, n_subset, (uint32_t)c->ordinal_base, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
-  }
-  return TAVB_OK;
-}
-
-// ---- masked batches on the 32/64-query tile (tavb_route.hip::search_masked_tile)
-// What both entry points check alike; *empty: nothing to scan (an empty corpus, no query, an empty span).
-static int check_masked_args(tavb_ctx* c, int32_t nq, int32_t min_nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, int32_t k,
-                             bool* empty) {
-  if (int rc = check_ctx(c)) return rc;
-  if (int rc = require_corpus(c)) return rc;
-  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
-  if (nq < min_nq) return fail(TAVB_E_INVALID, "nq must be >= %d", min_nq);
-  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
-  *empty = rows == 0 || nq == 0 || first_row > last_row;
-  if (!*empty && (first_row < 0 || last_row >= rows)) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
-  if (!*empty && !dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
-  if (!tavb::skinny_supported(c->dim, k, c->dtype != TAVB_F16))
-    return fail(TAVB_E_UNSUPPORTED, "the masked tile serves 1 <= k <= 64 and rows of a multiple of 64 bytes (k = %d, %d bytes): use the gather route", k,
-                c->dim * (c->dtype == TAVB_F16 ? 2 : 4));
-  return TAVB_OK;
-}
-
-int tavb_search_masked_batch(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
-                             int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
-  bool empty = false;
-  if (int rc = check_masked_args(c, nq, 0, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
-  if (nq == 0) return TAVB_OK;
-  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  if (int rc = c->h_out.reserve((size_t)nq * k * sizeof(u64_t))) return rc;
-  c->last_graph = 0;
-  if (int rc = search_masked_tile(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr))) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));  // (no D2H copy: the merge kernel wrote the keys into pinned host memory)
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
-  return TAVB_OK;
-}
-
-int tavb_search_masked_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
-                              int32_t k, const float* min_scores, tavb_key* out_keys) {
-  bool empty = false;
-  if (int rc = check_masked_args(c, nq, 0, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
-  if (nq == 0) return TAVB_OK;
-  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  DeviceGuard guard(c->device);
-  if (empty) {  // zero keys; no tile launch
-    const hipError_t e = tavb::launch_fill_keys(reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k, 0ull, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
-    return TAVB_OK;
-  }
-  return search_masked_tile(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
-}
-
-// ---- masked batches on the 128/256-query filter tile + rescoring (tavb_route.hip::search_masked_wide)
-static int check_masked_wide_args(tavb_ctx* c, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, const int32_t* dev_rows,
-                                  int64_t n_allowed, int32_t k, bool* empty) {
-  if (int rc = check_ctx(c)) return rc;
-  if (int rc = require_corpus(c)) return rc;
-  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
-  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
-  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
-  if (n_allowed < 0 || n_allowed > rows) return fail(TAVB_E_INVALID, "bad row list length");
-  *empty = rows == 0 || nq == 0 || first_row > last_row || n_allowed == 0;
-  if (!*empty && (first_row < 0 || last_row >= rows)) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
-  if (!*empty && (!dev_bits || !dev_rows)) return fail(TAVB_E_INVALID, "null dev_bits / dev_rows");
-  if ((reinterpret_cast<uintptr_t>(dev_bits) & 3) != 0) return fail(TAVB_E_INVALID, "dev_bits must be 4-byte aligned");
-  if (!masked_wide_supported(c, k))
-    return fail(TAVB_E_UNSUPPORTED, "the masked wide route serves fp16 corpora of up to 16384 halves per row and 1 <= k <= %d (k = %d): use another masked route",
-                TAVB_MAX_FUSED_K, k);
-  return TAVB_OK;
-}
-
-int tavb_search_masked_wide(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
-                            const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
-                            int32_t* out_counts) {
-  bool empty = false;
-  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
-  if (nq == 0) return TAVB_OK;
-  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
-  DeviceGuard guard(c->device);
-  const float* d_q;
-  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
-  // up to 4096 keys land in pinned host memory as the other batched forms' do; more are written in device memory and copied out once
-  const size_t n_keys = (size_t)nq * k;
-  const bool via_device = n_keys > 4096;
-  if (int rc = c->h_out.reserve(n_keys * sizeof(u64_t))) return rc;
-  if (via_device)
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-  u64_t* const target = reinterpret_cast<u64_t*>(via_device ? c->d_out.ptr : c->h_out.ptr);
-  c->last_graph = 0;
-  if (int rc = search_masked_wide(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, 0u, target)) return rc;
-  if (via_device) TAVB_HIP(hipMemcpyAsync(c->h_out.ptr, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
-  return TAVB_OK;
-}
-
-int tavb_search_masked_wide_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
-                                   const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, tavb_key* out_keys) {
-  bool empty = false;
-  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
-  if (nq == 0) return TAVB_OK;
-  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  if (c->ordinal_base + c->rows >= 0xFFFFFFFFll)
-    return fail(TAVB_E_UNSUPPORTED, "device-resident keys hold 32-bit ordinals: ordinal_base + rows must be < 2^32 - 1");
-  DeviceGuard guard(c->device);
-  if (empty) {  // zero keys; no tile launch
-    const hipError_t e = tavb::launch_fill_keys(reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k, 0ull, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "fill launch failed: %s", hipGetErrorString(e));
-    return TAVB_OK;
-  }
-  return search_masked_wide(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, (uint32_t)c->ordinal_base,
-                            reinterpret_cast<u64_t*>(out_keys));
-}
-
-// ---- row masks (tavb_mask.hip)
-int tavb_mask_expand(tavb_ctx* c, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap, int64_t* out_count) {
-  if (int rc = check_ctx(c)) return rc;
-  if (!out_count) return fail(TAVB_E_INVALID, "null argument");
-  *out_count = 0;
-  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
-  if (cap < 0 || (cap > 0 && !dev_rows_out)) return fail(TAVB_E_INVALID, "bad capacity");
-  if (rows == 0) return TAVB_OK;
-  if (!dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
-  DeviceGuard guard(c->device);
-  if (int rc = c->d_mask_counts.reserve((size_t)tavb::mask_blocks(rows) * sizeof(unsigned))) return rc;
-  if (int rc = c->h_out.reserve(sizeof(long long))) return rc;
-  long long* total = reinterpret_cast<long long*>(c->h_out.ptr);
-  *total = -1;
-  hipError_t e = tavb::launch_mask_expand(dev_bits, rows, reinterpret_cast<unsigned*>(c->d_mask_counts.ptr), dev_rows_out, cap, total, c->stream);
-  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask expansion launch failed: %s", hipGetErrorString(e));
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  if (*total < 0) return fail(TAVB_E_HIP, "mask expansion wrote no count (internal error)");
-  *out_count = (int64_t)*total;
-  if (dev_rows_out && *total > cap)
-    return fail(TAVB_E_INVALID, "the mask has %lld rows set, dev_rows_out holds %lld", *total, (long long)cap);
-  return TAVB_OK;
-}
-
-int tavb_mask_pack(tavb_ctx* c, const uint8_t* dev_bytes, int64_t rows, uint32_t* dev_bits_out) {
-  if (int rc = check_ctx(c)) return rc;
-  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
-  if (rows == 0) return TAVB_OK;
-  if (!dev_bytes || !dev_bits_out) return fail(TAVB_E_INVALID, "null argument");
-  DeviceGuard guard(c->device);
-  hipError_t e = tavb::launch_mask_pack(dev_bytes, rows, dev_bits_out, c->stream);
-  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask pack launch failed: %s", hipGetErrorString(e));
-  return TAVB_OK;
-}
 
 int tavb_search_after(tavb_ctx* c, const float* query_host, int32_t k, float min_score, float after_score,
                       int64_t after_ordinal, int64_t* out_ordinals, float* out_scores, int32_t* out_count) {
@@ -1286,9 +673,7 @@ int tavb_search_after(tavb_ctx* c, const float* query_host, int32_t k, float min
   const float* d_q;
   if (int rc = stage_queries(c, query_host, 1, &d_q)) return rc;
   if (int rc = search_device_impl(c, d_q, 1, k, &min_score, nullptr, c->rows, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr), bound)) return rc;
-  TAVB_HIP(hipStreamSynchronize(c->stream));
-  decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), 1, k, c->ordinal_base, out_ordinals, out_scores, out_count);
-  return TAVB_OK;
+  return sync_decode(c, 1, k, c->ordinal_base, out_ordinals, out_scores, out_count);
 }
 
 }  // extern "C"

@@ -1,0 +1,260 @@
+// The batched and masked lookups of the C ABI (include/tavb.h): the batched resident subset (the gather route of a masked batch), masked
+// batches on the 32/64-query tile and on the 128/256-query filter tile, and the row masks themselves.  Host code only: the tile routes are
+// tavb_route.hip's, the large-k passes tavb_lookup_topk.hip's, the staging tavb_lookup.hip's, the mask kernels live in tavb_mask.hip.
+
+#include "tavb_ctx.h"
+
+using namespace tavb::host;
+
+namespace {
+
+// ---- where the keys of a batched host-synchronous lookup land: up to kPinnedKeysMax of them in pinned host memory (h_out: the last kernel
+// writes them there, as in the single-query forms -- a remap of a few KiB runs on them in place); more are written in device memory
+// (d_out) and copied out once -- no merge writes megabytes over PCIe.
+constexpr size_t kPinnedKeysMax = 4096;
+
+int reserve_key_target(tavb_ctx* c, size_t n_keys, u64_t** target) {
+  if (int rc = c->h_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  *target = reinterpret_cast<u64_t*>(c->h_out.ptr);
+  if (n_keys <= kPinnedKeysMax) return TAVB_OK;
+  if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  *target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  return TAVB_OK;
+}
+
+// the keys at `target` -> h_out (when they are not there already), ONE synchronise, the caller's arrays
+int collect_keys(tavb_ctx* c, const u64_t* target, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts) {
+  if (target != c->h_out.ptr) TAVB_HIP(hipMemcpyAsync(c->h_out.ptr, target, (size_t)nq * k * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  return sync_decode(c, nq, k, base, ordinals, scores, counts);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the batched resident subset
+// nq queries over one resident row list: the passes of search_device_impl (k <= TAVB_MAX_FUSED_K: a scan + a merge per group of queries) or of
+// search_topk_impl (beyond), both of which take a row list with any number of queries; the remap runs on the keys wherever they landed.
+int tavb_search_subset_batch_resident(tavb_ctx* c, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                      const float* min_scores, int32_t remap, int64_t* out, float* out_scores, int32_t* out_counts) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (corpus ordinals)");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->masked_route = 1;  // the gather route of a masked batch
+  if (n_subset == 0 || c->rows == 0) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  u64_t* target;
+  if (int rc = reserve_key_target(c, n_keys, &target)) return rc;  // (h_out: the rounds behind the keys stay reserved)
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (k <= TAVB_MAX_FUSED_K) {
+    if (int rc = search_device_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  } else {
+    if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, dev_rows, n_subset, 0u, target, rounds)) return rc;
+  }
+  if (remap) {
+    hipError_t e = tavb::launch_remap_positions(target, target, (int64_t)n_keys, dev_rows, n_subset, 0u, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  }
+  if (int rc = collect_keys(c, target, nq, k, remap ? c->ordinal_base : 0, out, out_scores, out_counts)) return rc;
+  if (k > TAVB_MAX_FUSED_K) note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+// The no-wait twin of the call above: queries already on the device, keys to device (or device-writable pinned) memory.  remap = 1: the passes
+// write their positions into d_out and the remap kernel turns them into ordinal_base + dev_rows[position] on the way to out_keys -- one
+// launch either way, and a pinned out_keys is written once and never read over PCIe.
+int tavb_search_subset_batch_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int32_t k,
+                                    const float* min_scores, int32_t remap, tavb_key* out_keys) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (remap != 0 && remap != 1) return fail(TAVB_E_INVALID, "remap must be 0 (positions) or 1 (global ordinals)");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (remap)
+    if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->masked_route = 1;  // the gather route of a masked batch
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  const size_t n_keys = (size_t)nq * k;
+  if (n_subset == 0 || c->rows == 0) return fill_empty_keys(c, out, (int64_t)n_keys);  // nothing to scan (dev_rows may be null)
+  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  u64_t* target = out;
+  if (remap) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  if (k <= TAVB_MAX_FUSED_K) {
+    if (int rc = search_device_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  } else {
+    if (int rc = search_topk_async(c, dev_queries, nq, k, min_scores, dev_rows, n_subset, 0u, target)) return rc;
+  }
+  if (remap) {
+    hipError_t e = tavb::launch_remap_positions(target, out, (int64_t)n_keys, dev_rows, n_subset, (uint32_t)c->ordinal_base, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+// ---- masked batches on the 32/64-query tile (tavb_route.hip::search_masked_tile)
+// what every masked entry point checks first
+static int check_masked_head(tavb_ctx* c, int32_t nq, int64_t rows, int32_t k) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (k < 1) return fail(TAVB_E_INVALID, "k must be >= 1 (got %d)", k);
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  return TAVB_OK;
+}
+
+// the span of a masked lookup that has something to scan
+static int check_masked_span(bool empty, int64_t rows, int64_t first_row, int64_t last_row) {
+  if (!empty && (first_row < 0 || last_row >= rows)) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
+  return TAVB_OK;
+}
+
+// *empty: nothing to scan (an empty corpus, no query, an empty span).
+static int check_masked_args(tavb_ctx* c, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, int32_t k, bool* empty) {
+  if (int rc = check_masked_head(c, nq, rows, k)) return rc;
+  *empty = rows == 0 || nq == 0 || first_row > last_row;
+  if (int rc = check_masked_span(*empty, rows, first_row, last_row)) return rc;
+  if (!*empty && !dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
+  if (!tavb::skinny_supported(c->dim, k, c->dtype != TAVB_F16))
+    return fail(TAVB_E_UNSUPPORTED, "the masked tile serves 1 <= k <= 64 and rows of a multiple of 64 bytes (k = %d, %d bytes): use the gather route", k,
+                c->dim * (c->dtype == TAVB_F16 ? 2 : 4));
+  return TAVB_OK;
+}
+
+int tavb_search_masked_batch(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                             int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_masked_args(c, nq, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = c->h_out.reserve((size_t)nq * k * sizeof(u64_t))) return rc;
+  c->last_graph = 0;
+  if (int rc = search_masked_tile(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, 0u, reinterpret_cast<u64_t*>(c->h_out.ptr))) return rc;
+  return sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);  // (no D2H copy: the merge kernel wrote the keys into pinned host memory)
+}
+
+int tavb_search_masked_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                              int32_t k, const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_masked_args(c, nq, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  if (empty) return fill_empty_keys(c, reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k);  // no tile launch
+  return search_masked_tile(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
+}
+
+// ---- masked batches on the 128/256-query filter tile + rescoring (tavb_route.hip::search_masked_wide)
+static int check_masked_wide_args(tavb_ctx* c, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, const int32_t* dev_rows,
+                                  int64_t n_allowed, int32_t k, bool* empty) {
+  if (int rc = check_masked_head(c, nq, rows, k)) return rc;
+  if (n_allowed < 0 || n_allowed > rows) return fail(TAVB_E_INVALID, "bad row list length");
+  *empty = rows == 0 || nq == 0 || first_row > last_row || n_allowed == 0;
+  if (int rc = check_masked_span(*empty, rows, first_row, last_row)) return rc;
+  if (!*empty && (!dev_bits || !dev_rows)) return fail(TAVB_E_INVALID, "null dev_bits / dev_rows");
+  if ((reinterpret_cast<uintptr_t>(dev_bits) & 3) != 0) return fail(TAVB_E_INVALID, "dev_bits must be 4-byte aligned");
+  if (!masked_wide_supported(c, k))
+    return fail(TAVB_E_UNSUPPORTED, "the masked wide route serves fp16 corpora of up to 16384 halves per row and 1 <= k <= %d (k = %d): use another masked route",
+                TAVB_MAX_FUSED_K, k);
+  return TAVB_OK;
+}
+
+int tavb_search_masked_wide(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                            const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
+                            int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  u64_t* target;
+  if (int rc = reserve_key_target(c, (size_t)nq * k, &target)) return rc;
+  c->last_graph = 0;
+  if (int rc = search_masked_wide(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, 0u, target)) return rc;
+  return collect_keys(c, target, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+}
+
+int tavb_search_masked_wide_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                                   const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  if (empty) return fill_empty_keys(c, reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k);  // no tile launch
+  return search_masked_wide(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, (uint32_t)c->ordinal_base,
+                            reinterpret_cast<u64_t*>(out_keys));
+}
+
+// ---- row masks (tavb_mask.hip)
+int tavb_mask_expand(tavb_ctx* c, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap, int64_t* out_count) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!out_count) return fail(TAVB_E_INVALID, "null argument");
+  *out_count = 0;
+  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (cap < 0 || (cap > 0 && !dev_rows_out)) return fail(TAVB_E_INVALID, "bad capacity");
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bits) return fail(TAVB_E_INVALID, "null dev_bits");
+  DeviceGuard guard(c->device);
+  if (int rc = c->d_mask_counts.reserve((size_t)tavb::mask_blocks(rows) * sizeof(unsigned))) return rc;
+  if (int rc = c->h_out.reserve(sizeof(long long))) return rc;
+  long long* total = reinterpret_cast<long long*>(c->h_out.ptr);
+  *total = -1;
+  hipError_t e = tavb::launch_mask_expand(dev_bits, rows, reinterpret_cast<unsigned*>(c->d_mask_counts.ptr), dev_rows_out, cap, total, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask expansion launch failed: %s", hipGetErrorString(e));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  if (*total < 0) return fail(TAVB_E_HIP, "mask expansion wrote no count (internal error)");
+  *out_count = (int64_t)*total;
+  if (dev_rows_out && *total > cap)
+    return fail(TAVB_E_INVALID, "the mask has %lld rows set, dev_rows_out holds %lld", *total, (long long)cap);
+  return TAVB_OK;
+}
+
+int tavb_mask_pack(tavb_ctx* c, const uint8_t* dev_bytes, int64_t rows, uint32_t* dev_bits_out) {
+  if (int rc = check_ctx(c)) return rc;
+  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bytes || !dev_bits_out) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  hipError_t e = tavb::launch_mask_pack(dev_bytes, rows, dev_bits_out, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask pack launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+}  // extern "C"

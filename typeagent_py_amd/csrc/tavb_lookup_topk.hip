@@ -1,0 +1,387 @@
+// The large-k and sorted lookups of the C ABI (include/tavb.h): tavb_search_topk and its subset / device forms, tavb_search_sorted,
+// tavb_search_subset_sorted, tavb_sort_keys_device -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
+// tavb_topk.hip and tavb_sort.hip, the staging in tavb_lookup.hip.
+
+#include <optional>
+
+#include "tavb_ctx.h"
+
+using namespace tavb::host;
+
+namespace {
+
+// ---- the score pass of the large-k and sorted lookups: the queries go over the n_pos positions in groups of up to TAVB_MAX_STREAM_QUERIES
+// (fewer where the score array would pass topk_scores_bytes or the vector tier's LDS would overflow); per group a memset, ONE score pass
+// and the refinement rounds.  Every launch's grid is fixed on the host.
+struct ScorePlan {
+  int64_t n_pos;
+  int nb, cap;           // histogram buckets, capacity of a query's boundary list
+  int64_t per;           // queries per group
+  int rounds;            // refinement rounds of a group (0: nothing to refine)
+  int sel_blocks;        // grid of the passes over the score array
+  tavb::ScanGeometry g;  // of the score pass
+};
+
+// Sizes the groups and reserves the score array of one; d_topk, the selection's workspace, is the caller's to reserve.
+int plan_score_pass(tavb_ctx* c, int nq, int64_t n_pos, bool refine, ScorePlan* s) {
+  s->n_pos = n_pos;
+  s->nb = (int)c->topk_buckets;
+  s->cap = (int)c->topk_boundary_keys;
+  s->per = tavb::topk_queries_per_pass(c->dim, c->dtype, s->nb);
+  s->per = std::min<int64_t>(s->per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
+  s->per = std::min<int64_t>(s->per, nq);
+  s->rounds = refine ? tavb::topk_refine_rounds(n_pos, s->cap) : 0;
+  if (int rc = c->d_topk_scores.reserve((size_t)s->per * n_pos * sizeof(uint32_t))) return rc;
+  s->g = clamped_geometry(c);
+  s->g.blocks = scan_blocks_for(c, n_pos, s->g.waves, 2);
+  // the passes over the score array: 4 bytes per row and query, ~8 rows per thread and a grid of a few workgroups per CU in all
+  s->sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (n_pos + 2047) / 2048), std::max<int64_t>(1, 2048 / s->per));
+  return TAVB_OK;
+}
+
+// The pass for the queries [q0, q0 + n) of the batch (d_q, min_scores: the whole batch's; d_rows: a subset's rows, or null).  *t arrives
+// with the caller's own members set (k, out_keys, out_rounds, index_base) and leaves filled in, ready for the caller's selection launches.
+// `what` names the caller in the messages.  *tm: the TAVB_KERNEL_TOPK interval, opened in front of the refinement rounds -- the caller's
+// launches of the group that follow belong to it, and the caller closes it.
+int run_score_pass(tavb_ctx* c, const ScorePlan& s, const char* what, const float* d_q, const float* min_scores /*host*/, const int32_t* d_rows, int q0, int n,
+                   tavb::TopkLaunch* t, std::optional<Timed>* tm) {
+  TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
+  tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, s.n_pos, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
+  p.topk_scores = reinterpret_cast<unsigned*>(c->d_topk_scores.ptr);
+  p.topk_hist = reinterpret_cast<unsigned*>(c->d_topk.ptr);
+  p.topk_buckets = s.nb;
+  for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
+    const float ms = i < n ? min_scores[q0 + i] : INFINITY;
+    float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
+    if (lo > 1.0f) lo = 1.0f;
+    p.topk_lo[i] = t->lo[i] = lo;
+    p.topk_scale[i] = t->scale[i] = lo < 1.0f ? (float)s.nb / (1.0f - lo) : 0.0f;
+  }
+  {
+    Timed scan(c, TAVB_KERNEL_SCAN);
+    hipError_t e = tavb::launch_scan_topk(p, s.g, c->stream, &c->last_tier);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "%s score pass launch failed: %s", what, hipGetErrorString(e));
+  }
+  t->scores = p.topk_scores;
+  t->workspace = c->d_topk.ptr;
+  t->n_pos = s.n_pos;
+  t->nq = n;
+  t->buckets = s.nb;
+  t->cap = s.cap;
+  t->rounds = s.rounds;
+  t->blocks = s.sel_blocks;
+  tm->emplace(c, TAVB_KERNEL_TOPK);
+  for (int r = 0; r < s.rounds; ++r) {
+    hipError_t e = tavb::launch_topk_refine(*t, r, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "%s refinement launch failed: %s", what, hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+}  // namespace
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+
+// ---- exact top-k beyond the fused selection (tavb_topk.hip): queries on the device (d_q [nq, dim]) over n_pos positions (d_rows: the
+// subset's rows, or null) -> out_keys [nq][k] sorted, zero-filled, + out_rounds [nq], both in pinned host memory.  Per group of the score
+// pass: the compaction and the finish -- nothing is read back before the caller's one synchronise.
+int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
+                     uint32_t index_base, u64_t* out_keys, int32_t* out_rounds) {
+  ScorePlan s;
+  if (int rc = plan_score_pass(c, nq, n_pos, /*refine=*/true, &s)) return rc;
+  if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)s.per, k, s.nb, s.cap, s.rounds))) return rc;
+  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
+    const int n = (int)std::min<int64_t>(s.per, nq - q0);
+    tavb::TopkLaunch t{};
+    t.k = k;
+    t.out_keys = out_keys + (size_t)q0 * k;
+    t.out_rounds = out_rounds + q0;
+    t.index_base = index_base;
+    std::optional<Timed> tm;
+    if (int rc = run_score_pass(c, s, "top-k", d_q, min_scores, d_rows, q0, n, &t, &tm)) return rc;
+    hipError_t e = tavb::launch_topk_compact(t, c->stream);
+    if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k selection launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+int check_topk_args(tavb_ctx* c, int k) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (k < 1 || k > TAVB_MAX_LARGE_K) return fail(TAVB_E_INVALID, "k must be 1 .. %d (got %d)", TAVB_MAX_LARGE_K, k);
+  return TAVB_OK;
+}
+
+// the pinned keys [nq][k] + rounds [nq] of a large-k lookup
+int reserve_topk_out(tavb_ctx* c, int nq, int k, u64_t** keys, int32_t** rounds) {
+  const size_t kbytes = (size_t)nq * k * sizeof(u64_t);
+  if (int rc = c->h_out.reserve(kbytes + (size_t)nq * sizeof(int32_t))) return rc;
+  *keys = reinterpret_cast<u64_t*>(c->h_out.ptr);
+  *rounds = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->h_out.ptr) + kbytes);
+  return TAVB_OK;
+}
+
+void note_rounds(tavb_ctx* c, const int32_t* rounds, int nq) {
+  int m = 0;
+  for (int q = 0; q < nq; ++q) m = std::max(m, (int)rounds[q]);
+  c->last_topk_refine = m;
+}
+
+// queries already on the device, keys to device (or device-writable pinned) memory, nothing waited for: the refinement rounds of the queries
+// land in the context's own pinned words and become "last_topk_refine" at the next tavb_synchronize
+int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const int32_t* d_rows, int64_t n_pos, uint32_t index_base,
+                      u64_t* out_keys) {
+  c->topk_rounds_pending = 0;
+  c->last_topk_refine = 0;
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (n_pos == 0 || c->rows == 0) return fill_empty_keys(c, out_keys, (int64_t)nq * k);  // nothing to scan
+  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, d_rows, n_pos, index_base, out_keys, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+}  // namespace host
+}  // namespace tavb
+
+extern "C" {
+
+int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores,
+                     int32_t* out_counts) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
+  if (c->rows == 0) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, 0u, keys, rounds)) return rc;
+  if (int rc = sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts)) return rc;
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int32_t k, float min_score,
+                            int64_t* out_positions, float* out_scores, int32_t* out_count) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
+  if (!query_host || !out_positions || !out_scores || !out_count) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  if (n_subset == 0 || c->rows == 0) {
+    *out_count = 0;
+    return TAVB_OK;
+  }
+  if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
+  if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  const int32_t* d_rows;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, 1, k, &keys, &rounds)) return rc;
+  if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
+  if (int rc = search_topk_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, 0u, keys, rounds)) return rc;
+  if (int rc = sync_decode(c, 1, k, 0, out_positions, out_scores, out_count)) return rc;
+  note_rounds(c, rounds, 1);
+  return TAVB_OK;
+}
+
+int tavb_search_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                            int64_t n_subset, tavb_key* out_keys) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  if (dev_rows && nq != 1) return fail(TAVB_E_INVALID, "a subset goes with exactly one query");
+  if (!dev_rows && n_subset != 0) return fail(TAVB_E_INVALID, "null dev_rows");
+  if (!dev_rows)
+    if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  return dev_rows ? search_topk_async(c, dev_queries, 1, k, min_scores, dev_rows, n_subset, 0u, reinterpret_cast<u64_t*>(out_keys))
+                  : search_topk_async(c, dev_queries, nq, k, min_scores, nullptr, c->rows, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
+}
+
+// ---- sorted lookups: every survivor (k = 0) or the best k for any k, sorted on the device.  Per group of the score pass (refined
+// only when k < n_pos): the per-block key counts -> pinned, ONE synchronise; the host checks max_total and then, query by query: compaction in position order, the sort, and the decode of the
+// best `need` keys into h_out, which is copied to the caller's arrays whenever the next piece would not fit sort_stage_keys.
+namespace {
+struct SortedOut {  // the caller's concatenated results and how far they are filled
+  int64_t* ords;
+  float* scs;
+  int64_t done = 0;    // results copied to the caller
+  int64_t staged = 0;  // results decoded into h_out, not yet copied
+};
+
+int flush_staged(tavb_ctx* c, SortedOut& o, int64_t cap) {
+  if (o.staged == 0) return TAVB_OK;
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  const char* base = reinterpret_cast<const char*>(c->h_out.ptr);
+  parallel_copy(o.ords + o.done, base, (size_t)o.staged * sizeof(int64_t));
+  parallel_copy(o.scs + o.done, base + (size_t)cap * sizeof(int64_t), (size_t)o.staged * sizeof(float));
+  o.done += o.staged;
+  o.staged = 0;
+  return TAVB_OK;
+}
+}  // namespace
+
+static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /*1 .. n_pos*/, const float* min_scores /*host, nq*/,
+                              const int32_t* d_rows, int64_t n_pos, int64_t base, int64_t max_total, int64_t* out_ords, float* out_scores,
+                              int64_t* out_counts, int64_t* out_total) {
+  ScorePlan s;
+  if (int rc = plan_score_pass(c, nq, n_pos, /*refine=*/k < n_pos, &s)) return rc;  // (k = n_pos: every survivor, nothing to refine)
+  const int nb = s.nb, rounds = s.rounds;
+  int64_t chunk;
+  const int cblocks = tavb::sorted_blocks(n_pos, &chunk);
+  const size_t head = tavb::topk_head_bytes((int)s.per, nb, rounds);
+  if (int rc = c->d_topk.reserve(head + (size_t)s.per * cblocks * sizeof(unsigned))) return rc;
+  if (int rc = c->h_sort_info.reserve((size_t)s.per * (4 + cblocks) * sizeof(int32_t))) return rc;
+  const int64_t stage = c->sort_stage_keys;
+  if (int rc = c->h_out.reserve((size_t)stage * (sizeof(int64_t) + sizeof(float)))) return rc;
+  SortedOut o{out_ords, out_scores};
+  int64_t total = 0;
+  int max_rounds = 0;
+  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
+    const int n = (int)std::min<int64_t>(s.per, nq - q0);
+    unsigned* d_counts = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(c->d_topk.ptr) + head);
+    tavb::TopkLaunch t{};
+    t.k = (int32_t)k;
+    {
+      std::optional<Timed> tm;
+      if (int rc = run_score_pass(c, s, "sorted", d_q, min_scores, d_rows, q0, n, &t, &tm)) return rc;
+      hipError_t e = tavb::launch_sorted_count(t, d_counts, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted count launch failed: %s", hipGetErrorString(e));
+    }
+    int32_t* meta = reinterpret_cast<int32_t*>(c->h_sort_info.ptr);
+    unsigned* counts = reinterpret_cast<unsigned*>(meta + (size_t)n * 4);
+    TAVB_HIP(hipMemcpyAsync(meta, reinterpret_cast<char*>(c->d_topk.ptr) + tavb::topk_meta_offset(n, nb, rounds), (size_t)n * 4 * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, c->stream));
+    TAVB_HIP(hipMemcpyAsync(counts, d_counts, (size_t)n * cblocks * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    TAVB_HIP(hipStreamSynchronize(c->stream));
+    int64_t group_total = 0, most = 0;
+    for (int q = 0; q < n; ++q) {
+      int64_t kept = 0;
+      for (int b = 0; b < cblocks; ++b) kept += counts[(size_t)q * cblocks + b];
+      group_total += meta[q * 4 + 0];
+      most = std::max(most, kept);
+      max_rounds = std::max(max_rounds, (int)meta[q * 4 + 1]);
+    }
+    if (total + group_total > max_total)
+      return fail(TAVB_E_INVALID, "the lookup has more than max_total = %lld results (%lld so far)", (long long)max_total,
+                  (long long)(total + group_total));
+    if (most > 0) {
+      if (int rc = c->d_sort_keys.reserve((size_t)most * sizeof(u64_t))) return rc;
+      if (int rc = c->d_sort_ws.reserve(tavb::sort_workspace_bytes(most))) return rc;
+    }
+    for (int q = 0; q < n; ++q) {
+      const int64_t need = meta[q * 4 + 0];
+      out_counts[q0 + q] = need;
+      if (need == 0) continue;
+      int64_t kept = 0;
+      for (int b = 0; b < cblocks; ++b) kept += counts[(size_t)q * cblocks + b];
+      if (kept < need) return fail(TAVB_E_HIP, "sorted lookup: %lld keys kept for %lld results (internal error)", (long long)kept, (long long)need);
+      tavb::SortJob j{reinterpret_cast<u64_t*>(c->d_sort_keys.ptr), kept, 4, c->d_sort_ws.ptr, (int)c->sort_small_keys, false};
+      {
+        Timed tm(c, TAVB_KERNEL_TOPK);
+        hipError_t e = tavb::launch_sorted_compact(t, q, d_counts, j.keys, c->stream);
+        if (e == hipSuccess) e = tavb::launch_sort_desc(j, c->stream);
+        if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted compaction / sort launch failed: %s", hipGetErrorString(e));
+      }
+      for (int64_t off = 0; off < need;) {
+        if (o.staged == stage) {
+          if (int rc = flush_staged(c, o, stage)) return rc;
+        }
+        const int64_t len = std::min(need - off, stage - o.staged);
+        char* hb = reinterpret_cast<char*>(c->h_out.ptr);
+        Timed tm(c, TAVB_KERNEL_TOPK);
+        hipError_t e = tavb::launch_sort_decode(j, off, len, base, reinterpret_cast<int64_t*>(hb) + o.staged,
+                                                reinterpret_cast<float*>(hb + (size_t)stage * sizeof(int64_t)) + o.staged, c->stream);
+        if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted decode launch failed: %s", hipGetErrorString(e));
+        o.staged += len;
+        off += len;
+      }
+    }
+    total += group_total;
+  }
+  if (int rc = flush_staged(c, o, stage)) return rc;
+  c->last_topk_refine = max_rounds;
+  *out_total = total;
+  return TAVB_OK;
+}
+
+static int check_sorted_args(tavb_ctx* c, int64_t k, int64_t max_total, const void* out_total) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (k < 0) return fail(TAVB_E_INVALID, "k must be >= 0 (0 = every survivor)");
+  if (max_total < 0) return fail(TAVB_E_INVALID, "max_total must be >= 0");
+  if (!out_total) return fail(TAVB_E_INVALID, "null argument");
+  return TAVB_OK;
+}
+
+int tavb_search_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, int64_t k, const float* min_scores, int64_t max_total, int64_t* out_ordinals,
+                       float* out_scores, int64_t* out_counts, int64_t* out_total) {
+  if (int rc = check_sorted_args(c, k, max_total, out_total)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  *out_total = 0;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+  if (c->rows == 0) return TAVB_OK;
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  const int64_t kk = (k == 0 || k > c->rows) ? c->rows : k;
+  return search_sorted_impl(c, d_q, nq, kk, min_scores, nullptr, c->rows, c->ordinal_base, max_total, out_ordinals, out_scores, out_counts, out_total);
+}
+
+int tavb_search_subset_sorted(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int64_t k, float min_score,
+                              int64_t max_total, int64_t* out_positions, float* out_scores, int64_t* out_count) {
+  if (int rc = check_sorted_args(c, k, max_total, out_count)) return rc;
+  if (n_subset < 0) return fail(TAVB_E_INVALID, "n_subset must be >= 0");
+  *out_count = 0;
+  if (!query_host || (max_total > 0 && (!out_positions || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  if (n_subset == 0 || c->rows == 0) return TAVB_OK;
+  if (!rows_host) return fail(TAVB_E_INVALID, "null rows_host");
+  if (n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "subset too long");
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  const int32_t* d_rows;
+  if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
+  const int64_t kk = (k == 0 || k > n_subset) ? n_subset : k;
+  int64_t count = 0;
+  return search_sorted_impl(c, d_q, 1, kk, &min_score, d_rows, n_subset, 0, max_total, out_positions, out_scores, &count, out_count);
+}
+
+int tavb_sort_keys_device(tavb_ctx* c, tavb_key* dev_keys, int64_t n) {
+  if (int rc = check_ctx(c)) return rc;
+  if (n < 0 || n >= ((int64_t)1 << 32)) return fail(TAVB_E_INVALID, "n must be 0 .. 2^32 - 1");
+  if (n == 0) return TAVB_OK;
+  if (!dev_keys) return fail(TAVB_E_INVALID, "null dev_keys");
+  DeviceGuard guard(c->device);
+  if (int rc = c->d_sort_ws.reserve(tavb::sort_workspace_bytes(n))) return rc;
+  tavb::SortJob j{reinterpret_cast<u64_t*>(dev_keys), n, 0, c->d_sort_ws.ptr, (int)c->sort_small_keys, false};
+  {
+    Timed tm(c, TAVB_KERNEL_TOPK);
+    hipError_t e = tavb::launch_sort_desc(j, c->stream);
+    if (e == hipSuccess) e = tavb::launch_sort_copy_back(j, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "sort launch failed: %s", hipGetErrorString(e));
+  }
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  return TAVB_OK;
+}
+
+}  // extern "C"

@@ -408,6 +408,13 @@ float floor_of_min_score(float ms) {
   return f;
 }
 
+// every query of the batch has the same threshold, bit for bit (a batch of NaNs is uniform)
+bool uniform_min_scores(const float* min_scores, int nq) {
+  for (int i = 1; i < nq; ++i)
+    if (memcmp(&min_scores[i], &min_scores[0], sizeof(float)) != 0) return false;
+  return true;
+}
+
 // min_scores (host, [nq]) -> c->d_minscores: [nq_pad] the thresholds themselves (padding: +inf), then [nq_pad] the exclusive admission floors
 // that go with them (+inf for NaN / > 1 / padding).  A mixed batch is copied from pageable memory (staged by the runtime before the call
 // returns).  A uniform one -- every caller of the reference -- needs no host buffer in flight (the device-resident forms stay asynchronous):
@@ -416,8 +423,7 @@ int upload_min_scores(tavb_ctx* c, const float* min_scores, int nq, int nq_pad, 
   if (int rc = c->d_minscores.reserve((size_t)2 * nq_pad * sizeof(float))) return rc;
   float* d_ms = reinterpret_cast<float*>(c->d_minscores.ptr);
   float* d_floor = d_ms + nq_pad;
-  bool uniform = true;
-  for (int i = 1; i < nq; ++i) uniform = uniform && (memcmp(&min_scores[i], &min_scores[0], sizeof(float)) == 0);
+  const bool uniform = uniform_min_scores(min_scores, nq);
   if (!uniform) {
     std::vector<float> h((size_t)2 * nq_pad, INFINITY);
     for (int i = 0; i < nq; ++i) {
@@ -441,6 +447,37 @@ int upload_min_scores(tavb_ctx* c, const float* min_scores, int nq, int nq_pad, 
 // `mw` (fp16 corpora, not `small`): a MASKED batch -- the filter pass runs over the mask's span with the bit test in its admission path (the corpus
 // max-norm bound stays valid for any subset of the rows), the rescoring as ever; neither exact fallback has a masked form, so there is no early
 // verdict, and the flagged queries -- read back, one round trip -- are re-run on the gather route over the mask's resident row list.
+// The flagged queries of search_wide_exact's work list (d_nflag: their count, from slot 64 on their indices; `cap` slots), read back -- the one
+// host round trip of this file -- and re-run on the streaming kernels, their lists scattered back into the callers' rows of d_out.  fq32: where
+// their fp32 queries stand side by side -- `gathered`: already (gather_flagged_f32_kernel), else copied there from d_q here.  rows / n_rows:
+// the row list the re-run goes over, its positions then remapped to index_base + row; null: the whole corpus, keys carrying index_base.
+int rerun_flagged(tavb_ctx* c, const int* d_nflag, int cap, const float* d_q, float* fq32, bool gathered, int k, const float* min_scores /*host*/,
+                  const int32_t* rows, int64_t n_rows, uint32_t index_base, u64_t* d_out) {
+  int* h = reinterpret_cast<int*>(c->h_flag.ptr);
+  TAVB_HIP(hipMemcpyAsync(h, d_nflag, (size_t)(64 + cap) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  const int n_flagged = h[0] < cap ? h[0] : cap;
+  if (n_flagged == 0) return TAVB_OK;
+  std::vector<float> ms_f((size_t)n_flagged);
+  for (int i = 0; i < n_flagged; ++i) {
+    ms_f[i] = min_scores[h[64 + i]];
+    if (!gathered)
+      TAVB_HIP(hipMemcpyAsync(fq32 + (size_t)i * c->dim, d_q + (size_t)h[64 + i] * c->dim, (size_t)c->dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  }
+  u64_t* d_redo = reinterpret_cast<u64_t*>(c->d_fb_cand.ptr);
+  const int tier = c->last_tier;  // (the batch's route stays what "last_tier" reports: the re-run is a detail of it)
+  const int rc_redo = search_device_impl(c, fq32, n_flagged, k, ms_f.data(), rows, rows ? n_rows : c->rows, rows ? 0u : index_base, d_redo);
+  c->last_tier = tier;
+  if (rc_redo) return rc_redo;
+  if (rows) {
+    const hipError_t e = tavb::launch_remap_positions(d_redo, d_redo, (int64_t)n_flagged * k, rows, n_rows, index_base, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  }
+  for (int i = 0; i < n_flagged; ++i)
+    TAVB_HIP(hipMemcpyAsync(d_out + (size_t)h[64 + i] * k, d_redo + (size_t)i * k, (size_t)k * sizeof(u64_t), hipMemcpyDefault, c->stream));
+  return TAVB_OK;
+}
+
 struct MaskedWide {
   const uint32_t* bits;           // the mask over the corpus rows
   int64_t span_begin, span_end;   // rows [span_begin, span_end) hold every set bit; span_begin a multiple of 256
@@ -605,48 +642,10 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
                                              wide_fallback ? fb_band : nullptr, kExactBand, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
   }
-  if (mw) {
-    int* h = reinterpret_cast<int*>(c->h_flag.ptr);
-    TAVB_HIP(hipMemcpyAsync(h, d_nflag, (size_t)(64 + cap) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    TAVB_HIP(hipStreamSynchronize(c->stream));
-    const int n_flagged = h[0] < cap ? h[0] : cap;
-    if (n_flagged > 0) {  // their fp32 queries side by side in fb (cap x fdim x 4 bytes and more), their lists by position, then as index_base + row
-      std::vector<float> ms_f((size_t)n_flagged);
-      float* fq32 = reinterpret_cast<float*>(fb);
-      for (int i = 0; i < n_flagged; ++i) {
-        ms_f[i] = min_scores[h[64 + i]];
-        TAVB_HIP(hipMemcpyAsync(fq32 + (size_t)i * c->dim, d_q + (size_t)h[64 + i] * c->dim, (size_t)c->dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      }
-      u64_t* d_redo = reinterpret_cast<u64_t*>(c->d_fb_cand.ptr);
-      const int tier = c->last_tier;  // (the batch's route stays what "last_tier" reports: the re-run is a detail of it)
-      const int rc_redo = search_device_impl(c, fq32, n_flagged, k, ms_f.data(), mw->dev_rows, mw->n_allowed, 0u, d_redo);
-      c->last_tier = tier;
-      if (rc_redo) return rc_redo;
-      const hipError_t e = tavb::launch_remap_positions(d_redo, d_redo, (int64_t)n_flagged * k, mw->dev_rows, mw->n_allowed, index_base, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
-      for (int i = 0; i < n_flagged; ++i)
-        TAVB_HIP(hipMemcpyAsync(d_out + (size_t)h[64 + i] * k, d_redo + (size_t)i * k, (size_t)k * sizeof(u64_t), hipMemcpyDefault, c->stream));
-    }
-    return TAVB_OK;
-  }
-  if (f32_big_k) {
-    int* h = reinterpret_cast<int*>(c->h_flag.ptr);
-    TAVB_HIP(hipMemcpyAsync(h, d_nflag, (size_t)(64 + cap) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    TAVB_HIP(hipStreamSynchronize(c->stream));
-    const int n_flagged = h[0] < cap ? h[0] : cap;
-    if (n_flagged > 0) {  // (gather_flagged_f32_kernel has put their fp32 queries into fb[0 .. n_flagged))
-      std::vector<float> ms_f((size_t)n_flagged);
-      for (int i = 0; i < n_flagged; ++i) ms_f[i] = min_scores[h[64 + i]];
-      u64_t* d_redo = reinterpret_cast<u64_t*>(c->d_fb_cand.ptr);
-      const int tier = c->last_tier;  // (the batch's route stays what "last_tier" reports: the re-run is a detail of it)
-      const int rc_redo = search_device_impl(c, reinterpret_cast<const float*>(fb), n_flagged, k, ms_f.data(), nullptr, c->rows, index_base, d_redo);
-      c->last_tier = tier;
-      if (rc_redo) return rc_redo;
-      for (int i = 0; i < n_flagged; ++i)
-        TAVB_HIP(hipMemcpyAsync(d_out + (size_t)h[64 + i] * k, d_redo + (size_t)i * k, (size_t)k * sizeof(u64_t), hipMemcpyDefault, c->stream));
-    }
-    return TAVB_OK;
-  }
+  if (mw)  // their fp32 queries side by side in fb (cap x fdim x 4 bytes and more), their lists by position, then as index_base + row
+    return rerun_flagged(c, d_nflag, cap, d_q, reinterpret_cast<float*>(fb), /*gathered=*/false, k, min_scores, mw->dev_rows, mw->n_allowed, index_base, d_out);
+  if (f32_big_k)  // (gather_flagged_f32_kernel has put their fp32 queries into fb)
+    return rerun_flagged(c, d_nflag, cap, d_q, reinterpret_cast<float*>(fb), /*gathered=*/true, k, min_scores, nullptr, 0, index_base, d_out);
   {  // (run_tile_ladder times its own launches, in the same bucket)
     if (!big_k) {
       // the exact tile over the work list: returns at once when the list is empty (the normal case).  It ranks 64 rows per slot whatever k: the
@@ -707,6 +706,59 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   return TAVB_OK;
 }
 
+// A batch on the 32/64-query tile over the corpus' own rows (no shadow): fp32 queries on an fp32 corpus, split into an fp16 high and low plane
+// on an fp16 one; per-query thresholds ride as exclusive admission floors valid from the first row on.  mask (optional): the allow-mask
+// over the corpus rows, whose set bits all lie in [span_begin, span_end), span_begin a multiple of 256 -- the phases run over the span with
+// the bit test in the tile's admission path.  Scores are final -> sorted key lists d_out [nq, k] (async on the stream).
+int run_skinny_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, uint32_t index_base, u64_t* d_out,
+                    const uint32_t* mask = nullptr, int64_t span_begin = 0, int64_t span_end = 0) {
+  const bool q32 = c->dtype != TAVB_F16;
+  const int qt = tavb::skinny_query_tile(nq);
+  const int nq_pad = ((nq + qt - 1) / qt) * qt;
+  const size_t plane = (size_t)nq_pad * c->dim * (q32 ? 4 : 2);
+  const size_t qbytes = plane * (q32 ? 1 : 2);
+  if (int rc = c->d_queries_f16.reserve(qbytes)) return rc;
+  const bool uniform_thr = uniform_min_scores(min_scores, nq);
+  float *d_ms = nullptr, *d_ms_floor = nullptr;
+  if (!uniform_thr) {
+    bool uni = false;
+    if (int rc = upload_min_scores(c, min_scores, nq, nq_pad, &d_ms, &d_ms_floor, &uni)) return rc;
+  }
+  TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, qbytes, c->stream));
+  if (q32) {
+    TAVB_HIP(hipMemcpyAsync(c->d_queries_f16.ptr, d_q, (size_t)nq * c->dim * 4, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    hipError_t e = tavb::launch_f32_split_f16(d_q, c->d_queries_f16.ptr, reinterpret_cast<char*>(c->d_queries_f16.ptr) + plane, (int64_t)nq * c->dim, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "query split launch failed: %s", hipGetErrorString(e));
+  }
+  c->last_tier = 5;
+  TileRun r{};
+  r.skinny = true;
+  r.q32 = q32;
+  r.qt = qt;
+  r.nq = nq;
+  r.nq_pad = nq_pad;
+  r.k = k;
+  r.index_base = index_base;
+  r.kernel_min_score = uniform_thr ? min_scores[0] : lowest_min_score(min_scores, nq);
+  r.floor = d_ms_floor;
+  r.queries = c->d_queries_f16.ptr;
+  r.ladder = true;
+  r.mask = mask;
+  r.span_begin = span_begin;
+  r.span_end = span_end;
+  return run_tile_ladder(c, r, d_out, nullptr);
+}
+
+// Room for the wide filter's fp16 operand, d_shadow: the fp16 copy of an fp32 corpus, or the zero-padded copy of rows whose width is not a
+// multiple of 64 -- every row, search_wide_exact fills it in from norm_rows on.
+int reserve_shadow(tavb_ctx* c) {
+  const size_t need = (size_t)c->rows * (((size_t)c->dim + 63) / 64 * 64) * 2;
+  if (c->d_shadow.cap >= need) return TAVB_OK;
+  c->norm_rows = 0;  // reserve() does not keep the old contents
+  return c->d_shadow.reserve(need);
+}
+
 }  // namespace
 
 // Routes a device-resident query batch: streaming scan (few queries), 32/64-query tile (small batches; every batch on
@@ -715,8 +767,6 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
 // vectorbase.py:163-173), so a mixed batch takes the same route as a uniform one.
 int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores,
                                 uint32_t index_base, u64_t* d_out) {
-  bool uniform_thr = true;
-  for (int i = 1; i < nq; ++i) uniform_thr = uniform_thr && (memcmp(&min_scores[i], &min_scores[0], sizeof(float)) == 0);
   const bool f16c = (c->dtype == TAVB_F16);
   c->last_direct = 0;
   {  // small corpora, 2 .. 128 queries: the grouped streaming scan + one merge where it beats the tiles (plan_direct_group)
@@ -759,13 +809,8 @@ int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, co
   // (it keeps the best 64 candidates per query: k up to 48 leaves the slack the completeness test needs)
   bool shadow_small = !wide && !f16c && c->f32_shadow >= 2 && c->corpus && nq <= 64 && tavb::mfma_supported(c->dim, 64) && k <= 48 &&
                       tavb::skinny_supported(c->dim, k, false) && (int64_t)c->rows * c->dim * 4 >= c->f32_shadow_min_bytes;
-  if ((wide || shadow_small) && (!f16c || odd_width)) {  // the filter needs the fp16 shadow / padded copy; without the memory for it the other kernels serve the batch
-    const size_t need = (size_t)c->rows * wide_dim * 2;
-    if (c->d_shadow.cap < need) {
-      c->norm_rows = 0;  // reserve() does not keep the old contents
-      if (c->d_shadow.reserve(need) != TAVB_OK) wide = shadow_small = false;
-    }
-  }
+  if ((wide || shadow_small) && (!f16c || odd_width))  // the filter needs the fp16 shadow / padded copy; without the memory for it the other kernels serve the batch
+    if (reserve_shadow(c) != TAVB_OK) wide = shadow_small = false;
   c->last_shadow = 0;
   if (shadow_small) {
     c->last_tier = 5;
@@ -779,97 +824,22 @@ int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, co
     c->last_tier = 4;  // 1-3 = streaming tiers, 4 = 256-query MFMA tile, 5 = 32/64-query MFMA tile
     return search_wide_exact(c, d_q, nq, k, min_scores, index_base, d_out);
   }
-  if (skinny) {
-    const int qt = tavb::skinny_query_tile(nq);
-    const int nq_pad = ((nq + qt - 1) / qt) * qt;
-    const bool q32 = !f16c;  // on an fp32 corpus the tile multiplies fp32 queries, on an fp16 one fp32 queries split into fp16 high + low planes
-    const size_t plane = (size_t)nq_pad * c->dim * (q32 ? 4 : 2);
-    const size_t qbytes = plane * (q32 ? 1 : 2);
-    if (int rc = c->d_queries_f16.reserve(qbytes)) return rc;
-    float *d_ms = nullptr, *d_ms_floor = nullptr;
-    if (!uniform_thr) {  // per-query thresholds: exclusive admission floors valid from the first row on
-      bool uni = false;
-      if (int rc = upload_min_scores(c, min_scores, nq, nq_pad, &d_ms, &d_ms_floor, &uni)) return rc;
-    }
-    TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, qbytes, c->stream));
-    if (q32) {
-      TAVB_HIP(hipMemcpyAsync(c->d_queries_f16.ptr, d_q, (size_t)nq * c->dim * 4, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-      hipError_t e = tavb::launch_f32_split_f16(d_q, c->d_queries_f16.ptr, reinterpret_cast<char*>(c->d_queries_f16.ptr) + plane,
-                                                (int64_t)nq * c->dim, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "query split launch failed: %s", hipGetErrorString(e));
-    }
-    c->last_tier = 5;
-    TileRun r{};
-    r.skinny = true;
-    r.q32 = q32;
-    r.qt = qt;
-    r.nq = nq;
-    r.nq_pad = nq_pad;
-    r.k = k;
-    r.index_base = index_base;
-    r.kernel_min_score = uniform_thr ? min_scores[0] : lowest_min_score(min_scores, nq);
-    r.floor = d_ms_floor;
-    r.queries = c->d_queries_f16.ptr;
-    r.ladder = true;
-    return run_tile_ladder(c, r, d_out, nullptr);
-  }
+  if (skinny) return run_skinny_tile(c, d_q, nq, k, min_scores, index_base, d_out);  // (last_tier = 5)
   return search_device_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, index_base, d_out);
 }
 
-// Masked batch on the 32/64-query tile (tavb_search_masked_batch / tavb_search_masked_device; the callers have checked the arguments and that
-// skinny_supported holds): the queries as the unmasked tile route takes them -- fp32 on an fp32 corpus, split into an fp16 high and low plane on
-// an fp16 one, the corpus' own rows, no shadow -- over the span of the mask, the bit test in the tile's admission path.  Scores are final.
 namespace tavb {
 namespace host __attribute__((visibility("hidden"))) {
+// Masked batch on the 32/64-query tile (tavb_search_masked_batch / tavb_search_masked_device; the callers have checked the arguments and that
+// skinny_supported holds): run_skinny_tile over the span of the mask.
 int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* dev_bits, int64_t first_row, int64_t last_row,
                        uint32_t index_base, u64_t* d_out) {
-  const bool q32 = c->dtype != TAVB_F16;
-  const int qt = tavb::skinny_query_tile(nq);
-  const int nq_pad = ((nq + qt - 1) / qt) * qt;
-  const size_t plane = (size_t)nq_pad * c->dim * (q32 ? 4 : 2);
-  const size_t qbytes = plane * (q32 ? 1 : 2);
-  if (int rc = c->d_queries_f16.reserve(qbytes)) return rc;
-  bool uniform_thr = true;
-  for (int i = 1; i < nq; ++i) uniform_thr = uniform_thr && (memcmp(&min_scores[i], &min_scores[0], sizeof(float)) == 0);
-  float *d_ms = nullptr, *d_ms_floor = nullptr;
-  if (!uniform_thr) {
-    bool uni = false;
-    if (int rc = upload_min_scores(c, min_scores, nq, nq_pad, &d_ms, &d_ms_floor, &uni)) return rc;
-  }
-  TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, qbytes, c->stream));
-  if (q32) {
-    TAVB_HIP(hipMemcpyAsync(c->d_queries_f16.ptr, d_q, (size_t)nq * c->dim * 4, hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    hipError_t e = tavb::launch_f32_split_f16(d_q, c->d_queries_f16.ptr, reinterpret_cast<char*>(c->d_queries_f16.ptr) + plane, (int64_t)nq * c->dim, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "query split launch failed: %s", hipGetErrorString(e));
-  }
-  c->last_tier = 5;
   c->last_shadow = 0;
   c->last_direct = 0;
   c->masked_route = 2;
-  TileRun r{};
-  r.skinny = true;
-  r.q32 = q32;
-  r.qt = qt;
-  r.nq = nq;
-  r.nq_pad = nq_pad;
-  r.k = k;
-  r.index_base = index_base;
-  r.kernel_min_score = uniform_thr ? min_scores[0] : lowest_min_score(min_scores, nq);
-  r.floor = d_ms_floor;
-  r.queries = c->d_queries_f16.ptr;
-  r.ladder = true;
-  r.mask = dev_bits;
-  r.span_begin = first_row / 256 * 256;
-  r.span_end = last_row + 1;
-  return run_tile_ladder(c, r, d_out, nullptr);
+  return run_skinny_tile(c, d_q, nq, k, min_scores, index_base, d_out, dev_bits, first_row / 256 * 256, last_row + 1);
 }
-}  // namespace host
-}  // namespace tavb
 
-namespace tavb {
-namespace host __attribute__((visibility("hidden"))) {
 // fp16 corpora of any width (one that is no multiple of 64 filters on the zero-padded copy of the rows, as the unmasked route does), every k the
 // filter's band and the rescoring serve
 bool masked_wide_supported(const tavb_ctx* c, int k) {
@@ -878,13 +848,8 @@ bool masked_wide_supported(const tavb_ctx* c, int k) {
 
 int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* dev_bits, int64_t first_row, int64_t last_row,
                        const int32_t* dev_rows, int64_t n_allowed, uint32_t index_base, u64_t* d_out) {
-  if (c->dim % 64 != 0) {  // the filter reads the padded copy (search_wide_exact fills it in; the unmasked dispatcher reserves it the same way)
-    const size_t need = (size_t)c->rows * (((size_t)c->dim + 63) / 64 * 64) * 2;
-    if (c->d_shadow.cap < need) {
-      c->norm_rows = 0;  // reserve() does not keep the old contents
-      if (int rc = c->d_shadow.reserve(need)) return rc;
-    }
-  }
+  if (c->dim % 64 != 0)  // the filter reads the padded copy (search_wide_exact fills it in; the unmasked dispatcher reserves it the same way)
+    if (int rc = reserve_shadow(c)) return rc;
   c->last_tier = 4;
   c->last_direct = 0;
   c->masked_route = 3;
