@@ -453,6 +453,41 @@ int tavb_search_masked_wide_device(tavb_ctx* ctx, const float* dev_queries, int3
                                    int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores /*host*/,
                                    tavb_key* out_keys);
 
+/* ---- scoped message lookups: a scope of MESSAGE ordinals searched as a row mask, batches of queries aggregated to messages ----------------
+ * tavb_mask_from_messages: the row mask of a set of messages, built on the device from the context's row -> message map
+ * (tavb_set_row_messages) -- the scope never becomes a host row list.  accept_msgs_host [n_accept] (n_accept >= 0): the accepted message
+ * ordinals; duplicates are harmless, ordinals below 0 or at or beyond n_messages are ignored.  dev_bits_out [(rows + 31) / 32] words in the bit
+ * form above, rows == the corpus' rows: row r is set when 0 <= map[r] < n_messages and message map[r] is accepted -- rows mapped to -1 are
+ * never allowed -- and the bits at or beyond `rows` in the last word are ZERO (whole words compare equal to a host-packed mask).  Fails as
+ * tavb_search_messages does without a map (TAVB_E_NO_CORPUS) or with a map shorter than the corpus (TAVB_E_INVALID).  The accepted ordinals
+ * are copied to the device and turned into the accept bitmap there, then ONE launch (a wave takes 64 rows, its ballot is two words; no
+ * atomics on the mask) writes the words.  Asynchronous on the context's stream; the result feeds tavb_mask_expand and the masked lookups.
+ * Timed under TAVB_KERNEL_CONVERT.
+ *
+ * tavb_search_messages_masked: nq queries over the rows a mask names, aggregated to messages, in ONE submission: the masked batch on the
+ * route the caller names -- route 1 = the row list (dev_rows / n_allowed: tavb_search_subset_batch_resident's passes), 2 = the 32/64-query
+ * tile (tavb_search_masked_batch's; dev_rows may be NULL), 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide's) --
+ * leaves [nq, k] key lists carrying ordinal_base + row on the device; one launch of the message re-rank with nq workgroups turns each into
+ * the accepted first occurrence of every message in hit order, cut at max_messages (rows without a message are skipped); one device-to-host
+ * copy brings the [nq, k] message keys back.  Per query this is tavb_search_messages_subset over the mask's rows: bit for bit on routes 1
+ * and 3, and on route 2 up to what the 32/64-query tile differs from the streaming kernels by (float32 near-ties, scores within 1e-5).
+ * 1 <= k <= TAVB_MAX_FUSED_K.  The arguments of the route are checked as that route's own entry point checks them, and a shape it does
+ * not serve returns TAVB_E_UNSUPPORTED: the caller (the binding's planners, tavb_plan_masked / tavb_plan_masked_wide) picks another.
+ * min_scores: nq thresholds on the host.  out_messages / out_scores [nq, k], out_counts [nq].  "masked_route" reports the route.  The
+ * re-rank is timed under TAVB_KERNEL_MERGE.
+ *
+ * tavb_search_messages_batch: tavb_search_messages for nq queries in one submission: the full-corpus top-k of every query by the route any
+ * device-resident batch takes, THEN the optional accept filter (n_accept = -1: none; >= 0: that set, as tavb_search_messages), THEN the
+ * re-rank of all nq lists in one launch, one copy back.  Per query it equals tavb_search_messages wherever the batch route is bit-exact
+ * against the streaming kernels (the grouped streaming scan, the wide tile + rescoring); on the 32/64-query tile up to near-ties. */
+int tavb_mask_from_messages(tavb_ctx* ctx, const int32_t* accept_msgs_host, int64_t n_accept, int64_t rows, uint32_t* dev_bits_out);
+int tavb_search_messages_masked(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row,
+                                int64_t last_row, const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores,
+                                int32_t max_messages, int32_t route, int64_t* out_messages, float* out_scores, int32_t* out_counts);
+int tavb_search_messages_batch(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores,
+                               const int32_t* accept_msgs_host, int64_t n_accept, int32_t max_messages, int64_t* out_messages, float* out_scores,
+                               int32_t* out_counts);
+
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */
 int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k,

@@ -87,6 +87,10 @@ _SIGNATURES = [
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_masked_wide_device", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_mask_from_messages", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    ("tavb_search_messages_masked", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_messages_batch", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -853,6 +857,55 @@ class Engine:
         _check(self.lib, rc)
         m = int(cnt.value)
         return msgs[:m], scs[:m]
+
+    # scoped and batched message lookups ------------------------------------------
+    def mask_from_messages(self, accept):
+        """A scope of MESSAGE ordinals (int array; ordinals outside the map's range are ignored, duplicates are harmless) -> (torch int32
+        [count] on the device: the rows of those messages in ascending order; count; the packed mask, torch int32 [(rows + 31) // 32], tail
+        bits zero) -- the triple of `mask_to_rows_bits`, built from the row -> message map on the device (tavb_mask_from_messages, then
+        tavb_mask_expand): only the ordinals travel, no row list is made on the host.  Needs `set_row_messages`."""
+        torch = self._torch
+        acc = np.ascontiguousarray(accept, dtype=np.int32).reshape(-1)
+        rows = int(self.rows)
+        bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+        with self._lock:
+            rc = self.lib.tavb_mask_from_messages(self._h, _addr(acc) if acc.size else None, int(acc.size), rows, c_void_p(bits.data_ptr()) if rows else None)
+        _check(self.lib, rc)
+        return (*self.expand_mask_bits(bits, rows), bits)  # (same stream: nothing to wait for)
+
+    def _message_batch_out(self, queries, k: int, thrs):
+        a = np.ascontiguousarray(queries, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}]")
+        nq = a.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        return a, nq, t, np.empty((nq, k), dtype=np.int64), np.empty((nq, k), dtype=np.float32), np.zeros(nq, dtype=np.int32)
+
+    def search_messages_masked(self, queries, dev_bits, dev_rows, k: int, thrs, max_messages: int, route: int, span=None):
+        """A masked batch aggregated to messages in one submission (tavb_search_messages_masked): the arguments of `search_masked_wide`
+        plus `route` -- 1 = the row list, 2 = the 32/64-query tile, 3 = the 128/256-query filter tile + rescoring; TavbError
+        (TAVB_E_UNSUPPORTED) for a shape the route does not serve -- and max_messages; 1 <= k <= 256 -> (message ordinals [nq, k], scores
+        [nq, k], counts [nq]).  Per query: `search_messages(q, k, thr, max_messages, subset_rows=the mask's rows)`."""
+        a, nq, t, msgs, scs, cnts = self._message_batch_out(queries, k, thrs)
+        bits, first, last = self._masked_args(dev_bits, span)
+        rows_ptr, n_allowed = (None, 0) if dev_rows is None else self._masked_wide_rows(dev_rows)
+        with self._lock:
+            rc = self.lib.tavb_search_messages_masked(self._h, _addr(a), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k, _addr(t),
+                                                      int(max_messages), int(route), _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def search_messages_batch(self, queries, k: int, thrs, max_messages: int, accept=None):
+        """`search_messages` for a batch in one submission (tavb_search_messages_batch): queries f32 [nq, dim]; thrs float32 [nq] (or one
+        for all); accept as there -> (message ordinals [nq, k], scores [nq, k], counts [nq])."""
+        a, nq, t, msgs, scs, cnts = self._message_batch_out(queries, k, thrs)
+        acc = None if accept is None else np.ascontiguousarray(accept, dtype=np.int32)
+        with self._lock:
+            rc = self.lib.tavb_search_messages_batch(self._h, _addr(a), nq, k, _addr(t), _addr(acc) if acc is not None and acc.size else None,
+                                                     -1 if acc is None else acc.shape[0], int(max_messages), _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
 
     # split form (several contexts driven from one thread) --------------------
     def search_begin(self, queries: np.ndarray, k: int, thrs: np.ndarray, cursor_key: int | None = None) -> None:

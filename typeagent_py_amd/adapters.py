@@ -21,7 +21,7 @@ from collections.abc import Callable, Sequence
 
 import numpy as np
 
-from .vectorbase import ScoredInt, VectorBase
+from .vectorbase import RowMask, ScoredInt, VectorBase
 
 
 async def lookup_texts_batched(
@@ -165,6 +165,34 @@ def lookup_messages_in_subset(
         return out if max_matches is None else out[:max_matches]
     hits = vector_base.fuzzy_lookup_embedding_in_subset(embedding, list(rows_of_subset), max_hits=max_matches, min_score=threshold_score)
     return best_score_per_message(hits, row_to_message, max_matches)
+
+
+def lookup_messages_in_scope(
+    vector_base: VectorBase,
+    embedding_or_embeddings,
+    row_to_message,
+    scope,
+    max_matches: int | None = None,
+    threshold_score: float | None = None,
+):
+    """A scoped message lookup as the providers mean it -- search only the chunks of the messages in `scope` (a collection of MESSAGE
+    ordinals, or the `RowMask` an earlier call of `vector_base.message_mask(scope)` returned: a scope that serves several questions is
+    expanded once), best score per message, the cut of `lookup_messages_in_subset` -- without the host row list that function is handed:
+    the scope becomes a row mask on the device (`VectorBase.message_mask`) and the lookup is `lookup_messages_by_embeddings_masked`.  A 1-D
+    embedding returns one list of ScoredInt(message, score); a 2-D array of embeddings a list of such lists, served by ONE device
+    submission.  `row_to_message`: the array of message ordinals per index position (-1: none); a callable is not supported here."""
+    if callable(row_to_message):
+        raise TypeError("lookup_messages_in_scope needs row_to_message as a sequence (the map is searched on the device)")
+    _ensure_row_messages(vector_base, row_to_message)
+    mask = scope if isinstance(scope, RowMask) else vector_base.message_mask(scope)
+    queries = np.asarray(embedding_or_embeddings, dtype=np.float32)
+    if queries.ndim == 1:
+        out = vector_base.lookup_messages_by_embedding_masked(queries, mask, max_matches, threshold_score)
+        return out if max_matches is None else out[:max_matches]
+    if queries.ndim != 2:
+        raise ValueError(f"Expected a 1D embedding or a 2D array of embeddings, got {queries.ndim}D")
+    lists = vector_base.lookup_messages_by_embeddings_masked(queries, mask, max_matches, threshold_score)
+    return lists if max_matches is None else [out[:max_matches] for out in lists]
 
 
 def load_sqlite_embeddings(

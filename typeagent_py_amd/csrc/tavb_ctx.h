@@ -387,6 +387,13 @@ int check_key_ordinals(const tavb_ctx* c, bool device_resident);
 int fill_empty_keys(tavb_ctx* c, u64_t* out, int64_t n);
 // the tail of a host-synchronous lookup whose last kernel wrote [nq, k] keys into h_out: ONE synchronise, the keys decoded into the caller's arrays
 int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts);
+// the message lookups: the row -> message map is set and covers the corpus (check_message_map); that, plus context, corpus, 1 <= k <=
+// TAVB_MAX_FUSED_K and max_messages >= 0 (check_message_args)
+int check_message_map(const tavb_ctx* c);
+int check_message_args(tavb_ctx* c, int k, int32_t max_messages);
+// n_accept accepted message ordinals on the host -> their bitmap over n_messages ordinals in d_bits (zeroed first; ordinals outside
+// [0, n_messages) are ignored), all enqueued on the stream
+int stage_accept_bitmap(tavb_ctx* c, const int32_t* accept_msgs_host, int64_t n_accept, const uint32_t** d_bits);
 
 // ---- tavb_lookup_topk.hip
 int check_topk_args(tavb_ctx* c, int k);  // context, corpus, 1 <= k <= TAVB_MAX_LARGE_K

@@ -146,6 +146,10 @@ int mask_blocks(int64_t rows);
 hipError_t launch_mask_expand(const uint32_t* bits, int64_t rows, unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
                               hipStream_t stream);
 hipError_t launch_mask_pack(const uint8_t* bytes, int64_t rows, uint32_t* bits, hipStream_t stream);
+// mask_from_messages: the mask of a scope of messages -- row r set when 0 <= row_to_msg[r] < n_bits and the accept bitmap (launch_accept_bitmap's
+// words over n_bits message ordinals) has that message's bit -> every word of (rows + 31) / 32, the bits at or beyond `rows` ZERO.  One launch.
+hipError_t launch_mask_from_messages(const int32_t* row_to_msg, int64_t rows, const uint32_t* accept_bits, int64_t n_bits, uint32_t* bits,
+                                     hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (device, kernel) (tavb_misc.hip)
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);

@@ -100,6 +100,36 @@ int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, flo
   return TAVB_OK;
 }
 
+// ---- what the message lookups of both lookup files repeat
+int check_message_map(const tavb_ctx* c) {
+  if (!c->row_to_msg && c->rows > 0) return fail(TAVB_E_NO_CORPUS, "no row -> message map set (call tavb_set_row_messages first)");
+  if (c->row_to_msg_rows < c->rows) return fail(TAVB_E_INVALID, "the row -> message map covers %lld rows, the corpus has %lld", (long long)c->row_to_msg_rows, (long long)c->rows);
+  return TAVB_OK;
+}
+
+int check_message_args(tavb_ctx* c, int k, int32_t max_messages) {
+  if (int rc = check_search_args(c, k)) return rc;
+  if (int rc = check_message_map(c)) return rc;
+  if (max_messages < 0) return fail(TAVB_E_INVALID, "max_messages must be >= 0");
+  return TAVB_OK;
+}
+
+int stage_accept_bitmap(tavb_ctx* c, const int32_t* accept_msgs_host, int64_t n_accept, const uint32_t** d_bits) {
+  const size_t words = (size_t)((c->n_messages + 31) / 32) + 1;
+  if (int rc = c->d_bits.reserve(words * 4)) return rc;
+  TAVB_HIP(hipMemsetAsync(c->d_bits.ptr, 0, words * 4, c->stream));
+  if (n_accept > 0) {
+    if (int rc = c->d_accept.reserve((size_t)n_accept * 4)) return rc;
+    // (pageable source: the copy is staged by the runtime before the call returns)
+    TAVB_HIP(hipMemcpyAsync(c->d_accept.ptr, accept_msgs_host, (size_t)n_accept * 4, hipMemcpyHostToDevice, c->stream));
+    hipError_t e = tavb::launch_accept_bitmap(reinterpret_cast<const int32_t*>(c->d_accept.ptr), n_accept, reinterpret_cast<uint32_t*>(c->d_bits.ptr),
+                                              c->n_messages, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "bitmap launch failed: %s", hipGetErrorString(e));
+  }
+  *d_bits = reinterpret_cast<const uint32_t*>(c->d_bits.ptr);
+  return TAVB_OK;
+}
+
 }  // namespace host
 }  // namespace tavb
 
@@ -522,32 +552,12 @@ int tavb_set_row_messages(tavb_ctx* c, const int32_t* dev_row_to_msg, int64_t ro
 static int rerank_and_return(tavb_ctx* c, const u64_t* d_hits, int k, const int32_t* d_pos_to_row, const int32_t* accept_msgs_host, int64_t n_accept,
                              bool filtered, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_count) {
   const uint32_t* d_bits = nullptr;
-  if (filtered) {
-    const size_t words = (size_t)((c->n_messages + 31) / 32) + 1;
-    if (int rc = c->d_bits.reserve(words * 4)) return rc;
-    TAVB_HIP(hipMemsetAsync(c->d_bits.ptr, 0, words * 4, c->stream));
-    if (n_accept > 0) {
-      if (int rc = c->d_accept.reserve((size_t)n_accept * 4)) return rc;
-      // (pageable source: the copy is staged by the runtime before the call returns)
-      TAVB_HIP(hipMemcpyAsync(c->d_accept.ptr, accept_msgs_host, (size_t)n_accept * 4, hipMemcpyHostToDevice, c->stream));
-      hipError_t e = tavb::launch_accept_bitmap(reinterpret_cast<const int32_t*>(c->d_accept.ptr), n_accept, reinterpret_cast<uint32_t*>(c->d_bits.ptr),
-                                                c->n_messages, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "bitmap launch failed: %s", hipGetErrorString(e));
-    }
-    d_bits = reinterpret_cast<const uint32_t*>(c->d_bits.ptr);
-  }
+  if (filtered)
+    if (int rc = stage_accept_bitmap(c, accept_msgs_host, n_accept, &d_bits)) return rc;
   hipError_t e = tavb::launch_message_rerank(d_hits, 1, k, 0u, d_pos_to_row, c->row_to_msg, c->row_to_msg_rows, d_bits, c->n_messages, max_messages,
                                              reinterpret_cast<u64_t*>(c->h_out.ptr), c->stream);
   if (e != hipSuccess) return fail(TAVB_E_HIP, "re-rank launch failed: %s", hipGetErrorString(e));
   return sync_decode(c, 1, k, 0, out_messages, out_scores, out_count);
-}
-
-static int check_message_args(tavb_ctx* c, int k, int32_t max_messages) {
-  if (int rc = check_search_args(c, k)) return rc;
-  if (!c->row_to_msg && c->rows > 0) return fail(TAVB_E_NO_CORPUS, "no row -> message map set (call tavb_set_row_messages first)");
-  if (c->row_to_msg_rows < c->rows) return fail(TAVB_E_INVALID, "the row -> message map covers %lld rows, the corpus has %lld", (long long)c->row_to_msg_rows, (long long)c->rows);
-  if (max_messages < 0) return fail(TAVB_E_INVALID, "max_messages must be >= 0");
-  return TAVB_OK;
 }
 
 int tavb_search_messages(tavb_ctx* c, const float* query_host, int32_t k, float min_score, const int32_t* accept_msgs_host, int64_t n_accept,

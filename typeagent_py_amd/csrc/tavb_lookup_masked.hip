@@ -257,4 +257,118 @@ int tavb_mask_pack(tavb_ctx* c, const uint8_t* dev_bytes, int64_t rows, uint32_t
   return TAVB_OK;
 }
 
+int tavb_mask_from_messages(tavb_ctx* c, const int32_t* accept_msgs_host, int64_t n_accept, int64_t rows, uint32_t* dev_bits_out) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = require_corpus(c)) return rc;
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  if (int rc = check_message_map(c)) return rc;
+  if (rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (n_accept < 0 || (n_accept > 0 && !accept_msgs_host)) return fail(TAVB_E_INVALID, "bad accept list");
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bits_out) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  const uint32_t* d_accept_bits;
+  if (int rc = stage_accept_bitmap(c, accept_msgs_host, n_accept, &d_accept_bits)) return rc;
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  hipError_t e = tavb::launch_mask_from_messages(c->row_to_msg, rows, d_accept_bits, c->n_messages, dev_bits_out, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "message mask launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+// ---- batched message lookups: nq key lists [nq, k] on the device (keys carrying index_base + row) -> ONE message_rerank_kernel launch of nq
+// workgroups -> ONE device-to-host copy -> the callers' arrays.  d_out holds both: the hits in its first nq * k keys, the message keys behind.
+static int rerank_batch_and_return(tavb_ctx* c, const u64_t* d_hits, int nq, int k, uint32_t index_base, const uint32_t* d_accept_bits, int32_t max_messages,
+                                   int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* const d_msgs = reinterpret_cast<u64_t*>(c->d_out.ptr) + n_keys;
+  {
+    Timed t(c, TAVB_KERNEL_MERGE);
+    hipError_t e = tavb::launch_message_rerank(d_hits, nq, k, index_base, nullptr, c->row_to_msg, c->row_to_msg_rows, d_accept_bits, c->n_messages,
+                                               max_messages, d_msgs, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "re-rank launch failed: %s", hipGetErrorString(e));
+  }
+  TAVB_HIP(hipMemcpyAsync(c->h_out.ptr, d_msgs, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  return sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts);
+}
+
+// the buffers of such a lookup: pinned room for the message keys, device room for the hits and the message keys; *d_hits = the hits
+static int reserve_message_batch(tavb_ctx* c, int nq, int k, u64_t** d_hits) {
+  const size_t n_keys = (size_t)nq * k;
+  if (int rc = c->h_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  if (int rc = c->d_out.reserve(2 * n_keys * sizeof(u64_t))) return rc;
+  *d_hits = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  return TAVB_OK;
+}
+
+int tavb_search_messages_masked(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row,
+                                const int32_t* dev_rows, int64_t n_allowed, int32_t k, const float* min_scores, int32_t max_messages, int32_t route,
+                                int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  if (int rc = check_message_args(c, k, max_messages)) return rc;
+  if (route < 1 || route > 3) return fail(TAVB_E_INVALID, "route must be 1 (row list), 2 (32/64-query tile) or 3 (wide filter tile), got %d", route);
+  bool empty = false;
+  if (route == 1) {
+    if (int rc = check_masked_head(c, nq, rows, k)) return rc;
+    if (n_allowed < 0 || n_allowed >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad row list length");
+    empty = rows == 0 || nq == 0 || n_allowed == 0;
+    if (!empty && !dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  } else if (route == 2) {
+    if (int rc = check_masked_args(c, nq, dev_bits, rows, first_row, last_row, k, &empty)) return rc;
+  } else {
+    if (int rc = check_masked_wide_args(c, nq, dev_bits, rows, first_row, last_row, dev_rows, n_allowed, k, &empty)) return rc;
+  }
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  u64_t* d_hits;
+  if (int rc = reserve_message_batch(c, nq, k, &d_hits)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  c->last_graph = 0;
+  const uint32_t base = (uint32_t)c->ordinal_base;
+  if (route == 1) {
+    c->last_topk_refine = 0;
+    c->topk_rounds_pending = 0;
+    c->last_direct = 0;
+    c->masked_route = 1;  // the gather route of a masked batch
+    if (int rc = search_device_impl(c, d_q, nq, k, min_scores, dev_rows, n_allowed, 0u, d_hits)) return rc;
+    hipError_t e = tavb::launch_remap_positions(d_hits, d_hits, (int64_t)nq * k, dev_rows, n_allowed, base, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
+  } else if (route == 2) {
+    if (int rc = search_masked_tile(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, base, d_hits)) return rc;
+  } else {
+    if (int rc = search_masked_wide(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, dev_rows, n_allowed, base, d_hits)) return rc;
+  }
+  return rerank_batch_and_return(c, d_hits, nq, k, base, nullptr, max_messages, out_messages, out_scores, out_counts);
+}
+
+int tavb_search_messages_batch(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const int32_t* accept_msgs_host,
+                               int64_t n_accept, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  if (int rc = check_message_args(c, k, max_messages)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (n_accept < -1 || (n_accept > 0 && !accept_msgs_host)) return fail(TAVB_E_INVALID, "bad accept list");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (c->rows == 0) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  u64_t* d_hits;
+  if (int rc = reserve_message_batch(c, nq, k, &d_hits)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  c->last_graph = 0;
+  // keys carry LOCAL rows here (index_base 0): they only index the map
+  if (int rc = tavb_search_device_dispatch(c, d_q, nq, k, min_scores, 0u, d_hits)) return rc;
+  const uint32_t* d_accept_bits = nullptr;
+  if (n_accept >= 0)
+    if (int rc = stage_accept_bitmap(c, accept_msgs_host, n_accept, &d_accept_bits)) return rc;
+  return rerank_batch_and_return(c, d_hits, nq, k, 0u, d_accept_bits, max_messages, out_messages, out_scores, out_counts);
+}
+
 }  // extern "C"

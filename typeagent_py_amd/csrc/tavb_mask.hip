@@ -1,5 +1,6 @@
-// Row masks (tavb_mask_expand, tavb_mask_pack): an allow-mask of one bit per corpus row -> the int32 row list the subset lookups
-// gather by, in ascending row order, without a trip to the host.
+// Row masks (tavb_mask_expand, tavb_mask_pack, tavb_mask_from_messages): an allow-mask of one bit per corpus row -> the int32 row list the
+// subset lookups gather by, in ascending row order, without a trip to the host; and the mask of a SCOPE -- a set of message ordinals -- built
+// from the row -> message map on the device (mask_from_messages_kernel), so that a scoped message lookup never makes a host row list.
 //
 // The mask is uint32 words, row r = bit (r & 31) of word (r >> 5).  Two launches, both grids fixed on the host:
 //   mask_count_kernel   workgroup b popcounts its kMaskWordsPerBlock words -> counts[b]
@@ -116,6 +117,30 @@ __global__ void __launch_bounds__(kMaskThreads) mask_pack_kernel(const uint8_t* 
   }
 }
 
+// The mask of a scope: row r is set when its message (row_to_msg[r]; -1 = none) has its bit in the accept bitmap (accept_bitmap_kernel's
+// words, n_bits message ordinals).  A wave takes 64 rows per round, one entry of the map per lane (coalesced), and its ballot IS the two
+// words: every word of (rows + 31) / 32 is written, the bits at or beyond `rows` as zeros (their lanes vote no).  No atomics.
+__global__ void __launch_bounds__(kMaskThreads) mask_from_messages_kernel(const int32_t* __restrict__ row_to_msg, int64_t rows,
+                                                                          const uint32_t* __restrict__ accept_bits, int64_t n_bits,
+                                                                          uint32_t* __restrict__ bits_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * kMaskThreads + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * kMaskThreads) >> 6;
+  const int64_t n_words = (rows + 31) >> 5;
+  const int64_t groups = (rows + 63) >> 6;
+  for (int64_t g = wave; g < groups; g += n_waves) {  // (wave-uniform trip count)
+    const int64_t r = (g << 6) + lane;
+    bool on = false;
+    if (r < rows) {
+      const int64_t m = row_to_msg[r];
+      if (m >= 0 && m < n_bits) on = ((accept_bits[m >> 5] >> (m & 31)) & 1u) != 0u;
+    }
+    const unsigned long long v = __ballot(on);
+    const int64_t w = (g << 1) + lane;
+    if (lane < 2 && w < n_words) bits_out[w] = (uint32_t)(v >> (32 * lane));
+  }
+}
+
 }  // namespace
 
 int mask_blocks(int64_t rows) { return (int)((rows + TAVB_MASK_ROWS_PER_WORKGROUP - 1) / TAVB_MASK_ROWS_PER_WORKGROUP); }
@@ -138,6 +163,15 @@ hipError_t launch_mask_pack(const uint8_t* bytes, int64_t rows, uint32_t* bits, 
   const int64_t groups = (rows + 63) >> 6;
   const int64_t blocks = std::min<int64_t>((groups + kMaskThreads / 64 - 1) / (kMaskThreads / 64), 2048);
   hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)blocks), dim3(kMaskThreads), 0, stream, bytes, rows, n_words, bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_from_messages(const int32_t* row_to_msg, int64_t rows, const uint32_t* accept_bits, int64_t n_bits, uint32_t* bits,
+                                     hipStream_t stream) {
+  if (!row_to_msg || !accept_bits || !bits || rows < 1 || rows >= 0x7FFFFFFFll || n_bits < 0) return hipErrorInvalidValue;
+  const int64_t groups = (rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((groups + kMaskThreads / 64 - 1) / (kMaskThreads / 64), 2048);
+  hipLaunchKernelGGL(mask_from_messages_kernel, dim3((unsigned)blocks), dim3(kMaskThreads), 0, stream, row_to_msg, rows, accept_bits, n_bits, bits);
   return hipGetLastError();
 }
 

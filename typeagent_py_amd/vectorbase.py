@@ -14,8 +14,9 @@ Same names, arguments, defaults, return types and exceptions.  What differs is
 where the arithmetic runs: `fuzzy_lookup_embedding*` launch HIP kernels (fused
 dot + score + threshold + top-k) instead of np.dot/argpartition, and there are
 additive methods: `fuzzy_lookup_embeddings` (a batch of queries in one
-submission) and the masked lookups (`row_mask`, `fuzzy_lookup_embedding_masked`,
-`fuzzy_lookup_embeddings_masked`: search only among the rows an allow-mask names).  The host ndarray `_vectors` stays the authoritative copy for
+submission), the masked lookups (`row_mask`, `fuzzy_lookup_embedding_masked`,
+`fuzzy_lookup_embeddings_masked`: search only among the rows an allow-mask names) and the scoped message lookups (`message_mask`,
+`lookup_messages_by_embedding(s)_masked`, `lookup_messages_by_embeddings`: a scope of message ordinals searched as a mask, batches aggregated to messages).  The host ndarray `_vectors` stays the authoritative copy for
 serialize()/deserialize(); the device buffer mirrors it and is synced lazily,
 appends moving only the new rows.
 
@@ -1073,6 +1074,131 @@ class VectorBase:
             raise IndexError(f"index {int(subset[np.argmax(bad)])} is out of bounds for axis 0 with size {n}")
         msgs, scs = eng.search_messages(embedding, max_hits, thr, max_hits, subset_rows=rows)
         return [ScoredInt(int(m), float(sc)) for m, sc in zip(msgs.tolist(), scs.tolist())]
+
+    # ------------------------------------------------------------------ scoped and batched message lookups (additive)
+    def _check_row_messages(self) -> None:
+        if self._row_messages is None:
+            raise RuntimeError("set_row_messages() first")
+        if len(self._row_messages) < self._count:
+            raise ValueError(f"the row -> message map covers {len(self._row_messages)} rows, the index has {self._count}")
+
+    def _message_thresholds(self, queries: np.ndarray, max_matches, threshold_score):
+        """(max_hits, float32 threshold(s), the caller's thresholds per query or None) as `fuzzy_lookup_embeddings_masked` resolves them."""
+        if threshold_score is not None and not np.isscalar(threshold_score) and np.ndim(threshold_score) == 1:
+            if len(threshold_score) != len(queries):
+                raise ValueError(f"Number of thresholds {len(threshold_score)} does not match number of embeddings {len(queries)}")
+            per_query = list(threshold_score)
+            max_hits, _ = self._limits(max_matches, 0.0)
+            return max_hits, np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32), per_query
+        max_hits, thr = self._limits(max_matches, threshold_score)
+        return max_hits, thr, None
+
+    def message_mask(self, message_ordinals) -> RowMask:
+        """A scope of MESSAGE ordinals -> the `RowMask` of their chunk rows: equals
+        row_mask(np.isin(row_messages[:len(self)], message_ordinals) & (row_messages[:len(self)] >= 0)) -- ordinals that name no message
+        (negative, or beyond the map's largest) are ignored, rows without a message (-1) are never allowed.  Needs `set_row_messages`.  On a
+        single-GPU engine only the ordinals travel: the mask is built from the device copy of the map (tavb_mask_from_messages) and
+        expanded there, the scope never becomes a host row list.  Device groups and test doubles build the bool array on the host."""
+        self._check_row_messages()
+        acc = np.asarray(message_ordinals if isinstance(message_ordinals, np.ndarray) else list(message_ordinals))
+        if acc.size and acc.dtype.kind not in "iu":
+            raise TypeError("message ordinals must be integers")
+        acc = acc.astype(np.int64, copy=False).reshape(-1)
+        n = self._count
+        if n == 0:
+            return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
+        eng = self._messages_engine()
+        if eng is not None and self._masked_native(eng) and hasattr(eng, "mask_from_messages"):
+            dev_rows, count, dev_bits = eng.mask_from_messages(acc[(acc >= 0) & (acc < 2**31 - 1)])
+            return RowMask(self, n, count, dev_rows=dev_rows, dev_bits=dev_bits)
+        held = self._row_messages[:n]
+        return self.row_mask(np.isin(held, acc) & (held >= 0))
+
+    def lookup_messages_by_embedding_masked(
+        self,
+        embedding: NormalizedEmbedding,
+        allowed,
+        max_matches: int | None = None,
+        threshold_score: float | None = None,
+    ) -> list[ScoredInt]:
+        """`lookup_messages_in_subset_by_embedding` among the rows `allowed` names (a mask, see `row_mask`; a `RowMask`, e.g. from
+        `message_mask`): equals lookup_messages_in_subset_by_embedding(embedding, np.flatnonzero(allowed).tolist(), max_matches,
+        threshold_score)."""
+        q = np.asarray(embedding, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"Expected 1D embedding, got {q.ndim}D")
+        return self.lookup_messages_by_embeddings_masked(q.reshape(1, -1), allowed, max_matches, threshold_score)[0]
+
+    def lookup_messages_by_embeddings_masked(
+        self,
+        embeddings: NormalizedEmbeddings,
+        allowed,
+        max_matches: int | None = None,
+        threshold_score: float | None = None,
+    ) -> list[list[ScoredInt]]:
+        """Batch form over ONE mask: equals [lookup_messages_in_subset_by_embedding(e, np.flatnonzero(allowed).tolist(), max_matches,
+        threshold_score) for e in embeddings] -- a scoped search (the best `max_matches` chunk rows AMONG the allowed ones, then best score
+        per message), not the post-filter of `lookup_messages_by_embedding(accept_ordinals=...)`.  Rows of the mask that have no message
+        are skipped by the aggregation.  `threshold_score` may be a sequence with one threshold per query.
+
+        On a single-GPU engine with 1 <= max_matches <= 256 it is ONE submission (tavb_search_messages_masked): the masked batch on the
+        route `fuzzy_lookup_embeddings_masked` would take (options "mask_tile" / "mask_wide"; `engine.get_option("masked_route")` tells
+        which ran), the key lists left on the device, one launch of the message aggregation for all queries, one copy back.  On the row
+        list (route 1) and on the wide filter tile (route 3) the result equals the sequential calls bit for bit -- messages, float32 scores
+        and counts; on the 32/64-query tile (route 2) the messages are identical except among float32 near-ties and the scores agree
+        within 1e-5.  Everything else (max_matches outside 1..256, device groups, test doubles) goes through
+        `fuzzy_lookup_embeddings_masked` and the host aggregation."""
+        queries = np.asarray(embeddings, dtype=np.float32)
+        if queries.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
+        max_hits, thr, per_query = self._message_thresholds(queries, max_matches, threshold_score)
+        self._check_row_messages()
+        mask = self._resolve_mask(allowed)
+        nq = len(queries)
+        if self._count == 0 or mask.count == 0 or nq == 0:
+            return [[] for _ in range(nq)]
+        eng = self._messages_engine()
+        if eng is not None and self._masked_native(eng) and hasattr(eng, "search_messages_masked") and mask.dev_rows is not None and 1 <= max_hits <= _PAGE:
+            if self._mask_wide(eng, mask, nq, max_hits):
+                route = 3
+            elif max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
+                route = 2
+            else:
+                route = 1
+            msgs, scs, cnts = eng.search_messages_masked(queries, mask.dev_bits, mask.dev_rows, max_hits, thr, max_hits, route, span=mask.span)
+            return _scored_lists(msgs, scs, cnts, max_hits)
+        lists = self.fuzzy_lookup_embeddings_masked(queries, mask, max_matches, threshold_score if per_query is None else per_query)
+        return [self._host_rerank(hits, None) for hits in lists]
+
+    def lookup_messages_by_embeddings(
+        self,
+        embeddings: NormalizedEmbeddings,
+        max_matches: int | None = None,
+        threshold_score: float | None = None,
+        accept_ordinals=None,
+    ) -> list[list[ScoredInt]]:
+        """Batch form of `lookup_messages_by_embedding`: equals [lookup_messages_by_embedding(e, max_matches, threshold_score,
+        accept_ordinals) for e in embeddings], on a single-GPU engine with 1 <= max_matches <= 256 as ONE submission
+        (tavb_search_messages_batch: the batch's full-corpus top-k, the accept filter, the aggregation of every query in one launch).  Bit
+        for bit wherever the batch route is (the streaming kernels, the wide tile + rescoring); a batch the 32/64-query tile serves agrees
+        the way `fuzzy_lookup_embeddings` does there.  `threshold_score` may be a sequence with one threshold per query."""
+        queries = np.asarray(embeddings, dtype=np.float32)
+        if queries.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
+        max_hits, thr, per_query = self._message_thresholds(queries, max_matches, threshold_score)
+        nq = len(queries)
+        if self._count == 0 or nq == 0:
+            return [[] for _ in range(nq)]
+        accept = None if accept_ordinals is None else [int(x) for x in accept_ordinals]
+        eng = self._messages_engine()
+        if eng is None or not hasattr(eng, "search_messages_batch") or not (1 <= max_hits <= _PAGE):
+            return [self.lookup_messages_by_embedding(q, max_matches, threshold_score if per_query is None else per_query[i], accept) for i, q in enumerate(queries)]
+        acc = None if accept is None else np.asarray(accept, dtype=np.int64).reshape(-1)
+        if acc is not None:
+            acc = acc[(acc >= 0) & (acc < 2**31 - 1)]
+        cut = max_hits if max_matches is not None else max(max_hits, 1)
+        msgs, scs, cnts = eng.search_messages_batch(queries, max_hits, thr, cut, accept=acc)
+        return _scored_lists(msgs, scs, cnts, max_hits)
 
     async def fuzzy_lookup(
         self,
