@@ -277,6 +277,25 @@ def f32_threshold(min_score) -> np.float32:
         return np.float32(min_score)
 
 
+def batch_queries(queries, dim: int) -> np.ndarray:
+    """A host batch of queries as the library reads it: contiguous float32 [nq, dim]."""
+    a = np.ascontiguousarray(queries, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != dim:
+        raise ValueError(f"queries must be [nq, {dim}]")
+    return a
+
+
+def batch_thresholds(thrs, nq: int) -> np.ndarray:
+    """float32 [nq] thresholds (or one for all) as the library reads them: contiguous float32 [nq].  The two shapes every caller in the
+    package passes skip `np.broadcast_to`, whose read-only result also costs `_addr` its slow path: together 3 - 4 us of a batch's host time."""
+    t = np.asarray(thrs, dtype=np.float32)
+    if t.ndim == 0:
+        return np.full(nq, t, dtype=np.float32)
+    if t.shape == (nq,) and t.flags.c_contiguous:
+        return t
+    return np.ascontiguousarray(np.broadcast_to(t, (nq,)))
+
+
 class Engine:
     """One libtavb context on one GPU + the torch tensors that hold the corpus."""
 
@@ -466,6 +485,31 @@ class Engine:
             raise ValueError(f"shapes ({self.rows},{self.dim}) and {tuple(np.shape(q))} not aligned: query must have {self.dim} elements")
         return a
 
+    def _host_batch(self, queries, k: int, thrs):
+        """The arguments and outputs of a host batch: (queries f32 [nq, dim], nq, thresholds f32 [nq], ordinals int64 [nq, k], scores f32
+        [nq, k], counts int32 [nq], zeroed)."""
+        a = batch_queries(queries, self.dim)
+        nq = a.shape[0]
+        return a, nq, batch_thresholds(thrs, nq), np.empty((nq, k), dtype=np.int64), np.empty((nq, k), dtype=np.float32), np.zeros(nq, dtype=np.int32)
+
+    def _row_list(self, dev_rows):
+        """A resident row list (torch int32 [S] on this device) -> (its address, S); an empty tensor has no address to name "a list" by: (None, 0)."""
+        assert dev_rows.dtype == self._torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
+        n = int(dev_rows.numel())
+        return (c_void_p(dev_rows.data_ptr()) if n else None), n
+
+    def _single_query(self, k: int, call):
+        """One query over a subset: `call(positions, scores, count)` -- the last three arguments of the library call -- fills k-sized
+        outputs under the lock -> (positions int64[m], scores float32[m])."""
+        pos = np.empty(k, dtype=np.int64)
+        scs = np.empty(k, dtype=np.float32)
+        cnt = c_int32(0)
+        with self._lock:
+            rc = call(_addr(pos), _addr(scs), byref(cnt))
+        _check(self.lib, rc)
+        m = int(cnt.value)
+        return pos[:m], scs[:m]
+
     def _out_buffers(self, k: int):
         """Reused output arrays of the single-query calls, with their ctypes views: `ndarray.ctypes.data_as()` costs ~2 us a piece on the host --
         three of them were 6 us of a 33 us lookup on a 10k-row corpus.  Callers hold self._lock and copy the filled prefix out."""
@@ -501,20 +545,10 @@ class Engine:
         """rows: int64 corpus rows per subset position -> (positions int64[m], scores float32[m])."""
         a = self._query(q)
         r = np.ascontiguousarray(rows, dtype=np.int64)
-        pos = np.empty(k, dtype=np.int64)
-        scs = np.empty(k, dtype=np.float32)
-        cnt = c_int32(0)
-        with self._lock:
-            if after is None:
-                rc = self.lib.tavb_search_subset(self._h, _addr(a), _addr(r), r.shape[0], k,
-                                                 c_float(float(thr)), _addr(pos), _addr(scs), byref(cnt))
-            else:
-                rc = self.lib.tavb_search_subset_after(self._h, _addr(a), _addr(r), r.shape[0], k,
-                                                       c_float(float(thr)), c_float(after[0]), int(after[1]),
-                                                       _addr(pos), _addr(scs), byref(cnt))
-        _check(self.lib, rc)
-        m = int(cnt.value)
-        return pos[:m], scs[:m]
+        if after is None:
+            return self._single_query(k, lambda *out: self.lib.tavb_search_subset(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)), *out))
+        return self._single_query(k, lambda *out: self.lib.tavb_search_subset_after(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)),
+                                                                                   c_float(after[0]), int(after[1]), *out))
 
     def rows_to_device(self, rows: np.ndarray):
         """int64 corpus rows (already wrapped and range-checked) -> torch int32 [S] on this engine's device."""
@@ -527,6 +561,8 @@ class Engine:
         pos = np.empty(k, dtype=np.int64)
         scs = np.empty(k, dtype=np.float32)
         cnt = c_int32(0)
+        # Written out, not `_single_query`: its closure and call are 1 us of this 7 us path (the repeated-subset lookup of a small index).
+        # The address goes as it is, an empty list's included: `_row_list` would turn an empty view of a longer tensor into no pointer.
         with self._lock:
             rc = self.lib.tavb_search_subset_resident(self._h, _addr(a), c_void_p(dev_rows.data_ptr()), int(dev_rows.shape[0]), k,
                                                       c_float(float(thr)), _addr(pos), _addr(scs), byref(cnt))
@@ -611,14 +647,7 @@ class Engine:
         on this device, the mask over the whole corpus (`mask_to_rows_bits`, `pack_mask_tensor`); span = (first, last) allowed row (None:
         the whole corpus); 1 <= k <= 64; thrs float32 [nq] (or one for all) -> (ordinals [nq, k], scores [nq, k], counts [nq]), the layout
         of `search_batch`.  Raises TavbError (TAVB_E_UNSUPPORTED) for a shape the tile does not serve."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        ords = np.empty((nq, k), dtype=np.int64)
-        scs = np.empty((nq, k), dtype=np.float32)
-        cnts = np.zeros(nq, dtype=np.int32)
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
         bits, first, last = self._masked_args(dev_bits, span)
         with self._lock:
             rc = self.lib.tavb_search_masked_batch(self._h, _addr(a), nq, bits, int(self.rows), first, last, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
@@ -629,13 +658,7 @@ class Engine:
         """`search_masked_batch` with the queries on the device and nothing waited for (tavb_search_masked_device): dev_queries torch f32
         [nq, dim] -> torch int64 [nq, k] sorted, zero-padded keys carrying ordinal_base + row.  `out_keys`: a device tensor or a PINNED
         host tensor.  Async: `synchronize()` before reading."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
-        nq = int(dev_queries.shape[0])
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
         bits, first, last = self._masked_args(dev_bits, span)
         with self._lock:
             rc = self.lib.tavb_search_masked_device(self._h, c_void_p(dev_queries.data_ptr()), nq, bits, int(self.rows), first, last, k, _addr(t),
@@ -646,27 +669,15 @@ class Engine:
     # masked batches on the 128/256-query filter tile + rescoring --------------------------
     plan_masked_wide = staticmethod(plan_masked_wide)
 
-    def _masked_wide_rows(self, dev_rows):
-        torch = self._torch
-        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
-        return (c_void_p(dev_rows.data_ptr()) if dev_rows.numel() else None), int(dev_rows.numel())
-
     def search_masked_wide(self, queries, dev_bits, dev_rows, k: int, thrs, span=None):
         """A masked batch on the 128/256-query filter tile with exact rescoring (tavb_search_masked_wide; fp16 corpora, 1 <= k <= 256): the
         arguments of `search_masked_batch` plus dev_rows, the mask's resident row list (torch int32 [count], ascending: `mask_to_rows_bits`),
         over which a query whose candidate band did not fit is re-run -> (ordinals [nq, k], scores [nq, k], counts [nq]), equal to
         `search_subset_batch_resident(queries, dev_rows, k, thrs)` bit for bit.  Raises TavbError (TAVB_E_UNSUPPORTED) for an fp32 corpus or a
         k the route does not serve."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        ords = np.empty((nq, k), dtype=np.int64)
-        scs = np.empty((nq, k), dtype=np.float32)
-        cnts = np.zeros(nq, dtype=np.int32)
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
         bits, first, last = self._masked_args(dev_bits, span)
-        rows_ptr, n_allowed = self._masked_wide_rows(dev_rows)
+        rows_ptr, n_allowed = self._row_list(dev_rows)
         with self._lock:
             rc = self.lib.tavb_search_masked_wide(self._h, _addr(a), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k, _addr(t), _addr(ords),
                                                   _addr(scs), _addr(cnts))
@@ -677,15 +688,9 @@ class Engine:
         """`search_masked_wide` with the queries on the device and the keys left there (tavb_search_masked_wide_device): torch int64 [nq, k]
         sorted, zero-padded keys carrying ordinal_base + row.  The call synchronises the stream once (the list of flagged queries is read
         back); `synchronize()` before reading the keys all the same."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
-        nq = int(dev_queries.shape[0])
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
         bits, first, last = self._masked_args(dev_bits, span)
-        rows_ptr, n_allowed = self._masked_wide_rows(dev_rows)
+        rows_ptr, n_allowed = self._row_list(dev_rows)
         with self._lock:
             rc = self.lib.tavb_search_masked_wide_device(self._h, c_void_p(dev_queries.data_ptr()), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k,
                                                          _addr(t), c_void_p(out_keys.data_ptr()))
@@ -696,19 +701,10 @@ class Engine:
         """`search_subset_resident` for a batch: queries f32 [nq, dim] over ONE resident row list (torch int32 [S]: `mask_to_rows`, or
         wrapped, range-checked rows) in one submission, 1 <= k <= MAX_LARGE_K; thrs float32 [nq] (or one for all) -> (ordinals [nq, k],
         scores [nq, k], counts [nq]), the layout of `search_batch`.  remap=True: corpus ordinals (dev_rows ascending); False: positions."""
-        torch = self._torch
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        ords = np.empty((nq, k), dtype=np.int64)
-        scs = np.empty((nq, k), dtype=np.float32)
-        cnts = np.zeros(nq, dtype=np.int32)
-        n = int(dev_rows.shape[0])
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
+        rows_ptr, n = self._row_list(dev_rows)
         with self._lock:
-            rc = self.lib.tavb_search_subset_batch_resident(self._h, _addr(a), nq, c_void_p(dev_rows.data_ptr()) if n else None, n, k, _addr(t),
+            rc = self.lib.tavb_search_subset_batch_resident(self._h, _addr(a), nq, rows_ptr, n, k, _addr(t),
                                                             1 if remap else 0, _addr(ords), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
         return ords, scs, cnts
@@ -735,14 +731,7 @@ class Engine:
 
     def search_batch(self, queries, k: int, thrs):
         """queries f32 [nq, dim]; thrs float32 [nq] -> (ordinals [nq,k], scores [nq,k], counts [nq])."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        ords = np.empty((nq, k), dtype=np.int64)
-        scs = np.empty((nq, k), dtype=np.float32)
-        cnts = np.zeros(nq, dtype=np.int32)
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
         with self._lock:  # (five `ndarray.ctypes.data_as()` were 10 us of a 32 us two-query lookup on a small corpus)
             rc = self.lib.tavb_search_batch(self._h, _addr(a), nq, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
@@ -751,14 +740,7 @@ class Engine:
     def search_topk(self, queries, k: int, thrs):
         """Exact top-k for any 1 <= k <= MAX_LARGE_K after one corpus pass per 8 queries (tavb_search_topk): queries f32 [nq, dim]; thrs
         float32 [nq] (or one for all) -> (ordinals [nq,k], scores [nq,k], counts [nq]), the layout of `search_batch`."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        ords = np.empty((nq, k), dtype=np.int64)
-        scs = np.empty((nq, k), dtype=np.float32)
-        cnts = np.zeros(nq, dtype=np.int32)
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
         with self._lock:
             rc = self.lib.tavb_search_topk(self._h, _addr(a), nq, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
@@ -768,26 +750,17 @@ class Engine:
         """`search_topk` of one query over a subset (rows: int64 corpus row per subset position) -> (positions int64[m], scores float32[m])."""
         a = self._query(q)
         r = np.ascontiguousarray(rows, dtype=np.int64)
-        pos = np.empty(k, dtype=np.int64)
-        scs = np.empty(k, dtype=np.float32)
-        cnt = c_int32(0)
-        with self._lock:
-            rc = self.lib.tavb_search_subset_topk(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)), _addr(pos), _addr(scs), byref(cnt))
-        _check(self.lib, rc)
-        m = int(cnt.value)
-        return pos[:m], scs[:m]
+        return self._single_query(k, lambda *out: self.lib.tavb_search_subset_topk(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)), *out))
 
     def search_sorted(self, queries, k: int, thrs):
         """Every survivor (k = 0) or the best k for ANY k, sorted on the device after one corpus pass per 8 queries (tavb_search_sorted):
         queries f32 [nq, dim]; thrs float32 [nq] (or one for all) -> (ordinals int64 [total], scores float32 [total], counts int64 [nq]),
         query q's results at offsets counts[:q].sum() .. + counts[q].  Equal to `search_all` per query, bit for bit."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        a = batch_queries(queries, self.dim)
         if k < 0:
             raise ValueError("k must be >= 0")
         nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        t = batch_thresholds(thrs, nq)
         bound = nq * (self.rows if k == 0 else min(int(k), self.rows))
         ords = np.empty(max(bound, 1), dtype=np.int64)  # (lazy: only the pages the results touch are ever mapped)
         scs = np.empty(max(bound, 1), dtype=np.float32)
@@ -840,23 +813,14 @@ class Engine:
         """-> (message ordinals int64[m], scores float32[m]).  accept: int array of accepted message ordinals (sqlite
         provider's subset form) or None; subset_rows: int64 corpus rows (memory provider's subset gather) or None."""
         a = self._query(q)
-        msgs = np.empty(k, dtype=np.int64)
-        scs = np.empty(k, dtype=np.float32)
-        cnt = c_int32(0)
-        with self._lock:
-            if subset_rows is not None:
-                r = np.ascontiguousarray(subset_rows, dtype=np.int64)
-                rc = self.lib.tavb_search_messages_subset(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)),
-                                                          int(max_messages), _addr(msgs), _addr(scs), byref(cnt))
-            else:
-                acc = None if accept is None else np.ascontiguousarray(accept, dtype=np.int32)
-                rc = self.lib.tavb_search_messages(self._h, _addr(a), k, c_float(float(thr)),
-                                                   _addr(acc) if acc is not None and acc.size else None,
-                                                   -1 if acc is None else acc.shape[0], int(max_messages),
-                                                   _addr(msgs), _addr(scs), byref(cnt))
-        _check(self.lib, rc)
-        m = int(cnt.value)
-        return msgs[:m], scs[:m]
+        if subset_rows is not None:
+            r = np.ascontiguousarray(subset_rows, dtype=np.int64)
+            return self._single_query(k, lambda *out: self.lib.tavb_search_messages_subset(self._h, _addr(a), _addr(r), r.shape[0], k, c_float(float(thr)),
+                                                                                          int(max_messages), *out))
+        acc = None if accept is None else np.ascontiguousarray(accept, dtype=np.int32)
+        return self._single_query(k, lambda *out: self.lib.tavb_search_messages(self._h, _addr(a), k, c_float(float(thr)),
+                                                                               _addr(acc) if acc is not None and acc.size else None,
+                                                                               -1 if acc is None else acc.shape[0], int(max_messages), *out))
 
     # scoped and batched message lookups ------------------------------------------
     def mask_from_messages(self, accept):
@@ -874,22 +838,14 @@ class Engine:
         _check(self.lib, rc)
         return (*self.expand_mask_bits(bits, rows), bits)  # (same stream: nothing to wait for)
 
-    def _message_batch_out(self, queries, k: int, thrs):
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        return a, nq, t, np.empty((nq, k), dtype=np.int64), np.empty((nq, k), dtype=np.float32), np.zeros(nq, dtype=np.int32)
-
     def search_messages_masked(self, queries, dev_bits, dev_rows, k: int, thrs, max_messages: int, route: int, span=None):
         """A masked batch aggregated to messages in one submission (tavb_search_messages_masked): the arguments of `search_masked_wide`
         plus `route` -- 1 = the row list, 2 = the 32/64-query tile, 3 = the 128/256-query filter tile + rescoring; TavbError
         (TAVB_E_UNSUPPORTED) for a shape the route does not serve -- and max_messages; 1 <= k <= 256 -> (message ordinals [nq, k], scores
         [nq, k], counts [nq]).  Per query: `search_messages(q, k, thr, max_messages, subset_rows=the mask's rows)`."""
-        a, nq, t, msgs, scs, cnts = self._message_batch_out(queries, k, thrs)
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
         bits, first, last = self._masked_args(dev_bits, span)
-        rows_ptr, n_allowed = (None, 0) if dev_rows is None else self._masked_wide_rows(dev_rows)
+        rows_ptr, n_allowed = (None, 0) if dev_rows is None else self._row_list(dev_rows)
         with self._lock:
             rc = self.lib.tavb_search_messages_masked(self._h, _addr(a), nq, bits, int(self.rows), first, last, rows_ptr, n_allowed, k, _addr(t),
                                                       int(max_messages), int(route), _addr(msgs), _addr(scs), _addr(cnts))
@@ -899,7 +855,7 @@ class Engine:
     def search_messages_batch(self, queries, k: int, thrs, max_messages: int, accept=None):
         """`search_messages` for a batch in one submission (tavb_search_messages_batch): queries f32 [nq, dim]; thrs float32 [nq] (or one
         for all); accept as there -> (message ordinals [nq, k], scores [nq, k], counts [nq])."""
-        a, nq, t, msgs, scs, cnts = self._message_batch_out(queries, k, thrs)
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
         acc = None if accept is None else np.ascontiguousarray(accept, dtype=np.int32)
         with self._lock:
             rc = self.lib.tavb_search_messages_batch(self._h, _addr(a), nq, k, _addr(t), _addr(acc) if acc is not None and acc.size else None,
@@ -940,14 +896,29 @@ class Engine:
         if not on_device and not (dev.type == "cpu" and out_keys.is_pinned()):
             raise ValueError(f"out_keys must live on cuda:{self.device} or in pinned host memory")
 
+    def _out_keys(self, out_keys, nq: int, k: int, device):
+        """The caller's `out_keys`, checked, or a fresh torch int64 [nq, k] on `device`."""
+        if out_keys is None:
+            out_keys = self._torch.empty((nq, k), dtype=self._torch.int64, device=device)
+        self._check_out_keys(out_keys, nq, k)
+        return out_keys
+
+    def _device_batch(self, dev_queries, k: int, thrs, out_keys, flat: bool = False):
+        """The arguments of a lookup whose queries are on the device: dev_queries torch f32 [nq, dim] (flat: any shape of nq * dim
+        elements) -> (nq, thresholds f32 [nq] -- None for thrs=None: the forms that pass one scalar threshold --, `_out_keys`)."""
+        assert dev_queries.dtype == self._torch.float32 and dev_queries.is_contiguous()
+        if flat:
+            assert dev_queries.numel() % max(self.dim, 1) == 0
+            nq = dev_queries.numel() // self.dim if self.dim else 0
+        else:
+            assert dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
+            nq = int(dev_queries.shape[0])
+        t = None if thrs is None else batch_thresholds(thrs, nq)
+        return nq, t, self._out_keys(out_keys, nq, k, dev_queries.device)
+
     def search_device(self, dev_queries, k: int, thr: float, out_keys=None):
         """dev_queries: torch f32 [nq, dim] on this device -> torch int64 [nq, k] of packed keys (async)."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.shape[1] == self.dim
-        nq = dev_queries.shape[0]
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
+        nq, _, out_keys = self._device_batch(dev_queries, k, None, out_keys)
         with self._lock:
             rc = self.lib.tavb_search_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -958,24 +929,15 @@ class Engine:
         torch f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> torch int64 [nq, k] sorted, zero-padded keys
         carrying global ordinals -- or, with dev_rows (torch int32 [S], valid corpus rows; one query), subset positions.  `out_keys`: a
         device tensor or a PINNED host tensor.  Async: `synchronize()` before reading."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.numel() % max(self.dim, 1) == 0
-        nq = dev_queries.numel() // self.dim if self.dim else 0
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        if dev_rows is not None:
-            assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
-        if dev_rows is not None and dev_rows.shape[0] == 0:  # (an empty tensor has no address to tell the library "a subset" by)
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys, flat=True)  # (flat: one query may come as [dim])
+        rows_ptr, n_rows = (None, 0) if dev_rows is None else self._row_list(dev_rows)
+        if dev_rows is not None and n_rows == 0:  # (an empty tensor has no address to tell the library "a subset" by)
             self.synchronize()
             out_keys.view(-1)[: nq * k].zero_()
-            torch.cuda.current_stream(self.device).synchronize()
+            self._torch.cuda.current_stream(self.device).synchronize()
             return out_keys
         with self._lock:
-            rc = self.lib.tavb_search_topk_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t),
-                                                  None if dev_rows is None else c_void_p(dev_rows.data_ptr()),
-                                                  0 if dev_rows is None else int(dev_rows.shape[0]), c_void_p(out_keys.data_ptr()))
+            rc = self.lib.tavb_search_topk_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), rows_ptr, n_rows, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 
@@ -985,17 +947,10 @@ class Engine:
         rows); thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> torch int64 [nq, k] sorted, zero-padded keys.  remap=True:
         the keys carry global ordinals (ordinal_base + row: what the key merges take; dev_rows ascending); False: positions in dev_rows.
         `out_keys`: a device tensor or a PINNED host tensor.  Async: `synchronize()` before reading."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.dim() == 2 and dev_queries.shape[1] == self.dim
-        assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
-        nq = int(dev_queries.shape[0])
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
-        n = int(dev_rows.shape[0])
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        rows_ptr, n = self._row_list(dev_rows)
         with self._lock:  # (an empty tensor has no address to name "a subset" by: length 0 and no pointer -- the library enqueues zero keys)
-            rc = self.lib.tavb_search_subset_batch_device(self._h, c_void_p(dev_queries.data_ptr()), nq, c_void_p(dev_rows.data_ptr()) if n else None, n,
+            rc = self.lib.tavb_search_subset_batch_device(self._h, c_void_p(dev_queries.data_ptr()), nq, rows_ptr, n,
                                                           k, _addr(t), 1 if remap else 0, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
@@ -1006,9 +961,7 @@ class Engine:
         torch = self._torch
         assert dev_query.dtype == torch.float32 and dev_query.is_contiguous() and dev_query.numel() == self.dim
         assert dev_rows.dtype == torch.int32 and dev_rows.is_contiguous() and dev_rows.dim() == 1
-        if out_keys is None:
-            out_keys = torch.empty((1, k), dtype=torch.int64, device=dev_query.device)
-        self._check_out_keys(out_keys, 1, k)
+        out_keys = self._out_keys(out_keys, 1, k, dev_query.device)
         with self._lock:
             rc = self.lib.tavb_search_subset_device(self._h, c_void_p(dev_query.data_ptr()), c_void_p(dev_rows.data_ptr()),
                                                     dev_rows.shape[0], k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
@@ -1033,12 +986,7 @@ class Engine:
     def search_allgather(self, dev_queries, k: int, thr: float, out_keys=None):
         """Collective `search_device`: every rank passes the same queries and gets the merged whole-corpus key lists [nq, k].
         `out_keys`: a device tensor or a PINNED host tensor (int64 [nq, k]; the merge kernel writes it directly).  Async."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.shape[1] == self.dim
-        nq = dev_queries.shape[0]
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
+        nq, _, out_keys = self._device_batch(dev_queries, k, None, out_keys)
         with self._lock:
             rc = self.lib.tavb_search_allgather(self._h, c_void_p(dev_queries.data_ptr()), nq, k, c_float(float(thr)), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -1049,8 +997,7 @@ class Engine:
         torch = self._torch
         assert dev_local_keys.dtype == torch.int64 and dev_local_keys.is_contiguous() and dev_local_keys.dim() == 2
         nq, k = dev_local_keys.shape
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_local_keys.device)
+        out_keys = self._out_keys(out_keys, nq, k, dev_local_keys.device)
         with self._lock:
             rc = self.lib.tavb_allgather_merge(self._h, c_void_p(dev_local_keys.data_ptr()), nq, k, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -1059,13 +1006,7 @@ class Engine:
     def search_topk_allgather(self, dev_queries, k: int, thrs, out_keys=None):
         """Collective `search_topk_device` (tavb_search_topk_allgather): every rank passes the same queries and thresholds and gets the
         merged whole-corpus key lists [nq, k], 1 <= k <= MAX_LARGE_K.  `out_keys`: a device tensor or a PINNED host tensor.  Async."""
-        torch = self._torch
-        assert dev_queries.dtype == torch.float32 and dev_queries.is_contiguous() and dev_queries.shape[1] == self.dim
-        nq = dev_queries.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_queries.device)
-        self._check_out_keys(out_keys, nq, k)
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
         with self._lock:
             rc = self.lib.tavb_search_topk_allgather(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -1076,9 +1017,7 @@ class Engine:
         torch = self._torch
         assert dev_local_keys.dtype == torch.int64 and dev_local_keys.is_contiguous() and dev_local_keys.dim() == 2
         nq, k = dev_local_keys.shape
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_local_keys.device)
-        self._check_out_keys(out_keys, nq, k)
+        out_keys = self._out_keys(out_keys, nq, k, dev_local_keys.device)
         with self._lock:
             rc = self.lib.tavb_allgather_merge_topk(self._h, c_void_p(dev_local_keys.data_ptr()), nq, k, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
@@ -1097,13 +1036,11 @@ class Engine:
         torch = self._torch
         assert dev_lists.dtype == torch.int64 and dev_lists.is_contiguous() and dev_lists.dim() == 3
         n_lists, nq, k = dev_lists.shape
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_lists.device)
+        out_keys = self._out_keys(out_keys, nq, k, dev_lists.device)
         with self._lock:
             rc = self.lib.tavb_merge_device(self._h, c_void_p(dev_lists.data_ptr()), n_lists, nq, k, c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
-
 
     def merge_topk_device(self, dev_lists, out_keys=None, query_major: bool = False):
         """`merge_device` for lists of up to MAX_LARGE_K keys (tavb_merge_topk_device): dev_lists torch int64 [n_lists, nq, k] -- or
@@ -1114,9 +1051,7 @@ class Engine:
             nq, n_lists, k = dev_lists.shape
         else:
             n_lists, nq, k = dev_lists.shape
-        if out_keys is None:
-            out_keys = torch.empty((nq, k), dtype=torch.int64, device=dev_lists.device)
-        self._check_out_keys(out_keys, nq, k)
+        out_keys = self._out_keys(out_keys, nq, k, dev_lists.device)
         with self._lock:
             rc = self.lib.tavb_merge_topk_device(self._h, c_void_p(dev_lists.data_ptr()), -n_lists if query_major else n_lists, nq, k,
                                                  c_void_p(out_keys.data_ptr()))

@@ -188,11 +188,8 @@ class DeviceGroup:
         return ords[0, :m], scs[0, :m]
 
     def search_batch(self, queries, k: int, thrs):
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (a.shape[0],)))
-        return _native.decode_keys(self._gather(a, k, t))
+        a = _native.batch_queries(queries, self.dim)
+        return _native.decode_keys(self._gather(a, k, _native.batch_thresholds(thrs, a.shape[0])))
 
     # -- exact top-k past the fused selection (tavb_search_topk_device per shard + tavb_merge_topk_host) -------------------------
     def large_k_capable(self) -> bool:
@@ -234,26 +231,30 @@ class DeviceGroup:
             torch.cuda.current_stream(d).synchronize()
         return out
 
+    def _on_all_parts(self, parts, a: np.ndarray, k: int, enqueue) -> np.ndarray:
+        """One device-resident lookup per part -- parts: [(slot, engine, ...)]; `enqueue(part, that device's copy of the queries `a`, that
+        part's int64 [nq, k] of the pinned lists)` -- enqueued on every part before any is waited for -> the lists, uint64 [parts, nq, k]
+        (a view of the reused pinned buffer)."""
+        lists = self._topk_lists(len(parts), a.shape[0], k)
+        dqs = self._device_queries([part[:2] for part in parts], a)
+        for part, dq, out in zip(parts, dqs, lists):  # enqueue everywhere first: the devices scan concurrently
+            enqueue(part, dq, out)
+        for part in parts:
+            part[1].synchronize()
+        return lists.numpy().view(np.uint64)
+
     @_locked
     def search_topk(self, queries, k: int, thrs):
         """`Engine.search_topk` over the shards: queries f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K ->
         (ordinals [nq,k], scores [nq,k], counts [nq])."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        a = _native.batch_queries(queries, self.dim)
         nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
-        act = self._active()
-        if not act or nq == 0:
+        t = _native.batch_thresholds(thrs, nq)
+        parts = [(g, e) for g, (e, lo, hi) in enumerate(self._active())]
+        if not parts or nq == 0:
             return np.zeros((nq, k), np.int64), np.zeros((nq, k), np.float32), np.zeros(nq, np.int32)
-        lists = self._topk_lists(len(act), nq, k)
-        dqs = self._device_queries([(g, e) for g, (e, lo, hi) in enumerate(act)], a)
-        for g, (e, lo, hi) in enumerate(act):  # enqueue everywhere first: the devices scan concurrently
-            e.search_topk_device(dqs[g], k, t, out_keys=lists[g])
-        for e, lo, hi in act:
-            e.synchronize()
-        keys = lists.numpy().view(np.uint64)
-        return _native.decode_keys(keys[0] if len(act) == 1 else _native.merge_topk_keys(keys))
+        keys = self._on_all_parts(parts, a, k, lambda part, dq, out: part[1].search_topk_device(dq, k, t, out_keys=out))
+        return _native.decode_keys(keys[0] if len(parts) == 1 else _native.merge_topk_keys(keys))
 
     @_locked
     def search_subset_topk(self, q, rows: np.ndarray, k: int, thr: np.float32):
@@ -270,13 +271,7 @@ class DeviceGroup:
                 parts.append((g, e, idx, torch.from_numpy((rows[idx] - lo).astype(np.int32)).to(torch.device("cuda", e.device))))
         if not parts:
             return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
-        lists = self._topk_lists(len(parts), 1, k)
-        dqs = self._device_queries([(g, e) for g, e, idx, dev_rows in parts], a)
-        for i, (g, e, idx, dev_rows) in enumerate(parts):
-            e.search_topk_device(dqs[i], k, thr, out_keys=lists[i], dev_rows=dev_rows)
-        for g, e, idx, dev_rows in parts:
-            e.synchronize()
-        keys = lists.numpy().view(np.uint64).copy()
+        keys = self._on_all_parts(parts, a, k, lambda part, dq, out: part[1].search_topk_device(dq, k, thr, out_keys=out, dev_rows=part[3])).copy()
         low = np.uint64(0xFFFFFFFF)
         for i, (g, e, idx, dev_rows) in enumerate(parts):  # positions in the shard's part of the subset -> positions in the caller's list
             row = keys[i, 0]
@@ -330,23 +325,15 @@ class DeviceGroup:
         """`search_topk` among the rows of a mask (handles: `mask_to_rows` under the current bounds): queries f32 [nq, dim]; thrs float32
         [nq] (or one for all); 1 <= k <= MAX_LARGE_K -> (ordinals [nq,k], scores [nq,k], counts [nq]).  One batched call per shard that
         has a handle, all of them enqueued before any is waited for; shards without allowed rows are not visited."""
-        a = np.ascontiguousarray(queries, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != self.dim:
-            raise ValueError(f"queries must be [nq, {self.dim}]")
+        a = _native.batch_queries(queries, self.dim)
         if len(handles) != len(self.engines):
             raise ValueError("one handle (or None) per device")
         nq = a.shape[0]
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thrs, dtype=np.float32), (nq,)))
+        t = _native.batch_thresholds(thrs, nq)
         parts = [(g, e, handles[g]) for g, e in enumerate(self.engines) if handles[g] is not None and self.bounds[g + 1] > self.bounds[g]]
         if not parts or nq == 0:
             return np.zeros((nq, k), np.int64), np.zeros((nq, k), np.float32), np.zeros(nq, np.int32)
-        lists = self._topk_lists(len(parts), nq, k)
-        dqs = self._device_queries([(g, e) for g, e, rows in parts], a)
-        for i, (g, e, rows) in enumerate(parts):  # enqueue everywhere first: the devices scan concurrently
-            e.search_subset_batch_device(dqs[i], rows, k, t, out_keys=lists[i], remap=True)
-        for g, e, rows in parts:
-            e.synchronize()
-        keys = lists.numpy().view(np.uint64)
+        keys = self._on_all_parts(parts, a, k, lambda part, dq, out: part[1].search_subset_batch_device(dq, part[2], k, t, out_keys=out, remap=True))
         if len(parts) == 1:
             return _native.decode_keys(keys[0])
         return _native.decode_keys(_native.merge_keys(keys) if k <= _native.MAX_FUSED_K else _native.merge_topk_keys(keys))

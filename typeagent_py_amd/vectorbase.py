@@ -424,9 +424,7 @@ class VectorBase:
         else:
             host = t[:n].float().cpu().numpy()
         self._keep_host = True  # from here on the host matrix is the authoritative copy (like the reference's)
-        self._host, self._count = host, n  # device copy stays valid: same rows
-        if self._dtype == _native.TAVB_F16:
-            pass  # host copy holds the fp16 values widened to f32
+        self._host, self._count = host, n  # device copy stays valid: same rows (of an fp16 corpus the host copy holds the values widened to f32)
 
     def _reserve(self, extra: int) -> None:
         need = self._count + extra
@@ -465,9 +463,7 @@ class VectorBase:
             self._set_embedding_size(len(row))
         if len(row) != self._embedding_size:
             raise ValueError(f"Embedding size mismatch: expected {self._embedding_size}, got {len(row)}")
-        if self._stream_to_device(row.reshape(1, -1)):
-            pass
-        else:
+        if not self._stream_to_device(row.reshape(1, -1)):
             if self._device_only is not None:
                 self._materialize_host()
             self._reserve(1)
@@ -648,6 +644,62 @@ class VectorBase:
         single-GPU engine with the "sort_all" option on (the default); device groups and test doubles keep the emit-all route."""
         return (max_hits == 0 or max_hits > _native.MAX_LARGE_K) and isinstance(eng, _native.Engine) and eng.get_option("sort_all") != 0
 
+    def _batch_args(self, embeddings, max_hits: int | None, min_score):
+        """(queries float32 [Q, dim], max_hits, float32 threshold(s), the caller's thresholds per query or None) of a batch lookup;
+        `min_score` may be a sequence with one threshold per query."""
+        queries = np.asarray(embeddings, dtype=np.float32)
+        if queries.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
+        if min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1:
+            # one threshold per query (Q calls of the reference have Q `min_score` arguments, :163-173): same kernels as a uniform batch
+            if len(min_score) != len(queries):
+                raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(queries)}")
+            per_query = list(min_score)
+            max_hits, _ = self._limits(max_hits, 0.0)
+            return queries, max_hits, np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32), per_query
+        max_hits, thr = self._limits(max_hits, min_score)
+        return queries, max_hits, thr, None
+
+    @staticmethod
+    def _batch_of_one(embedding) -> np.ndarray:
+        q = np.asarray(embedding, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError(f"Expected 1D embedding, got {q.ndim}D")
+        return q.reshape(1, -1)
+
+    @staticmethod
+    def _wrap_subset(ordinals, n: int) -> tuple[np.ndarray, np.ndarray]:
+        """The caller's ordinals -> (they as int64 [S], the corpus rows they name), wrapped and range-checked as numpy indexes an array of n rows."""
+        subset = np.asarray(ordinals)
+        if subset.dtype.kind not in "iu":
+            raise IndexError("arrays used as indices must be of integer (or boolean) type")
+        subset = subset.astype(np.int64, copy=False).reshape(-1)
+        rows = np.where(subset < 0, subset + n, subset)  # numpy index wrap (:218)
+        bad = (rows < 0) | (rows >= n)
+        if bad.any():
+            raise IndexError(f"index {int(subset[np.argmax(bad)])} is out of bounds for axis 0 with size {n}")
+        return subset, rows
+
+    @staticmethod
+    def _empty_batch(nq: int, max_hits: int, as_arrays: bool):
+        if as_arrays:
+            return np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+        return [[] for _ in range(nq)]
+
+    @staticmethod
+    def _batch_result(ords, scs, cnts, max_hits: int, as_arrays: bool, base: int = 0):
+        """[Q, max_hits] result arrays -> what a batch lookup returns; `base`: the engine's ordinal_base where its ordinals carry it."""
+        if base:
+            ords -= base  # (rows of THIS index, as the subset lookup reports them)
+        if as_arrays:
+            return ords, scs, cnts
+        return _scored_lists(ords, scs, cnts, max_hits)
+
+    @staticmethod
+    def _accept_array(acc: np.ndarray | None) -> np.ndarray | None:
+        """int64 message ordinals -> those the device's int32 map can name (None: no filter)."""
+        return None if acc is None else acc[(acc >= 0) & (acc < 2**31 - 1)]
+
     def fuzzy_lookup_embedding(
         self,
         embedding: NormalizedEmbedding,
@@ -703,16 +755,7 @@ class VectorBase:
         if hit:
             subset, rows, dev_rows = cached[3], None, cached[4]
         else:
-            subset = np.asarray(ordinals_of_subset)
-            if subset.dtype.kind not in "iu":
-                raise IndexError("arrays used as indices must be of integer (or boolean) type")
-            subset = subset.astype(np.int64, copy=False).reshape(-1)
-            rows = np.where(subset < 0, subset + n, subset)  # numpy index wrap (:218)
-            bad = (rows < 0) | (rows >= n)
-            if bad.any():
-                first = int(subset[np.argmax(bad)])
-                raise IndexError(f"index {first} is out of bounds for axis 0 with size {n}")
-            dev_rows = None
+            (subset, rows), dev_rows = self._wrap_subset(ordinals_of_subset, n), None
         eng = self._sync_device()
         if 1 <= max_hits <= _PAGE and isinstance(eng, _native.Engine) and isinstance(ordinals_of_subset, (list, np.ndarray)):
             if dev_rows is None:
@@ -724,7 +767,7 @@ class VectorBase:
             pos, scs = eng.search_subset_resident(embedding, dev_rows, max_hits, thr)
         else:
             if rows is None:
-                rows = np.where(subset < 0, subset + n, subset)
+                rows = self._wrap_subset(subset, n)[1]
             if 1 <= max_hits <= _PAGE:
                 pos, scs = eng.search_subset(embedding, rows, max_hits, thr)
             elif self._large_k(eng, max_hits):
@@ -748,27 +791,11 @@ class VectorBase:
         `as_arrays=True` (1 <= max_hits <= 256) returns (ordinals int64 [Q, max_hits], scores float32 [Q, max_hits], counts
         int32 [Q]) instead of Q lists of ScoredInt: building 32k Python objects takes as long as a third of the 1024-query
         lookup over 10M rows itself."""
-        queries = np.asarray(embeddings, dtype=np.float32)
-        if queries.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
-        if min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1:
-            # one threshold per query (Q calls of the reference have Q `min_score` arguments, :163-173): same kernels as a uniform batch
-            if len(min_score) != len(queries):
-                raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(queries)}")
-            per_query = list(min_score)
-            max_hits, _ = self._limits(max_hits, 0.0)
-            thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32)
-            min_score = None
-        else:
-            per_query = None
-            max_hits, thr = self._limits(max_hits, min_score)
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
         if as_arrays and not (1 <= max_hits <= _PAGE):
             raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
         if self._count == 0 or len(queries) == 0:
-            if as_arrays:
-                nq = len(queries)
-                return np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
-            return [[] for _ in range(len(queries))]
+            return self._empty_batch(len(queries), max_hits, as_arrays)
         if not (1 <= max_hits <= _PAGE):
             eng = self._sync_device()
             if self._large_k(eng, max_hits):  # ONE call: a corpus pass per 8 queries, each query's own threshold
@@ -779,10 +806,7 @@ class VectorBase:
                 return _sorted_lists(ords, scs, cnts)
             return [self.fuzzy_lookup_embedding(q, max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
         eng = self._sync_device()
-        ords, scs, cnts = eng.search_batch(queries, max_hits, thr)
-        if as_arrays:
-            return ords, scs, cnts
-        return _scored_lists(ords, scs, cnts, max_hits)
+        return self._batch_result(*eng.search_batch(queries, max_hits, thr), max_hits, as_arrays)
 
     # ------------------------------------------------------------------ masked lookups (additive)
     def row_mask(self, allowed) -> RowMask:
@@ -826,46 +850,53 @@ class VectorBase:
         return RowMask(self, n, count, dev_rows=dev_rows)
 
     @staticmethod
-    def _mask_tile(eng, mask: RowMask, nq: int, k: int) -> bool:
+    def _mask_plan(eng, mask: RowMask, nq: int, k: int, wide: bool) -> bool:
+        """`_mask_tile` (wide=False) / `_mask_wide`: the engine has the call, the handle what the route reads, and the route's option
+        (0 = never, 2 = wherever the route serves the shape, 1 = where its plan function expects it to win) says so.  The answer is kept on the handle."""
+        call, plan, option, probe_nq, prefix = (("search_masked_wide", "plan_masked_wide", "mask_wide", _native.MFMA_MIN_BATCH, ("wide",)) if wide else
+                                                ("search_masked_batch", "plan_masked", "mask_tile", 64, ()))
+        if mask.dev_bits is None or mask.span is None or (wide and mask.dev_rows is None) or not (hasattr(eng, call) and hasattr(eng, plan)):
+            return False
+        cached = option + "_options"
+        opts = getattr(eng, cached)() if hasattr(eng, cached) else tuple(eng.get_option(n) for n in (option, "mask_tile_min_bytes", "mask_tile_pct"))
+        mode, min_bytes, pct = opts
+        if mode == 0:
+            return False
+        key = prefix + (nq, k, eng.dim, eng.dtype, opts)
+        yes = mask._plans.get(key)
+        if yes is None:
+            if mode == 2:
+                # (tile: 64 queries, wide: the fewest queries the rule takes; one allowed row in a span of one, no floors: the rule says yes
+                # exactly when the route serves the corpus, k and the width)
+                yes = bool(getattr(eng, plan)(probe_nq, k, eng.dim, eng.dtype, 1, 1, 0, 0))
+            else:
+                yes = bool(getattr(eng, plan)(nq, k, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_bytes, pct))
+            mask._plans[key] = yes
+        return yes
+
+    @classmethod
+    def _mask_tile(cls, eng, mask: RowMask, nq: int, k: int) -> bool:
         """Whether a masked batch takes the 32/64-query tile (Engine.search_masked_batch) instead of the gather route: the engine has the
         call, the handle the packed mask, and the option "mask_tile" (0 = never, 2 = wherever the tile serves the shape, 1 = where
         tavb_plan_masked expects it to win: a dense mask under a real batch) says so."""
-        if mask.dev_bits is None or mask.span is None or not (hasattr(eng, "search_masked_batch") and hasattr(eng, "plan_masked")):
-            return False
-        opts = eng.mask_tile_options() if hasattr(eng, "mask_tile_options") else tuple(eng.get_option(n) for n in ("mask_tile", "mask_tile_min_bytes", "mask_tile_pct"))
-        mode, min_bytes, pct = opts
-        if mode == 0:
-            return False
-        key = (nq, k, eng.dim, eng.dtype, opts)
-        tile = mask._plans.get(key)
-        if tile is None:
-            if mode == 2:  # (64 queries, one allowed row in a span of one, no floors: the rule says yes exactly when the tile serves k and the width)
-                tile = bool(eng.plan_masked(64, k, eng.dim, eng.dtype, 1, 1, 0, 0))
-            else:
-                tile = bool(eng.plan_masked(nq, k, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_bytes, pct))
-            mask._plans[key] = tile
-        return tile
+        return cls._mask_plan(eng, mask, nq, k, wide=False)
 
-    @staticmethod
-    def _mask_wide(eng, mask: RowMask, nq: int, k: int) -> bool:
+    @classmethod
+    def _mask_wide(cls, eng, mask: RowMask, nq: int, k: int) -> bool:
         """Whether a masked batch takes the 128/256-query filter tile + rescoring (Engine.search_masked_wide): the engine has the call, the
         handle the packed mask and the row list, and the option "mask_wide" (0 = never, 2 = wherever the route serves the shape, 1 = where
         tavb_plan_masked_wide expects it to win) says so.  The plan is kept on the handle like `_mask_tile`'s."""
-        if mask.dev_bits is None or mask.span is None or mask.dev_rows is None or not (hasattr(eng, "search_masked_wide") and hasattr(eng, "plan_masked_wide")):
-            return False
-        opts = eng.mask_wide_options() if hasattr(eng, "mask_wide_options") else tuple(eng.get_option(n) for n in ("mask_wide", "mask_tile_min_bytes", "mask_tile_pct"))
-        mode, min_bytes, pct = opts
-        if mode == 0:
-            return False
-        key = ("wide", nq, k, eng.dim, eng.dtype, opts)
-        wide = mask._plans.get(key)
-        if wide is None:
-            if mode == 2:  # (the fewest queries the rule takes, one allowed row in a span of one, no floors: yes exactly when the route serves the corpus and k)
-                wide = bool(eng.plan_masked_wide(_native.MFMA_MIN_BATCH, k, eng.dim, eng.dtype, 1, 1, 0, 0))
-            else:
-                wide = bool(eng.plan_masked_wide(nq, k, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_bytes, pct))
-            mask._plans[key] = wide
-        return wide
+        return cls._mask_plan(eng, mask, nq, k, wide=True)
+
+    @classmethod
+    def _masked_route(cls, eng, mask: RowMask, nq: int, k: int) -> int:
+        """The route of a masked batch of k >= 1 hits on a single-GPU engine, as "masked_route" numbers them: 3 = the 128/256-query filter
+        tile + rescoring (k <= 256; tried first), 2 = the 32/64-query tile (k <= 64), 1 = the row list."""
+        if k <= _PAGE and cls._mask_wide(eng, mask, nq, k):
+            return 3
+        if k <= 64 and cls._mask_tile(eng, mask, nq, k):
+            return 2
+        return 1
 
     @staticmethod
     def _masked_native(eng) -> bool:
@@ -897,10 +928,7 @@ class VectorBase:
     ) -> list[ScoredInt]:
         """`fuzzy_lookup_embedding` among the rows `allowed` names (a mask, see `row_mask`, or a `RowMask`): equals
         fuzzy_lookup_embedding_in_subset(embedding, np.flatnonzero(allowed).tolist(), max_hits, min_score)."""
-        q = np.asarray(embedding, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"Expected 1D embedding, got {q.ndim}D")
-        return self.fuzzy_lookup_embeddings_masked(q.reshape(1, -1), allowed, max_hits, min_score)[0]
+        return self.fuzzy_lookup_embeddings_masked(self._batch_of_one(embedding), allowed, max_hits, min_score)[0]
 
     def fuzzy_lookup_embeddings_masked(
         self,
@@ -931,50 +959,29 @@ class VectorBase:
         the 32/64-query tile, and its answers EQUAL the row list's bit for bit -- ordinals, float32 scores and counts -- because the
         rescoring is the streaming kernels' arithmetic; a query with more near-duplicates around its last hit than a candidate band holds is
         re-run over the row list.  `engine.get_option("masked_route")` tells which ran (1 = row list, 2 = 32/64-query tile, 3 = wide)."""
-        queries = np.asarray(embeddings, dtype=np.float32)
-        if queries.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
-        if min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1:
-            if len(min_score) != len(queries):
-                raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(queries)}")
-            per_query = list(min_score)
-            max_hits, _ = self._limits(max_hits, 0.0)
-            thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32)
-        else:
-            per_query = None
-            max_hits, thr = self._limits(max_hits, min_score)
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
         if as_arrays and not (1 <= max_hits <= _PAGE):
             raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
         mask = self._resolve_mask(allowed)
         nq = len(queries)
         if self._count == 0 or mask.count == 0 or nq == 0:
-            if as_arrays:
-                return np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
-            return [[] for _ in range(nq)]
+            return self._empty_batch(nq, max_hits, as_arrays)
         eng = self._sync_device()
         if self._masked_native(eng) and mask.dev_rows is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
-            if 1 <= max_hits <= _PAGE and self._mask_wide(eng, mask, nq, max_hits):
-                ords, scs, cnts = eng.search_masked_wide(queries, mask.dev_bits, mask.dev_rows, max_hits, thr, span=mask.span)
-            elif 1 <= max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
-                ords, scs, cnts = eng.search_masked_batch(queries, mask.dev_bits, max_hits, thr, span=mask.span)
+            route = self._masked_route(eng, mask, nq, max_hits)
+            if route == 3:
+                out = eng.search_masked_wide(queries, mask.dev_bits, mask.dev_rows, max_hits, thr, span=mask.span)
+            elif route == 2:
+                out = eng.search_masked_batch(queries, mask.dev_bits, max_hits, thr, span=mask.span)
             else:
-                ords, scs, cnts = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
-            if eng.ordinal_base:
-                ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
-            if as_arrays:
-                return ords, scs, cnts
-            return _scored_lists(ords, scs, cnts, max_hits)
+                out = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
+            return self._batch_result(*out, max_hits, as_arrays, base=eng.ordinal_base)
         if self._masked_group(eng) and mask.shards is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
             if mask.bounds != tuple(eng.bounds):
                 # the same index at the same length under other shard bounds (grown row by row, then re-uploaded from row 0): the
                 # caller has done nothing wrong -- the handle is cut again, once
                 mask.shards, _, mask.bounds = eng._rows_to_handles(mask.flat())
-            ords, scs, cnts = eng.search_masked(queries, mask.shards, max_hits, thr)
-            if eng.ordinal_base:
-                ords -= eng.ordinal_base  # (rows of THIS index, as the subset lookup reports them)
-            if as_arrays:
-                return ords, scs, cnts
-            return _scored_lists(ords, scs, cnts, max_hits)
+            return self._batch_result(*eng.search_masked(queries, mask.shards, max_hits, thr), max_hits, as_arrays, base=eng.ordinal_base)
         flat = mask.flat()
         lists = [self.fuzzy_lookup_embedding_in_subset(q, flat, max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
         if not as_arrays:
@@ -996,12 +1003,15 @@ class VectorBase:
         self._row_messages = np.array(row_to_message, dtype=np.int64).reshape(-1)  # a snapshot: never an alias of the caller's array
         self._row_messages_rows = -1  # (re-)uploaded on the next message lookup
 
-    def _messages_engine(self):
-        """engine with corpus AND map synced, or None when the aggregation has to run on the host (device group)."""
+    def _check_row_messages(self) -> None:
         if self._row_messages is None:
             raise RuntimeError("set_row_messages() first")
         if len(self._row_messages) < self._count:
             raise ValueError(f"the row -> message map covers {len(self._row_messages)} rows, the index has {self._count}")
+
+    def _messages_engine(self):
+        """engine with corpus AND map synced, or None when the aggregation has to run on the host (device group)."""
+        self._check_row_messages()
         eng = self._sync_device()
         if not isinstance(eng, _native.Engine):
             return None
@@ -1041,9 +1051,7 @@ class VectorBase:
         if eng is None or not (1 <= max_hits <= _PAGE):
             hits = self.fuzzy_lookup_embedding(embedding, max_hits=max_matches, min_score=threshold_score)
             return self._host_rerank(hits, max_matches, None if accept_ordinals is None else set(int(x) for x in accept_ordinals))
-        acc = None if accept_ordinals is None else np.fromiter((int(x) for x in accept_ordinals), dtype=np.int64)
-        if acc is not None:
-            acc = acc[(acc >= 0) & (acc < 2**31 - 1)]
+        acc = self._accept_array(None if accept_ordinals is None else np.fromiter((int(x) for x in accept_ordinals), dtype=np.int64))
         msgs, scs = eng.search_messages(embedding, max_hits, thr, cut, accept=acc)
         return [ScoredInt(int(m), float(sc)) for m, sc in zip(msgs.tolist(), scs.tolist())]
 
@@ -1063,36 +1071,11 @@ class VectorBase:
         if eng is None or not (1 <= max_hits <= _PAGE):
             hits = self.fuzzy_lookup_embedding_in_subset(embedding, rows_of_subset, max_hits=max_matches, min_score=threshold_score)
             return self._host_rerank(hits, None)
-        subset = np.asarray(rows_of_subset)
-        if subset.dtype.kind not in "iu":
-            raise IndexError("arrays used as indices must be of integer (or boolean) type")
-        subset = subset.astype(np.int64, copy=False).reshape(-1)
-        n = self._count
-        rows = np.where(subset < 0, subset + n, subset)
-        bad = (rows < 0) | (rows >= n)
-        if bad.any():
-            raise IndexError(f"index {int(subset[np.argmax(bad)])} is out of bounds for axis 0 with size {n}")
+        rows = self._wrap_subset(rows_of_subset, self._count)[1]
         msgs, scs = eng.search_messages(embedding, max_hits, thr, max_hits, subset_rows=rows)
         return [ScoredInt(int(m), float(sc)) for m, sc in zip(msgs.tolist(), scs.tolist())]
 
     # ------------------------------------------------------------------ scoped and batched message lookups (additive)
-    def _check_row_messages(self) -> None:
-        if self._row_messages is None:
-            raise RuntimeError("set_row_messages() first")
-        if len(self._row_messages) < self._count:
-            raise ValueError(f"the row -> message map covers {len(self._row_messages)} rows, the index has {self._count}")
-
-    def _message_thresholds(self, queries: np.ndarray, max_matches, threshold_score):
-        """(max_hits, float32 threshold(s), the caller's thresholds per query or None) as `fuzzy_lookup_embeddings_masked` resolves them."""
-        if threshold_score is not None and not np.isscalar(threshold_score) and np.ndim(threshold_score) == 1:
-            if len(threshold_score) != len(queries):
-                raise ValueError(f"Number of thresholds {len(threshold_score)} does not match number of embeddings {len(queries)}")
-            per_query = list(threshold_score)
-            max_hits, _ = self._limits(max_matches, 0.0)
-            return max_hits, np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in per_query], dtype=np.float32), per_query
-        max_hits, thr = self._limits(max_matches, threshold_score)
-        return max_hits, thr, None
-
     def message_mask(self, message_ordinals) -> RowMask:
         """A scope of MESSAGE ordinals -> the `RowMask` of their chunk rows: equals
         row_mask(np.isin(row_messages[:len(self)], message_ordinals) & (row_messages[:len(self)] >= 0)) -- ordinals that name no message
@@ -1109,7 +1092,7 @@ class VectorBase:
             return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
         eng = self._messages_engine()
         if eng is not None and self._masked_native(eng) and hasattr(eng, "mask_from_messages"):
-            dev_rows, count, dev_bits = eng.mask_from_messages(acc[(acc >= 0) & (acc < 2**31 - 1)])
+            dev_rows, count, dev_bits = eng.mask_from_messages(self._accept_array(acc))
             return RowMask(self, n, count, dev_rows=dev_rows, dev_bits=dev_bits)
         held = self._row_messages[:n]
         return self.row_mask(np.isin(held, acc) & (held >= 0))
@@ -1124,10 +1107,7 @@ class VectorBase:
         """`lookup_messages_in_subset_by_embedding` among the rows `allowed` names (a mask, see `row_mask`; a `RowMask`, e.g. from
         `message_mask`): equals lookup_messages_in_subset_by_embedding(embedding, np.flatnonzero(allowed).tolist(), max_matches,
         threshold_score)."""
-        q = np.asarray(embedding, dtype=np.float32)
-        if q.ndim != 1:
-            raise ValueError(f"Expected 1D embedding, got {q.ndim}D")
-        return self.lookup_messages_by_embeddings_masked(q.reshape(1, -1), allowed, max_matches, threshold_score)[0]
+        return self.lookup_messages_by_embeddings_masked(self._batch_of_one(embedding), allowed, max_matches, threshold_score)[0]
 
     def lookup_messages_by_embeddings_masked(
         self,
@@ -1148,10 +1128,7 @@ class VectorBase:
         and counts; on the 32/64-query tile (route 2) the messages are identical except among float32 near-ties and the scores agree
         within 1e-5.  Everything else (max_matches outside 1..256, device groups, test doubles) goes through
         `fuzzy_lookup_embeddings_masked` and the host aggregation."""
-        queries = np.asarray(embeddings, dtype=np.float32)
-        if queries.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
-        max_hits, thr, per_query = self._message_thresholds(queries, max_matches, threshold_score)
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_matches, threshold_score)
         self._check_row_messages()
         mask = self._resolve_mask(allowed)
         nq = len(queries)
@@ -1159,12 +1136,7 @@ class VectorBase:
             return [[] for _ in range(nq)]
         eng = self._messages_engine()
         if eng is not None and self._masked_native(eng) and hasattr(eng, "search_messages_masked") and mask.dev_rows is not None and 1 <= max_hits <= _PAGE:
-            if self._mask_wide(eng, mask, nq, max_hits):
-                route = 3
-            elif max_hits <= 64 and self._mask_tile(eng, mask, nq, max_hits):
-                route = 2
-            else:
-                route = 1
+            route = self._masked_route(eng, mask, nq, max_hits)
             msgs, scs, cnts = eng.search_messages_masked(queries, mask.dev_bits, mask.dev_rows, max_hits, thr, max_hits, route, span=mask.span)
             return _scored_lists(msgs, scs, cnts, max_hits)
         lists = self.fuzzy_lookup_embeddings_masked(queries, mask, max_matches, threshold_score if per_query is None else per_query)
@@ -1182,10 +1154,7 @@ class VectorBase:
         (tavb_search_messages_batch: the batch's full-corpus top-k, the accept filter, the aggregation of every query in one launch).  Bit
         for bit wherever the batch route is (the streaming kernels, the wide tile + rescoring); a batch the 32/64-query tile serves agrees
         the way `fuzzy_lookup_embeddings` does there.  `threshold_score` may be a sequence with one threshold per query."""
-        queries = np.asarray(embeddings, dtype=np.float32)
-        if queries.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {queries.ndim}D")
-        max_hits, thr, per_query = self._message_thresholds(queries, max_matches, threshold_score)
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_matches, threshold_score)
         nq = len(queries)
         if self._count == 0 or nq == 0:
             return [[] for _ in range(nq)]
@@ -1193,9 +1162,7 @@ class VectorBase:
         eng = self._messages_engine()
         if eng is None or not hasattr(eng, "search_messages_batch") or not (1 <= max_hits <= _PAGE):
             return [self.lookup_messages_by_embedding(q, max_matches, threshold_score if per_query is None else per_query[i], accept) for i, q in enumerate(queries)]
-        acc = None if accept is None else np.asarray(accept, dtype=np.int64).reshape(-1)
-        if acc is not None:
-            acc = acc[(acc >= 0) & (acc < 2**31 - 1)]
+        acc = self._accept_array(None if accept is None else np.asarray(accept, dtype=np.int64).reshape(-1))
         cut = max_hits if max_matches is not None else max(max_hits, 1)
         msgs, scs, cnts = eng.search_messages_batch(queries, max_hits, thr, cut, accept=acc)
         return _scored_lists(msgs, scs, cnts, max_hits)
