@@ -59,6 +59,15 @@ extern "C" {
 #define TAVB_MAX_STREAM_QUERIES 8
 /* Rows of a mask one workgroup of tavb_mask_expand covers (its two launches have ceil(rows / this) workgroups each). */
 #define TAVB_MASK_ROWS_PER_WORKGROUP 16384
+/* Scope algebra (tavb_mask_from_ranges, tavb_mask_combine): most range collections of one scope, most operands of one combination, the
+ * operations, and the most merged intervals (all collections together) a workgroup of the range kernel stages in LDS -- one more and it
+ * searches them in device memory. */
+#define TAVB_MAX_SCOPE_COLLECTIONS 8
+#define TAVB_MAX_MASK_OPERANDS 8
+#define TAVB_MASK_AND 0
+#define TAVB_MASK_OR 1
+#define TAVB_MASK_ANDNOT 2
+#define TAVB_SCOPE_LDS_RANGES 1024
 
 typedef struct tavb_ctx tavb_ctx;
 
@@ -487,6 +496,38 @@ int tavb_search_messages_masked(tavb_ctx* ctx, const float* queries_host, int32_
 int tavb_search_messages_batch(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores,
                                const int32_t* accept_msgs_host, int64_t n_accept, int32_t max_messages, int64_t* out_messages, float* out_scores,
                                int32_t* out_counts);
+
+/* ---- scope algebra: masks from ranges, and AND / OR / NOT of masks, on the device ------------------------------------------------------
+ * Both calls write a mask in the bit form above -- every word of (rows + 31) / 32, the bits at or beyond `rows` ZERO -- and, in the same
+ * launch, the per-chunk popcounts tavb_mask_expand's count pass would write and every chunk's count, first and last set row (pinned host
+ * memory, summed on the host after the call's one synchronise) -> *out_info: the mask's count and span (an empty mask: 0, 0, -1).
+ * rows == the corpus' rows.  dev_rows_out / cap as for tavb_mask_expand: NULL with cap == 0 asks for the mask and its info only (ONE
+ * launch); otherwise the write pass of tavb_mask_expand follows on the counts already made (TWO launches) and leaves the set rows in
+ * ascending order in dev_rows_out [0, count); cap < count returns TAVB_E_INVALID with *out_info filled and nothing written at or beyond
+ * cap.  rows == 0: empty info, nothing launched.  Each call synchronises the context's stream once.  No atomics on mask words.  Timed under
+ * TAVB_KERNEL_CONVERT.
+ *
+ * tavb_mask_from_ranges: the mask of a scope given as n_collections (0 .. TAVB_MAX_SCOPE_COLLECTIONS) collections of half-open integer
+ * ranges [start, end): ranges_host [total][2] holds the collections one after another, collection_sizes_host [n_collections] their
+ * lengths (total = their sum, at most 2^20).  domain 0 = rows: x = r; domain 1 = messages: x = map[r], the context's row -> message map
+ * (tavb_set_row_messages) -- a row whose map value is below 0 or at or beyond n_messages is never allowed, and the call fails as
+ * tavb_mask_from_messages does without a map or with one shorter than the corpus.  Row r is set when, for EVERY collection, x lies in one
+ * of its ranges: zero collections allow everything the domain can name, a collection with no non-empty range allows nothing.  Ranges may
+ * be unsorted, overlapping, duplicated or empty (start >= end) and may reach below 0 or beyond the domain: each collection is sorted,
+ * clipped and merged into disjoint ascending intervals on the host, copied to the device (8 bytes per interval), and the kernel does one
+ * binary search per collection and row -- in LDS when at most TAVB_SCOPE_LDS_RANGES intervals are left, else in device memory.
+ *
+ * tavb_mask_combine: dev_bits_out = op(m0 .. m(n-1)) word by word for 1 <= n_masks <= TAVB_MAX_MASK_OPERANDS masks of `rows` rows
+ * (dev_masks: a HOST array of n_masks device pointers): TAVB_MASK_AND, TAVB_MASK_OR, or TAVB_MASK_ANDNOT = m0 & ~(m1 | ..) -- with one
+ * operand the complement of m0.  Input bits at or beyond `rows` are ignored (they may hold anything).  dev_bits_out may be any of the
+ * operands: a thread reads its word of every operand before it writes it. */
+typedef struct {
+  int64_t count, first_row, last_row; /* an empty mask: 0, 0, -1 */
+} tavb_mask_info;
+int tavb_mask_from_ranges(tavb_ctx* ctx, const int64_t* ranges_host, const int32_t* collection_sizes_host, int32_t n_collections, int32_t domain,
+                          int64_t rows, uint32_t* dev_bits_out, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
+int tavb_mask_combine(tavb_ctx* ctx, int32_t op, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, uint32_t* dev_bits_out,
+                      int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
 
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */

@@ -23,6 +23,14 @@ MAX_FUSED_K = 256
 MAX_LARGE_K = 16384  # TAVB_MAX_LARGE_K: largest k of tavb_search_topk (exact top-k after one corpus pass)
 MAX_STREAM_QUERIES = 8
 MASK_ROWS_PER_WORKGROUP = 16384  # TAVB_MASK_ROWS_PER_WORKGROUP: rows of a mask one workgroup of tavb_mask_expand covers
+# scope algebra (tavb_mask_from_ranges, tavb_mask_combine): TAVB_MAX_SCOPE_COLLECTIONS, TAVB_MAX_MASK_OPERANDS, TAVB_MASK_AND / _OR / _ANDNOT,
+# TAVB_SCOPE_LDS_RANGES (most merged intervals of a scope the range kernel stages in LDS), the most ranges of one scope
+MAX_SCOPE_COLLECTIONS = 8
+MAX_MASK_OPERANDS = 8
+MASK_AND, MASK_OR, MASK_ANDNOT = 0, 1, 2
+SCOPE_LDS_RANGES = 1024
+MAX_SCOPE_RANGES = 1 << 20
+SCOPE_DOMAINS = {"rows": 0, "messages": 1}
 
 KERNEL_SCAN, KERNEL_MERGE, KERNEL_MFMA, KERNEL_NORMALIZE, KERNEL_CONVERT, KERNEL_MFMA_SAMPLE, KERNEL_SKINNY, KERNEL_RESCORE, KERNEL_EXCHANGE, KERNEL_TOPK = range(10)
 COMM_ID_BYTES = 128
@@ -91,6 +99,8 @@ _SIGNATURES = [
     ("tavb_search_messages_masked", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_messages_batch", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_mask_from_ranges", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_mask_combine", c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -135,6 +145,56 @@ def pack_mask_bits(mask: np.ndarray) -> np.ndarray:
     words = np.zeros(((m.shape[0] + 31) // 32) * 4, dtype=np.uint8)
     words[: packed.shape[0]] = packed
     return words.view("<u4")
+
+
+class MaskInfo(ctypes.Structure):
+    """tavb_mask_info: a mask's count and span (an empty mask: 0, 0, -1)."""
+
+    _fields_ = [("count", c_int64), ("first_row", c_int64), ("last_row", c_int64)]
+
+
+def range_collections(collections) -> list[np.ndarray]:
+    """The collections of a scope -- each a sequence of half-open integer (start, end) ranges, in any order, overlapping, duplicated or
+    empty -- -> one int64 [m, 2] array each.  Needs no GPU."""
+    out = []
+    for c in collections:
+        a = np.asarray(c if isinstance(c, np.ndarray) else list(c))
+        if a.size == 0:
+            a = np.zeros((0, 2), dtype=np.int64)
+        if a.dtype.kind not in "iu":
+            raise TypeError("range bounds must be integers")
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("a collection is a sequence of (start, end) pairs")
+        out.append(np.ascontiguousarray(a, dtype=np.int64))
+    if sum(len(a) for a in out) > MAX_SCOPE_RANGES:
+        raise ValueError(f"a scope has at most {MAX_SCOPE_RANGES} ranges")
+    return out
+
+
+def merge_ranges(ranges: np.ndarray, n: int) -> np.ndarray:
+    """int64 [m, 2] half-open ranges -> the same set inside [0, n) as disjoint ascending intervals, int64 [m', 2]: what
+    tavb_mask_from_ranges does to every collection before the upload.  Needs no GPU."""
+    a = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    s, e = np.maximum(a[:, 0], 0), np.minimum(a[:, 1], int(n))
+    keep = s < e
+    s, e = s[keep], e[keep]
+    if s.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if int(n) >= 1 << 31:
+        raise ValueError("ranges are merged over at most 2^31 - 1 values")
+    key = np.sort((s << 32) | e)  # by start, then end: both fit 31 bits
+    s, e = key >> 32, np.maximum.accumulate(key & 0xFFFFFFFF)
+    opens = np.concatenate([[True], s[1:] > e[:-1]])  # an interval that starts beyond everything before it
+    return np.stack([s[opens], e[np.concatenate([opens[1:], [True]])]], axis=1)
+
+
+def ranges_to_bool(ranges: np.ndarray, n: int) -> np.ndarray:
+    """bool [n]: the union of int64 [m, 2] half-open ranges inside [0, n).  Needs no GPU."""
+    m = merge_ranges(ranges, n)
+    edge = np.zeros(int(n) + 1, dtype=np.int64)
+    np.add.at(edge, m[:, 0], 1)
+    np.add.at(edge, m[:, 1], -1)
+    return np.cumsum(edge[:-1]) > 0
 
 
 def plan_ladder(rows: int, nq: int, n_cu: int = 256) -> list[int]:
@@ -837,6 +897,69 @@ class Engine:
             rc = self.lib.tavb_mask_from_messages(self._h, _addr(acc) if acc.size else None, int(acc.size), rows, c_void_p(bits.data_ptr()) if rows else None)
         _check(self.lib, rc)
         return (*self.expand_mask_bits(bits, rows), bits)  # (same stream: nothing to wait for)
+
+    # scope algebra -------------------------------------------------------------------
+    def _mask_algebra(self, call, bits, bound: int):
+        """One tavb_mask_from_ranges / tavb_mask_combine call that writes `bits` and a row list of at most `bound` rows ->
+        (dev_rows, count, bits, span), span = (first, last) set row or None.  A list that fills less than half of its bound is copied into
+        a tensor of its own size, so that a small result does not pin a large allocation."""
+        torch = self._torch
+        bound = int(bound)
+        out = torch.empty(bound, dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+        info = MaskInfo()
+        with self._lock:
+            rc = call(c_void_p(out.data_ptr()) if bound else None, bound, byref(info))
+        _check(self.lib, rc)
+        n = int(info.count)
+        dev_rows = out[:n].clone() if bound > 2 * n else out[:n]
+        return dev_rows, n, bits, ((int(info.first_row), int(info.last_row)) if n else None)
+
+    def mask_from_ranges(self, collections, domain="rows"):
+        """The mask of a scope of ranges (tavb_mask_from_ranges): `collections`, up to 8 of them, each a sequence of half-open (start, end)
+        ranges over the rows (domain "rows") or over the message ordinals of `set_row_messages` (domain "messages"); a row is set when
+        every collection has a range that holds it (its message) -> (torch int32 [count] on the device: the set rows in ascending order;
+        count; the packed mask, torch int32 [(rows + 31) // 32], tail bits zero; span = (first, last) set row, or None).  Rows: the
+        merged ranges bound the count, so it is one call of two launches.  Messages: the mask and its count first (one launch), then
+        the row list from the mask."""
+        torch = self._torch
+        dom = SCOPE_DOMAINS[domain] if isinstance(domain, str) else int(domain)
+        cols = range_collections(collections)
+        if len(cols) > MAX_SCOPE_COLLECTIONS:
+            raise ValueError(f"a scope has at most {MAX_SCOPE_COLLECTIONS} collections (got {len(cols)})")
+        rows = int(self.rows)
+        ranges = np.ascontiguousarray(np.concatenate(cols)) if cols else np.zeros((0, 2), dtype=np.int64)
+        sizes = np.array([len(c) for c in cols], dtype=np.int32)
+        bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=torch.device("cuda", self.device))
+        bits_ptr = c_void_p(bits.data_ptr()) if rows else None
+
+        def call(out_ptr, cap, info):
+            return self.lib.tavb_mask_from_ranges(self._h, _addr(ranges) if ranges.size else None, _addr(sizes) if sizes.size else None, len(cols), dom, rows,
+                                                  bits_ptr, out_ptr, cap, info)
+
+        if dom == 0:  # every collection's merged length bounds the count of their intersection
+            bound = min((int(np.diff(merge_ranges(c, rows), axis=1).sum()) for c in cols), default=rows)
+            return self._mask_algebra(call, bits, bound)
+        _, n, _, span = self._mask_algebra(call, bits, 0)
+        dev_rows, n = self.expand_mask_bits(bits, rows, cap=n)
+        return dev_rows, n, bits, span
+
+    def mask_combine(self, op: int, dev_bits_list, cap: int):
+        """AND / OR / ANDNOT of 1 .. 8 packed masks on the device (tavb_mask_combine; op: MASK_AND, MASK_OR, MASK_ANDNOT = the first
+        without the others, with one operand its complement) -> the quadruple of `mask_from_ranges`.  `cap`: a bound of the result's
+        count (a smaller one raises ValueError); 0 asks for the mask, its count and its span only."""
+        torch = self._torch
+        masks = list(dev_bits_list)
+        if not 1 <= len(masks) <= MAX_MASK_OPERANDS:
+            raise ValueError(f"a combination has 1 .. {MAX_MASK_OPERANDS} operands (got {len(masks)})")
+        rows = int(self.rows)
+        for m in masks:
+            assert m.dtype == torch.int32 and m.is_contiguous() and m.dim() == 1 and m.numel() * 32 >= rows
+        ptrs = (c_void_p * len(masks))(*[m.data_ptr() for m in masks])
+        bits = torch.empty((rows + 31) // 32, dtype=torch.int32, device=torch.device("cuda", self.device))
+        bits_ptr = c_void_p(bits.data_ptr()) if rows else None
+        return self._mask_algebra(lambda out_ptr, n, info: self.lib.tavb_mask_combine(self._h, int(op), ptrs, len(masks), rows, bits_ptr, out_ptr, n, info),
+                                  bits, cap)
 
     def search_messages_masked(self, queries, dev_bits, dev_rows, k: int, thrs, max_messages: int, route: int, span=None):
         """A masked batch aggregated to messages in one submission (tavb_search_messages_masked): the arguments of `search_masked_wide`

@@ -167,6 +167,47 @@ def lookup_messages_in_subset(
     return best_score_per_message(hits, row_to_message, max_matches)
 
 
+def _message_range(text_range) -> tuple[int, int]:
+    """A `TextRange` (duck-typed: `.start` / `.end` with `.message_ordinal` / `.chunk_ordinal`; end None = a point) -> the half-open range
+    of MESSAGE ordinals m whose first chunk it contains, i.e. `TextRange(TextLocation(m, 0)) in text_range` by the reference's
+    `__contains__` (knowpro/interfaces_core.py:266-297): (m, 0) >= start and (m, 1) <= the effective end."""
+    start, end = text_range.start, getattr(text_range, "end", None)
+    first = int(start.message_ordinal) + (0 if int(start.chunk_ordinal) == 0 else 1)
+    if end is None:  # the point (m, c): the chunk range [(m, c), (m, c + 1))
+        return (first, first + 1) if int(start.chunk_ordinal) == 0 else (first, first)
+    return first, int(end.message_ordinal) + (0 if int(end.chunk_ordinal) == 0 else 1)
+
+
+def _is_range_collection(obj) -> bool:
+    return hasattr(obj, "get_ranges") and not hasattr(obj, "text_ranges")
+
+
+def is_text_scope(scope) -> bool:
+    """Whether `scope` is a `TextRangesInScope`, a `TextRangeCollection`, or a non-empty list or tuple of either (duck-typed, no import
+    of typeagent)."""
+    if hasattr(scope, "text_ranges") or _is_range_collection(scope):
+        return True
+    return isinstance(scope, (list, tuple)) and len(scope) > 0 and all(hasattr(s, "text_ranges") or _is_range_collection(s) for s in scope)
+
+
+def scope_collections(scope) -> list[list[tuple[int, int]]]:
+    """A `TextRangesInScope` (knowpro/collections.py:541-562), a `TextRangeCollection` (:486-538), or a list of either -> the scope as
+    collections of half-open MESSAGE-ordinal ranges, what `VectorBase.range_mask(collections, of="messages")` takes: message m is in
+    the result's scope exactly when `scope.is_range_in_scope(TextRange(TextLocation(m, 0)))` -- some range of every collection contains
+    the message's first chunk.  A `TextRangesInScope` whose `text_ranges` is None contributes no collection (everything is in scope); an
+    empty `TextRangeCollection` one empty collection (nothing is)."""
+    if hasattr(scope, "text_ranges"):
+        return [] if scope.text_ranges is None else [[_message_range(r) for r in c.get_ranges()] for c in scope.text_ranges]
+    if _is_range_collection(scope):
+        return [[_message_range(r) for r in scope.get_ranges()]]
+    out: list[list[tuple[int, int]]] = []
+    for part in scope:
+        if not (hasattr(part, "text_ranges") or _is_range_collection(part)):
+            raise TypeError(f"expected a TextRangesInScope or a TextRangeCollection, got {type(part).__name__}")
+        out.extend(scope_collections(part))
+    return out
+
+
 def lookup_messages_in_scope(
     vector_base: VectorBase,
     embedding_or_embeddings,
@@ -180,11 +221,18 @@ def lookup_messages_in_scope(
     expanded once), best score per message, the cut of `lookup_messages_in_subset` -- without the host row list that function is handed:
     the scope becomes a row mask on the device (`VectorBase.message_mask`) and the lookup is `lookup_messages_by_embeddings_masked`.  A 1-D
     embedding returns one list of ScoredInt(message, score); a 2-D array of embeddings a list of such lists, served by ONE device
-    submission.  `row_to_message`: the array of message ordinals per index position (-1: none); a callable is not supported here."""
+    submission.  `row_to_message`: the array of message ordinals per index position (-1: none); a callable is not supported here.
+    `scope` may also be the reference's own scope object -- a `TextRangesInScope`, a `TextRangeCollection` or a list of either: it is turned
+    into ranges of message ordinals (`scope_collections`) and becomes the mask through `VectorBase.range_mask(..., of="messages")`."""
     if callable(row_to_message):
         raise TypeError("lookup_messages_in_scope needs row_to_message as a sequence (the map is searched on the device)")
     _ensure_row_messages(vector_base, row_to_message)
-    mask = scope if isinstance(scope, RowMask) else vector_base.message_mask(scope)
+    if isinstance(scope, RowMask):
+        mask = scope
+    elif is_text_scope(scope):  # the reference's own scope objects: ranges of message ordinals, intersected on the device
+        mask = vector_base.range_mask(scope_collections(scope), of="messages")
+    else:
+        mask = vector_base.message_mask(scope)
     queries = np.asarray(embedding_or_embeddings, dtype=np.float32)
     if queries.ndim == 1:
         out = vector_base.lookup_messages_by_embedding_masked(queries, mask, max_matches, threshold_score)

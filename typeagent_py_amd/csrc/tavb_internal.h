@@ -150,6 +150,29 @@ hipError_t launch_mask_pack(const uint8_t* bytes, int64_t rows, uint32_t* bits, 
 // words over n_bits message ordinals) has that message's bit -> every word of (rows + 31) / 32, the bits at or beyond `rows` ZERO.  One launch.
 hipError_t launch_mask_from_messages(const int32_t* row_to_msg, int64_t rows, const uint32_t* accept_bits, int64_t n_bits, uint32_t* bits,
                                      hipStream_t stream);
+// Scope algebra (tavb_mask.hip).  Both kernels write every word of the mask (tail bits zero) and, per chunk of TAVB_MASK_ROWS_PER_WORKGROUP
+// rows, counts[chunk] (mask_count_kernel's layout: launch_mask_write may follow) and info[chunk] (device-writable memory, e.g. pinned).
+// One launch of mask_blocks(rows) workgroups each.
+struct MaskChunkInfo {
+  uint32_t count;
+  int32_t first, last;  // the chunk's first and last set row; count == 0: INT32_MAX and -1
+};
+// the merged intervals of a scope: collection c is intervals [offset[c], offset[c + 1]) of `intervals` ({start, end} pairs, disjoint, ascending)
+struct ScopeCollections {
+  int32_t n;
+  int32_t offset[TAVB_MAX_SCOPE_COLLECTIONS + 1];
+};
+struct MaskOperands {
+  const uint32_t* m[TAVB_MAX_MASK_OPERANDS];
+  int32_t n, op;
+};
+// row_to_msg == nullptr: the rows domain (x = r); else x = row_to_msg[r], allowed only when 0 <= x < n_messages
+hipError_t launch_mask_from_ranges(const int32_t* intervals, const ScopeCollections& cols, const int32_t* row_to_msg, int64_t n_messages, int64_t rows,
+                                   uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
+hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
+// mask_expand's second launch alone, over counts one of the two kernels above (or its own count pass) wrote
+hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
+                             hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (device, kernel) (tavb_misc.hip)
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);

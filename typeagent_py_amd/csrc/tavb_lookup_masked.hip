@@ -275,6 +275,166 @@ int tavb_mask_from_messages(tavb_ctx* c, const int32_t* accept_msgs_host, int64_
   return TAVB_OK;
 }
 
+// ---- scope algebra (tavb_mask_from_ranges, tavb_mask_combine; the kernels are tavb_mask.hip's)
+// What a call leaves in pinned memory (h_out): the write pass' total, then one MaskChunkInfo per chunk of the mask.
+struct AlgebraOut {
+  unsigned* counts;  // device: the chunks' popcounts, mask_count_kernel's layout
+  long long* total;
+  tavb::MaskChunkInfo* info;
+  int blocks;
+};
+
+static void empty_mask_info(tavb_mask_info* info) {
+  info->count = 0;
+  info->first_row = 0;
+  info->last_row = -1;
+}
+
+// what both calls check after the context and their own arguments
+static int check_algebra_args(tavb_ctx* c, int64_t rows, int32_t* dev_rows_out, int64_t cap) {
+  if (int rc = require_corpus(c)) return rc;
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  if (rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (cap < 0 || (cap > 0 && !dev_rows_out)) return fail(TAVB_E_INVALID, "bad capacity");
+  return TAVB_OK;
+}
+
+static int reserve_algebra(tavb_ctx* c, int64_t rows, AlgebraOut* o) {
+  o->blocks = tavb::mask_blocks(rows);
+  if (int rc = c->d_mask_counts.reserve((size_t)o->blocks * sizeof(unsigned))) return rc;
+  if (int rc = c->h_out.reserve(16 + (size_t)o->blocks * sizeof(tavb::MaskChunkInfo))) return rc;
+  o->counts = reinterpret_cast<unsigned*>(c->d_mask_counts.ptr);
+  o->total = reinterpret_cast<long long*>(c->h_out.ptr);
+  o->info = reinterpret_cast<tavb::MaskChunkInfo*>(reinterpret_cast<char*>(c->h_out.ptr) + 16);
+  *o->total = -1;
+  for (int b = 0; b < o->blocks; ++b) o->info[b].first = -1;  // (a chunk the kernel wrote holds a row or INT32_MAX here)
+  return TAVB_OK;
+}
+
+// the row list, when the caller wants one: mask_expand's write pass over the counts the mask's own launch made
+static int algebra_write_pass(tavb_ctx* c, const AlgebraOut& o, const uint32_t* dev_bits, int64_t rows, int32_t* dev_rows_out, int64_t cap) {
+  if (!dev_rows_out || cap == 0) return TAVB_OK;
+  hipError_t e = tavb::launch_mask_write(dev_bits, rows, o.counts, dev_rows_out, cap, o.total, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask write launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+// ONE synchronise, then the chunks' infos -> *out_info
+static int algebra_collect(tavb_ctx* c, const AlgebraOut& o, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info) {
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  int64_t count = 0, first = 0x7FFFFFFFll, last = -1;
+  for (int b = 0; b < o.blocks; ++b) {
+    const tavb::MaskChunkInfo ci = o.info[b];
+    if (ci.first < 0) return fail(TAVB_E_HIP, "chunk %d of the mask wrote no info (internal error)", b);
+    count += ci.count;
+    first = std::min<int64_t>(first, ci.first);
+    last = std::max<int64_t>(last, ci.last);
+  }
+  if (count > 0) {
+    out_info->count = count;
+    out_info->first_row = first;
+    out_info->last_row = last;
+  }
+  if (dev_rows_out && cap > 0 && *o.total != count) return fail(TAVB_E_HIP, "the write pass counted %lld rows, the mask has %lld (internal error)", *o.total, (long long)count);
+  if (dev_rows_out && count > cap) return fail(TAVB_E_INVALID, "the mask has %lld rows set, dev_rows_out holds %lld", (long long)count, (long long)cap);
+  return TAVB_OK;
+}
+
+int tavb_mask_from_ranges(tavb_ctx* c, const int64_t* ranges_host, const int32_t* collection_sizes_host, int32_t n_collections, int32_t domain, int64_t rows,
+                          uint32_t* dev_bits_out, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!out_info) return fail(TAVB_E_INVALID, "null argument");
+  empty_mask_info(out_info);
+  if (domain != 0 && domain != 1) return fail(TAVB_E_INVALID, "domain must be 0 (rows) or 1 (messages), got %d", domain);
+  if (n_collections < 0 || n_collections > TAVB_MAX_SCOPE_COLLECTIONS)
+    return fail(TAVB_E_INVALID, "a scope has 0 .. %d collections (got %d)", TAVB_MAX_SCOPE_COLLECTIONS, n_collections);
+  if (n_collections > 0 && !collection_sizes_host) return fail(TAVB_E_INVALID, "null collection sizes");
+  int64_t total = 0;
+  for (int i = 0; i < n_collections; ++i) {
+    if (collection_sizes_host[i] < 0) return fail(TAVB_E_INVALID, "collection %d has a negative size", i);
+    total += collection_sizes_host[i];
+  }
+  if (total > ((int64_t)1 << 20)) return fail(TAVB_E_INVALID, "a scope has at most 2^20 ranges (got %lld)", (long long)total);
+  if (total > 0 && !ranges_host) return fail(TAVB_E_INVALID, "null ranges");
+  if (int rc = check_algebra_args(c, rows, dev_rows_out, cap)) return rc;
+  if (domain == 1)
+    if (int rc = check_message_map(c)) return rc;
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bits_out) return fail(TAVB_E_INVALID, "null dev_bits_out");
+  // every collection sorted, clipped to the domain and merged into disjoint ascending intervals
+  const int64_t domain_n = domain == 1 ? c->n_messages : rows;
+  tavb::ScopeCollections cols{};
+  cols.n = n_collections;
+  std::vector<int32_t> merged;
+  std::vector<std::pair<int64_t, int64_t>> one;
+  const int64_t* r = ranges_host;
+  for (int i = 0; i < n_collections; ++i) {
+    one.clear();
+    for (int j = 0; j < collection_sizes_host[i]; ++j, r += 2) {
+      const int64_t s = std::max<int64_t>(r[0], 0), e = std::min<int64_t>(r[1], domain_n);
+      if (s < e) one.emplace_back(s, e);
+    }
+    std::sort(one.begin(), one.end());
+    size_t kept = merged.size();
+    for (const auto& iv : one) {
+      if (merged.size() > kept && iv.first <= merged.back()) {
+        merged.back() = (int32_t)std::max<int64_t>(merged.back(), iv.second);
+      } else {
+        merged.push_back((int32_t)iv.first);
+        merged.push_back((int32_t)iv.second);
+      }
+    }
+    cols.offset[i + 1] = (int32_t)(merged.size() / 2);
+  }
+  for (int i = n_collections; i < TAVB_MAX_SCOPE_COLLECTIONS; ++i) cols.offset[i + 1] = cols.offset[n_collections];
+  DeviceGuard guard(c->device);
+  AlgebraOut o;
+  if (int rc = reserve_algebra(c, rows, &o)) return rc;
+  if (!merged.empty()) {
+    if (int rc = c->d_scope.reserve(merged.size() * sizeof(int32_t))) return rc;
+    // (pageable source: the copy is staged by the runtime before the call returns)
+    TAVB_HIP(hipMemcpyAsync(c->d_scope.ptr, merged.data(), merged.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  {
+    Timed t(c, TAVB_KERNEL_CONVERT);
+    hipError_t e = tavb::launch_mask_from_ranges(reinterpret_cast<const int32_t*>(c->d_scope.ptr), cols, domain == 1 ? c->row_to_msg : nullptr, c->n_messages,
+                                                 rows, dev_bits_out, o.counts, o.info, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "range mask launch failed: %s", hipGetErrorString(e));
+    if (int rc = algebra_write_pass(c, o, dev_bits_out, rows, dev_rows_out, cap)) return rc;
+  }
+  return algebra_collect(c, o, dev_rows_out, cap, out_info);
+}
+
+int tavb_mask_combine(tavb_ctx* c, int32_t op, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, uint32_t* dev_bits_out, int32_t* dev_rows_out,
+                      int64_t cap, tavb_mask_info* out_info) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!out_info) return fail(TAVB_E_INVALID, "null argument");
+  empty_mask_info(out_info);
+  if (op < TAVB_MASK_AND || op > TAVB_MASK_ANDNOT) return fail(TAVB_E_INVALID, "op must be 0 (and), 1 (or) or 2 (and-not), got %d", op);
+  if (n_masks < 1 || n_masks > TAVB_MAX_MASK_OPERANDS) return fail(TAVB_E_INVALID, "a combination has 1 .. %d operands (got %d)", TAVB_MAX_MASK_OPERANDS, n_masks);
+  if (!dev_masks) return fail(TAVB_E_INVALID, "null dev_masks");
+  if (int rc = check_algebra_args(c, rows, dev_rows_out, cap)) return rc;
+  if (rows == 0) return TAVB_OK;
+  if (!dev_bits_out) return fail(TAVB_E_INVALID, "null dev_bits_out");
+  tavb::MaskOperands ops{};
+  ops.n = n_masks;
+  ops.op = op;
+  for (int j = 0; j < n_masks; ++j) {
+    if (!dev_masks[j]) return fail(TAVB_E_INVALID, "operand %d is null", j);
+    ops.m[j] = dev_masks[j];
+  }
+  DeviceGuard guard(c->device);
+  AlgebraOut o;
+  if (int rc = reserve_algebra(c, rows, &o)) return rc;
+  {
+    Timed t(c, TAVB_KERNEL_CONVERT);
+    hipError_t e = tavb::launch_mask_combine(ops, rows, dev_bits_out, o.counts, o.info, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "mask combine launch failed: %s", hipGetErrorString(e));
+    if (int rc = algebra_write_pass(c, o, dev_bits_out, rows, dev_rows_out, cap)) return rc;
+  }
+  return algebra_collect(c, o, dev_rows_out, cap, out_info);
+}
+
 // ---- batched message lookups: nq key lists [nq, k] on the device (keys carrying index_base + row) -> ONE message_rerank_kernel launch of nq
 // workgroups -> ONE device-to-host copy -> the callers' arrays.  d_out holds both: the hits in its first nq * k keys, the message keys behind.
 static int rerank_batch_and_return(tavb_ctx* c, const u64_t* d_hits, int nq, int k, uint32_t index_base, const uint32_t* d_accept_bits, int32_t max_messages,

@@ -1,6 +1,8 @@
 // Row masks (tavb_mask_expand, tavb_mask_pack, tavb_mask_from_messages): an allow-mask of one bit per corpus row -> the int32 row list the
 // subset lookups gather by, in ascending row order, without a trip to the host; and the mask of a SCOPE -- a set of message ordinals -- built
 // from the row -> message map on the device (mask_from_messages_kernel), so that a scoped message lookup never makes a host row list.
+// Scope algebra (tavb_mask_from_ranges, tavb_mask_combine): the mask of a scope of range collections (mask_from_ranges_kernel) and AND /
+// OR / ANDNOT of masks (mask_combine_kernel), both of which also leave the counts mask_write_kernel needs and the mask's count and span.
 //
 // The mask is uint32 words, row r = bit (r & 31) of word (r >> 5).  Two launches, both grids fixed on the host:
 //   mask_count_kernel   workgroup b popcounts its kMaskWordsPerBlock words -> counts[b]
@@ -141,6 +143,136 @@ __global__ void __launch_bounds__(kMaskThreads) mask_from_messages_kernel(const 
   }
 }
 
+// ---- scope algebra: a mask from ranges, and AND / OR / ANDNOT of masks.  Unlike the two kernels above, a WORKGROUP here owns one chunk of
+// TAVB_MASK_ROWS_PER_WORKGROUP rows (mask_count_kernel's chunk), so that it can leave that chunk's popcount where mask_write_kernel reads it
+// and the chunk's count, first and last set row where the host sums them: no count pass, no read-back of the row list's ends.
+
+constexpr int kMaskWaves = kMaskThreads / 64;
+constexpr int kMaskRoundsPerBlock = TAVB_MASK_ROWS_PER_WORKGROUP / 64;
+static_assert(kMaskRoundsPerBlock % kMaskWaves == 0, "a workgroup's waves take its rounds of 64 rows in turn");
+
+// (n, first, last) of every wave (lane 0 holds them) -> counts[chunk], info[chunk]; every thread of the workgroup calls it
+__device__ __forceinline__ void mask_chunk_reduce(unsigned n, int first, int last, unsigned* __restrict__ counts, MaskChunkInfo* __restrict__ info) {
+  __shared__ unsigned wn[kMaskWaves];
+  __shared__ int wf[kMaskWaves], wl[kMaskWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    wn[wave] = n;
+    wf[wave] = first;
+    wl[wave] = last;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    MaskChunkInfo ci{0u, 0x7FFFFFFF, -1};
+    for (int w = 0; w < kMaskWaves; ++w) {
+      ci.count += wn[w];
+      ci.first = min(ci.first, wf[w]);
+      ci.last = max(ci.last, wl[w]);
+    }
+    counts[blockIdx.x] = ci.count;
+    info[blockIdx.x] = ci;
+  }
+}
+
+// The mask of a scope of ranges.  Row r votes yes when x (r itself, or its message: 0 <= row_to_msg[r] < n_messages) lies in an interval of
+// EVERY collection: one binary search per collection over that collection's disjoint ascending {start, end} pairs (the last start <= x,
+// then x < its end).  kLds: the workgroup first copies all intervals (at most TAVB_SCOPE_LDS_RANGES) into LDS and searches there.  A wave
+// takes 64 rows per round and its ballot IS the two words, as above; the ballots' popcounts, lowest and highest bits are the chunk's info.
+template <bool kLds>
+__global__ void __launch_bounds__(kMaskThreads) mask_from_ranges_kernel(const int2* __restrict__ intervals, ScopeCollections cols,
+                                                                        const int32_t* __restrict__ row_to_msg, int64_t n_messages, int64_t rows,
+                                                                        int64_t n_words, uint32_t* __restrict__ bits_out,
+                                                                        unsigned* __restrict__ counts, MaskChunkInfo* __restrict__ info) {
+  __shared__ int2 staged[kLds ? TAVB_SCOPE_LDS_RANGES : 1];
+  if (kLds) {
+    const int total = min(cols.offset[cols.n], TAVB_SCOPE_LDS_RANGES);
+    for (int i = threadIdx.x; i < total; i += kMaskThreads) staged[i] = intervals[i];
+    __syncthreads();
+  }
+  auto at = [&](int i) -> int2 {
+    if constexpr (kLds) return staged[i];
+    else return intervals[i];
+  };
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t g0 = (int64_t)blockIdx.x * kMaskRoundsPerBlock;
+  const int64_t groups = (rows + 63) >> 6;
+  unsigned n = 0;
+  int first = 0x7FFFFFFF, last = -1;
+  for (int i = wave; i < kMaskRoundsPerBlock; i += kMaskWaves) {  // (wave-uniform trip count)
+    const int64_t g = g0 + i;
+    if (g >= groups) break;
+    const int64_t r = (g << 6) + lane;
+    bool on = false;
+    if (r < rows) {
+      int64_t x = r;
+      on = true;
+      if (row_to_msg) {
+        x = row_to_msg[r];
+        on = x >= 0 && x < n_messages;
+      }
+      for (int c = 0; c < cols.n && on; ++c) {
+        const int begin = cols.offset[c];
+        int lo = begin, hi = cols.offset[c + 1];
+        while (lo < hi) {  // the number of intervals that start at or before x
+          const int mid = (lo + hi) >> 1;
+          if ((int64_t)at(mid).x <= x) lo = mid + 1;
+          else hi = mid;
+        }
+        on = lo > begin && x < (int64_t)at(lo - 1).y;
+      }
+    }
+    const unsigned long long v = __ballot(on);
+    const int64_t w = (g << 1) + lane;
+    if (lane < 2 && w < n_words) bits_out[w] = (uint32_t)(v >> (32 * lane));
+    if (v) {
+      n += (unsigned)__popcll(v);
+      first = min(first, (int)(g << 6) + __ffsll(v) - 1);
+      last = max(last, (int)(g << 6) + 63 - __clzll((long long)v));
+    }
+  }
+  mask_chunk_reduce(n, first, last, counts, info);
+}
+
+// out = op(m0 .. m(n-1)) word by word: a thread reads its word of EVERY operand (through mask_word: their bits at or beyond `rows` may hold
+// anything) before it writes it, so `out` may be any of them; the complement (ANDNOT) is cut at `rows`, so the output's tail bits are zero.
+__global__ void __launch_bounds__(kMaskThreads) mask_combine_kernel(MaskOperands ops, int64_t rows, int64_t n_words, uint32_t* out,
+                                                                    unsigned* __restrict__ counts, MaskChunkInfo* __restrict__ info) {
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock;
+  unsigned n = 0;
+  int first = 0x7FFFFFFF, last = -1;
+  for (int i = threadIdx.x; i < kMaskWordsPerBlock; i += kMaskThreads) {
+    const int64_t w = w0 + i;
+    if (w >= n_words) break;
+    uint32_t v = mask_word(ops.m[0], w, n_words, rows), rest = 0u;
+#pragma unroll
+    for (int j = 1; j < TAVB_MAX_MASK_OPERANDS; ++j) {
+      if (j < ops.n) {
+        const uint32_t t = mask_word(ops.m[j], w, n_words, rows);
+        if (ops.op == TAVB_MASK_AND) v &= t;
+        else if (ops.op == TAVB_MASK_OR) v |= t;
+        else rest |= t;
+      }
+    }
+    if (ops.op == TAVB_MASK_ANDNOT) {
+      v = ops.n == 1 ? ~v : v & ~rest;
+      const int tail = (int)(rows & 31);
+      if (w == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+    }
+    out[w] = v;
+    if (v) {
+      n += (unsigned)__popc(v);
+      first = min(first, (int)(w << 5) + __ffs((int)v) - 1);
+      last = max(last, (int)(w << 5) + 31 - __clz((int)v));
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) {  // lane 0 of every wave: the wave's sum, lowest and highest row
+    n += __shfl_down(n, d, 64);
+    first = min(first, __shfl_down(first, d, 64));
+    last = max(last, __shfl_down(last, d, 64));
+  }
+  mask_chunk_reduce(n, first, last, counts, info);
+}
+
 }  // namespace
 
 int mask_blocks(int64_t rows) { return (int)((rows + TAVB_MASK_ROWS_PER_WORKGROUP - 1) / TAVB_MASK_ROWS_PER_WORKGROUP); }
@@ -154,6 +286,42 @@ hipError_t launch_mask_expand(const uint32_t* bits, int64_t rows, unsigned* coun
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mask_write_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, bits, rows, n_words, counts, out, cap, total_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
+                             hipStream_t stream) {
+  if (!bits || !counts || !total_out || rows < 1 || rows >= 0x7FFFFFFFll || cap < 0 || (cap > 0 && !out)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_write_kernel, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, bits, rows, (rows + 31) >> 5, counts, out, cap, total_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_from_ranges(const int32_t* intervals, const ScopeCollections& cols, const int32_t* row_to_msg, int64_t n_messages, int64_t rows,
+                                   uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
+  if (!bits || !counts || !info || rows < 1 || rows >= 0x7FFFFFFFll || n_messages < 0 || cols.n < 0 || cols.n > TAVB_MAX_SCOPE_COLLECTIONS || cols.offset[0] != 0)
+    return hipErrorInvalidValue;
+  for (int c = 0; c < cols.n; ++c)
+    if (cols.offset[c + 1] < cols.offset[c]) return hipErrorInvalidValue;
+  const int total = cols.offset[cols.n];
+  if (total > 0 && !intervals) return hipErrorInvalidValue;
+  const int64_t n_words = (rows + 31) >> 5;
+  const int2* iv = reinterpret_cast<const int2*>(intervals);
+  if (total <= TAVB_SCOPE_LDS_RANGES)
+    hipLaunchKernelGGL(mask_from_ranges_kernel<true>, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, iv, cols, row_to_msg, n_messages, rows, n_words,
+                       bits, counts, info);
+  else
+    hipLaunchKernelGGL(mask_from_ranges_kernel<false>, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, iv, cols, row_to_msg, n_messages, rows, n_words,
+                       bits, counts, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
+  if (!bits || !counts || !info || rows < 1 || rows >= 0x7FFFFFFFll || ops.n < 1 || ops.n > TAVB_MAX_MASK_OPERANDS || ops.op < TAVB_MASK_AND ||
+      ops.op > TAVB_MASK_ANDNOT)
+    return hipErrorInvalidValue;
+  for (int j = 0; j < ops.n; ++j)
+    if (!ops.m[j]) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_combine_kernel, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, ops, rows, (rows + 31) >> 5, bits, counts, info);
   return hipGetLastError();
 }
 

@@ -273,17 +273,22 @@ class RowMask:
     raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it.  On a device group the
     handle holds one shard-local list per device (`shards`, cut by `bounds`), on a row-sharded index this rank's list and the packed mask.
     A single-GPU engine also keeps the packed mask on the device (`dev_bits`, int32 words: row r = bit r & 31 of word r >> 5) and
-    `span` = (first, last) allowed row, read once when the handle is built: what a batch on the 32/64-query tile reads instead of the list."""
+    `span` = (first, last) allowed row, read once when the handle is built (or handed in as `span=` by the scope algebra, whose kernels
+    report it): what a batch on the 32/64-query tile reads instead of the list.  Handles of one index combine: `a & b`, `a | b`, `a - b`,
+    `~a` (`VectorBase.intersect_masks` / `union_masks`)."""
 
     __slots__ = ("rows", "count", "dev_rows", "dev_bits", "span", "shards", "bounds", "layout", "bits", "_flat", "_owner", "_plans")
 
     def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None, shards=None, bounds=None, layout=None, bits=None,
-                 dev_bits=None):
+                 dev_bits=None, span=None):
         self.rows = int(rows)
         self.count = int(count)
         self.dev_rows = dev_rows
         self.dev_bits = dev_bits
-        self.span = (int(dev_rows[0]), int(dev_rows[-1])) if dev_bits is not None and dev_rows is not None and self.count > 0 else None
+        if span is not None:  # the scope algebra's kernels report it with the count: nothing is read back
+            self.span = (int(span[0]), int(span[1])) if self.count > 0 else None
+        else:
+            self.span = (int(dev_rows[0]), int(dev_rows[-1])) if dev_bits is not None and dev_rows is not None and self.count > 0 else None
         self._plans: dict = {}  # (queries, max_hits, the engine's mask_tile options) -> tile route or not: a handle is searched again and again
         # a device group (multidevice.DeviceGroup.mask_to_rows): one shard-local int32 row list per device (None: no allowed row there)
         # and the shard bounds the mask was cut by
@@ -309,6 +314,26 @@ class RowMask:
             else:
                 self._flat = np.zeros(0, np.int64) if self.dev_rows is None else self.dev_rows.cpu().numpy().astype(np.int64)
         return self._flat
+
+    # AND / OR / difference / complement with the masks of the same index at the same length (`VectorBase.intersect_masks` and the rest): on
+    # a single-GPU engine the packed masks are combined on the device and the result is a full handle
+    def _index(self):
+        owner = self._owner()
+        if owner is None:
+            raise ValueError("the index this RowMask was built by is gone")
+        return owner
+
+    def __and__(self, other) -> "RowMask":
+        return self._index().intersect_masks(self, other)
+
+    def __or__(self, other) -> "RowMask":
+        return self._index().union_masks(self, other)
+
+    def __sub__(self, other) -> "RowMask":
+        return self._index()._combine_masks(_native.MASK_ANDNOT, (self, other))
+
+    def __invert__(self) -> "RowMask":
+        return self._index()._combine_masks(_native.MASK_ANDNOT, (self,))
 
 
 def _is_tensor(x) -> bool:
@@ -918,6 +943,95 @@ class VectorBase:
         if allowed.rows != self._count:
             raise ValueError(f"mask covers {allowed.rows} rows, the index has {self._count}")
         return allowed
+
+    # ------------------------------------------------------------------ scope algebra (additive)
+    def _mask_bools(self, mask: RowMask) -> np.ndarray:
+        b = np.zeros(self._count, dtype=bool)
+        b[mask.flat()] = True
+        return b
+
+    def _combine_masks(self, op: int, masks) -> RowMask:
+        """AND / OR of any number of masks, or ANDNOT (the first without the others; one operand: its complement) of up to 8 -- `RowMask`s of
+        this index at this length, or anything `row_mask` takes.  On a single-GPU engine operands that hold their packed mask on the device
+        are combined there, up to 8 per launch (tavb_mask_combine; more are folded in groups), and the result is a full handle; everywhere
+        else the bool arrays are combined on the host and handed to `row_mask`."""
+        handles = [self._resolve_mask(m) for m in masks]
+        if not handles:
+            raise ValueError("at least one mask is needed")
+        n = self._count
+        if n == 0:
+            return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
+        eng = self._sync_device()
+        if self._masked_native(eng) and hasattr(eng, "mask_combine") and all(h.dev_bits is not None for h in handles):
+            most = _native.MAX_MASK_OPERANDS
+            if op == _native.MASK_ANDNOT and len(handles) > most:  # a \ (b | c | ...): the union first
+                handles = [handles[0], self._combine_masks(_native.MASK_OR, handles[1:])]
+            while True:
+                group, handles = handles[:most], handles[most:]
+                counts = [h.count for h in group]
+                if op == _native.MASK_AND:
+                    cap = min(counts)
+                elif op == _native.MASK_OR:
+                    cap = min(sum(counts), n)
+                else:
+                    cap = counts[0] if len(group) > 1 else n - counts[0]
+                dev_rows, count, dev_bits, span = eng.mask_combine(op, [h.dev_bits for h in group], cap)
+                out = RowMask(self, n, count, dev_rows=dev_rows, dev_bits=dev_bits, span=span)
+                if not handles:
+                    return out
+                handles.insert(0, out)
+        bools = [self._mask_bools(h) for h in handles]
+        if op == _native.MASK_AND:
+            return self.row_mask(np.logical_and.reduce(bools))
+        if op == _native.MASK_OR:
+            return self.row_mask(np.logical_or.reduce(bools))
+        return self.row_mask(bools[0] & ~np.logical_or.reduce(bools[1:]) if len(bools) > 1 else ~bools[0])
+
+    def intersect_masks(self, *masks) -> RowMask:
+        """The rows every one of `masks` allows: equals row_mask(A & B & ...) of their bool arrays.  `a & b` on two handles is this."""
+        return self._combine_masks(_native.MASK_AND, masks)
+
+    def union_masks(self, *masks) -> RowMask:
+        """The rows any of `masks` allows: equals row_mask(A | B | ...) of their bool arrays.  `a | b` on two handles is this; `a - b` is
+        row_mask(A & ~B) and `~a` row_mask(~A)."""
+        return self._combine_masks(_native.MASK_OR, masks)
+
+    def range_mask(self, collections, of: str = "rows") -> RowMask:
+        """The `RowMask` of a scope given as COLLECTIONS of half-open (start, end) ranges -- the reference's `TextRangesInScope`
+        (knowpro/collections.py:486-562): a row is allowed when EVERY collection has a range that holds it.  of="rows": the ranges are
+        over index positions, equals row_mask(np.logical_and.reduce([union of the collection's ranges as a bool array ...])); of="messages":
+        over message ordinals, tested on the row's message (`set_row_messages`; rows without a message are never allowed).  No collection
+        at all allows every row (every row with a message); a collection without a non-empty range allows none.  Ranges may be unsorted,
+        overlapping, duplicated, empty, or reach outside the index.  On a single-GPU engine only the ranges travel (8 collections per
+        launch of tavb_mask_from_ranges; more are intersected on the device); device groups and test doubles build the bool array on the
+        host."""
+        if of not in _native.SCOPE_DOMAINS:
+            raise ValueError(f'of must be "rows" or "messages", got {of!r}')
+        cols = _native.range_collections(collections)
+        if of == "messages":
+            self._check_row_messages()
+        n = self._count
+        if n == 0:
+            return RowMask(self, 0, 0, flat=np.zeros(0, np.int64))
+        eng = self._messages_engine() if of == "messages" else self._sync_device()
+        if eng is not None and self._masked_native(eng) and hasattr(eng, "mask_from_ranges"):
+            most = _native.MAX_SCOPE_COLLECTIONS
+            parts = []
+            for i in range(0, max(len(cols), 1), most):
+                dev_rows, count, dev_bits, span = eng.mask_from_ranges(cols[i:i + most], of)
+                parts.append(RowMask(self, n, count, dev_rows=dev_rows, dev_bits=dev_bits, span=span))
+            return parts[0] if len(parts) == 1 else self.intersect_masks(*parts)
+        if of == "rows":
+            ok = np.ones(n, dtype=bool)
+            for c in cols:
+                ok &= _native.ranges_to_bool(c, n)
+            return self.row_mask(ok)
+        held = self._row_messages[:n]
+        ok = held >= 0
+        n_messages = int(held.max()) + 1 if ok.any() else 0
+        for c in cols:
+            ok &= np.isin(held, np.flatnonzero(_native.ranges_to_bool(c, n_messages)))
+        return self.row_mask(ok)
 
     def fuzzy_lookup_embedding_masked(
         self,
