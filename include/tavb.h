@@ -203,6 +203,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "sort_small_keys" 0 .. 16384 (default 16384): a sort of up to this many keys (tavb_search_sorted, tavb_sort_keys_device) runs in ONE
  *                   workgroup in LDS; bigger ones take the multi-pass radix sort (3 launches per 8-bit digit that is not the same for
  *                   every key, + 2)
+ *   "compact_pass_rows" 0 .. 2^31 - 2 (default 0 = auto: about 64 MiB of rows): rows per pass of an in-place tavb_compact_rows, rounded up to a
+ *                   multiple of 64; its staging workspace holds one pass
  */
 int tavb_set_option(tavb_ctx* ctx, const char* name, int64_t value);
 int tavb_get_option(tavb_ctx* ctx, const char* name, int64_t* out_value);
@@ -528,6 +530,29 @@ int tavb_mask_from_ranges(tavb_ctx* ctx, const int64_t* ranges_host, const int32
                           int64_t rows, uint32_t* dev_bits_out, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
 int tavb_mask_combine(tavb_ctx* ctx, int32_t op, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, uint32_t* dev_bits_out,
                       int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
+
+/* ---- removing rows: compaction of the corpus on the device ---------------------------------------------------------------------------
+ * The removal the reference leaves as a TODO (storage/sqlite/reltermsindex.py:181-192 `remove_term`; knowpro/fuzzyindex.py:113-127, the
+ * commented `remove_at` around np.delete): dev_remove_bits is a mask in the bit form above in which a SET bit means "remove"; rows must equal
+ * the corpus' rows; bits at or beyond `rows` may hold anything.  Afterwards rows [0, kept) hold the kept rows in their old order, bit for
+ * bit -- np.delete(corpus, flatnonzero(mask), axis=0) -- *out_rows = kept, and the call has ended with tavb_set_corpus(.., kept, ..) (same
+ * dim, dtype and ordinal_base; the pointer is dev_dst when that is given) and tavb_corpus_modified(first removed row).
+ *   dev_dst == NULL: IN PLACE.  Rows only move down.  From the 64-row tile of the first removed row on, the corpus is taken in passes of
+ *     "compact_pass_rows" rows (option; rounded up to a multiple of 64; 0 = auto, the default: about 64 MiB of rows): one launch gathers a
+ *     pass' kept rows densely into a staging workspace of that size, a second copies them to their final place, which ends at or below the
+ *     end of the pass -- every later pass reads only rows beyond it.  The order between the launches is stream order and nothing else: no
+ *     workgroup waits for another.  Two launches per pass; bytes moved: four times the bytes from the first removed row to the end, at most.
+ *   dev_dst != NULL: OUT OF PLACE, one launch: the kept rows are gathered into dev_dst (device memory for at least `kept` rows -- `rows`
+ *     rows always do -- that does not overlap the corpus, aligned to the element size); the old corpus is read only.  The route for a corpus
+ *     buffer the caller may not write.
+ * A workgroup takes 64 rows, finds its first slot from the per-chunk counts (TAVB_MASK_ROWS_PER_WORKGROUP rows a chunk, as tavb_mask_expand's
+ * write pass does) and a wave copies a row with the widest of 16-, 8-, 4- and 2-byte accesses that the row bytes and the addresses allow.
+ * A mask with no bit set is a no-op: nothing moves, no cache is touched, dev_dst is neither written nor adopted.  Every bit set leaves 0
+ * rows.  rows == 0: *out_rows = 0.  The count pass is waited for (ONE synchronise: the host needs `kept`); the moves are enqueued on the
+ * context's stream and NOT waited for -- lookups on this context follow in stream order, anything else calls tavb_synchronize first.  The
+ * mask must stay alive until then.  Timed under TAVB_KERNEL_CONVERT.  The row -> message map (tavb_set_row_messages) is the caller's to
+ * compact and set again. */
+int tavb_compact_rows(tavb_ctx* ctx, const uint32_t* dev_remove_bits, int64_t rows, void* dev_dst /* NULL = in place */, int64_t* out_rows);
 
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */

@@ -101,6 +101,7 @@ _SIGNATURES = [
     ("tavb_search_messages_batch", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_mask_from_ranges", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_mask_combine", c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -506,6 +507,40 @@ class Engine:
         self.set_corpus_tensor(self.corpus, rows=n_new, ordinal_base=self.ordinal_base, _owned=True)
         _check(self.lib, self.lib.tavb_corpus_modified(self._h, int(start)))  # rows [start, n_new) were (re)written
         return True
+
+    def mask_bits_to_device(self, words: np.ndarray):
+        """A mask packed on the host (`pack_mask_bits`: uint32 words) -> torch int32 on this engine's device: rows / 8 bytes travel."""
+        torch = self._torch
+        return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(torch.device("cuda", self.device))
+
+    def compact_rows(self, dev_remove_bits) -> int:
+        """Remove the rows whose bit is set in `dev_remove_bits` (torch int32 [(rows + 31) // 32] on this device, the layout of
+        `pack_mask_bits`; set = remove) and move the others down in their old order (tavb_compact_rows): np.delete on the device ->
+        the rows kept.  A corpus buffer this engine allocated is compacted in place; a tensor adopted from the caller is never written:
+        its kept rows are gathered into a fresh tensor (capacity as `upload_rows` would pick), which becomes the owned corpus.  A mask
+        with no bit set changes nothing."""
+        torch = self._torch
+        rows = self.rows
+        if rows == 0 or self.corpus is None:
+            return 0
+        assert dev_remove_bits.dtype == torch.int32 and dev_remove_bits.is_contiguous() and dev_remove_bits.dim() == 1 and dev_remove_bits.numel() * 32 >= rows
+        if dev_remove_bits.device.type != "cuda" or (dev_remove_bits.device.index or 0) != self.device:
+            raise ValueError(f"the mask must live on cuda:{self.device}")
+        fresh = None
+        if not self._owns_corpus:
+            fresh = torch.empty((max(rows, 16), self.dim), dtype=self.corpus.dtype, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()  # whatever produced the mask (and the allocation above) ran on torch's stream
+        kept = c_int64(0)
+        with self._lock:
+            rc = self.lib.tavb_compact_rows(self._h, c_void_p(dev_remove_bits.data_ptr()), rows, c_void_p(fresh.data_ptr()) if fresh is not None else None,
+                                            byref(kept))
+        _check(self.lib, rc)
+        self.synchronize()  # the moves were only enqueued: the mask, and an adopted tensor, may be released once they are done
+        n = int(kept.value)
+        if fresh is not None and n < rows:
+            self.corpus, self._owns_corpus = fresh, True
+        self.rows = n
+        return n
 
     def clear(self) -> None:
         if self.corpus is not None:

@@ -89,6 +89,65 @@ def uninstall_batched_lookup_terms() -> None:
         setattr(cls, name, original)
 
 
+_patched_remove: list[tuple[type, str, object]] = []
+_ABSENT = object()  # the class had no such attribute of its own
+
+
+def install_remove_term() -> dict:
+    """Give typeagent's two fuzzy related-terms indexes a working `remove_term(text)` -- the sqlite class raises NotImplementedError
+    (storage/sqlite/reltermsindex.py:181-192: "TODO: Removal from VectorBase, _terms_list, _terms_to_ordinal"), the memory class has
+    none (`ITermToRelatedTermsFuzzy.remove_term`, knowpro/interfaces_core.py:185).  The term's ordinal is its position in the class'
+    text list; `VectorBase.remove_rows` removes the row (on the device: no re-upload), the list entry goes, later ordinals shift down
+    on both sides; the sqlite class also forgets the term in `_added_terms` and deletes its row of RelatedTermsFuzzy.  An unknown term
+    is a no-op.  Needs an index whose vector base is this package's (`install()`).  Report and failure rules as
+    `install_batched_lookup_terms`; `uninstall_remove_term()` restores what was there."""
+    report: dict = {"patched": [], "skipped": {}}
+
+    def patch(cls, fn, name):
+        _patched_remove.append((cls, "remove_term", cls.__dict__.get("remove_term", _ABSENT)))
+        cls.remove_term = fn
+        report["patched"].append(name)
+
+    def drop(vector_base, texts: list, term: str) -> bool:
+        if term not in texts:
+            return False
+        ordinal = texts.index(term)
+        vector_base.remove_rows([ordinal])
+        del texts[ordinal]
+        return True
+
+    try:
+        from typeagent.storage.memory import reltermsindex as mem  # type: ignore
+    except ImportError as exc:
+        report["skipped"]["typeagent.storage.memory.reltermsindex"] = f"{type(exc).__name__}: {exc}"
+    else:
+        async def remove_term(self, term: str) -> None:
+            drop(self._vectorbase, self._texts, term)
+
+        patch(mem.TermEmbeddingIndex, remove_term, "typeagent.storage.memory.reltermsindex.TermEmbeddingIndex")
+    try:
+        from typeagent.storage.sqlite import reltermsindex as sql  # type: ignore
+    except ImportError as exc:
+        report["skipped"]["typeagent.storage.sqlite.reltermsindex"] = f"{type(exc).__name__}: {exc}"
+    else:
+        async def remove_term_sql(self, term: str) -> None:
+            if drop(self._vector_base, self._terms_list, term):
+                self._added_terms.discard(term)
+                self.db.cursor().execute("DELETE FROM RelatedTermsFuzzy WHERE term = ?", (term,))
+
+        patch(sql.SqliteRelatedTermsFuzzy, remove_term_sql, "typeagent.storage.sqlite.reltermsindex.SqliteRelatedTermsFuzzy")
+    return report
+
+
+def uninstall_remove_term() -> None:
+    while _patched_remove:
+        cls, name, original = _patched_remove.pop()
+        if original is _ABSENT:
+            delattr(cls, name)
+        else:
+            setattr(cls, name, original)
+
+
 def best_score_per_message(
     hits: Sequence[ScoredInt],
     row_to_message: Callable[[int], int] | Sequence[int] | np.ndarray,

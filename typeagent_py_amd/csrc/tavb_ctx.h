@@ -172,6 +172,8 @@ struct tavb_ctx {
   // (tavb_sort.hip); the decoded results leave through h_out in pieces of at most sort_stage_keys
   Buffer d_sort_keys, d_sort_ws;
   Buffer d_mask_counts;  // row masks (tavb_mask_expand, tavb_mask.hip): set rows per workgroup chunk of the mask
+  Buffer d_compact;      // row compaction in place (tavb_compact_rows): the kept rows of one pass, densely, before they are written back further down
+  int64_t compact_pass_rows = 0;  // option: rows per pass of an in-place compaction, rounded up to a multiple of 64 (0 = auto: about 64 MiB of rows)
   Buffer d_scope;        // scope algebra (tavb_mask_from_ranges): the merged {start, end} intervals of a scope's collections, one after another
   Buffer h_sort_info{nullptr, 0, true};  // pinned: meta [nq][4] + per-block key counts [nq][blocks] of one group
   int64_t sort_all = 1;                   // option: 1 = the binding routes max_hits == 0 and max_hits > TAVB_MAX_LARGE_K through tavb_search_sorted
@@ -267,7 +269,7 @@ struct tavb_ctx {
   void for_each_buffer(F&& f) {
     for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
                       &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk,
-                      &d_sort_keys, &d_sort_ws, &d_mask_counts, &d_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
+                      &d_sort_keys, &d_sort_ws, &d_mask_counts, &d_compact, &d_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
                       &d_local, &d_xlocal, &d_gather})
       f(*b);
   }

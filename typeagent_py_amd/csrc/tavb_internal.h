@@ -173,6 +173,16 @@ hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* 
 // mask_expand's second launch alone, over counts one of the two kernels above (or its own count pass) wrote
 hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
                              hipStream_t stream);
+// Row compaction (tavb_mask.hip; `bits` names the rows to REMOVE).  compact_count: counts[chunk] = the chunk's KEPT rows, info[chunk] = that
+// count and the chunk's first and last removed row (device-writable memory).  compact_gather: the kept rows of src rows [r0, r1) -> dst rows
+// from (kept rows in [from, r0)) on, densely and in order; from <= r0, both multiples of 64, r1 a multiple of 64 or `rows`; src and dst
+// must not overlap.  compact_scatter: staging rows [0, kept in [r0, r1)) -> corpus rows from (kept in [0, r0)) on.  One launch each;
+// row_bytes even; nothing waits on another workgroup.
+hipError_t launch_compact_count(const uint32_t* bits, int64_t rows, unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
+hipError_t launch_compact_gather(const void* src, void* dst, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t from, int64_t r0,
+                                 int64_t r1, int64_t row_bytes, hipStream_t stream);
+hipError_t launch_compact_scatter(const void* staging, void* corpus, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t r0, int64_t r1,
+                                  int64_t row_bytes, hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (device, kernel) (tavb_misc.hip)
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);

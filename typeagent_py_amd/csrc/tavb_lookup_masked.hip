@@ -257,6 +257,70 @@ int tavb_mask_pack(tavb_ctx* c, const uint8_t* dev_bytes, int64_t rows, uint32_t
   return TAVB_OK;
 }
 
+// ---- row compaction (the kernels are tavb_mask.hip's): the count pass, ONE synchronise for the kept count and the first removed row, then
+// the moves, enqueued and not waited for.  In place the corpus goes through d_compact in passes: pass p's scatter writes only rows below
+// the end of pass p (it holds no more rows than the pass kept, and they start at or below the pass' first row), every later pass reads
+// only rows at or above that end, and the launches run in stream order -- so no row is overwritten before it was read.
+int tavb_compact_rows(tavb_ctx* c, const uint32_t* dev_remove_bits, int64_t rows, void* dev_dst, int64_t* out_rows) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!out_rows) return fail(TAVB_E_INVALID, "null argument");
+  *out_rows = 0;
+  if (int rc = require_corpus(c)) return rc;
+  if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+  if (rows == 0) return TAVB_OK;
+  if (!dev_remove_bits) return fail(TAVB_E_INVALID, "null dev_remove_bits");
+  if ((reinterpret_cast<uintptr_t>(dev_remove_bits) & 3) != 0) return fail(TAVB_E_INVALID, "dev_remove_bits must be 4-byte aligned");
+  const int64_t row_bytes = (int64_t)c->dim * (c->dtype == TAVB_F16 ? 2 : 4);
+  if ((reinterpret_cast<uintptr_t>(c->corpus) | reinterpret_cast<uintptr_t>(dev_dst)) % (c->dtype == TAVB_F16 ? 2 : 4) != 0)
+    return fail(TAVB_E_INVALID, "the corpus and dev_dst must be aligned to their element size");
+  DeviceGuard guard(c->device);
+  const int blocks = tavb::mask_blocks(rows);
+  if (int rc = c->d_mask_counts.reserve((size_t)blocks * sizeof(unsigned))) return rc;
+  if (int rc = c->h_out.reserve((size_t)blocks * sizeof(tavb::MaskChunkInfo))) return rc;
+  unsigned* counts = reinterpret_cast<unsigned*>(c->d_mask_counts.ptr);
+  tavb::MaskChunkInfo* info = reinterpret_cast<tavb::MaskChunkInfo*>(c->h_out.ptr);
+  for (int b = 0; b < blocks; ++b) info[b].first = -1;  // (a chunk the kernel wrote holds a row or INT32_MAX here)
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  hipError_t e = tavb::launch_compact_count(dev_remove_bits, rows, counts, info, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "compaction count launch failed: %s", hipGetErrorString(e));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  int64_t kept = 0, first = 0x7FFFFFFFll;
+  for (int b = 0; b < blocks; ++b) {
+    if (info[b].first < 0) return fail(TAVB_E_HIP, "chunk %d of the mask wrote no info (internal error)", b);
+    kept += info[b].count;
+    first = std::min<int64_t>(first, info[b].first);
+  }
+  *out_rows = kept;
+  if (kept == rows) return TAVB_OK;  // nothing to remove: no row moves, no cache is touched, dev_dst is not written and not adopted
+  if (kept > rows || first >= rows) return fail(TAVB_E_HIP, "the count pass kept %lld of %lld rows (internal error)", (long long)kept, (long long)rows);
+  const char* src = reinterpret_cast<const char*>(c->corpus);
+  if (dev_dst) {
+    const char* d = reinterpret_cast<const char*>(dev_dst);
+    if (d < src + rows * row_bytes && src < d + kept * row_bytes) return fail(TAVB_E_INVALID, "dev_dst overlaps the corpus: pass NULL to compact in place");
+    if (kept > 0) {
+      e = tavb::launch_compact_gather(src, dev_dst, dev_remove_bits, counts, rows, 0, 0, rows, row_bytes, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "compaction gather launch failed: %s", hipGetErrorString(e));
+    }
+  } else if (kept > first) {  // (rows below `first` stay where they are; with none kept beyond them there is nothing to move)
+    int64_t pass = c->compact_pass_rows > 0 ? c->compact_pass_rows : std::max<int64_t>(((int64_t)64 << 20) / row_bytes, 1);
+    pass = std::min<int64_t>((pass + 63) & ~(int64_t)63, (int64_t)1 << 31);
+    const int64_t start = first & ~(int64_t)63;  // whole tiles of 64 rows; the rows of the first tile below `first` are rewritten with themselves
+    if (int rc = c->d_compact.reserve((size_t)(std::min(pass, rows - start) * row_bytes))) return rc;
+    for (int64_t r0 = start; r0 < rows; r0 += pass) {
+      const int64_t r1 = std::min(r0 + pass, rows);
+      e = tavb::launch_compact_gather(src, c->d_compact.ptr, dev_remove_bits, counts, rows, r0, r0, r1, row_bytes, c->stream);
+      if (e == hipSuccess) e = tavb::launch_compact_scatter(c->d_compact.ptr, const_cast<char*>(src), dev_remove_bits, counts, rows, r0, r1, row_bytes, c->stream);
+      if (e != hipSuccess) {
+        // rows may already have moved: the corpus is in no state to search
+        c->norm_rows = 0;
+        return fail(TAVB_E_HIP, "compaction launch failed with rows [%lld, %lld) pending: %s", (long long)r0, (long long)rows, hipGetErrorString(e));
+      }
+    }
+  }
+  if (int rc = tavb_set_corpus(c, dev_dst ? dev_dst : c->corpus, kept, c->dim, c->dtype, c->ordinal_base)) return rc;
+  return tavb_corpus_modified(c, first);
+}
+
 int tavb_mask_from_messages(tavb_ctx* c, const int32_t* accept_msgs_host, int64_t n_accept, int64_t rows, uint32_t* dev_bits_out) {
   if (int rc = check_ctx(c)) return rc;
   if (int rc = require_corpus(c)) return rc;

@@ -3,6 +3,7 @@
 // from the row -> message map on the device (mask_from_messages_kernel), so that a scoped message lookup never makes a host row list.
 // Scope algebra (tavb_mask_from_ranges, tavb_mask_combine): the mask of a scope of range collections (mask_from_ranges_kernel) and AND /
 // OR / ANDNOT of masks (mask_combine_kernel), both of which also leave the counts mask_write_kernel needs and the mask's count and span.
+// Row compaction (tavb_compact_rows): the rows a mask names are removed and the others moved down, by the same per-chunk counts (further down).
 //
 // The mask is uint32 words, row r = bit (r & 31) of word (r >> 5).  Two launches, both grids fixed on the host:
 //   mask_count_kernel   workgroup b popcounts its kMaskWordsPerBlock words -> counts[b]
@@ -273,7 +274,189 @@ __global__ void __launch_bounds__(kMaskThreads) mask_combine_kernel(MaskOperands
   mask_chunk_reduce(n, first, last, counts, info);
 }
 
+// ---- row compaction (tavb_compact_rows): the mask names the rows to REMOVE, the kept rows move down in their old order.
+//   compact_count_kernel    chunk b -> counts[b] = its KEPT rows, info[b] = that count and the chunk's first and last removed row
+//   compact_gather_kernel   a workgroup takes a tile of 64 rows (two mask words) of the row range [r0, r1): the tile's first slot is the
+//                           number of kept rows in [from, tile) -- whole chunks from the counts, the rest from the mask's words -- a row's
+//                           slot the popcount of the tile's kept bits below it, and a wave copies a kept row to dst + slot
+//   compact_scatter_kernel  staging [0, kept in [r0, r1)) -> corpus rows from (kept in [0, r0)) on: a flat copy whose ends every workgroup
+//                           works out for itself from the counts and the mask
+// No workgroup waits for another: the order between a pass' gather, its scatter and the next pass is stream order between launches.  The
+// copies move V (16, 8, 4 or 2 bytes: the launchers pick the widest that divides the row bytes and every address) at a time.
+
+constexpr int kCompactTileRows = 64;
+
+// the kept rows of word w: the complement of the removal bits, cut at `rows`; 0 past the last word
+__device__ __forceinline__ uint32_t kept_word(const uint32_t* __restrict__ bits, int64_t w, int64_t n_words, int64_t rows) {
+  if (w >= n_words) return 0u;
+  uint32_t v = ~bits[w];
+  const int tail = (int)(rows & 31);
+  if (w == n_words - 1 && tail != 0) v &= (1u << tail) - 1u;
+  return v;
+}
+
+// Kept rows in [a, b), the same value on every thread of the workgroup (all of them call it): a is a multiple of 32, b a multiple of 32 or
+// `rows`, a <= b.  Whole chunks come from counts[], the ends from the words.  sh: one LDS word, free again on return.
+__device__ __forceinline__ unsigned kept_between(const uint32_t* __restrict__ bits, const unsigned* __restrict__ counts, int64_t a, int64_t b,
+                                                 int64_t n_words, int64_t rows, unsigned* sh) {
+  constexpr int64_t kChunk = TAVB_MASK_ROWS_PER_WORKGROUP;
+  const int64_t wa = a >> 5, wb = (b + 31) >> 5;
+  const int64_t ca = (a + kChunk - 1) / kChunk, cb = b / kChunk;  // the whole chunks inside: [ca, cb)
+  unsigned part = 0;
+  if (ca <= cb) {
+    for (int64_t w = wa + threadIdx.x; w < ca * kMaskWordsPerBlock; w += kMaskThreads) part += (unsigned)__popc(kept_word(bits, w, n_words, rows));
+    for (int64_t ch = ca + threadIdx.x; ch < cb; ch += kMaskThreads) part += counts[ch];
+    for (int64_t w = cb * kMaskWordsPerBlock + threadIdx.x; w < wb; w += kMaskThreads) part += (unsigned)__popc(kept_word(bits, w, n_words, rows));
+  } else {  // no chunk boundary in [a, b]
+    for (int64_t w = wa + threadIdx.x; w < wb; w += kMaskThreads) part += (unsigned)__popc(kept_word(bits, w, n_words, rows));
+  }
+  if (threadIdx.x == 0) *sh = 0u;
+  __syncthreads();
+  if (part) atomicAdd(sh, part);
+  __syncthreads();
+  const unsigned all = *sh;
+  __syncthreads();
+  return all;
+}
+
+__global__ void __launch_bounds__(kMaskThreads) compact_count_kernel(const uint32_t* __restrict__ bits, int64_t rows, int64_t n_words,
+                                                                     unsigned* __restrict__ counts, MaskChunkInfo* __restrict__ info) {
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock;
+  unsigned n = 0;
+  int first = 0x7FFFFFFF, last = -1;
+  for (int i = threadIdx.x; i < kMaskWordsPerBlock; i += kMaskThreads) {
+    const int64_t w = w0 + i;
+    if (w >= n_words) break;
+    const uint32_t v = mask_word(bits, w, n_words, rows);
+    n += (unsigned)__popc(kept_word(bits, w, n_words, rows));
+    if (v) {
+      first = min(first, (int)(w << 5) + __ffs((int)v) - 1);
+      last = max(last, (int)(w << 5) + 31 - __clz((int)v));
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_down(n, d, 64);
+    first = min(first, __shfl_down(first, d, 64));
+    last = max(last, __shfl_down(last, d, 64));
+  }
+  mask_chunk_reduce(n, first, last, counts, info);
+}
+
+// n V's from s to d (disjoint), a wave's 64 lanes side by side; four loads in flight per lane
+template <typename V>
+__device__ __forceinline__ void wave_copy(const V* __restrict__ s, V* __restrict__ d, int64_t n, int lane) {
+  int64_t j = lane;
+  for (; j + 192 < n; j += 256) {
+    const V a = s[j], b = s[j + 64], c = s[j + 128], e = s[j + 192];
+    d[j] = a;
+    d[j + 64] = b;
+    d[j + 128] = c;
+    d[j + 192] = e;
+  }
+  for (; j < n; j += 64) d[j] = s[j];
+}
+
+// kept rows of src rows [r0, r1) -> dst rows [kept in [from, r0), ..), densely, in order.  r0 and `from` are multiples of 64, from <= r0, r1
+// a multiple of 64 or `rows`; src and dst do not overlap.  Workgroup b takes rows [r0 + 64 b, r0 + 64 b + 64).
+template <typename V>
+__global__ void __launch_bounds__(kMaskThreads) compact_gather_kernel(const char* __restrict__ src, char* __restrict__ dst,
+                                                                      const uint32_t* __restrict__ bits, const unsigned* __restrict__ counts,
+                                                                      int64_t rows, int64_t n_words, int64_t from, int64_t r0, int64_t r1,
+                                                                      int64_t row_bytes) {
+  __shared__ unsigned sh;
+  const int64_t t0 = r0 + (int64_t)blockIdx.x * kCompactTileRows;
+  if (t0 >= r1) return;  // (block-uniform)
+  const int64_t base = kept_between(bits, counts, from, t0, n_words, rows, &sh);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t w = t0 >> 5;
+  const unsigned long long km = (unsigned long long)kept_word(bits, w, n_words, rows) | ((unsigned long long)kept_word(bits, w + 1, n_words, rows) << 32);
+  const int64_t n_vec = row_bytes / (int64_t)sizeof(V);
+  for (int i = wave; i < kCompactTileRows; i += kMaskWaves) {  // (wave-uniform)
+    if (!((km >> i) & 1ull)) continue;
+    const int64_t slot = base + __popcll(km & ((1ull << i) - 1ull));
+    wave_copy(reinterpret_cast<const V*>(src + (t0 + i) * row_bytes), reinterpret_cast<V*>(dst + slot * row_bytes), n_vec, lane);
+  }
+}
+
+// staging rows [0, kept in [r0, r1)) -> corpus rows [kept in [0, r0), ..): a grid-stride copy
+template <typename V>
+__global__ void __launch_bounds__(kMaskThreads) compact_scatter_kernel(const char* __restrict__ staging, char* __restrict__ corpus,
+                                                                       const uint32_t* __restrict__ bits, const unsigned* __restrict__ counts,
+                                                                       int64_t rows, int64_t n_words, int64_t r0, int64_t r1, int64_t row_bytes) {
+  __shared__ unsigned sh;
+  const int64_t dst_row = kept_between(bits, counts, 0, r0, n_words, rows, &sh);
+  const int64_t kept = kept_between(bits, counts, r0, r1, n_words, rows, &sh);
+  const int64_t n = kept * (row_bytes / (int64_t)sizeof(V));
+  const V* __restrict__ s = reinterpret_cast<const V*>(staging);
+  V* __restrict__ d = reinterpret_cast<V*>(corpus + dst_row * row_bytes);
+  const int64_t step = (int64_t)gridDim.x * kMaskThreads;
+  int64_t j = (int64_t)blockIdx.x * kMaskThreads + threadIdx.x;
+  for (; j + 3 * step < n; j += 4 * step) {
+    const V a = s[j], b = s[j + step], c = s[j + 2 * step], e = s[j + 3 * step];
+    d[j] = a;
+    d[j + step] = b;
+    d[j + 2 * step] = c;
+    d[j + 3 * step] = e;
+  }
+  for (; j < n; j += step) d[j] = s[j];
+}
+
+// the widest of 16, 8, 4, 2 bytes that divides `x` (row bytes or'ed with the addresses)
+int compact_vector_bytes(uint64_t x) {
+  for (int v = 16; v > 2; v >>= 1)
+    if (x % (uint64_t)v == 0) return v;
+  return 2;
+}
+
 }  // namespace
+
+hipError_t launch_compact_count(const uint32_t* bits, int64_t rows, unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
+  if (!bits || !counts || !info || rows < 1 || rows >= 0x7FFFFFFFll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(compact_count_kernel, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, bits, rows, (rows + 31) >> 5, counts, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_gather(const void* src, void* dst, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t from, int64_t r0,
+                                 int64_t r1, int64_t row_bytes, hipStream_t stream) {
+  if (!src || !dst || !bits || !counts || rows < 1 || rows >= 0x7FFFFFFFll || row_bytes < 2 || row_bytes % 2 != 0 || from < 0 || from > r0 || r0 >= r1 ||
+      r1 > rows || from % kCompactTileRows != 0 || r0 % kCompactTileRows != 0 || (r1 % kCompactTileRows != 0 && r1 != rows))
+    return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((r1 - r0 + kCompactTileRows - 1) / kCompactTileRows);
+  const int64_t n_words = (rows + 31) >> 5;
+  const char* s = reinterpret_cast<const char*>(src);
+  char* d = reinterpret_cast<char*>(dst);
+#define TAVB_GATHER(V) hipLaunchKernelGGL(compact_gather_kernel<V>, dim3(blocks), dim3(kMaskThreads), 0, stream, s, d, bits, counts, rows, n_words, from, r0, r1, row_bytes)
+  switch (compact_vector_bytes((uint64_t)row_bytes | reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst))) {
+    case 16: TAVB_GATHER(uint4); break;
+    case 8: TAVB_GATHER(uint2); break;
+    case 4: TAVB_GATHER(uint32_t); break;
+    default: TAVB_GATHER(uint16_t); break;
+  }
+#undef TAVB_GATHER
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_scatter(const void* staging, void* corpus, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t r0, int64_t r1,
+                                  int64_t row_bytes, hipStream_t stream) {
+  if (!staging || !corpus || !bits || !counts || rows < 1 || rows >= 0x7FFFFFFFll || row_bytes < 2 || row_bytes % 2 != 0 || r0 < 0 || r0 >= r1 || r1 > rows ||
+      r0 % kCompactTileRows != 0 || (r1 % kCompactTileRows != 0 && r1 != rows))
+    return hipErrorInvalidValue;
+  const int vb = compact_vector_bytes((uint64_t)row_bytes | reinterpret_cast<uintptr_t>(staging) | reinterpret_cast<uintptr_t>(corpus));
+  const int64_t most = (r1 - r0) * (row_bytes / vb);  // V's to copy when every row of the pass is kept
+  const unsigned blocks = (unsigned)std::min<int64_t>((most + 4 * kMaskThreads - 1) / (4 * kMaskThreads), 2048);
+  const int64_t n_words = (rows + 31) >> 5;
+  const char* s = reinterpret_cast<const char*>(staging);
+  char* d = reinterpret_cast<char*>(corpus);
+#define TAVB_SCATTER(V) hipLaunchKernelGGL(compact_scatter_kernel<V>, dim3(blocks), dim3(kMaskThreads), 0, stream, s, d, bits, counts, rows, n_words, r0, r1, row_bytes)
+  switch (vb) {
+    case 16: TAVB_SCATTER(uint4); break;
+    case 8: TAVB_SCATTER(uint2); break;
+    case 4: TAVB_SCATTER(uint32_t); break;
+    default: TAVB_SCATTER(uint16_t); break;
+  }
+#undef TAVB_SCATTER
+  return hipGetLastError();
+}
 
 int mask_blocks(int64_t rows) { return (int)((rows + TAVB_MASK_ROWS_PER_WORKGROUP - 1) / TAVB_MASK_ROWS_PER_WORKGROUP); }
 

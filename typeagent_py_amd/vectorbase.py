@@ -32,6 +32,7 @@ Documented deviations from the reference (none is exercised by its callers):
 
 from __future__ import annotations
 
+import ctypes
 import gc
 import os
 import time
@@ -270,19 +271,21 @@ class RowMask:
     """What `VectorBase.row_mask(allowed)` returns: the allowed rows of ONE index at ONE length, expanded once and kept where the lookups
     read them -- on a single-GPU engine an int32 row list in device memory (`dev_rows`, ascending; `count` of them), so that a masked
     lookup sends only its queries.  `rows` is the index length the mask was built for: a handle used after the index grew or shrank
-    raises ValueError.  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it.  On a device group the
+    raises ValueError, and so does one used after `VectorBase.remove_rows` removed a row, whatever the length is by then (`epoch`).  `flat()` is np.flatnonzero of the mask, made on first use; only the fallback route needs it.  On a device group the
     handle holds one shard-local list per device (`shards`, cut by `bounds`), on a row-sharded index this rank's list and the packed mask.
     A single-GPU engine also keeps the packed mask on the device (`dev_bits`, int32 words: row r = bit r & 31 of word r >> 5) and
     `span` = (first, last) allowed row, read once when the handle is built (or handed in as `span=` by the scope algebra, whose kernels
     report it): what a batch on the 32/64-query tile reads instead of the list.  Handles of one index combine: `a & b`, `a | b`, `a - b`,
     `~a` (`VectorBase.intersect_masks` / `union_masks`)."""
 
-    __slots__ = ("rows", "count", "dev_rows", "dev_bits", "span", "shards", "bounds", "layout", "bits", "_flat", "_owner", "_plans")
+    __slots__ = ("rows", "count", "dev_rows", "dev_bits", "span", "shards", "bounds", "layout", "bits", "epoch", "_flat", "_owner", "_plans")
 
     def __init__(self, owner, rows: int, count: int, dev_rows=None, flat: np.ndarray | None = None, shards=None, bounds=None, layout=None, bits=None,
                  dev_bits=None, span=None):
         self.rows = int(rows)
         self.count = int(count)
+        # the owner's removal epoch (`VectorBase.remove_rows` bumps it): the same length after a removal and an append is not the same rows
+        self.epoch = getattr(owner, "_removal_epoch", 0)
         self.dev_rows = dev_rows
         self.dev_bits = dev_bits
         if span is not None:  # the scope algebra's kernels report it with the count: nothing is read back
@@ -399,6 +402,7 @@ class VectorBase:
         self._subset_cache = None  # (caller's subset object, private copy, row count, ordinals int64, device int32 rows) of the last subset lookup
         self._row_messages: np.ndarray | None = None  # chunk row -> message ordinal (message re-rank on the device)
         self._row_messages_rows = -1  # rows of the map already on the device
+        self._removal_epoch = 0  # bumped by every remove_rows() that removed a row: a RowMask made before it names other rows now
         self.clear()
 
     # ------------------------------------------------------------------ storage
@@ -942,6 +946,8 @@ class VectorBase:
             raise ValueError("this RowMask was built by another index")
         if allowed.rows != self._count:
             raise ValueError(f"mask covers {allowed.rows} rows, the index has {self._count}")
+        if allowed.epoch != self._removal_epoch:
+            raise ValueError("this RowMask was built before rows were removed from the index: build it again")
         return allowed
 
     # ------------------------------------------------------------------ scope algebra (additive)
@@ -1294,6 +1300,106 @@ class VectorBase:
             min_score = self.settings.min_score
         embedding = await self.get_embedding(key)
         return self.fuzzy_lookup_embedding(embedding, max_hits=max_hits, min_score=min_score, predicate=predicate)
+
+    # ------------------------------------------------------------------ removal (additive)
+    def _removal_flags(self, which) -> tuple[np.ndarray | None, RowMask | None, int]:
+        """What `remove_rows` was handed -> (bool [len(self)] of the rows to remove, or None when a RowMask's packed mask on the device says
+        it; that RowMask; how many rows go)."""
+        n = self._count
+        if isinstance(which, RowMask):
+            mask = self._resolve_mask(which)
+            if mask.dev_bits is not None:
+                return None, mask, mask.count
+            return self._mask_bools(mask), None, mask.count
+        a = np.asarray(which)
+        if a.dtype == np.bool_:
+            if a.ndim != 1 or a.shape[0] != n:
+                raise ValueError("boolean array argument obj to delete must be one dimensional and match the axis length of " + str(n))
+            return a, None, int(np.count_nonzero(a))
+        if a.size == 0:
+            return np.zeros(n, dtype=bool), None, 0
+        if a.dtype.kind not in "iu":
+            raise IndexError("arrays used as indices must be of integer (or boolean) type")
+        a = a.reshape(-1).astype(np.int64)
+        bad = a[(a < -n) | (a >= n)]
+        if bad.size:
+            raise IndexError(f"index {int(bad[0])} is out of bounds for axis 0 with size {n}")
+        flags = np.zeros(n, dtype=bool)
+        flags[a] = True  # (negatives wrap, duplicates fall together: np.delete's rules)
+        return flags, None, int(np.count_nonzero(flags))
+
+    def remove_rows(self, which) -> int:
+        """Remove rows -> how many went.  `which`: integer ordinals with np.delete's rules (duplicates allowed, negatives wrap, out of range
+        raises IndexError), a bool array of length len(self), or a `RowMask` of this index.  Defined as the reference class with
+        `_vectors = np.delete(_vectors, which, axis=0)`: later ordinals shift down -- the removal the reference leaves as a TODO
+        (storage/sqlite/reltermsindex.py:181-192, knowpro/fuzzyindex.py:113-127).  On a single-GPU engine the device corpus is compacted on
+        the device (tavb_compact_rows): a mirror is not uploaded again, a device-only corpus is not copied to the host, a RowMask's packed
+        mask is used where it is; ordinals and bool arrays travel as rows / 8 bytes.  The host matrix, when there is one, is compacted in
+        its growth buffer -- unless somebody else holds it (a matrix adopted by deserialize(), a view handed out by serialize()): then the
+        index moves to a buffer of its own, as np.delete would.  The row -> message map loses the same rows.  Every `RowMask` built before
+        the call raises ValueError from then on.  A device group (`devices=[...]`) removes on the host and uploads again."""
+        flags, mask, removed = self._removal_flags(which)
+        if removed == 0:
+            return 0
+        n = self._count
+        eng = self._engine
+        native = eng is not None and hasattr(eng, "compact_rows")  # (a device group has no such call: the host route)
+        if self._device_only is not None and not native:
+            self._materialize_host()  # a device group: the host route
+        if native and self._device_only is None:
+            eng = self._sync_device()  # rows appended or edited since the last lookup reach the mirror first
+        need_host_list = self._device_only is None or self._row_messages is not None
+        if flags is None and (need_host_list or not native):
+            flags = self._mask_bools(mask)
+        if native:
+            dev_bits = mask.dev_bits if mask is not None else eng.mask_bits_to_device(_native.pack_mask_bits(flags))
+            kept = eng.compact_rows(dev_bits)
+            if kept != n - removed:
+                raise RuntimeError(f"the device kept {kept} rows of {n}, expected {n - removed}")
+        if self._device_only is not None:
+            self._device_only = eng.corpus
+            self._dev_rows, self._dev_valid = n - removed, True
+        else:
+            keep = ~flags
+            first = int(np.argmax(flags))
+            if self._handed_out or self._view_out:
+                # the caller's own matrix, or one somebody holds a view of: np.delete leaves theirs as it is
+                fresh = np.empty((max(n - removed, 4), self._embedding_size), dtype=np.float32)
+                fresh[: n - removed] = self._host[:n][keep]
+                self._host = fresh
+                self._handed_out = self._view_out = False
+                self._dev_fingerprint = None
+            else:
+                # in the growth buffer, a block at a time: a block's kept rows are copied out and land at or below where they were
+                dst, block = first, max(1, (64 << 20) // max(self._host.shape[1] * 4, 1))
+                row_bytes = self._host.strides[0]
+                for b0 in range(first, n, block):
+                    k = keep[b0 : b0 + block]
+                    if k.all() and self._host.flags.c_contiguous:  # a whole block moves down: one pass (the ranges may overlap)
+                        ctypes.memmove(self._host.ctypes.data + dst * row_bytes, self._host.ctypes.data + b0 * row_bytes, len(k) * row_bytes)
+                        dst += len(k)
+                        continue
+                    part = self._host[b0 : b0 + len(k)][k]
+                    self._host[dst : dst + len(part)] = part
+                    dst += len(part)
+            if native:
+                self._dev_rows, self._dev_valid = n - removed, True
+            else:
+                self._dev_rows, self._dev_valid = 0, False
+        self._count = n - removed
+        if self._row_messages is not None:
+            self._row_messages = np.delete(self._row_messages, np.flatnonzero(flags))
+            self._row_messages_src = None  # (the caller's object describes the rows as they were)
+            self._row_messages_rows = -1
+        self._subset_cache = None
+        self._removal_epoch += 1
+        return removed
+
+    def remove_at(self, pos: int) -> None:
+        """The method the reference keeps commented out (knowpro/fuzzyindex.py:113-127): remove the embedding at `pos`."""
+        if not 0 <= pos < self._count:
+            raise IndexError(f"Index {pos} out of bounds for embedding index of size {len(self)}")
+        self.remove_rows([pos])
 
     # ------------------------------------------------------------------ bookkeeping
     def _set_embedding_size(self, size: int) -> None:
