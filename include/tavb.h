@@ -112,6 +112,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                           (single queries included) on fp32 corpora of "f32_shadow_min_bytes" (default 2 GiB) and more filters on the
  *                           shadow with the 32/64-query tile: half the bytes per pass (1M x 1536: 0.93 -> 0.70 ms per query, 32 queries 1.46 -> 0.94 ms)
  *   "last_shadow"           (get) 1 when the last lookup's corpus pass read the shadow
+ *   "norm_rows"             (get) the corpus rows the cached row-norm maxima (and the shadow, where there is one) cover: a large batch extends them
+ *                           to every row, a rewrite of covered rows (tavb_corpus_modified) drops them to 0, tavb_scatter_rows keeps them
  *   "mfma_tile"             queries per workgroup tile of the wide fp16 kernel: 0 = auto (128 where that pads less: up to 128, 257..384, 513..640 queries; else 256), 128, 256
  *   "mfma_splits", "mfma_sched", "mfma_ablate"  measurement knobs: row ranges per launch; staging variant (256-query tile: 1 / 2 = other piece
  *                           schedules, 3 / 4 / 5 = other issue orders of a slice's MFMAs -- profiles/r06_mfma_power.md; 32-query tile: 7 = LDS-DMA ring (the default), 8 = deep corpus ring, 5 = register staging four K steps
@@ -203,8 +205,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "sort_small_keys" 0 .. 16384 (default 16384): a sort of up to this many keys (tavb_search_sorted, tavb_sort_keys_device) runs in ONE
  *                   workgroup in LDS; bigger ones take the multi-pass radix sort (3 launches per 8-bit digit that is not the same for
  *                   every key, + 2)
- *   "compact_pass_rows" 0 .. 2^31 - 2 (default 0 = auto: about 64 MiB of rows): rows per pass of an in-place tavb_compact_rows, rounded up to a
- *                   multiple of 64; its staging workspace holds one pass
+ *   "compact_pass_rows" 0 .. 2^31 - 2 (default 0 = auto: about 64 MiB of rows): rows per pass of an in-place tavb_compact_rows or tavb_expand_rows,
+ *                   rounded up to a multiple of 64; their staging workspace holds one pass
  */
 int tavb_set_option(tavb_ctx* ctx, const char* name, int64_t value);
 int tavb_get_option(tavb_ctx* ctx, const char* name, int64_t* out_value);
@@ -553,6 +555,36 @@ int tavb_mask_combine(tavb_ctx* ctx, int32_t op, const uint32_t* const* dev_mask
  * mask must stay alive until then.  Timed under TAVB_KERNEL_CONVERT.  The row -> message map (tavb_set_row_messages) is the caller's to
  * compact and set again. */
 int tavb_compact_rows(tavb_ctx* ctx, const uint32_t* dev_remove_bits, int64_t rows, void* dev_dst /* NULL = in place */, int64_t* out_rows);
+
+/* ---- inserting and overwriting rows: expansion of the corpus on the device, scattered row writes ---------------------------------------
+ * The insertion the reference keeps commented out (knowpro/fuzzyindex.py:50-83, `insert_at` around np.vstack), in two calls: tavb_expand_rows
+ * opens the holes, tavb_scatter_rows fills them (and, alone, overwrites rows).
+ * tavb_expand_rows: dev_hole_bits is a mask in the bit form above over the NEW row count new_rows, in which a SET bit means "a hole for a new
+ * row"; its clear bits below new_rows must number exactly the corpus' rows -- else the call fails with TAVB_E_INVALID and moves nothing; bits
+ * at or beyond new_rows may hold anything.  Afterwards old row i stands, bit for bit, at the i-th row whose bit is clear -- the old rows of
+ * np.insert's result -- the holes hold whatever was there, *out_old_rows = the clear bits counted, and the call has ended with
+ * tavb_set_corpus(.., new_rows, ..) (same dim, dtype and ordinal_base; the pointer is dev_dst when that is given) and
+ * tavb_corpus_modified(first hole).
+ *   dev_dst == NULL: IN PLACE.  The corpus buffer must hold new_rows rows (the caller's to guarantee).  Rows only move up.  From the 64-row
+ *     tile of the first hole on, the new rows are taken in passes of "compact_pass_rows" rows, FROM THE TAIL: the old rows of a pass are one
+ *     contiguous range; one launch copies it into the staging workspace, a second writes its rows to their new places inside the pass.  A pass
+ *     reads only old rows at or below its own first new row, and writes only its own new rows, which every later (lower) pass neither reads
+ *     nor writes.  The order between the launches is stream order and nothing else: no workgroup waits for another.  Two launches per pass;
+ *     every row moves at most twice.  Holes only behind the last old row move nothing.
+ *   dev_dst != NULL: OUT OF PLACE, one launch: the old rows are written to their new places in dev_dst (device memory for at least new_rows
+ *     rows that does not overlap the corpus, aligned to the element size); the old corpus is read only.  The route for a corpus buffer the
+ *     caller may not write, or one that is too small.
+ * A mask with no bit set (new_rows == the corpus' rows) is a no-op: nothing moves, no cache is touched, dev_dst is neither written nor
+ * adopted.  An empty corpus takes every row as a hole.  The count pass is waited for (ONE synchronise); the moves are enqueued on the context's
+ * stream and NOT waited for, as tavb_compact_rows' are.  Timed under TAVB_KERNEL_CONVERT.  The row -> message map is the caller's to set again.
+ * tavb_scatter_rows: n host rows [n, dim] (fp32; dim must be the corpus') -> corpus rows dev_positions[j] (int32, in device memory, each in
+ * [0, rows) and no two alike: the caller resolves duplicates), converted to the corpus dtype exactly as tavb_upload_rows converts, through the
+ * same staging slots.  The positions are checked on the device before anything is written: one outside the corpus fails the call with
+ * TAVB_E_INVALID.  The per-corpus caches are KEPT: a row that the cached row-norm maxima cover also gets its fp16 shadow row (fp32 corpora,
+ * and fp16 corpora whose width is not a multiple of 64) and folds its norms into the maxima, which stay upper bounds (a replaced row's old
+ * norm is not taken out).  Returns when the rows are written (rows_host may be reused).  Timed under TAVB_KERNEL_CONVERT. */
+int tavb_expand_rows(tavb_ctx* ctx, const uint32_t* dev_hole_bits, int64_t new_rows, void* dev_dst /* NULL = in place */, int64_t* out_old_rows);
+int tavb_scatter_rows(tavb_ctx* ctx, const float* rows_host_f32, int64_t n, int32_t dim, const int32_t* dev_positions_i32);
 
 /* Merge `n_lists` sorted key lists per query (dev_lists [n_lists, nq, k], e.g. the
  * all-gathered per-shard results) into one list per query: dev_out_keys [nq, k]. */

@@ -102,6 +102,8 @@ _SIGNATURES = [
     ("tavb_mask_from_ranges", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_mask_combine", c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
+    ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
+    ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -541,6 +543,65 @@ class Engine:
             self.corpus, self._owns_corpus = fresh, True
         self.rows = n
         return n
+
+    def _check_device_words(self, t, what: str) -> None:
+        torch = self._torch
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1
+        if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device}")
+
+    def expand_rows(self, dev_hole_bits, new_rows: int) -> int:
+        """Make room for new rows: `dev_hole_bits` (torch int32 [(new_rows + 31) // 32] on this device, the layout of `pack_mask_bits`)
+        covers the NEW row count, a set bit is a hole; the old rows -- the clear bits must number `self.rows` -- move up in their old
+        order to the rows whose bit is clear (tavb_expand_rows): the old rows of np.insert on the device -> how many old rows there
+        were.  The holes hold anything until `scatter_rows` fills them.  A corpus buffer this engine allocated that holds `new_rows`
+        rows is expanded in place; otherwise -- a tensor adopted from the caller, which is never written, or no capacity left -- the
+        rows are placed in a fresh tensor of max(new_rows, twice the capacity, 16) rows, which becomes the owned corpus.  A mask with
+        no bit set changes nothing."""
+        torch = self._torch
+        new_rows = int(new_rows)
+        if self.corpus is None:
+            raise RuntimeError("no corpus to expand: upload_rows() or set_corpus_tensor() first")
+        self._check_device_words(dev_hole_bits, "the mask")
+        assert dev_hole_bits.numel() * 32 >= new_rows
+        fresh = None
+        if new_rows > self.rows and (not self._owns_corpus or self.corpus.shape[0] < new_rows):
+            fresh = torch.empty((max(new_rows, 2 * self.corpus.shape[0], 16), self.dim), dtype=self.corpus.dtype, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()  # whatever produced the mask (and the allocation above) ran on torch's stream
+        old = c_int64(0)
+        with self._lock:
+            rc = self.lib.tavb_expand_rows(self._h, c_void_p(dev_hole_bits.data_ptr()), new_rows, c_void_p(fresh.data_ptr()) if fresh is not None else None,
+                                           byref(old))
+        _check(self.lib, rc)
+        self.synchronize()  # the moves were only enqueued: the mask, and the old tensor, may be released once they are done
+        if fresh is not None:
+            self.corpus, self._owns_corpus = fresh, True
+        self.rows = new_rows
+        return int(old.value)
+
+    def scatter_rows(self, host_rows: np.ndarray, positions) -> None:
+        """Write `host_rows` (f32 [n, dim]) to corpus rows `positions` (n int32 ordinals, all different, each below `self.rows`: a torch
+        int32 tensor on this device, or anything numpy makes one of -- 4 bytes a row travel), converted as `upload_rows` converts them
+        (tavb_scatter_rows): the holes `expand_rows` left, or rows to overwrite.  The library's per-corpus caches survive: rows they cover
+        get their fp16 shadow row written and their norms folded into the cached maxima.  A tensor adopted from the caller is never
+        written: the corpus moves to a tensor of the engine's first."""
+        torch = self._torch
+        src = np.ascontiguousarray(host_rows, dtype=np.float32)
+        if src.ndim != 2 or self.corpus is None or src.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        if not isinstance(positions, torch.Tensor):
+            positions = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)).to(torch.device("cuda", self.device))
+        self._check_device_words(positions, "the positions")
+        if positions.numel() != src.shape[0]:
+            raise ValueError(f"{positions.numel()} positions for {src.shape[0]} rows")
+        if src.shape[0] == 0:
+            return
+        if not self._owns_corpus:
+            self.set_corpus_tensor(self.corpus.clone(), rows=self.rows, ordinal_base=self.ordinal_base, _owned=True)
+        torch.cuda.current_stream(self.device).synchronize()  # the positions (and the copy above) were made on torch's stream
+        with self._lock:
+            rc = self.lib.tavb_scatter_rows(self._h, _addr(src), src.shape[0], self.dim, c_void_p(positions.data_ptr()))
+        _check(self.lib, rc)
 
     def clear(self) -> None:
         if self.corpus is not None:

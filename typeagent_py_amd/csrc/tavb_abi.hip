@@ -255,6 +255,7 @@ const Option kOptions[] = {
     READ_ONLY("masked_route", masked_route),
     RANGE("mask_wide", mask_wide, 0, 2),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
+    READ_ONLY("norm_rows", norm_rows),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),
     READ_ONLY("last_topk_refine", last_topk_refine),

@@ -183,6 +183,20 @@ hipError_t launch_compact_gather(const void* src, void* dst, const uint32_t* bit
                                  int64_t r1, int64_t row_bytes, hipStream_t stream);
 hipError_t launch_compact_scatter(const void* staging, void* corpus, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t r0, int64_t r1,
                                   int64_t row_bytes, hipStream_t stream);
+// Row expansion (tavb_mask.hip; `bits` covers the NEW `rows` and names the HOLES; counts: launch_compact_count's over the same mask, so
+// "kept" reads "clear bit" = an old row).  expand_stage: the old rows of new rows [r0, r1) -- corpus rows [clear bits in [0, r0), clear bits
+// in [0, r1)) -> staging rows from 0 on.  expand_scatter: src rows from (clear bits in [from, r0)) on -> the rows of dst rows [r0, r1) whose
+// bit is clear, in order; holes are left as they are.  The same rules for from, r0, r1 and row_bytes as above; src and dst must not overlap.
+hipError_t launch_expand_stage(const void* corpus, void* staging, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t r0, int64_t r1,
+                               int64_t row_bytes, hipStream_t stream);
+hipError_t launch_expand_scatter(const void* src, void* dst, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t from, int64_t r0,
+                                 int64_t r1, int64_t row_bytes, hipStream_t stream);
+// Scattered row writes (tavb_mask.hip).  scatter_check: *bad = 1 (memory the device can write; zeroed by the caller) when a position is outside
+// [0, rows).  scatter_rows: fp32 device rows src [n, dim] -> corpus rows positions[j] (unique), converted as launch_f32_to_f16 converts; rows
+// below norm_rows also get their fp16 shadow row (shadow != NULL: sdim halves per row) and fold their norms into stats (the cached maxima).
+hipError_t launch_scatter_check(const int32_t* positions, int64_t n, int64_t rows, int* bad, hipStream_t stream);
+hipError_t launch_scatter_rows(const float* src, int64_t n, int dim, const int32_t* positions, int64_t rows, void* corpus, bool f16, void* shadow, int sdim,
+                               int64_t norm_rows, float* stats, hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per (device, kernel) (tavb_misc.hip)
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "tavb_device.h"
 #include "tavb_internal.h"
 
 namespace tavb {
@@ -356,6 +357,21 @@ __device__ __forceinline__ void wave_copy(const V* __restrict__ s, V* __restrict
   for (; j < n; j += 64) d[j] = s[j];
 }
 
+// n V's from s to d (disjoint), the whole grid side by side: a grid-stride copy, four loads in flight per thread
+template <typename V>
+__device__ __forceinline__ void grid_copy(const V* __restrict__ s, V* __restrict__ d, int64_t n) {
+  const int64_t step = (int64_t)gridDim.x * kMaskThreads;
+  int64_t j = (int64_t)blockIdx.x * kMaskThreads + threadIdx.x;
+  for (; j + 3 * step < n; j += 4 * step) {
+    const V a = s[j], b = s[j + step], c = s[j + 2 * step], e = s[j + 3 * step];
+    d[j] = a;
+    d[j + step] = b;
+    d[j + 2 * step] = c;
+    d[j + 3 * step] = e;
+  }
+  for (; j < n; j += step) d[j] = s[j];
+}
+
 // kept rows of src rows [r0, r1) -> dst rows [kept in [from, r0), ..), densely, in order.  r0 and `from` are multiples of 64, from <= r0, r1
 // a multiple of 64 or `rows`; src and dst do not overlap.  Workgroup b takes rows [r0 + 64 b, r0 + 64 b + 64).
 template <typename V>
@@ -386,19 +402,7 @@ __global__ void __launch_bounds__(kMaskThreads) compact_scatter_kernel(const cha
   __shared__ unsigned sh;
   const int64_t dst_row = kept_between(bits, counts, 0, r0, n_words, rows, &sh);
   const int64_t kept = kept_between(bits, counts, r0, r1, n_words, rows, &sh);
-  const int64_t n = kept * (row_bytes / (int64_t)sizeof(V));
-  const V* __restrict__ s = reinterpret_cast<const V*>(staging);
-  V* __restrict__ d = reinterpret_cast<V*>(corpus + dst_row * row_bytes);
-  const int64_t step = (int64_t)gridDim.x * kMaskThreads;
-  int64_t j = (int64_t)blockIdx.x * kMaskThreads + threadIdx.x;
-  for (; j + 3 * step < n; j += 4 * step) {
-    const V a = s[j], b = s[j + step], c = s[j + 2 * step], e = s[j + 3 * step];
-    d[j] = a;
-    d[j + step] = b;
-    d[j + 2 * step] = c;
-    d[j + 3 * step] = e;
-  }
-  for (; j < n; j += step) d[j] = s[j];
+  grid_copy(reinterpret_cast<const V*>(staging), reinterpret_cast<V*>(corpus + dst_row * row_bytes), kept * (row_bytes / (int64_t)sizeof(V)));
 }
 
 // the widest of 16, 8, 4, 2 bytes that divides `x` (row bytes or'ed with the addresses)
@@ -408,7 +412,212 @@ int compact_vector_bytes(uint64_t x) {
   return 2;
 }
 
+// ---- row expansion (tavb_expand_rows): the mirror image.  The mask covers the NEW row count and names the HOLES that new rows will fill; the
+// old rows -- as many as the mask has clear bits -- move up, in order, to the rows whose bit is clear.  kept_word / kept_between count clear
+// bits, so "kept rows before r" is old row o(r) = the source of new row r.
+//   expand_stage_kernel    the old rows of new rows [r0, r1) are the contiguous range [o(r0), o(r1)): a flat copy of them into staging,
+//                          whose ends every workgroup works out for itself (in place only)
+//   expand_scatter_kernel  a workgroup takes a tile of 64 new rows of [r0, r1): the tile's first source slot is the number of clear bits in
+//                          [from, tile) -- from = r0 over the staging of the pass, 0 over the whole old corpus (out of place) -- and a wave
+//                          copies source row slot + (clear bits of the tile below i) to row tile + i for every clear bit i.  Holes are not
+//                          written: tavb_scatter_rows fills them.
+// In place the passes run FROM THE TAIL (tavb_expand_rows says why that is safe); the order between launches is stream order, nothing else.
+
+template <typename V>
+__global__ void __launch_bounds__(kMaskThreads) expand_stage_kernel(const char* __restrict__ corpus, char* __restrict__ staging,
+                                                                    const uint32_t* __restrict__ bits, const unsigned* __restrict__ counts,
+                                                                    int64_t rows, int64_t n_words, int64_t r0, int64_t r1, int64_t row_bytes) {
+  __shared__ unsigned sh;
+  const int64_t o0 = kept_between(bits, counts, 0, r0, n_words, rows, &sh);
+  const int64_t n_old = kept_between(bits, counts, r0, r1, n_words, rows, &sh);
+  grid_copy(reinterpret_cast<const V*>(corpus + o0 * row_bytes), reinterpret_cast<V*>(staging), n_old * (row_bytes / (int64_t)sizeof(V)));
+}
+
+// src rows [clear bits in [from, r0), ..) -> the rows of dst rows [r0, r1) whose bit is clear, in order.  r0 and `from` are multiples of 64,
+// from <= r0, r1 a multiple of 64 or `rows`; src and dst do not overlap.  Workgroup b takes rows [r0 + 64 b, r0 + 64 b + 64).
+template <typename V>
+__global__ void __launch_bounds__(kMaskThreads) expand_scatter_kernel(const char* __restrict__ src, char* __restrict__ dst,
+                                                                      const uint32_t* __restrict__ bits, const unsigned* __restrict__ counts,
+                                                                      int64_t rows, int64_t n_words, int64_t from, int64_t r0, int64_t r1,
+                                                                      int64_t row_bytes) {
+  __shared__ unsigned sh;
+  const int64_t t0 = r0 + (int64_t)blockIdx.x * kCompactTileRows;
+  if (t0 >= r1) return;  // (block-uniform)
+  const int64_t base = kept_between(bits, counts, from, t0, n_words, rows, &sh);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t w = t0 >> 5;
+  const unsigned long long km = (unsigned long long)kept_word(bits, w, n_words, rows) | ((unsigned long long)kept_word(bits, w + 1, n_words, rows) << 32);
+  const int64_t n_vec = row_bytes / (int64_t)sizeof(V);
+  for (int i = wave; i < kCompactTileRows; i += kMaskWaves) {  // (wave-uniform)
+    if (!((km >> i) & 1ull)) continue;
+    const int64_t slot = base + __popcll(km & ((1ull << i) - 1ull));
+    wave_copy(reinterpret_cast<const V*>(src + slot * row_bytes), reinterpret_cast<V*>(dst + (t0 + i) * row_bytes), n_vec, lane);
+  }
+}
+
+// ---- scattered row writes (tavb_scatter_rows): n staged fp32 rows -> corpus rows positions[j], converted to the corpus' dtype as the load
+// path converts them ((_Float16)x: v_cvt_f16_f32, round to nearest even), so a row written here equals the same row uploaded.
+//   scatter_check_kernel   *bad = 1 when a position lies outside [0, rows) (host memory the device writes; the host zeroes it first)
+//   scatter_rows_kernel    one wave per row.  A row BELOW norm_rows is covered by the per-corpus caches, which are kept up to date instead of
+//                          thrown away: its fp16 shadow row is written where there is a shadow (`shadow`, sdim halves per row, the tail zero),
+//                          and its squared norms are folded into the cached maxima (stats[0] = max sum(x16^2), fp32 corpora also stats[1] =
+//                          max sum((x - x16)^2)) -- summed in the order shadow_convert_kernel / corpus_max_norm_kernel sum them (a lane takes
+//                          groups of 4 floats, or 8 halves, 64 groups apart), folded with the same atomic maximum.  The old norm of a replaced
+//                          row stays in the maximum: it is an upper bound, which is all the filter needs.
+
+__global__ void __launch_bounds__(kMaskThreads) scatter_check_kernel(const int32_t* __restrict__ positions, int64_t n, int64_t rows, int* __restrict__ bad) {
+  for (int64_t j = (int64_t)blockIdx.x * kMaskThreads + threadIdx.x; j < n; j += (int64_t)gridDim.x * kMaskThreads) {
+    const int32_t p = positions[j];
+    if (p < 0 || (int64_t)p >= rows) *bad = 1;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kMaskThreads) scatter_rows_kernel(const float* __restrict__ src, int64_t n, int dim,
+                                                                    const int32_t* __restrict__ positions, int64_t rows, T* __restrict__ corpus,
+                                                                    _Float16* __restrict__ shadow, int sdim, int64_t norm_rows,
+                                                                    float* __restrict__ stats) {
+  constexpr bool kF32 = sizeof(T) == 4;
+  constexpr int G = kF32 ? 4 : 8;  // elements of one lane's step: shadow_convert_kernel's (fp32 rows) and corpus_max_norm_kernel's (fp16 rows)
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * kMaskWaves + (threadIdx.x >> 6);
+  const int64_t n_waves = (int64_t)gridDim.x * kMaskWaves;
+  const int groups = (dim + G - 1) / G;
+  const bool whole = dim % G == 0 && ((uintptr_t)src | (uintptr_t)corpus) % 16 == 0;  // 16-byte loads and stores (rows are then 16-byte multiples)
+  float best16 = 0.f, best_err = 0.f;
+  bool folded = false;
+  for (int64_t j = wave; j < n; j += n_waves) {  // (wave-uniform)
+    const int64_t p = positions[j];
+    if (p < 0 || p >= rows) continue;  // (the host has checked: never taken)
+    const bool cached = p < norm_rows;
+    const float* x = src + j * (int64_t)dim;
+    T* y = corpus + p * (int64_t)dim;
+    _Float16* s = (cached && shadow) ? shadow + p * (int64_t)sdim : nullptr;
+    float ss = 0.f, se = 0.f;
+    for (int g = lane; g < groups; g += 64) {
+      float e[G];
+      _Float16 h[G];
+      const int i0 = g * G;
+      if (whole) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(x + i0);
+        e[0] = a.x; e[1] = a.y; e[2] = a.z; e[3] = a.w;
+        if constexpr (!kF32) {
+          const f32x4 b = *reinterpret_cast<const f32x4*>(x + i0 + 4);
+          e[4] = b.x; e[5] = b.y; e[6] = b.z; e[7] = b.w;
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < G; ++t) e[t] = (i0 + t < dim) ? x[i0 + t] : 0.0f;
+      }
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        h[t] = (_Float16)e[t];
+        const float hf = (float)h[t];
+        ss = fmaf(hf, hf, ss);
+        if constexpr (kF32) {
+          const float d = e[t] - hf;
+          se = fmaf(d, d, se);
+        }
+      }
+      if (whole) {
+        if constexpr (kF32) {
+          *reinterpret_cast<f32x4*>(y + i0) = f32x4{e[0], e[1], e[2], e[3]};
+          if (s) *reinterpret_cast<uint2*>(s + i0) = *reinterpret_cast<const uint2*>(h);
+        } else {
+          *reinterpret_cast<uint4*>(y + i0) = *reinterpret_cast<const uint4*>(h);
+          if (s) *reinterpret_cast<uint4*>(s + i0) = *reinterpret_cast<const uint4*>(h);
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+          if (i0 + t >= dim) break;
+          if constexpr (kF32) y[i0 + t] = e[t]; else y[i0 + t] = h[t];
+          if (s) s[i0 + t] = h[t];
+        }
+      }
+    }
+    if (s)
+      for (int i = dim + lane; i < sdim; i += 64) s[i] = (_Float16)0.0f;
+    if (!cached) continue;
+    ss = wave_sum(ss);
+    se = wave_sum(se);
+    if (!(ss < __builtin_inff())) ss = __builtin_inff();  // NaN / inf rows: the bound is useless, every query takes the exact path
+    if (!(se < __builtin_inff())) se = __builtin_inff();
+    best16 = fmaxf(best16, ss);
+    best_err = fmaxf(best_err, se);
+    folded = true;
+  }
+  if (folded && lane == 0) {
+    // non-negative floats (and +inf) order like their bit patterns
+    atomicMax(reinterpret_cast<unsigned int*>(stats), __float_as_uint(best16));
+    if constexpr (kF32) atomicMax(reinterpret_cast<unsigned int*>(stats + 1), __float_as_uint(best_err));
+  }
+}
+
 }  // namespace
+
+hipError_t launch_expand_stage(const void* corpus, void* staging, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t r0, int64_t r1,
+                               int64_t row_bytes, hipStream_t stream) {
+  if (!corpus || !staging || !bits || !counts || rows < 1 || rows >= 0x7FFFFFFFll || row_bytes < 2 || row_bytes % 2 != 0 || r0 < 0 || r0 >= r1 || r1 > rows ||
+      r0 % kCompactTileRows != 0 || (r1 % kCompactTileRows != 0 && r1 != rows))
+    return hipErrorInvalidValue;
+  const int vb = compact_vector_bytes((uint64_t)row_bytes | reinterpret_cast<uintptr_t>(staging) | reinterpret_cast<uintptr_t>(corpus));
+  const int64_t most = (r1 - r0) * (row_bytes / vb);  // V's to copy when the pass has no hole
+  const unsigned blocks = (unsigned)std::min<int64_t>((most + 4 * kMaskThreads - 1) / (4 * kMaskThreads), 2048);
+  const int64_t n_words = (rows + 31) >> 5;
+  const char* s = reinterpret_cast<const char*>(corpus);
+  char* d = reinterpret_cast<char*>(staging);
+#define TAVB_STAGE(V) hipLaunchKernelGGL(expand_stage_kernel<V>, dim3(blocks), dim3(kMaskThreads), 0, stream, s, d, bits, counts, rows, n_words, r0, r1, row_bytes)
+  switch (vb) {
+    case 16: TAVB_STAGE(uint4); break;
+    case 8: TAVB_STAGE(uint2); break;
+    case 4: TAVB_STAGE(uint32_t); break;
+    default: TAVB_STAGE(uint16_t); break;
+  }
+#undef TAVB_STAGE
+  return hipGetLastError();
+}
+
+hipError_t launch_expand_scatter(const void* src, void* dst, const uint32_t* bits, const unsigned* counts, int64_t rows, int64_t from, int64_t r0,
+                                 int64_t r1, int64_t row_bytes, hipStream_t stream) {
+  if (!src || !dst || !bits || !counts || rows < 1 || rows >= 0x7FFFFFFFll || row_bytes < 2 || row_bytes % 2 != 0 || from < 0 || from > r0 || r0 >= r1 ||
+      r1 > rows || from % kCompactTileRows != 0 || r0 % kCompactTileRows != 0 || (r1 % kCompactTileRows != 0 && r1 != rows))
+    return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((r1 - r0 + kCompactTileRows - 1) / kCompactTileRows);
+  const int64_t n_words = (rows + 31) >> 5;
+  const char* s = reinterpret_cast<const char*>(src);
+  char* d = reinterpret_cast<char*>(dst);
+#define TAVB_EXPAND(V) hipLaunchKernelGGL(expand_scatter_kernel<V>, dim3(blocks), dim3(kMaskThreads), 0, stream, s, d, bits, counts, rows, n_words, from, r0, r1, row_bytes)
+  switch (compact_vector_bytes((uint64_t)row_bytes | reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst))) {
+    case 16: TAVB_EXPAND(uint4); break;
+    case 8: TAVB_EXPAND(uint2); break;
+    case 4: TAVB_EXPAND(uint32_t); break;
+    default: TAVB_EXPAND(uint16_t); break;
+  }
+#undef TAVB_EXPAND
+  return hipGetLastError();
+}
+
+hipError_t launch_scatter_check(const int32_t* positions, int64_t n, int64_t rows, int* bad, hipStream_t stream) {
+  if (!positions || !bad || n < 1 || rows < 0) return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + kMaskThreads - 1) / kMaskThreads, 1024);
+  hipLaunchKernelGGL(scatter_check_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, positions, n, rows, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_scatter_rows(const float* src, int64_t n, int dim, const int32_t* positions, int64_t rows, void* corpus, bool f16, void* shadow, int sdim,
+                               int64_t norm_rows, float* stats, hipStream_t stream) {
+  if (!src || !positions || !corpus || n < 1 || dim < 1 || rows < 1 || (norm_rows > 0 && !stats) || (shadow && sdim < dim)) return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + kMaskWaves - 1) / kMaskWaves, 256 * 8);
+  _Float16* sh = reinterpret_cast<_Float16*>(shadow);
+  if (f16)
+    hipLaunchKernelGGL(scatter_rows_kernel<_Float16>, dim3(blocks), dim3(kMaskThreads), 0, stream, src, n, dim, positions, rows, reinterpret_cast<_Float16*>(corpus), sh,
+                       sdim, norm_rows, stats);
+  else
+    hipLaunchKernelGGL(scatter_rows_kernel<float>, dim3(blocks), dim3(kMaskThreads), 0, stream, src, n, dim, positions, rows, reinterpret_cast<float*>(corpus), sh, sdim,
+                       norm_rows, stats);
+  return hipGetLastError();
+}
 
 hipError_t launch_compact_count(const uint32_t* bits, int64_t rows, unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
   if (!bits || !counts || !info || rows < 1 || rows >= 0x7FFFFFFFll) return hipErrorInvalidValue;

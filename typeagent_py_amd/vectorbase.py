@@ -402,7 +402,8 @@ class VectorBase:
         self._subset_cache = None  # (caller's subset object, private copy, row count, ordinals int64, device int32 rows) of the last subset lookup
         self._row_messages: np.ndarray | None = None  # chunk row -> message ordinal (message re-rank on the device)
         self._row_messages_rows = -1  # rows of the map already on the device
-        self._removal_epoch = 0  # bumped by every remove_rows() that removed a row: a RowMask made before it names other rows now
+        self._removal_epoch = 0  # bumped by every remove_rows() / insert_rows() that changed a row's ordinal: a RowMask made before it names other rows now
+        self._epoch_change = "removed from"  # what the last bump did ("removed from" / "inserted into"): the refusal says it
         self.clear()
 
     # ------------------------------------------------------------------ storage
@@ -947,7 +948,7 @@ class VectorBase:
         if allowed.rows != self._count:
             raise ValueError(f"mask covers {allowed.rows} rows, the index has {self._count}")
         if allowed.epoch != self._removal_epoch:
-            raise ValueError("this RowMask was built before rows were removed from the index: build it again")
+            raise ValueError(f"this RowMask was built before rows were {self._epoch_change} the index: build it again")
         return allowed
 
     # ------------------------------------------------------------------ scope algebra (additive)
@@ -1393,6 +1394,7 @@ class VectorBase:
             self._row_messages_rows = -1
         self._subset_cache = None
         self._removal_epoch += 1
+        self._epoch_change = "removed from"
         return removed
 
     def remove_at(self, pos: int) -> None:
@@ -1400,6 +1402,208 @@ class VectorBase:
         if not 0 <= pos < self._count:
             raise IndexError(f"Index {pos} out of bounds for embedding index of size {len(self)}")
         self.remove_rows([pos])
+
+    # ------------------------------------------------------------------ insertion and overwrite (additive)
+    def _rows_argument(self, embeddings) -> np.ndarray:
+        """One row [dim] or rows [m, dim] -> float32 [m, dim] of this index' width (learned here on an empty index of unknown width)."""
+        rows = np.asarray(embeddings, dtype=np.float32)
+        if rows.ndim == 1:
+            rows = rows.reshape(1, -1)
+        if rows.ndim != 2:
+            raise ValueError(f"Expected 1D or 2D embeddings array, got {rows.ndim}D")
+        if self._embedding_size == 0 and rows.shape[1] > 0:
+            self._set_embedding_size(rows.shape[1])
+        if rows.shape[1] != self._embedding_size:
+            raise ValueError(f"Embedding size mismatch: expected {self._embedding_size}, got {rows.shape[1]}")
+        return rows
+
+    @staticmethod
+    def _insert_positions(at, n: int, m: int) -> np.ndarray:
+        """np.insert's rule: where the m new rows stand in the matrix of n + m rows (int64 [m], row j of the values at [j])."""
+        a = np.asarray(at)
+        if a.dtype.kind not in "iu" and a.size:
+            raise IndexError("arrays used as indices must be of integer (or boolean) type")
+        if a.ndim > 1:
+            raise ValueError("index array argument obj to insert must be one dimensional or scalar")
+        idx = a.reshape(-1).astype(np.int64)
+        bad = idx[(idx < -n) | (idx > n)]
+        if bad.size:
+            raise IndexError(f"index {int(bad[0])} is out of bounds for axis 0 with size {n}")
+        idx[idx < 0] += n
+        if idx.size == 1:  # one position: every row goes in front of it, in order
+            return idx[0] + np.arange(m, dtype=np.int64)
+        if idx.size != m:
+            raise ValueError(f"shape mismatch: {m} rows cannot be inserted at {idx.size} positions")
+        order = np.lexsort((idx,))  # (a stable sort: equal positions keep their order)
+        idx[order] += np.arange(m, dtype=np.int64)
+        return idx
+
+    def insert_rows(self, at, embeddings, row_messages=None) -> int:
+        """Insert rows -> how many went in.  Defined as the reference class with `_vectors = np.insert(_vectors, at, embeddings, axis=0)`:
+        `embeddings` is one row [dim] or [m, dim]; `at` one integer (all m rows go in front of old row `at`; `at == len(self)` appends) or
+        a sequence of m integers (row j goes in front of old row at[j]; equal positions keep their order; one row and many positions
+        inserts the row at each); negatives wrap, anything outside [-n, n] or a non-integer `at` raises IndexError, a width mismatch
+        ValueError.  Later ordinals shift up -- the insertion the reference keeps commented out (knowpro/fuzzyindex.py:50-83).  On a
+        single-GPU engine the device corpus is expanded on the device (tavb_expand_rows) and only the new rows travel
+        (tavb_scatter_rows): a mirror is not uploaded again, a device-only corpus is not copied to the host.  The host matrix, when there
+        is one, is opened up in its growth buffer, from the tail -- unless somebody else holds it (a matrix adopted by deserialize(), a
+        view handed out by serialize()): then the index moves to a buffer of its own, as np.insert would.  The row -> message map gets
+        `row_messages` (one int, or one per new row) at the same positions, -1 where none is given.  Every `RowMask` built before the
+        call raises ValueError from then on.  A device group (`devices=[...]`) inserts on the host and uploads from the first new row."""
+        n = self._count
+        new = self._rows_argument(embeddings)
+        a = np.asarray(at)
+        if new.shape[0] == 1 and a.ndim == 1 and a.size > 1:
+            new = np.repeat(new, a.size, axis=0)
+        m = new.shape[0]
+        pos = self._insert_positions(a, n, m)
+        msgs = None
+        if row_messages is not None:
+            msgs = np.asarray(row_messages, dtype=np.int64).reshape(-1)
+            if msgs.size == 1:
+                msgs = np.repeat(msgs, m)
+            if msgs.size != m:
+                raise ValueError(f"{msgs.size} row messages for {m} rows")
+        if m == 0:
+            return 0
+        flags = np.zeros(n + m, dtype=bool)  # the holes, in the new index space
+        flags[pos] = True
+        first = int(pos.min())
+        eng = self._engine
+        native = eng is not None and hasattr(eng, "expand_rows") and hasattr(eng, "scatter_rows")  # (a device group has neither: the host route)
+        if n == 0:
+            ordered = np.empty_like(new)
+            ordered[pos] = new  # into an empty index: an append, in np.insert's order
+            self.add_embeddings(None, ordered)
+        else:
+            if self._device_only is not None and not native:
+                self._materialize_host()
+            if native and self._device_only is None:
+                eng = self._sync_device()  # rows appended or edited since the last lookup reach the mirror first
+            if self._device_only is None:
+                self._open_host_rows(flags, pos, new)
+            if native:
+                eng.expand_rows(eng.mask_bits_to_device(_native.pack_mask_bits(flags)), n + m)
+                eng.scatter_rows(new, pos.astype(np.int32))
+                if self._device_only is not None:
+                    self._device_only = eng.corpus
+                self._dev_rows, self._dev_valid = n + m, True
+            else:
+                self._dev_rows = min(self._dev_rows, first)  # the upload does the rest
+            self._count = n + m
+        if self._row_messages is not None or msgs is not None:
+            old = np.full(n, -1, dtype=np.int64)
+            if self._row_messages is not None:
+                k = min(n, len(self._row_messages))
+                old[:k] = self._row_messages[:k]
+            merged = np.empty(n + m, dtype=np.int64)
+            merged[~flags] = old
+            merged[pos] = -1 if msgs is None else msgs
+            self._row_messages = merged
+            self._row_messages_src = None  # (the caller's object describes the rows as they were)
+            self._row_messages_rows = -1
+        self._subset_cache = None
+        self._removal_epoch += 1
+        self._epoch_change = "inserted into"
+        return m
+
+    _host_block_bytes = 64 << 20  # the host matrix is opened up in blocks of about this size
+
+    def _open_host_rows(self, flags: np.ndarray, pos: np.ndarray, new: np.ndarray) -> None:
+        """The host side of `insert_rows`: the old rows move to the rows of `flags` that are clear, `new` goes to `pos`."""
+        n, total = self._count, len(flags)
+        if self._handed_out or self._view_out:
+            # the caller's own matrix, or one somebody holds a view of: np.insert leaves theirs as it is
+            fresh = np.empty((max(total, 4), self._embedding_size), dtype=np.float32)
+            fresh[:total][~flags] = self._host[:n]
+            self._host = fresh
+            self._handed_out = self._view_out = False
+            self._dev_fingerprint = None
+        else:
+            # in the growth buffer, a block at a time FROM THE TAIL: a block's old rows lie at or below it, and are copied out before the
+            # block is written; the blocks still to come read only rows below them
+            self._reserve(total - n)
+            host = self._host
+            first = int(pos.min())
+            before = np.concatenate(([0], np.cumsum(flags, dtype=np.int64)))  # holes below a row
+            block = max(1, self._host_block_bytes // max(host.shape[1] * 4, 1))
+            row_bytes = host.strides[0]
+            for b0 in reversed(range(first, total, block)):
+                b1 = min(b0 + block, total)
+                o0, o1 = b0 - int(before[b0]), b1 - int(before[b1])
+                if o1 - o0 == b1 - b0 and host.flags.c_contiguous:  # no hole in the block: it moves up in one pass (the ranges may overlap)
+                    if o0 != b0:
+                        ctypes.memmove(host.ctypes.data + b0 * row_bytes, host.ctypes.data + o0 * row_bytes, (b1 - b0) * row_bytes)
+                    continue
+                part = host[o0:o1].copy()
+                host[b0:b1][~flags[b0:b1]] = part
+        self._host[pos] = new
+
+    def insert_at(self, index: int, embeddings) -> None:
+        """The method the reference keeps commented out (knowpro/fuzzyindex.py:50-83): insert one embedding, or a list of embeddings, in
+        front of the row at `index`."""
+        if not 0 <= index <= self._count:
+            raise IndexError(f"Index {index} out of bounds for insertion in embedding index of size {len(self)}")
+        rows = np.vstack([np.asarray(e, dtype=np.float32).reshape(1, -1) for e in embeddings]) if isinstance(embeddings, list) else embeddings
+        self.insert_rows(int(index), rows)
+
+    def set_rows(self, which, embeddings) -> int:
+        """Overwrite rows -> how many rows were written.  Defined as `_vectors[which] = embeddings`: `which` is integer ordinals (negatives
+        wrap, out of range raises IndexError, duplicates allowed: the last one wins), a bool array of length len(self), or a `RowMask`
+        of this index (its rows in ascending order take `embeddings` in order); `embeddings` is [len(which), dim], or one row [dim]
+        written to every named row.  The length does not change, `RowMask`s stay valid, the subset cache is kept.  On a single-GPU
+        engine only the new rows travel (tavb_scatter_rows): a device-only corpus is not copied to the host, a mirror is not uploaded
+        again, and the fp16 shadow and the row-norm maxima are brought up to date instead of being rebuilt; a host matrix is written
+        as well.  A device group writes the host matrix and uploads from the first written row."""
+        n = self._count
+        if isinstance(which, RowMask):
+            rows = self._resolve_mask(which).flat().astype(np.int64)
+        else:
+            a = np.asarray(which)
+            if a.dtype == np.bool_:
+                if a.ndim != 1 or a.shape[0] != n:
+                    raise IndexError(f"boolean index did not match indexed array along axis 0; size of axis is {n} but size of corresponding boolean axis is {a.shape[0] if a.ndim else 1}")
+                rows = np.flatnonzero(a).astype(np.int64)
+            elif a.size == 0:
+                rows = np.zeros(0, dtype=np.int64)
+            elif a.dtype.kind not in "iu":
+                raise IndexError("arrays used as indices must be of integer (or boolean) type")
+            else:
+                rows = a.reshape(-1).astype(np.int64)
+                bad = rows[(rows < -n) | (rows >= n)]
+                if bad.size:
+                    raise IndexError(f"index {int(bad[0])} is out of bounds for axis 0 with size {n}")
+                rows[rows < 0] += n
+        if len(rows) == 0:
+            return 0
+        new = self._rows_argument(embeddings)
+        if new.shape[0] == 1 and len(rows) != 1:
+            new = np.repeat(new, len(rows), axis=0)
+        if new.shape[0] != len(rows):
+            raise ValueError(f"shape mismatch: {new.shape[0]} rows cannot be written to {len(rows)} positions")
+        # duplicates are resolved here, the last one wins: the device never sees two writers of one row
+        uniq, last = np.unique(rows[::-1], return_index=True)
+        if len(uniq) != len(rows):
+            new = new[len(rows) - 1 - last]
+            rows = uniq
+        eng = self._engine
+        native = eng is not None and hasattr(eng, "scatter_rows")
+        if self._device_only is not None and not native:
+            self._materialize_host()
+        if self._device_only is not None:
+            eng.scatter_rows(new, rows.astype(np.int32))
+            self._device_only = eng.corpus
+            return len(rows)
+        if native:
+            eng = self._sync_device()  # the mirror as the matrix was: what was appended or edited before this call
+        self._host[rows] = new
+        if native:
+            eng.scatter_rows(new, rows.astype(np.int32))
+            if self._handed_out or self._view_out:
+                self._dev_fingerprint = self._fingerprint()
+        else:
+            self._dev_rows = min(self._dev_rows, int(rows.min()))  # the upload does the rest
+        return len(rows)
 
     # ------------------------------------------------------------------ bookkeeping
     def _set_embedding_size(self, size: int) -> None:
