@@ -196,7 +196,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "mask_tile_pct" (default 100 = byte parity) the tile is taken when the gather route's bytes (allowed rows once per 8 queries) are at least this
  *                   many per cent of the tile's (the mask's span once per 64 queries)
  *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the
- *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide)
+ *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide), 4 = a scoped batch (one mask per
+ *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped)
  *   "mask_wide"     masked batches on fp16 corpora (the binding reads it; the rule is tavb_plan_masked_wide, with "mask_tile_min_bytes" / "mask_tile_pct"):
  *                   1 (default) = a batch takes the 128/256-query filter tile with the bit test in its admission path + exact rescoring
  *                   (tavb_search_masked_wide) where tavb_plan_masked_wide says so -- it then wins over "mask_tile"; 0 = never; 2 = wherever that route
@@ -532,6 +533,45 @@ int tavb_mask_from_ranges(tavb_ctx* ctx, const int64_t* ranges_host, const int32
                           int64_t rows, uint32_t* dev_bits_out, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
 int tavb_mask_combine(tavb_ctx* ctx, int32_t op, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, uint32_t* dev_bits_out,
                       int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
+
+/* ---- scoped batches: one row mask PER QUERY in a single submission ----------------------------------------------------------------------
+ * A compiled question is a handful of lookups, each under its own scope (a time range, a thread, a set of messages): query q searches the
+ * rows dev_masks[q] names.  dev_masks: a HOST array of nq device pointers (tavb_mask_combine's convention) to packed masks in the bit form
+ * above over `rows` == the corpus' rows, 4-byte aligned, none NULL; pointers may repeat; bits at or beyond `rows` are ignored.  Per query the
+ * result is tavb_search_subset_batch_resident over that mask's row list (remap = 1), bit for bit: ordinals, float32 scores and counts.
+ * 1 <= k <= TAVB_MAX_FUSED_K.  The queries go in passes of TAVB_MAX_STREAM_QUERIES (4 for 64 < k), as everywhere -- fewer where eight queries of
+ * the corpus' width do not fit the vector tier's LDS (from about 4.7k floats per row on: 4, 2 or 1), so that a pass runs on the tier ONE query
+ * of this corpus runs on and the bit-for-bit equality holds at every width; option "force_tier" = 3 sends both to the scalar tier (1 and 2 leave a scoped pass on this rule).  Per pass, on the device:
+ * the OR of the pass' masks (tavb_mask_combine's kernel) and its ascending row list (tavb_mask_expand's write pass); one membership byte per
+ * list position (bit j = the pass' query j holds the row; tavb_mask_membership's kernel); ONE streaming scan over the union list -- every
+ * row of the union is read once per pass, however many scopes hold it -- in which a row is offered to a query only when its bit is set; the
+ * merge; the remap of list positions to rows.  Equal scores keep ascending-ordinal order because the union list is ascending and the keys
+ * carry list positions, as for tavb_mask_expand.  No mask word visits the host.  The passes go in WAVES of at most 16 (128 queries; fewer on
+ * corpora beyond 4M rows: at most 64M union positions per wave, at least one pass): a wave's unions are enqueued first and ONE synchronise
+ * reads their counts; everything else is enqueued behind it.  A batch of up to a wave therefore waits once for its counts, a longer one once per
+ * wave.  Workspace, kept by the context: rows / 8 bytes per pass of a wave and 5 bytes per union position of a wave -- at most 2 x rows + 5 x
+ * max(64M, rows) bytes however many queries.  "masked_route" reports 4.  Timed under TAVB_KERNEL_CONVERT (unions,
+ * lists, membership), TAVB_KERNEL_SCAN and TAVB_KERNEL_MERGE (merge, remap, re-rank).
+ *   tavb_search_scoped_batch: queries on the host, one more synchronise at the end; outputs [nq, k] / [nq] as tavb_search_batch (ordinals
+ *     carry ordinal_base).
+ *   tavb_search_scoped_device: dev_queries device float32 [nq, dim]; out_keys [nq, k] sorted, zero-padded keys carrying ordinal_base + row, in
+ *     device memory or device-writable pinned memory; waits only for the unions' counts.  min_scores: nq thresholds on the HOST.
+ *   tavb_search_messages_scoped: the batch, its keys left on the device, then tavb_search_messages_masked's re-rank launch for all queries
+ *     and one copy back: per query tavb_search_messages_masked on route 1 over that mask.  Needs the row -> message map.
+ * NULL arguments, rows != the corpus' rows, k outside 1 .. TAVB_MAX_FUSED_K and a NULL mask pointer are TAVB_E_INVALID with a message.  nq
+ * == 0 or an empty corpus: zero counts / zero keys, nothing launched.  A query whose mask is empty gets an empty list.
+ *
+ * tavb_mask_membership: the membership bytes alone -- dev_member_out[p] (device uint8 [n]) = bit j set when dev_masks[j] (HOST array of 1 ..
+ * TAVB_MAX_MASK_OPERANDS device pointers, masks over `rows` rows) holds row dev_rows[p] (device int32 [n], n <= rows; a value outside
+ * [0, rows) gives 0).  One launch, asynchronous on the context's stream.  Timed under TAVB_KERNEL_CONVERT. */
+int tavb_search_scoped_batch(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                             const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_scoped_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                              const float* min_scores /*host*/, tavb_key* out_keys);
+int tavb_search_messages_scoped(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_counts);
+int tavb_mask_membership(tavb_ctx* ctx, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, const int32_t* dev_rows, int64_t n,
+                         uint8_t* dev_member_out);
 
 /* ---- removing rows: compaction of the corpus on the device ---------------------------------------------------------------------------
  * The removal the reference leaves as a TODO (storage/sqlite/reltermsindex.py:181-192 `remove_term`; knowpro/fuzzyindex.py:113-127, the

@@ -101,6 +101,10 @@ _SIGNATURES = [
     ("tavb_search_messages_batch", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_mask_from_ranges", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_mask_combine", c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_search_scoped_batch", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_scoped_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_messages_scoped", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_mask_membership", c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -1070,6 +1074,72 @@ class Engine:
                                                       int(max_messages), int(route), _addr(msgs), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
         return msgs, scs, cnts
+
+    # scoped batches: one mask per query ---------------------------------------------------
+    def _mask_pointers(self, dev_bits_list, n: int):
+        """n packed masks (torch int32 [(rows + 31) // 32] on this device, repeats allowed) -> the host array of their device pointers the
+        scoped calls take (tavb_mask_combine's convention)."""
+        torch = self._torch
+        masks = list(dev_bits_list)
+        if len(masks) != n:
+            raise ValueError(f"{len(masks)} masks for {n} queries")
+        for i, m in enumerate(masks):
+            if not isinstance(m, torch.Tensor) or m.dtype != torch.int32:
+                raise TypeError(f"mask {i} must be a torch int32 tensor of packed words")
+            if m.dim() != 1 or not m.is_contiguous() or m.numel() * 32 < self.rows:
+                raise ValueError(f"mask {i} must be a contiguous 1-D tensor of at least {(self.rows + 31) // 32} words (the corpus has {self.rows} rows)")
+            if not m.is_cuda or (m.device.index or 0) != self.device:
+                raise ValueError(f"mask {i} must live on cuda:{self.device}")
+        return (c_void_p * max(n, 1))(*[m.data_ptr() for m in masks])
+
+    def search_scoped_batch(self, queries, dev_bits_list, k: int, thrs):
+        """A batch whose queries carry their own scopes, in one submission (tavb_search_scoped_batch): queries f32 [nq, dim];
+        dev_bits_list: nq packed masks on this device, one per query; 1 <= k <= 256; thrs float32 [nq] (or one for all) -> (ordinals
+        [nq, k], scores [nq, k], counts [nq]), per query `search_subset_batch_resident` over that mask's row list, bit for bit."""
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_batch(self._h, _addr(a), nq, ptrs, int(self.rows), k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_scoped_device(self, dev_queries, dev_bits_list, k: int, thrs, out_keys=None):
+        """`search_scoped_batch` with the queries on the device (tavb_search_scoped_device): dev_queries torch f32 [nq, dim] -> torch int64
+        [nq, k] sorted, zero-padded keys carrying ordinal_base + row.  `out_keys`: a device tensor or a PINNED host tensor.  The call
+        waits for the unions' counts only: `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), k, _addr(t), c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def search_messages_scoped(self, queries, dev_bits_list, k: int, thrs, max_messages: int):
+        """`search_scoped_batch` aggregated to messages in one submission (tavb_search_messages_scoped) -> (message ordinals [nq, k], scores
+        [nq, k], counts [nq]); per query `search_messages_masked` on route 1 over that mask."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_messages_scoped(self._h, _addr(a), nq, ptrs, int(self.rows), k, _addr(t), int(max_messages), _addr(msgs), _addr(scs),
+                                                      _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def mask_membership(self, dev_bits_list, dev_rows):
+        """Which of 1 .. 8 packed masks hold each row of a resident row list (tavb_mask_membership): torch uint8 [S] on the device, bit j of
+        byte p = mask j holds row dev_rows[p] -- what a scoped pass reads per row of its union.  Async on the engine's stream."""
+        torch = self._torch
+        masks = list(dev_bits_list)
+        if not 1 <= len(masks) <= MAX_MASK_OPERANDS:
+            raise ValueError(f"a membership test has 1 .. {MAX_MASK_OPERANDS} masks (got {len(masks)})")
+        ptrs = self._mask_pointers(masks, len(masks))
+        rows_ptr, n = self._row_list(dev_rows)
+        out = torch.empty(n, dtype=torch.uint8, device=dev_rows.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        with self._lock:
+            rc = self.lib.tavb_mask_membership(self._h, ptrs, len(masks), int(self.rows), rows_ptr, n, c_void_p(out.data_ptr()) if n else None)
+        _check(self.lib, rc)
+        return out
 
     def search_messages_batch(self, queries, k: int, thrs, max_messages: int, accept=None):
         """`search_messages` for a batch in one submission (tavb_search_messages_batch): queries f32 [nq, dim]; thrs float32 [nq] (or one

@@ -267,6 +267,48 @@ def scope_collections(scope) -> list[list[tuple[int, int]]]:
     return out
 
 
+def _scope_mask(vector_base: VectorBase, scope) -> RowMask:
+    """One scope of `lookup_messages_in_scope` / `lookup_messages_in_scopes` -> its `RowMask`."""
+    if isinstance(scope, RowMask):
+        return scope
+    if is_text_scope(scope):  # the reference's own scope objects: ranges of message ordinals, intersected on the device
+        return vector_base.range_mask(scope_collections(scope), of="messages")
+    return vector_base.message_mask(scope)
+
+
+def lookup_messages_in_scopes(
+    vector_base: VectorBase,
+    embeddings,
+    row_to_message,
+    scopes,
+    max_matches: int | None = None,
+    threshold_score=None,
+):
+    """`lookup_messages_in_scope` for the lookups of one compiled question, each under its own `when` filter: `embeddings` is a 2-D array and
+    `scopes` a sequence with one scope per embedding, each of the kinds `lookup_messages_in_scope` takes (a collection of message ordinals,
+    a `RowMask`, a `TextRangesInScope`, a `TextRangeCollection` or a list of either).  Returns one list of ScoredInt(message, score) per
+    embedding: per query what `lookup_messages_in_scope(vector_base, e, row_to_message, scope, ...)` returns.  A scope object that appears
+    several times becomes one mask.  The lookup is `VectorBase.lookup_messages_by_embeddings_scoped`: on a single-GPU engine ONE device
+    submission, whatever the scopes.  `threshold_score` may be a sequence with one threshold per query."""
+    if callable(row_to_message):
+        raise TypeError("lookup_messages_in_scopes needs row_to_message as a sequence (the map is searched on the device)")
+    queries = np.asarray(embeddings, dtype=np.float32)
+    if queries.ndim != 2:
+        raise ValueError(f"Expected a 2D array of embeddings, got {queries.ndim}D")
+    scopes = list(scopes)
+    if len(scopes) != len(queries):
+        raise ValueError(f"Number of scopes {len(scopes)} does not match number of embeddings {len(queries)}")
+    _ensure_row_messages(vector_base, row_to_message)
+    made: dict[int, RowMask] = {}
+    masks = []
+    for s in scopes:
+        if id(s) not in made:
+            made[id(s)] = _scope_mask(vector_base, s)
+        masks.append(made[id(s)])
+    lists = vector_base.lookup_messages_by_embeddings_scoped(queries, masks, max_matches, threshold_score)
+    return lists if max_matches is None else [out[:max_matches] for out in lists]
+
+
 def lookup_messages_in_scope(
     vector_base: VectorBase,
     embedding_or_embeddings,
@@ -286,12 +328,7 @@ def lookup_messages_in_scope(
     if callable(row_to_message):
         raise TypeError("lookup_messages_in_scope needs row_to_message as a sequence (the map is searched on the device)")
     _ensure_row_messages(vector_base, row_to_message)
-    if isinstance(scope, RowMask):
-        mask = scope
-    elif is_text_scope(scope):  # the reference's own scope objects: ranges of message ordinals, intersected on the device
-        mask = vector_base.range_mask(scope_collections(scope), of="messages")
-    else:
-        mask = vector_base.message_mask(scope)
+    mask = _scope_mask(vector_base, scope)
     queries = np.asarray(embedding_or_embeddings, dtype=np.float32)
     if queries.ndim == 1:
         out = vector_base.lookup_messages_by_embedding_masked(queries, mask, max_matches, threshold_score)

@@ -36,6 +36,9 @@ struct ScanParams {
   int32_t topk_buckets;
   float topk_lo[TAVB_MAX_STREAM_QUERIES];
   float topk_scale[TAVB_MAX_STREAM_QUERIES];
+  // scoped batch (launch_scan_scoped, plain form only): [n_pos] bytes, bit q of byte p = query q of the pass may take position p
+  // (launch_scope_member); read by no other launch
+  const uint8_t* scope_member;
 };
 
 struct ScanGeometry {
@@ -57,6 +60,13 @@ bool launch_scan_inline_query(const ScanParams& p, const ScanGeometry& g, hipStr
 // the score pass of a large-k lookup (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES) queries, index_base 0, the streaming kernels'
 // arithmetic row for row -- the scores are those the fused selection sees, bit for bit -- with ScanParams::topk_* as the output
 hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// one pass of a scoped batch (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES; 4 for k > 64) queries over p.row_ids, the ascending row
+// list of the union of their scopes, index_base 0; query q is offered position pos only when bit q of p.scope_member[pos] is set.
+// Otherwise launch_scan's plain form: the same lists at p.lists, the same per-row arithmetic on the vector or the scalar tier.
+hipError_t launch_scan_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// queries per scoped pass: TAVB_MAX_STREAM_QUERIES (4 for k > 64), halved until they fit the vector tier's LDS wherever ONE query of this
+// corpus runs on the vector tier -- a pass then has the single-query lookup's per-row arithmetic at every width
+int scoped_queries_per_pass(const void* corpus, int dim, int dtype, int k, const ScanGeometry& g);
 // queries per score pass that keep the vector tier's LDS (queries + histograms) within budget: 1, 2, 4 or 8
 int topk_queries_per_pass(int dim, int dtype, int buckets);
 
@@ -173,6 +183,9 @@ hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* 
 // mask_expand's second launch alone, over counts one of the two kernels above (or its own count pass) wrote
 hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
                              hipStream_t stream);
+// Scoped batches (tavb_mask.hip): member[p] = the scopes of rows[p], p < n -- bit j set when mask ops.m[j] (j < ops.n; ops.op unused) holds
+// row rows[p]; bits from ops.n on are zero.  rows: n valid rows of masks over `n_rows` rows.  One launch.
+hipError_t launch_scope_member(const MaskOperands& ops, const int32_t* rows, int64_t n, int64_t n_rows, uint8_t* member, hipStream_t stream);
 // Row compaction (tavb_mask.hip; `bits` names the rows to REMOVE).  compact_count: counts[chunk] = the chunk's KEPT rows, info[chunk] = that
 // count and the chunk's first and last removed row (device-writable memory).  compact_gather: the kept rows of src rows [r0, r1) -> dst rows
 // from (kept rows in [from, r0)) on, densely and in order; from <= r0, both multiples of 64, r1 a multiple of 64 or `rows`; src and dst

@@ -702,6 +702,113 @@ int tavb_search_messages_masked(tavb_ctx* c, const float* queries_host, int32_t 
   return rerank_batch_and_return(c, d_hits, nq, k, base, nullptr, max_messages, out_messages, out_scores, out_counts);
 }
 
+// ---- scoped batches: one mask per query (tavb_route.hip::search_scoped_impl)
+// what the three entry points check after their own head; *empty: nothing to scan (an empty corpus, no query)
+static int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, bool* empty) {
+  if (int rc = check_masked_head(c, nq, rows, k)) return rc;
+  if (k > TAVB_MAX_FUSED_K) return fail(TAVB_E_INVALID, "a scoped batch serves 1 <= k <= %d (got %d)", TAVB_MAX_FUSED_K, k);
+  if (rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  *empty = rows == 0 || nq == 0;
+  if (*empty) return TAVB_OK;
+  if (!dev_masks) return fail(TAVB_E_INVALID, "null dev_masks");
+  for (int q = 0; q < nq; ++q) {
+    if (!dev_masks[q]) return fail(TAVB_E_INVALID, "the mask of query %d is null", q);
+    if ((reinterpret_cast<uintptr_t>(dev_masks[q]) & 3) != 0) return fail(TAVB_E_INVALID, "the mask of query %d must be 4-byte aligned", q);
+  }
+  return TAVB_OK;
+}
+
+static void note_scoped_route(tavb_ctx* c) {
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->last_graph = 0;
+  c->masked_route = 4;  // a scoped batch
+}
+
+int tavb_search_scoped_batch(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                             const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_route(c);
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  u64_t* target;
+  if (int rc = reserve_key_target(c, (size_t)nq * k, &target)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_scoped_impl(c, d_q, nq, k, min_scores, dev_masks, 0u, target, target)) return rc;
+  return collect_keys(c, target, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+}
+
+int tavb_search_scoped_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                              const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  note_scoped_route(c);
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
+  // (the merges write positions into d_out and the remaps turn them into ordinal_base + row on the way to out_keys: a pinned out_keys is
+  //  written once and never read over PCIe)
+  if (int rc = c->d_out.reserve((size_t)nq * k * sizeof(u64_t))) return rc;
+  return search_scoped_impl(c, dev_queries, nq, k, min_scores, dev_masks, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(c->d_out.ptr), out);
+}
+
+int tavb_search_messages_scoped(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  if (int rc = check_message_args(c, k, max_messages)) return rc;
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_route(c);
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  u64_t* d_hits;
+  if (int rc = reserve_message_batch(c, nq, k, &d_hits)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  const uint32_t base = (uint32_t)c->ordinal_base;
+  if (int rc = search_scoped_impl(c, d_q, nq, k, min_scores, dev_masks, base, d_hits, d_hits)) return rc;
+  return rerank_batch_and_return(c, d_hits, nq, k, base, nullptr, max_messages, out_messages, out_scores, out_counts);
+}
+
+int tavb_mask_membership(tavb_ctx* c, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, const int32_t* dev_rows, int64_t n, uint8_t* dev_member_out) {
+  if (int rc = check_ctx(c)) return rc;
+  if (n_masks < 1 || n_masks > TAVB_MAX_MASK_OPERANDS) return fail(TAVB_E_INVALID, "a membership test has 1 .. %d masks (got %d)", TAVB_MAX_MASK_OPERANDS, n_masks);
+  if (rows < 0 || rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (n < 0 || n > rows) return fail(TAVB_E_INVALID, "bad row list length");
+  if (n == 0) return TAVB_OK;
+  if (!dev_masks || !dev_rows || !dev_member_out) return fail(TAVB_E_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(dev_rows) & 3) != 0) return fail(TAVB_E_INVALID, "dev_rows must be 4-byte aligned");
+  tavb::MaskOperands ops{};
+  ops.n = n_masks;
+  ops.op = TAVB_MASK_OR;
+  for (int j = 0; j < n_masks; ++j) {
+    if (!dev_masks[j]) return fail(TAVB_E_INVALID, "mask %d is null", j);
+    if ((reinterpret_cast<uintptr_t>(dev_masks[j]) & 3) != 0) return fail(TAVB_E_INVALID, "mask %d must be 4-byte aligned", j);
+    ops.m[j] = dev_masks[j];
+  }
+  DeviceGuard guard(c->device);
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  hipError_t e = tavb::launch_scope_member(ops, dev_rows, n, rows, dev_member_out, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "membership launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
 int tavb_search_messages_batch(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const int32_t* accept_msgs_host,
                                int64_t n_accept, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
   if (int rc = check_message_args(c, k, max_messages)) return rc;

@@ -275,6 +275,26 @@ __global__ void __launch_bounds__(kMaskThreads) mask_combine_kernel(MaskOperands
   mask_chunk_reduce(n, first, last, counts, info);
 }
 
+// ---- scoped batches (tavb_search_scoped_batch): which of a pass' scopes hold each row of their union.  A thread takes one position of the
+// union's row list (coalesced) and reads that row's word of every operand -- the masks are rows / 8 bytes each and stay in L2 -- and writes
+// one byte: bit j = operand j holds the row.  The scan then needs one byte per row, not a word of every mask.  A row outside [0, n_rows)
+// (there is none in a list the write pass made) gets 0: no query takes it.
+__global__ void __launch_bounds__(kMaskThreads) scope_member_kernel(MaskOperands ops, const int32_t* __restrict__ rows, int64_t n, int64_t n_rows,
+                                                                    uint8_t* __restrict__ member) {
+  static_assert(TAVB_MAX_MASK_OPERANDS <= 8, "one bit of the byte per operand");
+  const int64_t stride = (int64_t)gridDim.x * kMaskThreads;
+  for (int64_t p = (int64_t)blockIdx.x * kMaskThreads + threadIdx.x; p < n; p += stride) {
+    const int64_t r = rows[p];
+    unsigned m = 0u;
+    if (r >= 0 && r < n_rows) {
+#pragma unroll
+      for (int j = 0; j < TAVB_MAX_MASK_OPERANDS; ++j)
+        if (j < ops.n) m |= ((ops.m[j][r >> 5] >> (r & 31)) & 1u) << j;
+    }
+    member[p] = (uint8_t)m;
+  }
+}
+
 // ---- row compaction (tavb_compact_rows): the mask names the rows to REMOVE, the kept rows move down in their old order.
 //   compact_count_kernel    chunk b -> counts[b] = its KEPT rows, info[b] = that count and the chunk's first and last removed row
 //   compact_gather_kernel   a workgroup takes a tile of 64 rows (two mask words) of the row range [r0, r1): the tile's first slot is the
@@ -668,6 +688,15 @@ hipError_t launch_compact_scatter(const void* staging, void* corpus, const uint3
 }
 
 int mask_blocks(int64_t rows) { return (int)((rows + TAVB_MASK_ROWS_PER_WORKGROUP - 1) / TAVB_MASK_ROWS_PER_WORKGROUP); }
+
+hipError_t launch_scope_member(const MaskOperands& ops, const int32_t* rows, int64_t n, int64_t n_rows, uint8_t* member, hipStream_t stream) {
+  if (!rows || !member || n < 1 || n_rows < 1 || n_rows >= 0x7FFFFFFFll || ops.n < 1 || ops.n > TAVB_MAX_MASK_OPERANDS) return hipErrorInvalidValue;
+  for (int j = 0; j < ops.n; ++j)
+    if (!ops.m[j]) return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)std::min<int64_t>((n + kMaskThreads - 1) / kMaskThreads, 2048);
+  hipLaunchKernelGGL(scope_member_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, ops, rows, n, n_rows, member);
+  return hipGetLastError();
+}
 
 hipError_t launch_mask_expand(const uint32_t* bits, int64_t rows, unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
                               hipStream_t stream) {

@@ -121,6 +121,115 @@ int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float
   return TAVB_OK;
 }
 
+// A scoped batch (tavb_search_scoped_batch and its twins), in WAVES of passes.  A wave's unions are enqueued first (mask_combine_kernel, OR:
+// one launch each, which also leaves the per-chunk counts the write pass starts from and the chunks' infos in pinned memory), ONE
+// synchronise brings their counts, and only then is anything sized: the row lists and the membership bytes of the wave's passes share two
+// workspaces of exactly the unions' total length.  Per pass then: the write pass, the membership bytes, the scoped scan, the merge, the
+// remap -- five launches, nothing waited for.  No mask word visits the host.
+// A wave is at most kScopedWavePasses passes (128 queries) and at most kScopedWavePositions union positions in the worst case (every union
+// the whole corpus), which bounds the workspaces whatever the batch: rows / 8 bytes of union mask per pass of the wave, 5 bytes per union
+// position -- at most 2 x rows + 5 x max(64M, rows) bytes, about 0.34 GB for any corpus of up to 64M rows, and only when every scope is
+// dense; the workspaces grow to what the largest wave so far needed and are released with the context.
+// Batches of up to a wave synchronise once for their counts; longer ones once per wave.
+constexpr int kScopedWavePasses = 16;
+constexpr int64_t kScopedWavePositions = (int64_t)64 << 20;
+
+// one wave: nq queries (at most kScopedWavePasses passes of per_pass), every pointer at the wave's first query
+static int scoped_wave(tavb_ctx* c, const float* d_q, int nq, int k, int per_pass, const float* min_scores, const uint32_t* const* masks, uint32_t index_base,
+                       u64_t* work, u64_t* out) {
+  static_assert(TAVB_MAX_STREAM_QUERIES <= TAVB_MAX_MASK_OPERANDS, "a pass' masks are the operands of one mask_combine launch and the bits of one membership byte");
+  const int passes = (nq + per_pass - 1) / per_pass;
+  const int64_t rows = c->rows, n_words = (rows + 31) >> 5;
+  const int chunks = tavb::mask_blocks(rows);
+  if (int rc = c->d_scope_bits.reserve((size_t)passes * n_words * sizeof(uint32_t))) return rc;
+  if (int rc = c->d_mask_counts.reserve((size_t)passes * chunks * sizeof(unsigned))) return rc;
+  constexpr size_t info_at = kScopedWavePasses * sizeof(long long);  // (fixed: the totals of an earlier, longer wave never lie under this wave's infos)
+  if (int rc = c->h_scope.reserve(info_at + (size_t)passes * chunks * sizeof(tavb::MaskChunkInfo))) return rc;
+  uint32_t* const bits = reinterpret_cast<uint32_t*>(c->d_scope_bits.ptr);
+  unsigned* const counts = reinterpret_cast<unsigned*>(c->d_mask_counts.ptr);
+  long long* const totals = reinterpret_cast<long long*>(c->h_scope.ptr);  // (the write passes leave their totals here; nothing reads them: a pass of
+                                                                            //  an earlier wave may still be writing its own)
+  tavb::MaskChunkInfo* const info = reinterpret_cast<tavb::MaskChunkInfo*>(reinterpret_cast<char*>(c->h_scope.ptr) + info_at);
+  for (int i = 0; i < passes * chunks; ++i) info[i].first = -1;  // (a chunk the kernel wrote holds a row or INT32_MAX here)
+  std::vector<tavb::MaskOperands> ops((size_t)passes);
+  {
+    Timed t(c, TAVB_KERNEL_CONVERT);
+    for (int p = 0; p < passes; ++p) {
+      const int q0 = p * per_pass, n = std::min(per_pass, nq - q0);
+      ops[p] = tavb::MaskOperands{};
+      ops[p].n = n;
+      ops[p].op = TAVB_MASK_OR;
+      for (int j = 0; j < n; ++j) ops[p].m[j] = masks[q0 + j];
+      hipError_t e = tavb::launch_mask_combine(ops[p], rows, bits + (size_t)p * n_words, counts + (size_t)p * chunks, info + (size_t)p * chunks, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "scope union launch failed: %s", hipGetErrorString(e));
+    }
+  }
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  std::vector<int64_t> n_union((size_t)passes, 0), first_pos((size_t)passes, 0);
+  int64_t total = 0, most = 0;
+  for (int p = 0; p < passes; ++p) {
+    for (int b = 0; b < chunks; ++b) {
+      const tavb::MaskChunkInfo ci = info[(size_t)p * chunks + b];
+      if (ci.first < 0) return fail(TAVB_E_HIP, "chunk %d of the union of pass %d wrote no info (internal error)", b, p);
+      n_union[p] += ci.count;
+    }
+    if (n_union[p] > rows) return fail(TAVB_E_HIP, "the union of pass %d counted %lld of %lld rows (internal error)", p, (long long)n_union[p], (long long)rows);
+    first_pos[p] = total;
+    total += n_union[p];
+    most = std::max(most, n_union[p]);
+  }
+  if (total == 0) return fill_empty_keys(c, out, (int64_t)nq * k);
+  if (int rc = c->d_scope_rows.reserve((size_t)total * sizeof(int32_t))) return rc;
+  if (int rc = c->d_scope_member.reserve((size_t)total)) return rc;
+  tavb::ScanGeometry g = clamped_geometry(c);
+  if (int rc = c->d_lists.reserve((size_t)per_pass * scan_blocks_for(c, most, g.waves, g.unroll) * k * sizeof(u64_t))) return rc;
+  for (int p = 0; p < passes; ++p) {
+    const int q0 = p * per_pass, n = std::min(per_pass, nq - q0);
+    const int64_t n_pos = n_union[p];
+    if (n_pos == 0) {  // every scope of the pass is empty
+      if (int rc = fill_empty_keys(c, out + (size_t)q0 * k, (int64_t)n * k)) return rc;
+      continue;
+    }
+    int32_t* const list = reinterpret_cast<int32_t*>(c->d_scope_rows.ptr) + first_pos[p];
+    uint8_t* const member = reinterpret_cast<uint8_t*>(c->d_scope_member.ptr) + first_pos[p];
+    {
+      Timed t(c, TAVB_KERNEL_CONVERT);
+      hipError_t e = tavb::launch_mask_write(bits + (size_t)p * n_words, rows, counts + (size_t)p * chunks, list, n_pos, totals + p, c->stream);
+      if (e == hipSuccess) e = tavb::launch_scope_member(ops[p], list, n_pos, rows, member, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "scope list launch failed: %s", hipGetErrorString(e));
+    }
+    g.blocks = scan_blocks_for(c, n_pos, g.waves, g.unroll);
+    tavb::ScanParams sp = scan_params(c, d_q + (size_t)q0 * c->dim, list, n_pos, n, k, 0u, ~0ull, reinterpret_cast<u64_t*>(c->d_lists.ptr), min_scores + q0,
+                                      TAVB_MAX_STREAM_QUERIES);
+    sp.scope_member = member;
+    {
+      Timed t(c, TAVB_KERNEL_SCAN);
+      hipError_t e = tavb::launch_scan_scoped(sp, g, c->stream, &c->last_tier);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "scoped scan launch failed: %s", hipGetErrorString(e));
+    }
+    {
+      Timed t(c, TAVB_KERNEL_MERGE);
+      hipError_t e = tavb::launch_merge(sp.lists, g.blocks, n, k, /*query_major=*/true, work + (size_t)q0 * k, c->stream);
+      if (e == hipSuccess) e = tavb::launch_remap_positions(work + (size_t)q0 * k, out + (size_t)q0 * k, (int64_t)n * k, list, n_pos, index_base, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "merge / remap launch failed: %s", hipGetErrorString(e));
+    }
+  }
+  return TAVB_OK;
+}
+
+int search_scoped_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* const* masks, uint32_t index_base, u64_t* work,
+                       u64_t* out) {
+  const int per_pass = tavb::scoped_queries_per_pass(c->corpus, c->dim, c->dtype, k, clamped_geometry(c));
+  const int wave_passes = (int)std::min<int64_t>(kScopedWavePasses, std::max<int64_t>(1, kScopedWavePositions / std::max<int64_t>(c->rows, 1)));
+  const int wave = wave_passes * per_pass;
+  for (int q0 = 0; q0 < nq; q0 += wave) {
+    if (int rc = scoped_wave(c, d_q + (size_t)q0 * c->dim, std::min(wave, nq - q0), k, per_pass, min_scores + q0, masks + q0, index_base, work + (size_t)q0 * k,
+                             out + (size_t)q0 * k))
+      return rc;
+  }
+  return TAVB_OK;
+}
+
 }  // namespace host
 }  // namespace tavb
 

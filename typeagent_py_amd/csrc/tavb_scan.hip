@@ -73,6 +73,7 @@ __device__ __forceinline__ float dot_slice<_Float16>(f32x4 raw, const float* __r
 template <int NQ, int KPL>
 struct Selector {
   static constexpr bool kScorePass = false;
+  static constexpr bool kScoped = false;
   WaveTopK<KPL> top[NQ];
   u64 thr[NQ];  // key at rank k-1: a candidate must beat it (wave-uniform)
 
@@ -119,6 +120,7 @@ __device__ __forceinline__ QueryGroup query_group(const ScanParams& p) {
 template <int NQ>
 struct ScoreSink {
   static constexpr bool kScorePass = true;
+  static constexpr bool kScoped = false;
   unsigned* hist;     // LDS [NQ][nb]
   unsigned* scores;   // [nq][n_pos]
   unsigned* ghist;    // [nq][nb]
@@ -163,9 +165,26 @@ struct ScoreSink {
   }
 };
 
+// The Selector of a scoped batch (launch_scan_scoped): every query of the pass has a scope of its own, the scan runs over the ascending row
+// list of the scopes' UNION, and member[position] says which queries' scopes hold that row (bit q = query q of the pass;
+// scope_member_kernel, tavb_mask.hip).  A row is offered to query q only when its bit is set -- the score, the threshold test, the key and the
+// merge are the Selector's own, so query q ends with exactly what a scan over its own scope's row list leaves, the positions being those of
+// the union list.  One byte per row, the same address on every lane; a row no scope of the remaining queries holds skips the wave reduction.
+template <int NQ, int KPL>
+struct ScopedSelector : Selector<NQ, KPL> {
+  static constexpr bool kScoped = true;
+  const uint8_t* member;  // [n_pos]
+
+  __device__ __forceinline__ void offer(int q, float partial, uint32_t index, float min_score, int k, int lane, u64 bound) {
+    const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)member[index]);  // (index_base is 0: the index IS the position)
+    if ((m >> q) & 1u) Selector<NQ, KPL>::offer(q, partial, index, min_score, k, lane, bound);  // wave-uniform
+  }
+};
+
 template <int NQ, int KPL, typename SEL>
 __device__ __forceinline__ void start_epilogue(SEL& sel, const ScanParams& p, const QueryGroup& qg, void* lds) {
   if constexpr (SEL::kScorePass) sel.setup(p, qg, lds);
+  if constexpr (SEL::kScoped) sel.member = p.scope_member;
   sel.clear();
 }
 
@@ -780,6 +799,76 @@ hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStrea
   if (tier_used) *tier_used = tier;
   if (tier == 1) return f16 ? go_topk_fixed<_Float16, 3>(p, g, stream) : go_topk_fixed<float, 6>(p, g, stream);
   return f16 ? dispatch_topk<_Float16>(p, g, stream, tier, nqt) : dispatch_topk<float>(p, g, stream, tier, nqt);
+}
+
+// ---------------------------------------------------------------------------
+// scoped batches (tavb_search_scoped_batch): the vector and scalar tiers with the ScopedSelector, picked as launch_scan picks the tier of ONE
+// query of the corpus (scoped_tier) -- the passes are cut to the queries that fit the vector tier's LDS.  A pass of ONE query at width 1536 takes
+// the vector tier too (tier 1 has no scoped form): the per-row arithmetic of tiers 1 and 2 is the same, so its scores are those of the
+// single-query lookup bit for bit.
+// ---------------------------------------------------------------------------
+namespace {
+
+template <typename T, int NQ, int KPL>
+hipError_t go_scoped_vec(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
+  const size_t qbytes = (((size_t)NQ * p.dim * sizeof(float)) + 15) & ~(size_t)15;
+  const size_t lds = qbytes + scratch_bytes(KPL, g.waves);
+  auto launch = [&](auto kern) -> hipError_t {
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
+    hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
+    return hipGetLastError();
+  };
+  if (g.nt) return launch(scan_vec_kernel<T, NQ, KPL, true, ScopedSelector<NQ, KPL>>);
+  return launch(scan_vec_kernel<T, NQ, KPL, false, ScopedSelector<NQ, KPL>>);
+}
+
+template <typename T, int NQ, int KPL>
+hipError_t go_scoped_scalar(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
+  const size_t lds = scratch_bytes(KPL, g.waves);
+  hipLaunchKernelGGL((scan_scalar_kernel<T, NQ, KPL, ScopedSelector<NQ, KPL>>), dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dispatch_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t s, int tier, int nqt, int kpl) {
+#define TAVB_F(NQ, KPL) \
+  if (nqt == NQ && kpl == KPL) return tier == 2 ? go_scoped_vec<T, NQ, KPL>(p, g, s) : go_scoped_scalar<T, NQ, KPL>(p, g, s);
+  TAVB_F(1, 1) TAVB_F(1, 4) TAVB_F(2, 1) TAVB_F(2, 4) TAVB_F(4, 1) TAVB_F(4, 4) TAVB_F(8, 1)
+#undef TAVB_F
+  return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+// The tier of a scoped pass of nqt (1, 2, 4 or 8) query slots: what launch_scan gives ONE query of this corpus, so that the per-row arithmetic
+// -- and with it every score bit -- is the single-query lookup's: the scalar tier when the geometry forces it (tier 3) or the rows are not
+// 16-byte slices, else the vector tier (tier 1's arithmetic is the vector tier's) -- provided the pass' queries fit its LDS.  0: they do not.
+static int scoped_tier(const void* corpus, int dim, int dtype, int nqt, int kpl, const ScanGeometry& g) {
+  const int epl = dtype == TAVB_F16 ? 8 : 4;
+  const bool aligned = ((uintptr_t)corpus % 16) == 0 && (dim % epl) == 0;
+  if (g.tier == 3 || !aligned) return 3;
+  const size_t one = (size_t)dim * 4 + 16 + scratch_bytes(kpl, g.waves);
+  if (one > 150 * 1024) return 3;  // (not even one query fits: launch_scan sends the single query to the scalar tier as well)
+  return (size_t)nqt * dim * 4 + 16 + scratch_bytes(kpl, g.waves) <= 150 * 1024 ? 2 : 0;
+}
+
+int scoped_queries_per_pass(const void* corpus, int dim, int dtype, int k, const ScanGeometry& g) {
+  int n = k > 64 ? 4 : TAVB_MAX_STREAM_QUERIES;
+  while (n > 1 && scoped_tier(corpus, dim, dtype, n, k <= 64 ? 1 : 4, g) == 0) n /= 2;
+  return n;
+}
+
+hipError_t launch_scan_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used) {
+  if (p.nq < 1 || p.nq > TAVB_MAX_STREAM_QUERIES || p.group != 0 || p.k < 1 || p.k > TAVB_MAX_FUSED_K || p.dim < 1 || p.index_base != 0 ||
+      !p.scope_member || !p.row_ids)
+    return hipErrorInvalidValue;
+  if (p.k > 64 && p.nq > 4) return hipErrorInvalidValue;  // 256-deep lists: at most 4 queries per pass (registers)
+  const int nqt = p.nq <= 1 ? 1 : p.nq <= 2 ? 2 : p.nq <= 4 ? 4 : 8;
+  const int kpl = p.k <= 64 ? 1 : 4;
+  const int tier = scoped_tier(p.corpus, p.dim, p.dtype, nqt, kpl, g);
+  if (tier == 0) return hipErrorInvalidValue;  // (scoped_queries_per_pass sizes the passes)
+  if (tier_used) *tier_used = tier;
+  return p.dtype == TAVB_F16 ? dispatch_scoped<_Float16>(p, g, stream, tier, nqt, kpl) : dispatch_scoped<float>(p, g, stream, tier, nqt, kpl);
 }
 
 }  // namespace tavb

@@ -1105,14 +1105,100 @@ class VectorBase:
             return self._batch_result(*eng.search_masked(queries, mask.shards, max_hits, thr), max_hits, as_arrays, base=eng.ordinal_base)
         flat = mask.flat()
         lists = [self.fuzzy_lookup_embedding_in_subset(q, flat, max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
-        if not as_arrays:
-            return lists
+        return self._lists_as_arrays(lists, max_hits) if as_arrays else lists
+
+    @staticmethod
+    def _lists_as_arrays(lists, max_hits: int):
+        """Q lists of ScoredInt -> the (ordinals [Q, max_hits], scores [Q, max_hits], counts [Q]) form of `as_arrays=True`."""
+        nq = len(lists)
         ords, scs = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32)
         cnts = np.array([len(hits) for hits in lists], dtype=np.int32)
         for i, hits in enumerate(lists):
             ords[i, : len(hits)] = [h.item for h in hits]
             scs[i, : len(hits)] = [h.score for h in hits]
         return ords, scs, cnts
+
+    # ------------------------------------------------------------------ scoped batches: one mask per query (additive)
+    def _resolve_scopes(self, scopes, nq: int) -> list[RowMask]:
+        """One scope per query -> their handles (`_resolve_mask` each; an object that appears several times is resolved once, so that its
+        queries share a handle)."""
+        scopes = list(scopes)
+        if len(scopes) != nq:
+            raise ValueError(f"Number of scopes {len(scopes)} does not match number of embeddings {nq}")
+        seen: dict[int, RowMask] = {}
+        handles = []
+        for s in scopes:
+            h = seen.get(id(s))
+            if h is None:
+                h = seen[id(s)] = self._resolve_mask(s)
+            handles.append(h)
+        return handles
+
+    @staticmethod
+    def _scoped_order(handles) -> list[int]:
+        """The queries that have something to search, ordered so that identical handles sit next to each other (groups in the order of their
+        first query, queries in the caller's order inside a group): queries of one scope share the passes of the native call, and a pass'
+        union is then the fewest rows.  Empty scopes take no slot."""
+        first: dict[int, int] = {}
+        for i, h in enumerate(handles):
+            first.setdefault(id(h), i)
+        return sorted((i for i, h in enumerate(handles) if h.count > 0), key=lambda i: (first[id(handles[i])], i))
+
+    @staticmethod
+    def _scoped_native(eng, call: str, handles, order, max_hits: int) -> bool:
+        """The native route of a scoped batch: a single-GPU engine that has `call`, 1 <= max_hits <= 256, and every searched scope holds its
+        packed mask on the device."""
+        return (isinstance(eng, _native.Engine) and hasattr(eng, call) and 1 <= max_hits <= _PAGE
+                and all(handles[i].dev_bits is not None for i in order))
+
+    def fuzzy_lookup_embeddings_scoped(
+        self,
+        embeddings: NormalizedEmbeddings,
+        scopes,
+        max_hits: int | None = None,
+        min_score: float | None = None,
+        as_arrays: bool = False,
+    ):
+        """A batch whose queries carry their OWN scopes -- the lookups of one compiled question, each under its `when` filter: `scopes` is a
+        sequence with one entry per query, each anything `fuzzy_lookup_embedding_masked` takes (a `RowMask` of this index, a bool array, a
+        bool tensor).  Equals [fuzzy_lookup_embedding_masked(e, s, max_hits, min_score_i) for e, s in zip(embeddings, scopes)], and so
+        fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(s).tolist(), ...) per query.  `min_score` may be a sequence with one threshold per
+        query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings_masked`.  A different number of scopes and embeddings
+        raises ValueError; a handle of another index, another length or from before an edit raises what the masked lookups raise.
+
+        When every scope is the same handle this IS `fuzzy_lookup_embeddings_masked` over it.  Otherwise, on a single-GPU engine with 1 <=
+        max_hits <= 256 whose scopes all hold their packed mask on the device (handles from `row_mask`, `range_mask`, `message_mask` and
+        the scope algebra do), the batch is ONE submission (tavb_search_scoped_batch): the queries are ordered so that identical handles sit
+        next to each other, go in passes of eight (four for max_hits > 64; fewer on rows so wide -- from about 4.7k floats -- that eight
+        queries do not fit the vector tier's on-chip memory, so that a pass keeps the per-row arithmetic of a single query) over the UNION
+        of the pass' scopes -- built, listed and tested on the device; a row several scopes share is read once per pass -- and the answers
+        come back in the caller's order, bit for bit those of the per-query calls on the row list: ordinals, float32 scores and counts.
+        Batches beyond 16 passes (128 queries) go in waves of that many, each with one wait for its unions' sizes, which bounds the
+        device workspace whatever the batch.  A query whose scope is empty gets an empty answer
+        and takes no slot.  `engine.get_option("masked_route")` is then 4.
+
+        Everything else loops over `fuzzy_lookup_embedding_masked`: max_hits == 0 and max_hits > 256, device groups, `ShardedVectorBase`,
+        test doubles, and a handle without a device mask.  The matrix-core tiles are not used for per-query scopes, and queries are not
+        reordered by how much their scopes overlap -- only identical handles are grouped."""
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
+        if as_arrays and not (1 <= max_hits <= _PAGE):
+            raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
+        nq = len(queries)
+        handles = self._resolve_scopes(scopes, nq)
+        if nq and all(h is handles[0] for h in handles):
+            return self.fuzzy_lookup_embeddings_masked(queries, handles[0], max_hits, min_score if per_query is None else per_query, as_arrays)
+        order = self._scoped_order(handles)
+        if self._count == 0 or not order:
+            return self._empty_batch(nq, max_hits, as_arrays)
+        eng = self._sync_device()
+        if self._scoped_native(eng, "search_scoped_batch", handles, order, max_hits):
+            t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
+            o, s, c = eng.search_scoped_batch(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits, np.ascontiguousarray(t[order]))
+            ords, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+            ords[order], scs[order], cnts[order] = o - eng.ordinal_base, s, c
+            return (ords, scs, cnts) if as_arrays else _scored_lists(ords, scs, cnts, max_hits)
+        lists = [self.fuzzy_lookup_embedding_masked(q, handles[i], max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
+        return self._lists_as_arrays(lists, max_hits) if as_arrays else lists
 
     # ------------------------------------------------------------------ message re-rank (additive)
     def set_row_messages(self, row_to_message) -> None:
@@ -1262,6 +1348,40 @@ class VectorBase:
             return _scored_lists(msgs, scs, cnts, max_hits)
         lists = self.fuzzy_lookup_embeddings_masked(queries, mask, max_matches, threshold_score if per_query is None else per_query)
         return [self._host_rerank(hits, None) for hits in lists]
+
+    def lookup_messages_by_embeddings_scoped(
+        self,
+        embeddings: NormalizedEmbeddings,
+        scopes,
+        max_matches: int | None = None,
+        threshold_score: float | None = None,
+    ) -> list[list[ScoredInt]]:
+        """`fuzzy_lookup_embeddings_scoped` aggregated to messages: one scope per query, and per query the result equals
+        lookup_messages_by_embedding_masked(e, s, max_matches, threshold_score_i).  `threshold_score` may be a sequence with one threshold
+        per query.  When every scope is the same handle this IS `lookup_messages_by_embeddings_masked`.  Otherwise a single-GPU engine with
+        1 <= max_matches <= 256 whose scopes hold their packed mask on the device makes ONE submission (tavb_search_messages_scoped: the
+        scoped batch, its key lists left on the device, one launch of the message aggregation, one copy back), bit for bit the per-query
+        calls on the row list; everything else (max_matches outside 1..256, device groups, test doubles, a handle without a device mask)
+        loops over `lookup_messages_by_embedding_masked`."""
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_matches, threshold_score)
+        self._check_row_messages()
+        nq = len(queries)
+        handles = self._resolve_scopes(scopes, nq)
+        if nq and all(h is handles[0] for h in handles):
+            return self.lookup_messages_by_embeddings_masked(queries, handles[0], max_matches, threshold_score if per_query is None else per_query)
+        order = self._scoped_order(handles)
+        if self._count == 0 or not order:
+            return [[] for _ in range(nq)]
+        eng = self._messages_engine()
+        if eng is not None and self._scoped_native(eng, "search_messages_scoped", handles, order, max_hits):
+            t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
+            m, s, c = eng.search_messages_scoped(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                 np.ascontiguousarray(t[order]), max_hits)
+            msgs, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+            msgs[order], scs[order], cnts[order] = m, s, c
+            return _scored_lists(msgs, scs, cnts, max_hits)
+        return [self.lookup_messages_by_embedding_masked(q, handles[i], max_matches, threshold_score if per_query is None else per_query[i])
+                for i, q in enumerate(queries)]
 
     def lookup_messages_by_embeddings(
         self,
