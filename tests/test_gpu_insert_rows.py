@@ -188,7 +188,16 @@ def test_lookups_after_insert_rows_and_set_rows_equal_a_fresh_index(dtype, stora
         mask_flags = np.random.default_rng(len(model)).random(len(model)) < 0.4
         got, want = _all_lookups(vb, qs, mask_flags), _all_lookups(fresh, qs, mask_flags)
         for name in want:
-            assert got[name] == want[name], name  # bit for bit: a stale shadow or stale norm maxima would show here
+            assert got[name] == want[name], name  # bit for bit
+        # a corpus this small sends the 128-query batch to the grouped streaming scan, which reads neither the shadow nor the maxima: the wide
+        # tile is forced, and a stale shadow or stale norm maxima show HERE
+        eng = vb.engine
+        grouped = eng.get_option("direct_group_max_nq")
+        eng.set_option("direct_group_max_nq", 0)
+        wide = [_pairs(r) for r in vb.fuzzy_lookup_embeddings(qs, max_hits=32, min_score=0.0)]
+        assert eng.get_option("last_tier") == 4 and eng.get_option("last_shadow") == int(dtype == "fp32") and eng.get_option("norm_rows") == len(model)
+        eng.set_option("direct_group_max_nq", grouped)
+        assert wide == want["batch128"]
 
     at = np.concatenate([[0, 0, N, -1], rng.integers(-N, N + 1, size=496)])
     new_msgs = rng.integers(0, N // 3, size=500)

@@ -153,9 +153,20 @@ def test_lookups_after_remove_rows_equal_a_fresh_index(n, d, dtype):
     mask_flags = rng.random(len(w)) < 0.4
     got = _all_lookups(vb, qs, subset, mask_flags)
     assert vb.engine.corpus is tensor
+    # a corpus this small sends the 70-query batch to the grouped streaming scan, which reads neither the shadow nor the maxima: the wide tile
+    # is forced.  The removal dropped the maxima (row 0 went); this batch rebuilds them and filters on the rebuilt shadow
+    grouped = eng.get_option("direct_group_max_nq")
+    eng.set_option("direct_group_max_nq", 0)
+    wide = [_pairs(r) for r in vb.fuzzy_lookup_embeddings(qs, max_hits=32, min_score=0.0)]
+    if dtype == "fp16" or d % 16 == 0:
+        assert eng.get_option("last_tier") == 4 and eng.get_option("last_shadow") == int(dtype == "fp32" or d % 64 != 0) and eng.get_option("norm_rows") == len(w)
+    else:  # fp32 rows of 100 floats: the wide tile does not serve the width, the streaming tiers take the batch and no cache is read
+        assert eng.get_option("last_tier") == 2 and eng.get_option("norm_rows") == 0
+    eng.set_option("direct_group_max_nq", grouped)
+    assert wide == got["batch70"]  # the rescored wide tile carries the streaming kernels' scores: a stale shadow row would lose a true hit here
     want = _all_lookups(fresh, qs, subset, mask_flags)
     for name in want:
-        assert got[name] == want[name], name  # bit for bit: a stale shadow or stale norm maxima would show here
+        assert got[name] == want[name], name  # bit for bit (the batches among them ran on the grouped streaming scan: no cache is read here)
     _check_against_oracle(got, np.delete(ref, idx, axis=0), qs, subset, mask_flags, np.delete(row_to_msg, idx))
     np.testing.assert_array_equal(np.asarray(vb.serialize()), w)
 
