@@ -197,7 +197,11 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   many per cent of the tile's (the mask's span once per 64 queries)
  *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the
  *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide), 4 = a scoped batch (one mask per
- *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped)
+ *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped), 5 = a scoped batch on the 32/64-query tile
+ *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile)
+ *   "scope_tile"    scoped batches, one mask per query (the binding reads it; the rule is tavb_plan_scoped, with "mask_tile_min_bytes" /
+ *                   "mask_tile_pct"): 1 (default) = the 32/64-query tile (tavb_search_scoped_tile) where tavb_plan_scoped says so, else the
+ *                   row-list route (tavb_search_scoped_batch); 0 = never; 2 = wherever the tile serves the shape (tests, measurements)
  *   "mask_wide"     masked batches on fp16 corpora (the binding reads it; the rule is tavb_plan_masked_wide, with "mask_tile_min_bytes" / "mask_tile_pct"):
  *                   1 (default) = a batch takes the 128/256-query filter tile with the bit test in its admission path + exact rescoring
  *                   (tavb_search_masked_wide) where tavb_plan_masked_wide says so -- it then wins over "mask_tile"; 0 = never; 2 = wherever that route
@@ -573,6 +577,39 @@ int tavb_search_messages_scoped(tavb_ctx* ctx, const float* queries_host, int32_
 int tavb_mask_membership(tavb_ctx* ctx, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, const int32_t* dev_rows, int64_t n,
                          uint8_t* dev_member_out);
 
+/* ---- scoped batches on the 32/64-query tile: one scope per query on the matrix cores ----------------------------------------------------
+ * The scoped batch above reads, per pass of eight queries, the union of the pass' scopes; dense, independent or disjoint scopes make that
+ * union most of the span once per eight queries.  These calls read the SPAN of the batch's union once per 64 queries instead, on the
+ * 32/64-query MFMA tile (the tile of tavb_search_masked_batch), with the per-query test in the tile's admission path.  Same dev_masks (HOST
+ * array of nq device pointers, none NULL, 4-byte aligned, repeats allowed); [first_row, last_row] must hold every set bit of every mask
+ * (first_row > last_row: every scope is empty -- zero counts / zero keys, nothing launched).  1 <= k <= 64 and rows of a multiple of 64
+ * bytes, else TAVB_E_UNSUPPORTED; NULL arguments, a NULL mask pointer, rows != the corpus' rows and a span outside the corpus are
+ * TAVB_E_INVALID, each with a message.
+ * CONTRACT: the tile's, not the row list's.  Scores are the tile's float32 dot products (fp32 accumulation inside the matrix pipe), so per
+ * query the answer equals the streaming routes' (tavb_search_scoped_batch, tavb_search_subset_batch_resident over that mask's row list)
+ * except among float32 near-ties, scores within a few 1e-7.  A batch whose masks all hold the same bits returns tavb_search_masked_device's
+ * keys for that batch and mask bit for bit; with every mask all ones, the keys of the unmasked 32/64-query tile.
+ * On the device, in WAVES of query tiles: the membership PLANES of the wave -- per block of 32 queries one uint32 per row of the span, bit i
+ * = the scope of query i of the block holds the row (a 32 x 32 bit transpose of the masks' words, one launch per 64 queries) -- then the
+ * tile's phases over rows [first_row / 256 * 256, last_row].  A wave is as many 64-query tiles as fit 64 MiB of planes, at least one (1M
+ * rows: 512 queries); the workspace is max(64 MiB, 8 bytes x span) whatever the batch.  Nothing is waited for before the result.
+ * "masked_route" reports 5, "last_tier" 5, "last_skinny_kernel" the tile's instantiation.  Timed under TAVB_KERNEL_CONVERT (planes),
+ * TAVB_KERNEL_SKINNY / TAVB_KERNEL_MFMA_SAMPLE and TAVB_KERNEL_MERGE.
+ *   tavb_search_scoped_tile / _device / tavb_search_messages_scoped_tile: the three forms of the scoped batch above.
+ *   tavb_scope_planes: the planes alone.  With span_begin = first_row / 256 * 256, stride = (last_row + 32) / 32 * 32 - span_begin and n_blocks =
+ *     1 for n_masks <= 32, else 2 * ceil(n_masks / 64) (the tile-padded batch): dev_planes_out (device uint32 [n_blocks * stride], 64-byte
+ *     aligned) [b * stride + r - span_begin] has bit i set when dev_masks[32 b + i] holds row r, r <= last_row; zero for padding queries and
+ *     behind last_row, whatever the masks' last words hold at or beyond `rows`.  Asynchronous on the context's stream. */
+int tavb_search_scoped_tile(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                            int64_t last_row, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_scoped_tile_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                   int64_t last_row, int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
+int tavb_search_messages_scoped_tile(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                     int64_t last_row, int32_t k, const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores,
+                                     int32_t* out_counts);
+int tavb_scope_planes(tavb_ctx* ctx, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, int64_t first_row, int64_t last_row,
+                      uint32_t* dev_planes_out);
+
 /* ---- removing rows: compaction of the corpus on the device ---------------------------------------------------------------------------
  * The removal the reference leaves as a TODO (storage/sqlite/reltermsindex.py:181-192 `remove_term`; knowpro/fuzzyindex.py:113-127, the
  * commented `remove_at` around np.delete): dev_remove_bits is a mask in the bit form above in which a SET bit means "remove"; rows must equal
@@ -732,6 +769,14 @@ int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int
  * "skinny_min_batch_f16"), allowed x row bytes >= min_bytes, and ceil(nq / 8) x allowed x 100 >= ceil(nq / 64) x span x pct -- the gather
  * route's bytes are at least pct % of the tile's.  Negative: an argument out of range.  A pure function, needs no context and no GPU. */
 int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_bytes, int64_t pct);
+
+/* Which route a scoped batch (one mask per query) takes under option "scope_tile" = 1: 1 = the 32/64-query tile (tavb_search_scoped_tile), 0 =
+ * the row-list route (tavb_search_scoped_batch).  gather_rows: over the row-list route's passes of eight queries, in the order they are
+ * submitted, the sum of each pass' LARGEST scope -- a lower bound of the rows that route reads; span: rows from the first set row of any
+ * scope, rounded down to a multiple of 256, to the last.  1 when the tile serves the shape (1 <= k <= 64, rows of a multiple of 64 bytes,
+ * nq at least the unmasked tile's lower bound), gather_rows x row bytes >= ceil(nq / 8) x min_bytes, and gather_rows x 100 >= ceil(nq / 64)
+ * x span x pct.  0 otherwise; negative: an argument out of range.  Needs no GPU. */
+int tavb_plan_scoped(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t gather_rows, int64_t span, int64_t min_bytes, int64_t pct);
 
 /* Whether a masked batch takes the 128/256-query filter tile + rescoring (tavb_search_masked_wide) under option "mask_wide" = 1; the arguments
  * of tavb_plan_masked.  1 when the corpus is fp16 and the route serves the shape (dim <= 16384, 1 <= k <= TAVB_MAX_FUSED_K), nq is at least the

@@ -40,6 +40,12 @@ def kernel_id(symbol):
             if pack is not None:
                 pos += pack.end()
                 continue
+            pack = re.match(r"JNS\d*_(\d+)", symbol[pos:])  # ... unless it is a struct (ScopePlanes: the per-query mode of MASKED = true), which names the mode
+            if pack is not None:
+                start = pos + pack.end()
+                args.append(symbol[start : start + int(pack.group(1))])
+                pos = start + int(pack.group(1)) + 2  # the struct's and the pack's closing E
+                continue
             m = re.match(r"Li(\d+)E|Ln(\d+)E|Lb([01])E|(f)|(DF16_)", symbol[pos:])
             if m is None:
                 raise ValueError(f"template argument not understood at {symbol[pos:]!r}")

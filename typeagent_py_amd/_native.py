@@ -105,6 +105,11 @@ _SIGNATURES = [
     ("tavb_search_scoped_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_search_messages_scoped", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_mask_membership", c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
+    ("tavb_search_scoped_tile", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_scoped_tile_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_messages_scoped_tile", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_scope_planes", c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -126,6 +131,7 @@ _SIGNATURES = [
     ("tavb_plan_filter_shape", c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     ("tavb_plan_masked", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
     ("tavb_plan_masked_wide", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
+    ("tavb_plan_scoped", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
 ]
 
 ABI_SYMBOLS = [name for name, _, _ in _SIGNATURES]
@@ -246,6 +252,30 @@ def plan_masked_wide(nq: int, k: int, dim: int, dtype: int, allowed: int, span: 
     r = lib.tavb_plan_masked_wide(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
     _check(lib, r if r < 0 else 0)
     return bool(r)
+
+
+def plan_scoped(nq: int, k: int, dim: int, dtype: int, gather_rows: int, span: int, min_bytes: int = MASK_TILE_MIN_BYTES, pct: int = MASK_TILE_PCT) -> bool:
+    """True: a scoped batch (one mask per query) of `nq` queries takes the 32/64-query tile under option "scope_tile" = 1, False: the
+    row-list route (tavb_plan_scoped).  gather_rows: over the row-list route's passes of eight queries, the sum of each pass' largest
+    scope (`scoped_gather_rows`); span: the rows of the span of the scopes' union.  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_scoped(int(nq), int(k), int(dim), int(dtype), int(gather_rows), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
+
+
+def scoped_gather_rows(counts, per_pass: int = 8) -> int:
+    """`plan_scoped`'s gather_rows for scopes of `counts` rows in submission order: the largest scope of every pass of `per_pass` queries,
+    summed -- a lower bound of the rows the row-list route reads (a pass reads the union of its scopes)."""
+    counts = [int(c) for c in counts]
+    return sum(max(counts[i : i + per_pass]) for i in range(0, len(counts), per_pass))
+
+
+def scope_plane_shape(n_masks: int, first_row: int, last_row: int) -> tuple[int, int, int]:
+    """(blocks of 32 queries, words per plane, first row of a plane) of tavb_scope_planes' output for that batch and span: the blocks of
+    the tile-padded batch, rows first_row // 256 * 256 .. last_row rounded up to whole 32-row blocks."""
+    begin = first_row // 256 * 256
+    return (1 if n_masks <= 32 else 2 * ((n_masks + 63) // 64)), (last_row + 32) // 32 * 32 - begin, begin
 
 
 def library_path() -> str:
@@ -417,6 +447,7 @@ class Engine:
         _check(self.lib, self.lib.tavb_set_option(self._h, name.encode(), int(value)))
         self.__dict__.pop("_mask_tile_opts", None)
         self.__dict__.pop("_mask_wide_opts", None)
+        self.__dict__.pop("_scope_tile_opts", None)
 
     def mask_tile_options(self) -> tuple[int, int, int]:
         """("mask_tile", "mask_tile_min_bytes", "mask_tile_pct") as the library holds them, read once and again after any `set_option`: a
@@ -431,6 +462,13 @@ class Engine:
         opts = self.__dict__.get("_mask_wide_opts")
         if opts is None:
             opts = self._mask_wide_opts = tuple(self.get_option(n) for n in ("mask_wide", "mask_tile_min_bytes", "mask_tile_pct"))
+        return opts
+
+    def scope_tile_options(self) -> tuple[int, int, int]:
+        """("scope_tile", "mask_tile_min_bytes", "mask_tile_pct"), cached like `mask_tile_options`."""
+        opts = self.__dict__.get("_scope_tile_opts")
+        if opts is None:
+            opts = self._scope_tile_opts = tuple(self.get_option(n) for n in ("scope_tile", "mask_tile_min_bytes", "mask_tile_pct"))
         return opts
 
     def get_option(self, name: str) -> int:
@@ -1124,6 +1162,64 @@ class Engine:
                                                       _addr(cnts))
         _check(self.lib, rc)
         return msgs, scs, cnts
+
+    # scoped batches on the 32/64-query tile ----------------------------------------------
+    plan_scoped = staticmethod(plan_scoped)
+
+    def _scope_span(self, span):
+        return (0, int(self.rows) - 1) if span is None else (int(span[0]), int(span[1]))
+
+    def search_scoped_tile(self, queries, dev_bits_list, k: int, thrs, span=None):
+        """A scoped batch on the 32/64-query MFMA tile (tavb_search_scoped_tile): the arguments of `search_scoped_batch` plus span = (first,
+        last) row of the union of the scopes (None: the whole corpus); 1 <= k <= 64 -> (ordinals [nq, k], scores [nq, k], counts [nq]).
+        The tile's contract: per query `search_scoped_batch`'s answer except among float32 near-ties.  Raises TavbError
+        (TAVB_E_UNSUPPORTED) for a shape the tile does not serve."""
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_tile(self._h, _addr(a), nq, ptrs, int(self.rows), first, last, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_scoped_tile_device(self, dev_queries, dev_bits_list, k: int, thrs, span=None, out_keys=None):
+        """`search_scoped_tile` with the queries on the device (tavb_search_scoped_tile_device) -> torch int64 [nq, k] sorted, zero-padded
+        keys carrying ordinal_base + row; nothing is waited for: `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_tile_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), first, last, k, _addr(t),
+                                                         c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def search_messages_scoped_tile(self, queries, dev_bits_list, k: int, thrs, max_messages: int, span=None):
+        """`search_scoped_tile` aggregated to messages in one submission (tavb_search_messages_scoped_tile) -> (message ordinals [nq, k],
+        scores [nq, k], counts [nq])."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_messages_scoped_tile(self._h, _addr(a), nq, ptrs, int(self.rows), first, last, k, _addr(t), int(max_messages),
+                                                           _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def scope_planes(self, dev_bits_list, span=None):
+        """The membership planes of a scoped batch on the tile (tavb_scope_planes): torch int32 [blocks, words] on the device, shaped by
+        `scope_plane_shape` -- bit i of [b, r - first // 256 * 256] = mask 32 b + i holds row r.  Async on the engine's stream."""
+        torch = self._torch
+        masks = list(dev_bits_list)
+        ptrs = self._mask_pointers(masks, len(masks))
+        first, last = self._scope_span(span)
+        blocks, words, _ = scope_plane_shape(len(masks), first, last)
+        out = torch.empty((blocks, max(words, 0)), dtype=torch.int32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+        with self._lock:
+            rc = self.lib.tavb_scope_planes(self._h, ptrs, len(masks), int(self.rows), first, last, c_void_p(out.data_ptr()) if out.numel() else None)
+        _check(self.lib, rc)
+        return out
 
     def mask_membership(self, dev_bits_list, dev_rows):
         """Which of 1 .. 8 packed masks hold each row of a resident row list (tavb_mask_membership): torch uint8 [S] on the device, bit j of

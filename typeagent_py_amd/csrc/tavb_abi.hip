@@ -254,6 +254,7 @@ const Option kOptions[] = {
     RANGE("mask_tile_pct", mask_tile_pct, 0, 1000000),
     READ_ONLY("masked_route", masked_route),
     RANGE("mask_wide", mask_wide, 0, 2),
+    RANGE("scope_tile", scope_tile, 0, 2),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
     READ_ONLY("norm_rows", norm_rows),
     READ_ONLY("last_direct", last_direct),

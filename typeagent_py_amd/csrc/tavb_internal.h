@@ -186,6 +186,17 @@ hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned*
 // Scoped batches (tavb_mask.hip): member[p] = the scopes of rows[p], p < n -- bit j set when mask ops.m[j] (j < ops.n; ops.op unused) holds
 // row rows[p]; bits from ops.n on are zero.  rows: n valid rows of masks over `n_rows` rows.  One launch.
 hipError_t launch_scope_member(const MaskOperands& ops, const int32_t* rows, int64_t n, int64_t n_rows, uint8_t* member, hipStream_t stream);
+// Scoped batches on the 32/64-query tile (tavb_mask.hip): the membership planes of up to kScopePlaneMasks masks over `rows` rows for
+// the rows [span_begin, span_begin + stride) -- span_begin and stride multiples of 32 -- planes[b * stride + r - span_begin], b < n_blocks: bit
+// i = mask 32 b + i (i < ms.n - 32 b) holds row r and r <= last_row (< rows); every other bit zero, whatever the masks' last words hold behind
+// `rows`.  Every one of the n_blocks * stride words is written.  One launch.
+constexpr int kScopePlaneMasks = 64;  // masks per launch: one 64-query tile (two blocks of 32)
+struct ScopeMasks {
+  const uint32_t* m[kScopePlaneMasks];
+  int32_t n;
+};
+hipError_t launch_scope_planes(const ScopeMasks& ms, int n_blocks, int64_t rows, int64_t span_begin, int64_t last_row, int64_t stride, uint32_t* planes,
+                               hipStream_t stream);
 // Row compaction (tavb_mask.hip; `bits` names the rows to REMOVE).  compact_count: counts[chunk] = the chunk's KEPT rows, info[chunk] = that
 // count and the chunk's first and last removed row (device-writable memory).  compact_gather: the kept rows of src rows [r0, r1) -> dst rows
 // from (kept rows in [from, r0)) on, densely and in order; from <= r0, both multiples of 64, r1 a multiple of 64 or `rows`; src and dst
@@ -295,6 +306,12 @@ struct MfmaParams {
   // optional (the skinny kernel; the shipping filter variants of the 128/256-query kernel): allow-mask (tavb.h "row masks"), the word that holds the bit of row 0 of `corpus` -- the launch's first row must
   // be a multiple of 32 in the mask's numbering, so that bit 0 of that word IS row 0.  Rows whose bit is clear are never candidates.
   const uint32_t* mask;
+  // optional (the skinny kernel only, never together with `mask`): one scope PER QUERY as membership planes (launch_scope_planes) -- the word
+  // of row 0 of `corpus` in the plane of query block 0 (64-byte aligned, a multiple of 32 rows into the planes), scope_stride words (a multiple
+  // of 32, at least `rows` rounded up to 32) from one block's plane to the next; nq_padded / 32 planes.  A row is a candidate of query q only
+  // where bit q & 31 of its word in plane q >> 5 is set.
+  const uint32_t* scope_planes;
+  int64_t scope_stride;
 };
 hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream);
 int mfma_tile_shape(const MfmaParams& p);  // M = N of the MFMA the 128/256-query kernel launch_mfma_scan picks for p runs on: 16 or 32

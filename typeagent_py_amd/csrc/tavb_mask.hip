@@ -295,6 +295,39 @@ __global__ void __launch_bounds__(kMaskThreads) scope_member_kernel(MaskOperands
   }
 }
 
+// ---- scoped batches on the 32/64-query tile (tavb_search_scoped_tile): the membership PLANES the tile's admission path reads -- per block of
+// 32 queries one word per row, bit i = the scope of query i of the block holds the row: a 32 x 32 bit transpose of the masks' words per
+// 32-row block.  A wave takes two 32-row blocks of one query block at a time: lane l reads word (block pair * 2 + (l >> 5)) of mask l & 31 --
+// 32 masks x 8 bytes -- clears the bits behind last_row (the stray bits of a mask's last word among them) and the words of missing masks
+// (padding queries), then 32 ballots turn the columns into rows: ballot r is {bit r of every lane's word} = the plane word of row r of the
+// lower block in its low half and of the upper block in its high half.  Lane l keeps ballot l & 31's half l >> 5 and the wave stores 64
+// consecutive plane words.  Reads n masks x span / 8 bytes, writes as much.
+__global__ void __launch_bounds__(kMaskThreads) scope_planes_kernel(ScopeMasks ms, int n_blocks, int64_t span_begin, int64_t last_row, int64_t stride,
+                                                                    uint32_t* __restrict__ planes) {
+  const int lane = threadIdx.x & 63;
+  const int64_t pairs = (stride + 63) >> 6;  // pairs of 32-row blocks per plane
+  const int64_t n_items = pairs * n_blocks;
+  const int64_t wave0 = (int64_t)blockIdx.x * kMaskWaves + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * kMaskWaves;
+  for (int64_t item = wave0; item < n_items; item += n_waves) {
+    const int b = (int)(item / pairs);
+    const int64_t rel = (item % pairs) * 64 + (lane >> 5) * 32;  // this half-wave's 32-row block, relative to span_begin
+    const int64_t row = span_begin + rel;
+    const int q = 32 * b + (lane & 31);
+    uint32_t w = 0u;
+    if (q < ms.n && rel < stride && row <= last_row) {
+      w = ms.m[q][row >> 5];
+      if (last_row - row < 31) w &= (2u << (int)(last_row - row)) - 1u;
+    }
+    uint32_t mine = 0u;
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+      const unsigned long long col = __ballot((w >> r) & 1u);
+      if ((lane & 31) == r) mine = (uint32_t)(col >> (lane & 32));
+    }
+    if (rel < stride) planes[(int64_t)b * stride + rel + (lane & 31)] = mine;
+  }
+}
+
 // ---- row compaction (tavb_compact_rows): the mask names the rows to REMOVE, the kept rows move down in their old order.
 //   compact_count_kernel    chunk b -> counts[b] = its KEPT rows, info[b] = that count and the chunk's first and last removed row
 //   compact_gather_kernel   a workgroup takes a tile of 64 rows (two mask words) of the row range [r0, r1): the tile's first slot is the
@@ -695,6 +728,20 @@ hipError_t launch_scope_member(const MaskOperands& ops, const int32_t* rows, int
     if (!ops.m[j]) return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)std::min<int64_t>((n + kMaskThreads - 1) / kMaskThreads, 2048);
   hipLaunchKernelGGL(scope_member_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, ops, rows, n, n_rows, member);
+  return hipGetLastError();
+}
+
+hipError_t launch_scope_planes(const ScopeMasks& ms, int n_blocks, int64_t rows, int64_t span_begin, int64_t last_row, int64_t stride, uint32_t* planes,
+                               hipStream_t stream) {
+  if (!planes || rows < 1 || rows >= 0x7FFFFFFFll || ms.n < 1 || ms.n > kScopePlaneMasks || n_blocks < (ms.n + 31) / 32 || n_blocks > kScopePlaneMasks / 32)
+    return hipErrorInvalidValue;
+  if (span_begin < 0 || span_begin % 32 != 0 || stride < 32 || stride % 32 != 0 || last_row < span_begin || last_row >= rows || last_row >= span_begin + stride)
+    return hipErrorInvalidValue;
+  for (int j = 0; j < ms.n; ++j)
+    if (!ms.m[j]) return hipErrorInvalidValue;
+  const int64_t items = ((stride + 63) >> 6) * n_blocks;
+  const unsigned blocks = (unsigned)std::min<int64_t>((items + kMaskWaves - 1) / kMaskWaves, 4096);
+  hipLaunchKernelGGL(scope_planes_kernel, dim3(blocks), dim3(kMaskThreads), 0, stream, ms, n_blocks, span_begin, last_row, stride, planes);
   return hipGetLastError();
 }
 

@@ -96,9 +96,25 @@ struct SkinnyGeom {
 // K step waits out anyway) -- a vector or flat load the compiler can see among the staging loads would make its wait-count pass drain the whole
 // staging queue (see `need_compact` and the candidate store).
 typedef const __attribute__((address_space(4))) uint32_t const_u32;
+// SCOPED: the third mask mode -- one scope PER QUERY (tavb.h "scoped batches on the tile").  The extra argument of a MASKED instantiation is
+// then not a mask but the membership PLANES of the batch (scope_planes_kernel, tavb_mask.hip): for every block of 32 queries one uint32 per row
+// of the span, bit i = the scope of query 32 * block + i holds the row; `stride` words from one block's plane to the next.  The mode is the
+// TYPE of the argument (`const uint32_t*`: one mask; ScopePlanes: per-query scopes), so the unmasked and the one-mask instantiations keep
+// their names and compile to what they compiled to before the mode existed.  `words` names the word of the launch's first row (a multiple of
+// 32 rows into the span), as the one mask's pointer does.  A lane of the admission path is (half << 5) | query_in_block and tests row
+// r_off (+ 4 in the upper half) of its 32-row block: the lanes a row pair may admit are plane[row] | plane[row + 4] << 32 -- one scalar AND
+// into the compare's wave mask.  The 32 words of a (block, ni) pair are wave-uniform and come through the scalar data path like the one
+// mask's word (two 16-word loads, lgkmcnt), only behind a non-zero ballot.
+struct ScopePlanes {
+  const uint32_t* words;
+  int64_t stride;
+};
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef const __attribute__((address_space(4))) u32x16 const_u32x16;
 template <typename T, int NI, int STEP, bool DEEP = false, int DR = 0, bool HALF = false, bool MASKED = false, typename... MaskArg>
 __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) == 2)) ? 1 : 2)) skinny_scan_kernel(const MfmaDeviceParams p, MaskArg... mask_arg) {
   static_assert(sizeof...(MaskArg) == (MASKED ? 1 : 0), "the mask is an argument of the masked instantiations only");
+  constexpr bool SCOPED = (std::is_same_v<MaskArg, ScopePlanes> || ...);  // per-query scopes: the argument is the membership planes
   using G = SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>;
   constexpr int BMT = G::BMT, RW = G::RW, MI = G::MI;
   constexpr int SQ = G::SQ;
@@ -383,7 +399,19 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
         const bool any = top > thr_pre;
         if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
           [[maybe_unused]] uint32_t allow = ~0u;  // MASKED: the word of this 32-row block; bit r_off + 4 * (lane >> 5) is the row a lane tests
-          if constexpr (MASKED) {
+          [[maybe_unused]] u32x16 plane[2];       // SCOPED: the plane words of this block's 32 rows for the 32 queries of `ni`
+          if constexpr (SCOPED) {
+            const int64_t block_row = row0 + wave * RW + mi * 32;  // (a multiple of 32, as r_begin and the tile are)
+            if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no plane words (and admits nothing either way)
+            const ScopePlanes sp = (mask_arg, ...);
+            const char* words = sgpr_ptr(reinterpret_cast<const char*>(sp.words) + ((size_t)(qtile * NI + ni) * (size_t)sp.stride + (size_t)block_row) * sizeof(uint32_t));
+            plane[0] = *(const const_u32x16*)(uintptr_t)words;  // s_load_dwordx16 x 2: lgkmcnt, not vmcnt
+            plane[1] = *(const const_u32x16*)(uintptr_t)(words + 16 * sizeof(uint32_t));
+            uint32_t any_row = 0u;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) any_row |= plane[0][w] | plane[1][w];
+            if (any_row == 0u) continue;  // no scope of these 32 queries holds a row of this block
+          } else if constexpr (MASKED) {
             const int64_t block_row = row0 + wave * RW + mi * 32;  // (a multiple of 32, as r_begin and the tile are)
             if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no word (and admits nothing either way)
             const char* word = sgpr_ptr(reinterpret_cast<const char*>((mask_arg, ...)) + (size_t)(block_row >> 5) * sizeof(uint32_t));
@@ -403,13 +431,18 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
               sc[j] = fmaf(acc[mi][ni][4 * g + j], 0.5f, 0.5f);
               asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(m[j]) : "v"(sc[j]), "v"(thr));
             }
+            if constexpr (SCOPED) {  // rows 8g .. 8g + 7 are words 8 (g & 1) .. of half g >> 1: lanes 0-31 test row r_off, lanes 32-63 row r_off + 4
+#pragma unroll
+              for (int j = 0; j < 4; ++j) m[j] &= (u64)plane[g >> 1][8 * (g & 1) + j] | ((u64)plane[g >> 1][8 * (g & 1) + j + 4] << 32);
+            }
             if ((m[0] | m[1] | m[2] | m[3]) == 0ull) continue;  // wave-uniform
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const int r_off = j + 8 * g;
               if (m[j] == 0ull) continue;
-              // (MASKED: bits at or beyond `rows` in the last word may hold anything -- rows_left cuts those rows)
-              if (((m[j] >> lane) & 1ull) != 0ull && r_off < rows_left && (!MASKED || ((allow >> (r_off + 4 * (lane >> 5))) & 1u) != 0u)) {
+              // (MASKED: bits at or beyond `rows` in the last word may hold anything -- rows_left cuts those rows.  SCOPED: m[j] is already cut
+              //  to the lanes whose query holds the row; the planes are zero behind the corpus, rows_left cuts the rows of a later phase)
+              if (((m[j] >> lane) & 1ull) != 0ull && r_off < rows_left && (!MASKED || SCOPED || ((allow >> (r_off + 4 * (lane >> 5))) & 1u) != 0u)) {
                 const int pos = lds_add_rtn(&cnt_lds[ql], 1);
                 if (pos + 1 > CAP - BMT) lds_store_i32(need_compact, 1);  // this buffer could overflow on the next tile
                 float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
@@ -533,6 +566,10 @@ hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
   const int tile = p.skinny_tile == 64 ? 64 : 32;
   if (!skinny_supported(p.dim, p.k, f32) || p.nq_padded % tile != 0 || p.n_splits < 1 || !p.workspace) return hipErrorInvalidValue;
   if (p.mask && (p.active || (reinterpret_cast<uintptr_t>(p.mask) & 3) != 0)) return hipErrorInvalidValue;  // (no work-list form of the masked tile)
+  // per-query scopes: 64-byte aligned plane words (the 16-word scalar loads), whole 32-row blocks per plane, never together with one mask
+  if (p.scope_planes && (p.mask || p.active || (reinterpret_cast<uintptr_t>(p.scope_planes) & 63) != 0 || p.scope_stride % 32 != 0 || p.scope_stride < ((p.rows + 31) & ~(int64_t)31)))
+    return hipErrorInvalidValue;
+  const ScopePlanes planes{p.scope_planes, p.scope_stride};
   const MfmaDeviceParams d = fill_device_params(p, tile, BM);
   const int groups = (p.n_splits + 7) / 8;
   const int grid = groups * d.n_qtiles * 8;
@@ -543,9 +580,10 @@ hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
     return hipGetLastError();
   };
   // (one case per instantiation, keyed by the value the "last_skinny_kernel" getter reports: the getter cannot drift from the dispatch)
-  // (p.mask: the same seven variants in their MASKED form, the mask as their second argument)
+  // (p.mask: the same seven variants in their MASKED form, the mask as their second argument; p.scope_planes: in their SCOPED form, the planes)
 #define TAVB_SKINNY_T(T, NI, STEP, DEEP, DR, HALF)                                                                                   \
-  (p.mask ? go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF, true, const uint32_t*>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS, p.mask) \
+  (p.scope_planes ? go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF, true, ScopePlanes>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS, planes) \
+   : p.mask ? go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF, true, const uint32_t*>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS, p.mask) \
           : go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS))
 #define TAVB_SKINNY(NI, STEP, DEEP, DR, HALF) (f32 ? TAVB_SKINNY_T(float, NI, STEP, DEEP, DR, HALF) : TAVB_SKINNY_T(_Float16, NI, STEP, DEEP, DR, HALF))
   switch (skinny_kernel_id(p)) {

@@ -296,6 +296,10 @@ struct TileRun {
   // own bytes -- and only rows whose bit is set are candidates.  nullptr: no mask, the whole corpus.
   const uint32_t* mask;
   int64_t span_begin, span_end;
+  // the 32/64-query tile only, instead of `mask`: one scope per query as membership planes (launch_scope_planes) over the same span -- word 0
+  // of a plane = row span_begin, plane_stride words from one block of 32 queries to the next
+  const uint32_t* planes;
+  int64_t plane_stride;
 };
 
 // Width (in score) of the band the exact fallbacks keep below their k-th best before the candidates are scored again with the streaming
@@ -371,9 +375,11 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   auto launch = [&](const tavb::MfmaParams& q) { return r.skinny ? tavb::launch_skinny_scan(q, c->stream) : tavb::launch_mfma_scan(q, c->stream); };
   const int nq = r.nq, k = r.k;
   const bool wide = !r.skinny;  // the 256-query tile leaves unsorted buffers + counts, one select kernel picks the best k over them
-  const int64_t row_first = r.mask ? r.span_begin : 0;  // the rows the phases cover: the mask's span, or the corpus
-  const int64_t n_rows = (r.mask ? r.span_end : c->rows) - row_first;
-  if (r.mask && ((wide && (r.active || r.split_plane > 0)) || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
+  const bool spanned = r.mask || r.planes;
+  const int64_t row_first = spanned ? r.span_begin : 0;  // the rows the phases cover: the mask's span, or the corpus
+  const int64_t n_rows = (spanned ? r.span_end : c->rows) - row_first;
+  if (r.planes && (wide || r.mask || r.active)) return fail(TAVB_E_INVALID, "bad scoped tile run (internal error)");
+  if (spanned && ((wide && (r.active || r.split_plane > 0)) || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
   const int splits = c->mfma_splits > 0 ? (int)c->mfma_splits : pick_splits(n_rows);
   if (!wide)
     if (int rc = c->d_lists.reserve((size_t)nq * (splits + 1) * k * sizeof(u64_t))) return rc;  // + the carried-over top-k
@@ -425,9 +431,13 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
     pp.corpus = reinterpret_cast<const char*>(p.corpus) + (size_t)ph_first * row_bytes;
     pp.rows = bounds[ph + 1] - bounds[ph];
     pp.index_base = r.index_base + (uint32_t)ph_first;
-    if (r.mask) {  // whole words: a 32-row block of the tile's epilogue is one word of the mask (ladder_bounds gives multiples of 640 or 256; the wide tile's: of 320 or 256)
+    if (spanned) {  // whole words: a 32-row block of the tile's epilogue is one word of the mask (ladder_bounds gives multiples of 640 or 256; the wide tile's: of 320 or 256)
       if (ph_first % 32 != 0) return fail(TAVB_E_INVALID, "masked tile phase %d starts at row %lld, not a multiple of 32 (internal error)", ph, (long long)ph_first);
-      pp.mask = r.mask + (ph_first >> 5);
+      if (r.mask) pp.mask = r.mask + (ph_first >> 5);
+      if (r.planes) {  // (the planes start at the span: one word per row)
+        pp.scope_planes = r.planes + (ph_first - row_first);
+        pp.scope_stride = r.plane_stride;
+      }
     }
     pp.n_splits = pick_splits(pp.rows);
     if (c->mfma_splits > 0 || pp.n_splits > splits) pp.n_splits = splits;  // lists / candidate buffers are sized for `splits`
@@ -820,7 +830,7 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
 // over the corpus rows, whose set bits all lie in [span_begin, span_end), span_begin a multiple of 256 -- the phases run over the span with
 // the bit test in the tile's admission path.  Scores are final -> sorted key lists d_out [nq, k] (async on the stream).
 int run_skinny_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, uint32_t index_base, u64_t* d_out,
-                    const uint32_t* mask = nullptr, int64_t span_begin = 0, int64_t span_end = 0) {
+                    const uint32_t* mask = nullptr, int64_t span_begin = 0, int64_t span_end = 0, const uint32_t* planes = nullptr, int64_t plane_stride = 0) {
   const bool q32 = c->dtype != TAVB_F16;
   const int qt = tavb::skinny_query_tile(nq);
   const int nq_pad = ((nq + qt - 1) / qt) * qt;
@@ -856,6 +866,8 @@ int run_skinny_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* m
   r.mask = mask;
   r.span_begin = span_begin;
   r.span_end = span_end;
+  r.planes = planes;
+  r.plane_stride = plane_stride;
   return run_tile_ladder(c, r, d_out, nullptr);
 }
 
@@ -949,6 +961,60 @@ int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
   return run_skinny_tile(c, d_q, nq, k, min_scores, index_base, d_out, dev_bits, first_row / 256 * 256, last_row + 1);
 }
 
+// A scoped batch on the 32/64-query tile (tavb_search_scoped_tile and its twins; the callers have checked the arguments and that
+// skinny_supported holds), in WAVES of query tiles: a wave's membership planes are built (one scope_planes_kernel launch per 64 queries) and
+// its tile ladder runs over the span of the union, then the next wave reuses the workspace -- everything on the one stream, nothing waited
+// for.  A plane is 4 bytes per row of the span per 32 queries, so a wave is as many 64-query tiles as fit kScopeWavePlaneBytes of planes (at
+// least one): at 1M rows 8 MiB per tile, 8 tiles = 512 queries per wave.  64 MiB: what a wave costs beyond its tiles' passes is one
+// ladder's launches (about ten), which eight passes over any span that fills the budget outweigh many times; a longer wave would only
+// grow the workspace.  The workspace is max(64 MiB, 8 bytes x span rows) whatever the batch.
+constexpr int64_t kScopeWavePlaneBytes = (int64_t)64 << 20;
+
+int64_t scope_plane_stride(int64_t first_row, int64_t last_row) { return ((last_row + 32) & ~(int64_t)31) - first_row / 256 * 256; }
+
+// the planes of masks[0 .. n) (HOST array of device pointers), padded to n_blocks blocks of 32, at `planes`: one launch per 64 masks
+int build_scope_planes(tavb_ctx* c, const uint32_t* const* masks, int n, int n_blocks, int64_t first_row, int64_t last_row, uint32_t* planes) {
+  const int64_t span_begin = first_row / 256 * 256, stride = scope_plane_stride(first_row, last_row);
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  for (int b0 = 0; b0 < n_blocks; b0 += tavb::kScopePlaneMasks / 32) {
+    const int blocks = std::min(tavb::kScopePlaneMasks / 32, n_blocks - b0);
+    tavb::ScopeMasks ms{};
+    ms.n = std::max(0, std::min(32 * blocks, n - 32 * b0));
+    for (int j = 0; j < ms.n; ++j) ms.m[j] = masks[32 * b0 + j];
+    if (ms.n == 0) {  // (blocks of padding only: a batch the caller padded beyond a tile)
+      TAVB_HIP(hipMemsetAsync(planes + (size_t)b0 * stride, 0, (size_t)blocks * stride * sizeof(uint32_t), c->stream));
+      continue;
+    }
+    hipError_t e = tavb::launch_scope_planes(ms, blocks, c->rows, span_begin, last_row, stride, planes + (size_t)b0 * stride, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "scope plane launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+int scope_plane_blocks(int n) { return tavb::skinny_query_tile(n) == 32 ? 1 : ((n + 63) / 64) * 2; }
+
+int search_scoped_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* const* masks, int64_t first_row, int64_t last_row,
+                       uint32_t index_base, u64_t* d_out) {
+  c->last_shadow = 0;
+  c->last_direct = 0;
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->masked_route = 5;
+  const int64_t stride = scope_plane_stride(first_row, last_row);
+  const int64_t tile_bytes = 2 * stride * (int64_t)sizeof(uint32_t);
+  const int wave = 64 * (int)std::max<int64_t>(1, std::min<int64_t>(kScopeWavePlaneBytes / tile_bytes, 1 << 20));
+  for (int q0 = 0; q0 < nq; q0 += wave) {
+    const int n = std::min(wave, nq - q0), n_blocks = scope_plane_blocks(n);
+    if (int rc = c->d_scope_planes.reserve((size_t)n_blocks * stride * sizeof(uint32_t))) return rc;
+    uint32_t* const planes = reinterpret_cast<uint32_t*>(c->d_scope_planes.ptr);
+    if (int rc = build_scope_planes(c, masks + q0, n, n_blocks, first_row, last_row, planes)) return rc;
+    if (int rc = run_skinny_tile(c, d_q + (size_t)q0 * c->dim, n, k, min_scores + q0, index_base, d_out + (size_t)q0 * k, nullptr, first_row / 256 * 256, last_row + 1,
+                                 planes, stride))
+      return rc;
+  }
+  return TAVB_OK;
+}
+
 // fp16 corpora of any width (one that is no multiple of 64 filters on the zero-padded copy of the rows, as the unmasked route does), every k the
 // filter's band and the rescoring serve
 bool masked_wide_supported(const tavb_ctx* c, int k) {
@@ -996,6 +1062,20 @@ extern "C" int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtyp
   const __int128 gather = (__int128)((nq + 7) / 8) * allowed * 100;
   const __int128 tile = (__int128)((nq + 63) / 64) * span * pct;
   return gather >= tile ? 1 : 0;
+}
+
+extern "C" int tavb_plan_scoped(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t gather_rows, int64_t span, int64_t min_bytes, int64_t pct) {
+  if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");
+  if (nq < 0 || gather_rows < 0 || span < 0 || min_bytes < 0 || pct < 0) return fail(TAVB_E_INVALID, "bad shape");
+  const bool f32 = dtype == TAVB_F32;
+  if (dim <= 0 || !tavb::skinny_supported(dim, k, f32)) return 0;
+  if (nq < (f32 ? kSkinnyMinBatchF32 : kSkinnyMinBatchF16)) return 0;  // (the unmasked tile's own lower bounds, as they ship)
+  // gather_rows: over the row-list route's passes of eight queries, the sum of each pass' LARGEST scope -- a lower bound of the rows that
+  // route reads (a pass reads the union of its scopes), so the rule errs towards the route that is there already.  The floor is per pass:
+  // a pass below it is a launch-bound scan the tile's ladder does not beat.  The tile reads the span once per 64 queries.
+  const __int128 passes = (nq + 7) / 8;
+  if ((__int128)gather_rows * dim * (f32 ? 4 : 2) < passes * min_bytes) return 0;
+  return (__int128)gather_rows * 100 >= (__int128)((nq + 63) / 64) * span * pct ? 1 : 0;
 }
 
 extern "C" int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate) {

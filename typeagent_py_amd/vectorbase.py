@@ -1151,6 +1151,28 @@ class VectorBase:
         return (isinstance(eng, _native.Engine) and hasattr(eng, call) and 1 <= max_hits <= _PAGE
                 and all(handles[i].dev_bits is not None for i in order))
 
+    @staticmethod
+    def _scoped_tile(eng, call: str, handles, order, max_hits: int):
+        """Whether a scoped batch the native route serves takes the 32/64-query tile (`call`: Engine.search_scoped_tile /
+        search_messages_scoped_tile): max_hits <= 64, every searched handle knows its span, and the option "scope_tile" (0 = never, 2 =
+        wherever the tile serves the shape, 1 = where tavb_plan_scoped expects it to win: dense scopes under a real batch) says so.
+        Returns the span (first, last) of the union of the searched scopes, or None: the row-list route.  Decided once per call from the
+        handles' counts and spans -- no device work, nothing kept."""
+        if max_hits > 64 or not (hasattr(eng, call) and hasattr(eng, "plan_scoped")) or any(handles[i].span is None for i in order):
+            return None
+        opts = eng.scope_tile_options() if hasattr(eng, "scope_tile_options") else tuple(
+            eng.get_option(n) for n in ("scope_tile", "mask_tile_min_bytes", "mask_tile_pct"))
+        mode, min_bytes, pct = opts
+        if mode == 0:
+            return None
+        first, last = min(handles[i].span[0] for i in order), max(handles[i].span[1] for i in order)
+        if mode == 2:  # (64 queries, one row in a span of one, no floors: yes exactly when the tile serves the corpus, max_hits and the width)
+            yes = eng.plan_scoped(64, max_hits, eng.dim, eng.dtype, 1, 1, 0, 0)
+        else:
+            gather = _native.scoped_gather_rows([handles[i].count for i in order])
+            yes = eng.plan_scoped(len(order), max_hits, eng.dim, eng.dtype, gather, last + 1 - first // 256 * 256, min_bytes, pct)
+        return (first, last) if yes else None
+
     def fuzzy_lookup_embeddings_scoped(
         self,
         embeddings: NormalizedEmbeddings,
@@ -1177,9 +1199,17 @@ class VectorBase:
         device workspace whatever the batch.  A query whose scope is empty gets an empty answer
         and takes no slot.  `engine.get_option("masked_route")` is then 4.
 
+        DENSE scopes under a real batch (1 <= max_hits <= 64, rows of a multiple of 64 bytes; engine option "scope_tile": by default where
+        tavb_plan_scoped says so -- the row-list route would read at least 128 MiB per pass and at least as many rows as the tile) run on
+        the 32/64-query matrix-core tile instead (tavb_search_scoped_tile): the span of the union of the scopes is read once per 64
+        queries and each query's scope is tested in the tile's admission path.  The answers are then the TILE's -- those of
+        `fuzzy_lookup_embeddings_masked` on its tile route: equal to the per-query calls except among float32 near-ties, scores within a
+        few 1e-7, not bit for bit.  `engine.get_option("masked_route")` is then 5.
+
         Everything else loops over `fuzzy_lookup_embedding_masked`: max_hits == 0 and max_hits > 256, device groups, `ShardedVectorBase`,
-        test doubles, and a handle without a device mask.  The matrix-core tiles are not used for per-query scopes, and queries are not
-        reordered by how much their scopes overlap -- only identical handles are grouped."""
+        test doubles, and a handle without a device mask.  The tile route serves single-GPU engines only: device groups,
+        `ShardedVectorBase` and `FusedIndexQuery` do not take it, nor does max_hits > 64 (no 128/256-query tile form for per-query scopes),
+        and queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
         if as_arrays and not (1 <= max_hits <= _PAGE):
             raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
@@ -1193,7 +1223,13 @@ class VectorBase:
         eng = self._sync_device()
         if self._scoped_native(eng, "search_scoped_batch", handles, order, max_hits):
             t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
-            o, s, c = eng.search_scoped_batch(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits, np.ascontiguousarray(t[order]))
+            span = self._scoped_tile(eng, "search_scoped_tile", handles, order, max_hits)
+            if span is not None:
+                o, s, c = eng.search_scoped_tile(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                 np.ascontiguousarray(t[order]), span=span)
+            else:
+                o, s, c = eng.search_scoped_batch(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                  np.ascontiguousarray(t[order]))
             ords, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
             ords[order], scs[order], cnts[order] = o - eng.ordinal_base, s, c
             return (ords, scs, cnts) if as_arrays else _scored_lists(ords, scs, cnts, max_hits)
@@ -1361,7 +1397,8 @@ class VectorBase:
         per query.  When every scope is the same handle this IS `lookup_messages_by_embeddings_masked`.  Otherwise a single-GPU engine with
         1 <= max_matches <= 256 whose scopes hold their packed mask on the device makes ONE submission (tavb_search_messages_scoped: the
         scoped batch, its key lists left on the device, one launch of the message aggregation, one copy back), bit for bit the per-query
-        calls on the row list; everything else (max_matches outside 1..256, device groups, test doubles, a handle without a device mask)
+        calls on the row list -- or, where `fuzzy_lookup_embeddings_scoped` would take the 32/64-query tile (option "scope_tile"),
+        tavb_search_messages_scoped_tile with the tile's contract: the same messages except among float32 near-ties; everything else (max_matches outside 1..256, device groups, test doubles, a handle without a device mask)
         loops over `lookup_messages_by_embedding_masked`."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_matches, threshold_score)
         self._check_row_messages()
@@ -1375,8 +1412,13 @@ class VectorBase:
         eng = self._messages_engine()
         if eng is not None and self._scoped_native(eng, "search_messages_scoped", handles, order, max_hits):
             t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
-            m, s, c = eng.search_messages_scoped(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
-                                                 np.ascontiguousarray(t[order]), max_hits)
+            span = self._scoped_tile(eng, "search_messages_scoped_tile", handles, order, max_hits)
+            if span is not None:
+                m, s, c = eng.search_messages_scoped_tile(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                          np.ascontiguousarray(t[order]), max_hits, span=span)
+            else:
+                m, s, c = eng.search_messages_scoped(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                     np.ascontiguousarray(t[order]), max_hits)
             msgs, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
             msgs[order], scs[order], cnts[order] = m, s, c
             return _scored_lists(msgs, scs, cnts, max_hits)
