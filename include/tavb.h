@@ -198,7 +198,13 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "masked_route"  (read only) 0 before the first masked lookup, 1 = the last one took the gather route (tavb_search_subset_batch_resident / _device), 2 = the
  *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide), 4 = a scoped batch (one mask per
  *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped), 5 = a scoped batch on the 32/64-query tile
- *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile)
+ *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile), 6 = a scoped batch on the 128/256-query filter tile +
+ *                   rescoring (tavb_search_scoped_wide / _device, tavb_search_messages_scoped_wide)
+ *   "scope_wide"    scoped batches on fp16 corpora (the binding reads it; the rule is tavb_plan_scoped_wide, with "mask_tile_min_bytes" /
+ *                   "mask_tile_pct"): 1 (default) = the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide) where
+ *                   tavb_plan_scoped_wide says so -- it then wins over "scope_tile"; 0 = never; 2 = wherever that route serves the shape
+ *   "scope_wave_bytes"  most bytes of membership planes one wave of tavb_search_scoped_wide builds (default 64 MiB, >= 1; one query tile's
+ *                   planes are built whatever this says: tests set it to 1 to split a small batch into waves)
  *   "scope_tile"    scoped batches, one mask per query (the binding reads it; the rule is tavb_plan_scoped, with "mask_tile_min_bytes" /
  *                   "mask_tile_pct"): 1 (default) = the 32/64-query tile (tavb_search_scoped_tile) where tavb_plan_scoped says so, else the
  *                   row-list route (tavb_search_scoped_batch); 0 = never; 2 = wherever the tile serves the shape (tests, measurements)
@@ -610,6 +616,26 @@ int tavb_search_messages_scoped_tile(tavb_ctx* ctx, const float* queries_host, i
 int tavb_scope_planes(tavb_ctx* ctx, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, int64_t first_row, int64_t last_row,
                       uint32_t* dev_planes_out);
 
+/* ---- scoped batches on the 128/256-query filter tile: exact, 1 <= k <= 256 ---------------------------------------------------------------
+ * The per-query-scope twin of tavb_search_masked_wide, for fp16 corpora of any width (one that is no multiple of 64 filters on the zero-padded
+ * copy of the rows) and 1 <= k <= TAVB_MAX_FUSED_K, else TAVB_E_UNSUPPORTED (the message names the row-list route).  The arguments, the span
+ * rule and the argument errors of tavb_search_scoped_tile.  In WAVES of query tiles: the membership planes of the wave (as
+ * tavb_scope_planes writes them, 8 blocks per 256-query tile, 4 per 128-query tile), the filter ladder of the 128/256-query tile over rows
+ * [first_row / 256 * 256, last_row] with the per-query test in the tile's admission path, the band selection and the rescoring with the
+ * streaming kernels' arithmetic.  A query with more near-duplicates around its k-th best than "band_max" keys is flagged; the flagged
+ * queries are read back -- one synchronise per wave -- and re-run on the row-list scoped route with their own masks ("last_flagged" counts
+ * them).  CONTRACT: tavb_search_scoped_batch's answers BIT FOR BIT -- ordinals, float32 scores, counts.  A wave is as many whole 256-query
+ * tiles as fit "scope_wave_bytes" (64 MiB) of planes, at least one tile; the planes' workspace is at most max(64 MiB, 32 bytes x span rows)
+ * whatever the batch.  "masked_route" reports 6, "last_tier" 4, "last_mfma_shape" the filter's MFMA.  Timed under TAVB_KERNEL_CONVERT
+ * (planes), TAVB_KERNEL_MFMA / TAVB_KERNEL_MFMA_SAMPLE, TAVB_KERNEL_MERGE and TAVB_KERNEL_RESCORE. */
+int tavb_search_scoped_wide(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                            int64_t last_row, int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_scoped_wide_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                   int64_t last_row, int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
+int tavb_search_messages_scoped_wide(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                     int64_t last_row, int32_t k, const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores,
+                                     int32_t* out_counts);
+
 /* ---- removing rows: compaction of the corpus on the device ---------------------------------------------------------------------------
  * The removal the reference leaves as a TODO (storage/sqlite/reltermsindex.py:181-192 `remove_term`; knowpro/fuzzyindex.py:113-127, the
  * commented `remove_at` around np.delete): dev_remove_bits is a mask in the bit form above in which a SET bit means "remove"; rows must equal
@@ -777,6 +803,14 @@ int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t 
  * nq at least the unmasked tile's lower bound), gather_rows x row bytes >= ceil(nq / 8) x min_bytes, and gather_rows x 100 >= ceil(nq / 64)
  * x span x pct.  0 otherwise; negative: an argument out of range.  Needs no GPU. */
 int tavb_plan_scoped(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t gather_rows, int64_t span, int64_t min_bytes, int64_t pct);
+
+/* Whether a scoped batch takes the 128/256-query filter tile + rescoring (tavb_search_scoped_wide) under option "scope_wide" = 1; where this
+ * and tavb_plan_scoped both say yes the wide route wins.  The arguments of tavb_plan_scoped, except that gather_rows counts passes of FOUR
+ * queries for k > 64 (the row-list route's passes there), eight otherwise.  1 when the corpus is fp16 and the route serves the shape (dim <=
+ * 16384, 1 <= k <= TAVB_MAX_FUSED_K), nq is at least the shipped default of "mfma_min_batch" (65), gather_rows x row bytes >= passes x
+ * min_bytes, and gather_rows x 100 >= ceil(nq / qt) x span x pct, qt = the query tile the filter picks for nq queries over `span` rows on 256
+ * compute units.  0 otherwise; negative: an argument out of range.  Needs no GPU. */
+int tavb_plan_scoped_wide(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t gather_rows, int64_t span, int64_t min_bytes, int64_t pct);
 
 /* Whether a masked batch takes the 128/256-query filter tile + rescoring (tavb_search_masked_wide) under option "mask_wide" = 1; the arguments
  * of tavb_plan_masked.  1 when the corpus is fp16 and the route serves the shape (dim <= 16384, 1 <= k <= TAVB_MAX_FUSED_K), nq is at least the

@@ -110,6 +110,10 @@ _SIGNATURES = [
     ("tavb_search_messages_scoped_tile", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_scope_planes", c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p]),
+    ("tavb_search_scoped_wide", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_scoped_wide_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_messages_scoped_wide", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -132,6 +136,7 @@ _SIGNATURES = [
     ("tavb_plan_masked", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
     ("tavb_plan_masked_wide", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
     ("tavb_plan_scoped", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
+    ("tavb_plan_scoped_wide", c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64]),
 ]
 
 ABI_SYMBOLS = [name for name, _, _ in _SIGNATURES]
@@ -260,6 +265,16 @@ def plan_scoped(nq: int, k: int, dim: int, dtype: int, gather_rows: int, span: i
     scope (`scoped_gather_rows`); span: the rows of the span of the scopes' union.  Needs no GPU."""
     lib = load_library(preload_torch=False)
     r = lib.tavb_plan_scoped(int(nq), int(k), int(dim), int(dtype), int(gather_rows), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
+
+
+def plan_scoped_wide(nq: int, k: int, dim: int, dtype: int, gather_rows: int, span: int, min_bytes: int = MASK_TILE_MIN_BYTES, pct: int = MASK_TILE_PCT) -> bool:
+    """True: a scoped batch of `nq` queries takes the 128/256-query filter tile + rescoring under option "scope_wide" = 1
+    (tavb_plan_scoped_wide); it then wins over `plan_scoped`.  gather_rows: `scoped_gather_rows` with passes of four queries for k > 64,
+    eight otherwise; span: the rows of the span of the scopes' union.  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_scoped_wide(int(nq), int(k), int(dim), int(dtype), int(gather_rows), int(span), int(min_bytes), int(pct))
     _check(lib, r if r < 0 else 0)
     return bool(r)
 
@@ -448,6 +463,7 @@ class Engine:
         self.__dict__.pop("_mask_tile_opts", None)
         self.__dict__.pop("_mask_wide_opts", None)
         self.__dict__.pop("_scope_tile_opts", None)
+        self.__dict__.pop("_scope_wide_opts", None)
 
     def mask_tile_options(self) -> tuple[int, int, int]:
         """("mask_tile", "mask_tile_min_bytes", "mask_tile_pct") as the library holds them, read once and again after any `set_option`: a
@@ -469,6 +485,13 @@ class Engine:
         opts = self.__dict__.get("_scope_tile_opts")
         if opts is None:
             opts = self._scope_tile_opts = tuple(self.get_option(n) for n in ("scope_tile", "mask_tile_min_bytes", "mask_tile_pct"))
+        return opts
+
+    def scope_wide_options(self) -> tuple[int, int, int]:
+        """("scope_wide", "mask_tile_min_bytes", "mask_tile_pct"), cached like `mask_tile_options`."""
+        opts = self.__dict__.get("_scope_wide_opts")
+        if opts is None:
+            opts = self._scope_wide_opts = tuple(self.get_option(n) for n in ("scope_wide", "mask_tile_min_bytes", "mask_tile_pct"))
         return opts
 
     def get_option(self, name: str) -> int:
@@ -1202,6 +1225,45 @@ class Engine:
         first, last = self._scope_span(span)
         with self._lock:
             rc = self.lib.tavb_search_messages_scoped_tile(self._h, _addr(a), nq, ptrs, int(self.rows), first, last, k, _addr(t), int(max_messages),
+                                                           _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    # scoped batches on the 128/256-query filter tile + rescoring ---------------------------
+    plan_scoped_wide = staticmethod(plan_scoped_wide)
+
+    def search_scoped_wide(self, queries, dev_bits_list, k: int, thrs, span=None):
+        """A scoped batch on the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide): the arguments of
+        `search_scoped_tile`; fp16 corpora, 1 <= k <= 256 -> (ordinals [nq, k], scores [nq, k], counts [nq]), `search_scoped_batch`'s
+        answer bit for bit.  Raises TavbError (TAVB_E_UNSUPPORTED) for a shape the route does not serve."""
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_wide(self._h, _addr(a), nq, ptrs, int(self.rows), first, last, k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_scoped_wide_device(self, dev_queries, dev_bits_list, k: int, thrs, span=None, out_keys=None):
+        """`search_scoped_wide` with the queries on the device (tavb_search_scoped_wide_device) -> torch int64 [nq, k] sorted, zero-padded
+        keys carrying ordinal_base + row; `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_wide_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), first, last, k, _addr(t),
+                                                         c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def search_messages_scoped_wide(self, queries, dev_bits_list, k: int, thrs, max_messages: int, span=None):
+        """`search_scoped_wide` aggregated to messages in one submission (tavb_search_messages_scoped_wide) -> (message ordinals [nq, k],
+        scores [nq, k], counts [nq])."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        first, last = self._scope_span(span)
+        with self._lock:
+            rc = self.lib.tavb_search_messages_scoped_wide(self._h, _addr(a), nq, ptrs, int(self.rows), first, last, k, _addr(t), int(max_messages),
                                                            _addr(msgs), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
         return msgs, scs, cnts

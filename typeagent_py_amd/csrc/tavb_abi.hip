@@ -255,6 +255,8 @@ const Option kOptions[] = {
     READ_ONLY("masked_route", masked_route),
     RANGE("mask_wide", mask_wide, 0, 2),
     RANGE("scope_tile", scope_tile, 0, 2),
+    RANGE("scope_wide", scope_wide, 0, 2),
+    RANGE("scope_wave_bytes", scope_wave_bytes, 1, (int64_t)1 << 40),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
     READ_ONLY("norm_rows", norm_rows),
     READ_ONLY("last_direct", last_direct),

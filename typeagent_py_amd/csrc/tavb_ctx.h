@@ -179,10 +179,12 @@ struct tavb_ctx {
   // byte per list position (tavb_mask.hip scope_member_kernel); pinned: every pass' total, then its chunks' MaskChunkInfo
   Buffer d_scope_bits, d_scope_rows, d_scope_member;
   Buffer h_scope{nullptr, 0, true};
-  // scoped batches on the 32/64-query tile (tavb_search_scoped_tile): the membership planes of one wave of query tiles -- per block of 32
+  // scoped batches on the 32/64-query tile (tavb_search_scoped_tile) and on the 128/256-query filter tile (tavb_search_scoped_wide): the membership planes of one wave of query tiles -- per block of 32
   // queries one uint32 per row of the span (tavb_mask.hip scope_planes_kernel)
   Buffer d_scope_planes;
   int64_t scope_tile = 1;  // option: scoped batches on the 32/64-query tile: 1 = follow tavb_plan_scoped (with "mask_tile_min_bytes" / "mask_tile_pct"), 0 = never, 2 = always where supported
+  int64_t scope_wide = 1;  // option: scoped batches on the 128/256-query filter tile (tavb_search_scoped_wide): 1 = follow tavb_plan_scoped_wide (same thresholds), 0 = never, 2 = always where supported
+  int64_t scope_wave_bytes = (int64_t)64 << 20;  // option: most bytes of membership planes one wave of tavb_search_scoped_wide builds (at least one query tile's are built whatever this says)
   Buffer h_sort_info{nullptr, 0, true};  // pinned: meta [nq][4] + per-block key counts [nq][blocks] of one group
   int64_t sort_all = 1;                   // option: 1 = the binding routes max_hits == 0 and max_hits > TAVB_MAX_LARGE_K through tavb_search_sorted
   int64_t sort_stage_keys = (int64_t)1 << 21;  // option: most results decoded into pinned memory before they are copied to the caller (12 B each)
@@ -206,7 +208,7 @@ struct tavb_ctx {
   int64_t mask_tile = 1;                            // option: 1 = follow tavb_plan_masked, 0 = never the tile, 2 = always where supported
   int64_t mask_tile_min_bytes = (int64_t)128 << 20;  // option: allowed rows x row bytes below which the gather route (one launch there) is kept; the default of small_direct_bytes
   int64_t mask_tile_pct = 100;                      // option: the tile when the gather route's bytes are at least this many % of the tile's (100 = byte parity)
-  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile
+  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile, 6 = a scoped batch on the 128/256-query filter tile + rescoring
   int64_t mask_wide = 1;                            // option: masked batches on the 128/256-query filter tile (tavb_search_masked_wide): 1 = follow tavb_plan_masked_wide, 0 = never, 2 = always where supported
   int64_t last_skinny_kernel = 0;  // option "last_skinny_kernel" (get): what the last launch of the 32/64-query tile instantiated, tavb::skinny_kernel_id (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
@@ -402,6 +404,13 @@ int search_scoped_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
 int64_t scope_plane_stride(int64_t first_row, int64_t last_row);
 int scope_plane_blocks(int n);
 int build_scope_planes(tavb_ctx* c, const uint32_t* const* masks, int n, int n_blocks, int64_t first_row, int64_t last_row, uint32_t* planes);
+// A scoped batch on the 128/256-query filter tile + exact rescoring (fp16 corpora; masked_wide_supported): the same masks and span.  Per wave
+// of query tiles the membership planes (c->d_scope_planes, at most "scope_wave_bytes" of them, at least one 256-query tile's), the filter
+// ladder over the span with the per-query test in its admission path, the band selection and the rescoring; flagged queries are read back
+// (one synchronise per wave) and re-run through search_scoped_impl with their own masks.  Scores are the streaming kernels' float32 scores:
+// search_scoped_impl's answers bit for bit.  keys carry index_base + row -> d_out [nq, k].
+int search_scoped_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks, int64_t first_row,
+                       int64_t last_row, uint32_t index_base, u64_t* d_out);
 
 // ---- tavb_lookup.hip
 // Staging: [nq, dim] queries of the caller -> pinned h_stage (stage_queries_host; *d_q = where submit_queries then copies them) -- stage_queries

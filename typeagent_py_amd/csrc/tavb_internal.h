@@ -306,7 +306,7 @@ struct MfmaParams {
   // optional (the skinny kernel; the shipping filter variants of the 128/256-query kernel): allow-mask (tavb.h "row masks"), the word that holds the bit of row 0 of `corpus` -- the launch's first row must
   // be a multiple of 32 in the mask's numbering, so that bit 0 of that word IS row 0.  Rows whose bit is clear are never candidates.
   const uint32_t* mask;
-  // optional (the skinny kernel only, never together with `mask`): one scope PER QUERY as membership planes (launch_scope_planes) -- the word
+  // optional (the skinny kernel; the shipping filter variants of the 128/256-query kernel; never together with `mask`): one scope PER QUERY as membership planes (launch_scope_planes) -- the word
   // of row 0 of `corpus` in the plane of query block 0 (64-byte aligned, a multiple of 32 rows into the planes), scope_stride words (a multiple
   // of 32, at least `rows` rounded up to 32) from one block's plane to the next; nq_padded / 32 planes.  A row is a candidate of query q only
   // where bit q & 31 of its word in plane q >> 5 is set.

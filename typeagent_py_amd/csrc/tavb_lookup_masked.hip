@@ -882,6 +882,84 @@ int tavb_scope_planes(tavb_ctx* c, const uint32_t* const* dev_masks, int32_t n_m
   return build_scope_planes(c, dev_masks, n_masks, scope_plane_blocks(n_masks), first_row, last_row, dev_planes_out);
 }
 
+// ---- scoped batches on the 128/256-query filter tile + rescoring (tavb_route.hip::search_scoped_wide)
+// check_scoped_tile_args with the wide route's shapes
+static int check_scoped_wide_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row, int64_t last_row, int32_t k,
+                                  bool* empty) {
+  if (int rc = check_masked_head(c, nq, rows, k)) return rc;
+  if (rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  *empty = rows == 0 || nq == 0 || first_row > last_row;
+  if (int rc = check_masked_span(*empty, rows, first_row, last_row)) return rc;
+  if (!*empty) {
+    if (!dev_masks) return fail(TAVB_E_INVALID, "null dev_masks");
+    for (int q = 0; q < nq; ++q) {
+      if (!dev_masks[q]) return fail(TAVB_E_INVALID, "the mask of query %d is null", q);
+      if ((reinterpret_cast<uintptr_t>(dev_masks[q]) & 3) != 0) return fail(TAVB_E_INVALID, "the mask of query %d must be 4-byte aligned", q);
+    }
+  }
+  if (!masked_wide_supported(c, k))
+    return fail(TAVB_E_UNSUPPORTED, "the scoped wide route serves fp16 corpora of up to 16384 halves per row and 1 <= k <= %d (k = %d): use the row-list route",
+                TAVB_MAX_FUSED_K, k);
+  return TAVB_OK;
+}
+
+int tavb_search_scoped_wide(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row, int64_t last_row,
+                            int32_t k, const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_scoped_wide_args(c, nq, dev_masks, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  u64_t* target;
+  if (int rc = reserve_key_target(c, (size_t)nq * k, &target)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  c->last_graph = 0;
+  if (int rc = search_scoped_wide(c, d_q, nq, k, min_scores, dev_masks, first_row, last_row, 0u, target)) return rc;
+  return collect_keys(c, target, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts);
+}
+
+int tavb_search_scoped_wide_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                   int64_t last_row, int32_t k, const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_scoped_wide_args(c, nq, dev_masks, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  if (empty) return fill_empty_keys(c, reinterpret_cast<u64_t*>(out_keys), (int64_t)nq * k);  // no tile launch
+  c->last_graph = 0;
+  return search_scoped_wide(c, dev_queries, nq, k, min_scores, dev_masks, first_row, last_row, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(out_keys));
+}
+
+int tavb_search_messages_scoped_wide(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t first_row,
+                                     int64_t last_row, int32_t k, const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores,
+                                     int32_t* out_counts) {
+  if (int rc = check_message_args(c, k, max_messages)) return rc;
+  bool empty = false;
+  if (int rc = check_scoped_wide_args(c, nq, dev_masks, rows, first_row, last_row, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  DeviceGuard guard(c->device);
+  u64_t* d_hits;
+  if (int rc = reserve_message_batch(c, nq, k, &d_hits)) return rc;
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  c->last_graph = 0;
+  const uint32_t base = (uint32_t)c->ordinal_base;
+  if (int rc = search_scoped_wide(c, d_q, nq, k, min_scores, dev_masks, first_row, last_row, base, d_hits)) return rc;
+  return rerank_batch_and_return(c, d_hits, nq, k, base, nullptr, max_messages, out_messages, out_scores, out_counts);
+}
+
 int tavb_mask_membership(tavb_ctx* c, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, const int32_t* dev_rows, int64_t n, uint8_t* dev_member_out) {
   if (int rc = check_ctx(c)) return rc;
   if (n_masks < 1 || n_masks > TAVB_MAX_MASK_OPERANDS) return fail(TAVB_E_INVALID, "a membership test has 1 .. %d masks (got %d)", TAVB_MAX_MASK_OPERANDS, n_masks);

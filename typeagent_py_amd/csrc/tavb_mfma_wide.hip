@@ -178,11 +178,31 @@ __device__ __forceinline__ void mfma_f16(Acc& acc, const f16x8& a, const f16x8& 
 // mask's numbering (the launcher and run_tile_ladder check); every row0 is then a multiple of 32 too (row ranges are whole 320-row tiles).  The
 // bit test sits in the admission SLOW path only, behind the ballot: the words are wave-uniform and come in through the scalar data path
 // (constant address space: lgkmcnt, never vmcnt -- the staging queue is not drained), the K loop and the `top > thr_pre` test are untouched.
+// SCOPED (the filter pass of a scoped batch, tavb_route.hip::search_scoped_wide): one scope PER QUERY.  A third __global__ template around the
+// same text, `mfma_scan_scoped_kernel`, whose one extra argument is the membership PLANES of the batch (scope_planes_kernel, tavb_mask.hip): for
+// every block of 32 queries of the tile-padded batch one uint32 per row of the span, bit i = the scope of query 32 * block + i holds the row;
+// `stride` words from one block's plane to the next; `words` names the word of the launch's first row in plane 0 (a multiple of 32 rows into
+// the span, 64-byte aligned).  Like the one mask's word, the plane words are read only in the admission slow path, behind the ballot, through
+// the scalar data path (lgkmcnt); nothing is stored that the other forms do not store.
+//   * 32 x 32 form: a lane is (half << 5) | query of the 32-query block ni and tests row r_off + 4 * half of the 32-row block mi; the lanes row
+//     pair (r_off, r_off + 4) may admit are plane[r_off] | plane[r_off + 4] << 32 of plane block (qtile * BN + wn * WQ) / 32 + ni -- one
+//     scalar AND into the compare's wave mask.  The block's 32 words come in as two 16-word loads; all zero: the block is skipped.
+//   * 16 x 16 form: lane l holds query l & 15 of query fragment n and rows 16 m + j + 4 (l >> 4) of its 80-row group; fragment n is half n & 1
+//     of plane block (qtile * BN + wn * WQ) / 32 + n / 2.  The lanes row quadruple (m, j) may admit are the 16-bit halves
+//     (plane[16 m + j + 4 g] >> 16 (n & 1)) & 0xffff at bits 16 g, g = 0 .. 3: one 16-word scalar load per m that has a candidate at all (64-byte
+//     aligned: a group starts at a multiple of 16 rows), the four masks assembled in scalar registers.
+struct ScopePlanes {
+  const uint32_t* words;
+  int64_t stride;
+};
 typedef const __attribute__((address_space(4))) uint32_t const_u32;
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef const __attribute__((address_space(4))) u32x16 const_u32x16;
 template <int ABL, int NI, int N3, int N0, int N1, bool SPLIT = false, bool BD = false, bool M16 = false>
 __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p) {
-  constexpr bool MASKED = false;
+  constexpr bool MASKED = false, SCOPED = false;
   [[maybe_unused]] const uint32_t* const mask = nullptr;
+  [[maybe_unused]] constexpr ScopePlanes planes{nullptr, 0};
 #include "tavb_mfma_wide_body.inc"
 }
 
@@ -190,7 +210,17 @@ __global__ void __launch_bounds__(NT6) mfma_scan_kernel(const MfmaDeviceParams p
 template <int NI, int N3, int N0, int N1, bool BD = false, bool M16 = false>
 __global__ void __launch_bounds__(NT6) mfma_scan_masked_kernel(const MfmaDeviceParams p, const uint32_t* mask) {
   constexpr int ABL = 0;
-  constexpr bool SPLIT = false, MASKED = true;
+  constexpr bool SPLIT = false, MASKED = true, SCOPED = false;
+  [[maybe_unused]] constexpr ScopePlanes planes{nullptr, 0};
+#include "tavb_mfma_wide_body.inc"
+}
+
+// the SCOPED form of the same four variants: the per-query test compiled in instead
+template <int NI, int N3, int N0, int N1, bool BD = false, bool M16 = false>
+__global__ void __launch_bounds__(NT6) mfma_scan_scoped_kernel(const MfmaDeviceParams p, const ScopePlanes planes) {
+  constexpr int ABL = 0;
+  constexpr bool SPLIT = false, MASKED = false, SCOPED = true;
+  [[maybe_unused]] const uint32_t* const mask = nullptr;
 #include "tavb_mfma_wide_body.inc"
 }
 
@@ -251,8 +281,14 @@ hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream) {
   if (!p.workspace || !p.counts) return hipErrorInvalidValue;
   // a masked launch: the shipping filter variants only (no work list, no exact SPLIT form, no measurement variant), a word-aligned pointer
   if (p.mask && (p.active || p.split_plane > 0 || p.ablate != 0 || p.sched != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 3) != 0)) return hipErrorInvalidValue;
+  // a scoped launch: the same restrictions, never together with one mask; 64-byte aligned plane words (the 16-word scalar loads), whole
+  // 32-row blocks per plane, a plane for every block of 32 queries of the padded batch
+  if (p.scope_planes && (p.mask || p.active || p.split_plane > 0 || p.ablate != 0 || p.sched != 0 || (reinterpret_cast<uintptr_t>(p.scope_planes) & 63) != 0 ||
+                         p.scope_stride % 32 != 0 || p.scope_stride < ((p.rows + 31) & ~(int64_t)31)))
+    return hipErrorInvalidValue;
+  const ScopePlanes planes{p.scope_planes, p.scope_stride};
   MfmaDeviceParams d = fill_device_params(p, tile, BM6);
-  if (p.mask && d.rows_per_split % 32 != 0) return hipErrorInvalidValue;  // (a whole number of 320-row tiles: every row0 is a multiple of 32)
+  if ((p.mask || p.scope_planes) && d.rows_per_split % 32 != 0) return hipErrorInvalidValue;  // (a whole number of 320-row tiles: every row0 is a multiple of 32)
   d.counts = p.counts;
   d.band = p.band;
   d.lost = p.lost;
@@ -281,6 +317,12 @@ hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream) {
       if (mfma_tile_shape(p) == 16) return go(mfma_scan_masked_kernel<4, 8, 6, 4, false, true>, NT6, LDS256, p.mask);
       if (p.bdirect) return go(mfma_scan_masked_kernel<4, 4, 3, 3, true>, NT6, 3 * SLOT_A6 + BN * 8 + 16, p.mask);
       return go(mfma_scan_masked_kernel<4, 8, 6, 4>, NT6, LDS256, p.mask);
+    }
+    if (p.scope_planes) {  // ... and in their SCOPED form: the membership planes are their second argument
+      if (tile == 128) return go(mfma_scan_scoped_kernel<2, 6, 4, 4>, NT6, LDS128, planes);
+      if (mfma_tile_shape(p) == 16) return go(mfma_scan_scoped_kernel<4, 8, 6, 4, false, true>, NT6, LDS256, planes);
+      if (p.bdirect) return go(mfma_scan_scoped_kernel<4, 4, 3, 3, true>, NT6, 3 * SLOT_A6 + BN * 8 + 16, planes);
+      return go(mfma_scan_scoped_kernel<4, 8, 6, 4>, NT6, LDS256, planes);
     }
     if (tile == 128) {
       switch (p.ablate) {  // (measurement: what bounds the 128-query width, profiles/r05_mid_batch.md)

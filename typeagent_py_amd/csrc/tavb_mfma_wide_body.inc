@@ -1,7 +1,9 @@
-// The body of the 128/256-query tile kernel (tavb_mfma_wide.hip: read its header first), included once into each of its two __global__ templates:
-// `mfma_scan_kernel` (MASKED = false, mask = nullptr) and `mfma_scan_masked_kernel` (MASKED = true, ABL = 0, SPLIT = false).  In scope where it is
-// included: ABL, NI, N3, N0, N1, SPLIT, BD, M16, MASKED, the parameter block `p` and `mask`.  Not a header: no include guard, nothing else includes it.
-  static_assert(!MASKED || (ABL == 0 && !SPLIT), "masked forms exist for the shipping filter variants only");
+// The body of the 128/256-query tile kernel (tavb_mfma_wide.hip: read its header first), included once into each of its three __global__ templates:
+// `mfma_scan_kernel` (MASKED = SCOPED = false, mask = nullptr), `mfma_scan_masked_kernel` (MASKED = true, ABL = 0, SPLIT = false) and
+// `mfma_scan_scoped_kernel` (SCOPED = true, ABL = 0, SPLIT = false).  In scope where it is included: ABL, NI, N3, N0, N1, SPLIT, BD, M16, MASKED,
+// SCOPED, the parameter block `p`, `mask` and `planes`.  Not a header: no include guard, nothing else includes it.
+  static_assert(!(MASKED || SCOPED) || (ABL == 0 && !SPLIT), "masked and scoped forms exist for the shipping filter variants only");
+  static_assert(!(MASKED && SCOPED), "one mask or one scope per query, not both");
   static_assert(BM6 % 32 == 0 && 160 % 32 == 0 && 80 % 16 == 0, "a 32-row block is one mask word, an 80-row group starts at bit 0 or 16 of one");
   using G = WideGeom<NI>;
   constexpr int BN = G::QT, NT = G::NT, SLOT_B6 = G::SLOT_B, PIECES_B6 = G::PIECES_B, B_RING6 = G::B_RING;
@@ -476,6 +478,23 @@
                   asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(mk[j]) : "v"(sc[j]), "v"(thr));
                 }
                 if ((mk[0] | mk[1] | mk[2] | mk[3]) == 0ull) continue;  // wave-uniform
+                if constexpr (SCOPED) {
+                  // the 16 plane words of rows 16 m .. 16 m + 15 of this group for the 32-query block that holds fragment n (half n & 1 of it): lane l
+                  // tests row 16 m + j + 4 (l >> 4) for query l & 15, so the lanes (m, j) may admit are four 16-bit halves, one per g = l >> 4
+                  const int64_t quad_row = row0 + wm * 160 + h * 80 + 16 * m;  // (a multiple of 16: the load is 64-byte aligned)
+                  if (quad_row >= r_end) continue;  // wave-uniform: rows behind the row range have no plane word (and rows_left cuts them either way)
+                  const char* words = sgpr_ptr(reinterpret_cast<const char*>(planes.words) +
+                                               ((size_t)((qtile * BN + wn * G::WQ) / 32 + n / 2) * (size_t)planes.stride + (size_t)quad_row) * sizeof(uint32_t));
+                  const u32x16 pw = *(const const_u32x16*)(uintptr_t)words;  // s_load_dwordx16: lgkmcnt, not vmcnt
+                  const int sh = 16 * (n & 1);
+#pragma unroll
+                  for (int j = 0; j < 4; ++j) {
+                    const uint32_t lo = ((pw[j] >> sh) & 0xffffu) | (((pw[j + 4] >> sh) & 0xffffu) << 16);
+                    const uint32_t hi = ((pw[j + 8] >> sh) & 0xffffu) | (((pw[j + 12] >> sh) & 0xffffu) << 16);
+                    mk[j] &= ((u64)hi << 32) | lo;
+                  }
+                  if ((mk[0] | mk[1] | mk[2] | mk[3]) == 0ull) continue;  // no scope of these 16 queries holds a row that beats its threshold
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                   const int r_off = 16 * m + j;
@@ -515,6 +534,19 @@
           if constexpr (NO_ADMIT) asm volatile("" ::"v"(top));
           if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
             [[maybe_unused]] uint32_t allow = ~0u;  // MASKED: the word of this 32-row block; bit r_off + 4 * (lane >> 5) is the row a lane tests
+            [[maybe_unused]] u32x16 plane[2];       // SCOPED: the plane words of this block's 32 rows for the 32 queries of `ni`
+            if constexpr (SCOPED) {
+              const int64_t block_row = row0 + wm * 160 + mi * 32;  // (a multiple of 32, as r_begin, the tile and the wave's 160 rows are)
+              if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no plane words (and admits nothing either way)
+              const char* words = sgpr_ptr(reinterpret_cast<const char*>(planes.words) +
+                                           ((size_t)((qtile * BN + wn * G::WQ) / 32 + ni) * (size_t)planes.stride + (size_t)block_row) * sizeof(uint32_t));
+              plane[0] = *(const const_u32x16*)(uintptr_t)words;  // s_load_dwordx16 x 2: lgkmcnt, not vmcnt
+              plane[1] = *(const const_u32x16*)(uintptr_t)(words + 16 * sizeof(uint32_t));
+              uint32_t any_row = 0u;
+#pragma unroll
+              for (int w = 0; w < 16; ++w) any_row |= plane[0][w] | plane[1][w];
+              if (any_row == 0u) continue;  // no scope of these 32 queries holds a row of this block
+            }
             if constexpr (MASKED) {
               const int64_t block_row = row0 + wm * 160 + mi * 32;  // (a multiple of 32, as r_begin, the tile and the wave's 160 rows are)
               if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no word (and admits nothing either way)
@@ -538,6 +570,10 @@
               for (int j = 0; j < 4; ++j) {
                 sc[j] = fmaf(dots[4 * g + j], 0.5f, 0.5f);
                 asm volatile("v_cmp_gt_f32 %0, %1, %2" : "=s"(m[j]) : "v"(sc[j]), "v"(thr));  // (the builtin ballot goes through a 0/1 VGPR and back)
+              }
+              if constexpr (SCOPED) {  // rows 8g .. 8g + 7 are words 8 (g & 1) .. of half g >> 1: lanes 0-31 test row r_off, lanes 32-63 row r_off + 4
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m[j] &= (u64)plane[g >> 1][8 * (g & 1) + j] | ((u64)plane[g >> 1][8 * (g & 1) + j + 4] << 32);
               }
               if ((m[0] | m[1] | m[2] | m[3]) == 0ull) continue;  // wave-uniform: nobody admits any of the four
 #pragma unroll

@@ -296,8 +296,8 @@ struct TileRun {
   // own bytes -- and only rows whose bit is set are candidates.  nullptr: no mask, the whole corpus.
   const uint32_t* mask;
   int64_t span_begin, span_end;
-  // the 32/64-query tile only, instead of `mask`: one scope per query as membership planes (launch_scope_planes) over the same span -- word 0
-  // of a plane = row span_begin, plane_stride words from one block of 32 queries to the next
+  // instead of `mask` (the 32/64-query tile; the filter pass of the 128/256-query tile): one scope per query as membership planes
+  // (launch_scope_planes) over the same span -- word 0 of a plane = row span_begin, plane_stride words from one block of 32 queries to the next
   const uint32_t* planes;
   int64_t plane_stride;
 };
@@ -378,7 +378,7 @@ int run_tile_ladder(tavb_ctx* c, const TileRun& r, u64_t* d_out, const int* scat
   const bool spanned = r.mask || r.planes;
   const int64_t row_first = spanned ? r.span_begin : 0;  // the rows the phases cover: the mask's span, or the corpus
   const int64_t n_rows = (spanned ? r.span_end : c->rows) - row_first;
-  if (r.planes && (wide || r.mask || r.active)) return fail(TAVB_E_INVALID, "bad scoped tile run (internal error)");
+  if (r.planes && (r.mask || r.active)) return fail(TAVB_E_INVALID, "bad scoped tile run (internal error)");
   if (spanned && ((wide && (r.active || r.split_plane > 0)) || row_first % 256 != 0 || n_rows < 1 || r.span_end > c->rows)) return fail(TAVB_E_INVALID, "bad masked tile run (internal error)");
   const int splits = c->mfma_splits > 0 ? (int)c->mfma_splits : pick_splits(n_rows);
   if (!wide)
@@ -566,6 +566,8 @@ int upload_min_scores(tavb_ctx* c, const float* min_scores, int nq, int nq_pad, 
 // `mw` (fp16 corpora, not `small`): a MASKED batch -- the filter pass runs over the mask's span with the bit test in its admission path (the corpus
 // max-norm bound stays valid for any subset of the rows), the rescoring as ever; neither exact fallback has a masked form, so there is no early
 // verdict, and the flagged queries -- read back, one round trip -- are re-run on the gather route over the mask's resident row list.
+// `sw` (the same, never with `mw`): a SCOPED batch -- one mask per query; the filter reads the batch's membership planes, built here, and the
+// flagged queries are re-run on the row-list scoped route with their own masks.
 // The flagged queries of search_wide_exact's work list (d_nflag: their count, from slot 64 on their indices; `cap` slots), read back -- the one
 // host round trip of this file -- and re-run on the streaming kernels, their lists scattered back into the callers' rows of d_out.  fq32: where
 // their fp32 queries stand side by side -- `gathered`: already (gather_flagged_f32_kernel), else copied there from d_q here.  rows / n_rows:
@@ -597,14 +599,49 @@ int rerun_flagged(tavb_ctx* c, const int* d_nflag, int cap, const float* d_q, fl
   return TAVB_OK;
 }
 
+// ... of a SCOPED batch (search_wide_exact with `sw`): re-run on the row-list scoped route with their own masks (search_scoped_impl: what
+// tavb_search_scoped_batch would have answered for them), their lists copied into the callers' rows of d_out.  *n_out: how many there were.
+int rerun_flagged_scoped(tavb_ctx* c, const int* d_nflag, int cap, const float* d_q, float* fq32, int k, const float* min_scores /*host*/,
+                         const uint32_t* const* masks /*host*/, uint32_t index_base, u64_t* d_out, int* n_out) {
+  int* h = reinterpret_cast<int*>(c->h_flag.ptr);
+  TAVB_HIP(hipMemcpyAsync(h, d_nflag, (size_t)(64 + cap) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  const int n_flagged = h[0] < cap ? h[0] : cap;
+  *n_out = n_flagged;
+  if (n_flagged == 0) return TAVB_OK;
+  std::vector<float> ms_f((size_t)n_flagged);
+  std::vector<const uint32_t*> masks_f((size_t)n_flagged);
+  std::vector<int> slot((size_t)n_flagged);  // (h is pinned memory the re-run may use again)
+  for (int i = 0; i < n_flagged; ++i) {
+    slot[i] = h[64 + i];
+    ms_f[i] = min_scores[slot[i]];
+    masks_f[i] = masks[slot[i]];
+    TAVB_HIP(hipMemcpyAsync(fq32 + (size_t)i * c->dim, d_q + (size_t)slot[i] * c->dim, (size_t)c->dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  }
+  u64_t* d_redo = reinterpret_cast<u64_t*>(c->d_fb_cand.ptr);
+  const int tier = c->last_tier;  // (the batch's route stays what "last_tier" reports: the re-run is a detail of it)
+  const int rc_redo = tavb::host::search_scoped_impl(c, fq32, n_flagged, k, ms_f.data(), masks_f.data(), index_base, d_redo, d_redo);
+  c->last_tier = tier;
+  if (rc_redo) return rc_redo;
+  for (int i = 0; i < n_flagged; ++i)
+    TAVB_HIP(hipMemcpyAsync(d_out + (size_t)slot[i] * k, d_redo + (size_t)i * k, (size_t)k * sizeof(u64_t), hipMemcpyDefault, c->stream));
+  return TAVB_OK;
+}
+
 struct MaskedWide {
   const uint32_t* bits;           // the mask over the corpus rows
   int64_t span_begin, span_end;   // rows [span_begin, span_end) hold every set bit; span_begin a multiple of 256
   const int32_t* dev_rows;        // the allowed rows in ascending order (device), n_allowed of them
   int64_t n_allowed;
 };
+// the scoped twin: one mask per query (HOST array of nq device pointers); [first_row, last_row] holds every set bit of every mask
+struct ScopedWide {
+  const uint32_t* const* masks;
+  int64_t first_row, last_row;
+  int* n_flagged;  // out: the queries that were re-run
+};
 int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, uint32_t index_base, u64_t* d_out, bool small = false,
-                      const MaskedWide* mw = nullptr) {
+                      const MaskedWide* mw = nullptr, const ScopedWide* sw = nullptr) {
   // candidates per query handed to the rescoring: the wide tile selects a BAND (every row within 2 delta of the approximate k-th best: as many
   // as the data makes it, up to kBandMax), the 32/64-query tile (`small`) the best 64 by approximate score
   const int KC = small ? 64 : (int)c->band_max;
@@ -617,7 +654,7 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   const int fdim = padded ? ((c->dim + 63) / 64) * 64 : c->dim;
   const bool shadow_ops = f32c || padded;  // the filter's corpus operand is d_shadow
   const bool big_k = k > 64;  // beyond what the 64-query exact tile ranks: every flagged query goes to the wide split-plane form (fp16 corpora only: the caller checked)
-  const int64_t scan_rows = mw ? mw->span_end - mw->span_begin : c->rows;  // the rows the filter walks
+  const int64_t scan_rows = mw ? mw->span_end - mw->span_begin : sw ? sw->last_row + 1 - sw->first_row / 256 * 256 : c->rows;  // the rows the filter walks
   const int qt = small ? tavb::skinny_query_tile(nq) : (c->mfma_tile > 0 ? (int)c->mfma_tile : tavb::mfma_query_tile_for(nq, scan_rows, c->n_cu));
   const int nq_pad = ((nq + qt - 1) / qt) * qt;
   const bool bdirect = !small && qt == 256 && c->mfma_bdirect && c->mfma_ablate == 0;
@@ -626,13 +663,13 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   // 16 passes of the 64-query tile per 1024 flagged queries otherwise (round 2-3: "stated, not solved").  Both are fixed-shape
   // launches over the same device-side list and return at once when it is empty or is the other one's share.  Either one hands its best rows
   // (and a small band below them) to the rescoring kernel in slot mode: a query served by a fallback gets the streaming kernels' float32 scores.
-  const bool wide_fallback = !mw && !small && !f32c && c->wide_fallback && (nq >= 256 || big_k);
+  const bool wide_fallback = !mw && !sw && !small && !f32c && c->wide_fallback && (nq >= 256 || big_k);
   // k > 64 on an FP32 corpus (end of round 6): the filter, the band and the rescoring serve any k up to TAVB_MAX_FUSED_K, but no exact tile ranks
   // more than 64 fp32 rows per query.  A flagged query -- more than band_max near-duplicates around its k-th best: rare -- is therefore re-run on
   // the streaming kernels, which takes the one host round trip of this file (the work list is read back; nothing flagged: nothing more to do).
   // Until then such batches took the streaming kernels four queries per corpus pass: 128 queries over 2M x 1536 fp32 rows, k = 65: 66 ms against 1.3.
   const bool f32_big_k = !small && f32c && big_k;
-  if (big_k && !wide_fallback && !f32_big_k && !mw) return fail(TAVB_E_UNSUPPORTED, "k > 64 on the batched tile of an fp16 corpus needs the wide_fallback option");
+  if (big_k && !wide_fallback && !f32_big_k && !mw && !sw) return fail(TAVB_E_UNSUPPORTED, "k > 64 on the batched tile of an fp16 corpus needs the wide_fallback option");
   const int cap = wide_fallback ? ((nq + 255) / 256) * 256 : ((nq + 63) / 64) * 64;  // slots of the work list
   const size_t q16_bytes = (size_t)nq_pad * fdim * 2 * (small ? 2 : 1);  // small: high and low plane
   if (int rc = c->d_queries_f16.reserve(q16_bytes)) return rc;
@@ -650,9 +687,9 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   }
   if (!big_k || f32_big_k)
     if (int rc = c->d_fb_cand.reserve((size_t)cap * (f32_big_k ? k : 64) * sizeof(u64_t))) return rc;
-  if (f32_big_k || mw)
+  if (f32_big_k || mw || sw)
     if (int rc = c->h_flag.reserve((size_t)(64 + cap) * sizeof(int))) return rc;
-  if (mw)  // the re-run's lists
+  if (mw || sw)  // the re-run's lists
     if (int rc = c->d_fb_cand.reserve((size_t)cap * k * sizeof(u64_t))) return rc;
   if (int rc = c->d_norm.reserve(256)) return rc;
   float *d_ms = nullptr, *d_ms_floor = nullptr;
@@ -733,6 +770,16 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
     filt.span_begin = mw->span_begin;
     filt.span_end = mw->span_end;
   }
+  if (sw) {  // the membership planes of this batch: one per block of 32 queries of the padded batch, over the span (the padding queries' are zero)
+    const int64_t stride = tavb::host::scope_plane_stride(sw->first_row, sw->last_row);
+    if (int rc = c->d_scope_planes.reserve((size_t)(nq_pad / 32) * stride * sizeof(uint32_t))) return rc;
+    uint32_t* const planes = reinterpret_cast<uint32_t*>(c->d_scope_planes.ptr);
+    if (int rc = tavb::host::build_scope_planes(c, sw->masks, nq, nq_pad / 32, sw->first_row, sw->last_row, planes)) return rc;
+    filt.planes = planes;
+    filt.plane_stride = stride;
+    filt.span_begin = sw->first_row / 256 * 256;
+    filt.span_end = sw->last_row + 1;
+  }
   // a batch MOST of whose bands are not going to fit (every query next to more near-duplicates than a band holds) is found out before the last --
   // the big -- filter phase and goes straight to the exact split-plane form: the filter's last phase, its selection and the rescoring return at once
   const bool early = wide_fallback && c->early_exact;
@@ -755,7 +802,7 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
     // the exact fallbacks start from what the filter has proven: the cut its last selection left in d_thr (the one before it when the early
     // verdict skipped the last phase) less the filter's error bound is a valid admission threshold on exact scores, so ONE phase each
     const float* seed = small ? nullptr : reinterpret_cast<const float*>(c->d_thr.ptr);
-    if (!mw)  // (a masked batch re-runs its flagged queries from their fp32 rows in d_q: nothing to gather)
+    if (!mw && !sw)  // (a masked or scoped batch re-runs its flagged queries from their fp32 rows in d_q: nothing to gather)
       e = f32c ? tavb::launch_gather_flagged_f32(d_q, c->dim, d_ms, d_nflag, d_flagged, cap, reinterpret_cast<float*>(fb), fb_thr, seed, d_delta, c->stream)
                : tavb::launch_gather_flagged(fq, fdim, d_ms, d_nflag, d_flagged, cap, fb, fb + (size_t)cap * fdim * 2, fb_thr, seed, d_delta,
                                              wide_fallback ? fb_band : nullptr, kExactBand, c->stream);
@@ -763,6 +810,8 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   }
   if (mw)  // their fp32 queries side by side in fb (cap x fdim x 4 bytes and more), their lists by position, then as index_base + row
     return rerun_flagged(c, d_nflag, cap, d_q, reinterpret_cast<float*>(fb), /*gathered=*/false, k, min_scores, mw->dev_rows, mw->n_allowed, index_base, d_out);
+  if (sw)  // the same, each with its own mask
+    return rerun_flagged_scoped(c, d_nflag, cap, d_q, reinterpret_cast<float*>(fb), k, min_scores, sw->masks, index_base, d_out, sw->n_flagged);
   if (f32_big_k)  // (gather_flagged_f32_kernel has put their fp32 queries into fb)
     return rerun_flagged(c, d_nflag, cap, d_q, reinterpret_cast<float*>(fb), /*gathered=*/true, k, min_scores, nullptr, 0, index_base, d_out);
   {  // (run_tile_ladder times its own launches, in the same bucket)
@@ -1031,6 +1080,45 @@ int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
   const MaskedWide mw{dev_bits, first_row / 256 * 256, last_row + 1, dev_rows, n_allowed};
   return search_wide_exact(c, d_q, nq, k, min_scores, index_base, d_out, /*small=*/false, &mw);
 }
+
+// A scoped batch on the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide and its twins; the callers have checked the
+// arguments and masked_wide_supported), in WAVES of query tiles like search_scoped_tile: per wave search_wide_exact builds the membership
+// planes, runs the filter ladder over the span of the union with the per-query test in its admission path, selects the bands, rescores, and
+// re-runs the wave's flagged queries on the row-list scoped route (one synchronise per wave: the flag list is read back).  A plane is 4 bytes
+// per row of the span per 32 queries: a 256-query tile takes 32 bytes per row, a 128-query tile 16.  A wave is as many whole 256-query tiles as
+// fit "scope_wave_bytes" (64 MiB) of planes, at least one tile: at 1M rows two tiles, 512 queries.  Whole multiples of 256 queries, so that
+// whichever tile width search_wide_exact picks for a wave pads it to no more than the wave; where not even one 256-query tile fits (spans
+// beyond 2M rows) and the batch runs on 128-query tiles, one of those.  The planes' workspace is therefore at most max(64 MiB, 32 bytes x
+// span rows) whatever the batch.
+int search_scoped_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* const* masks, int64_t first_row, int64_t last_row,
+                       uint32_t index_base, u64_t* d_out) {
+  if (c->dim % 64 != 0)  // the filter reads the padded copy, as for one mask
+    if (int rc = reserve_shadow(c)) return rc;
+  c->last_tier = 4;
+  c->last_direct = 0;
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->masked_route = 6;
+  const int64_t stride = scope_plane_stride(first_row, last_row);
+  const int qt_all = c->mfma_tile > 0 ? (int)c->mfma_tile : tavb::mfma_query_tile_for(nq, stride, c->n_cu);
+  const int64_t fit256 = c->scope_wave_bytes / (8 * stride * (int64_t)sizeof(uint32_t));  // whole 256-query tiles in the budget
+  const int wave = fit256 >= 1 ? 256 * (int)std::min<int64_t>(fit256, 1 << 20) : qt_all;
+  int flagged = 0, waves = 0;
+  for (int q0 = 0; q0 < nq; q0 += wave, ++waves) {
+    int n_flagged = 0;
+    const ScopedWide sw{masks + q0, first_row, last_row, &n_flagged};
+    if (int rc = search_wide_exact(c, d_q + (size_t)q0 * c->dim, std::min(wave, nq - q0), k, min_scores + q0, index_base, d_out + (size_t)q0 * k, /*small=*/false,
+                                   nullptr, &sw))
+      return rc;
+    flagged += n_flagged;
+  }
+  if (waves > 1) {  // "last_flagged" reads the work list's header: the batch's count, not the last wave's
+    int* h = reinterpret_cast<int*>(c->h_flag.ptr);
+    h[0] = flagged;  // (every wave has synchronised behind its read-back: nothing in flight reads or writes h)
+    TAVB_HIP(hipMemcpyAsync(c->d_flag.ptr, h, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  return TAVB_OK;
+}
 }  // namespace host
 }  // namespace tavb
 
@@ -1076,6 +1164,22 @@ extern "C" int tavb_plan_scoped(int32_t nq, int32_t k, int32_t dim, int32_t dtyp
   const __int128 passes = (nq + 7) / 8;
   if ((__int128)gather_rows * dim * (f32 ? 4 : 2) < passes * min_bytes) return 0;
   return (__int128)gather_rows * 100 >= (__int128)((nq + 63) / 64) * span * pct ? 1 : 0;
+}
+
+extern "C" int tavb_plan_scoped_wide(int32_t nq, int32_t k, int32_t dim, int32_t dtype, int64_t gather_rows, int64_t span, int64_t min_bytes, int64_t pct) {
+  if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");
+  if (nq < 0 || gather_rows < 0 || span < 0 || min_bytes < 0 || pct < 0) return fail(TAVB_E_INVALID, "bad shape");
+  if (dtype != TAVB_F16) return 0;  // (an fp32 corpus would filter on its shadow: not built)
+  if (dim <= 0 || dim > 16384 || !tavb::mfma_supported(((dim + 63) / 64) * 64, k)) return 0;
+  if (nq < kMfmaMinBatch) return 0;  // (the unmasked dispatcher's own lower bound for the wide tile, as it ships)
+  // tavb_plan_scoped's rule with the wide tile's reads: gather_rows is the lower bound of what the row-list route reads -- over its passes
+  // (of four queries for k > 64, else eight) the sum of each pass' largest scope; the floor is per pass; the wide tile reads the span once
+  // per query tile (128 or 256 queries: what the filter pass picks for this batch over `span` rows)
+  const int per_pass = k > 64 ? 4 : 8;
+  const __int128 passes = (nq + per_pass - 1) / per_pass;
+  if ((__int128)gather_rows * dim * 2 < passes * min_bytes) return 0;
+  const int qt = tavb::mfma_query_tile_for(nq, span, kPlanComputeUnits);
+  return (__int128)gather_rows * 100 >= (__int128)((nq + qt - 1) / qt) * span * pct ? 1 : 0;
 }
 
 extern "C" int tavb_plan_filter_shape(int32_t shape, int32_t query_tile, int32_t split, int32_t bdirect, int32_t sched, int32_t ablate) {

@@ -1173,6 +1173,28 @@ class VectorBase:
             yes = eng.plan_scoped(len(order), max_hits, eng.dim, eng.dtype, gather, last + 1 - first // 256 * 256, min_bytes, pct)
         return (first, last) if yes else None
 
+    @staticmethod
+    def _scoped_wide(eng, call: str, handles, order, max_hits: int):
+        """Whether a scoped batch the native route serves takes the 128/256-query filter tile + rescoring (`call`:
+        Engine.search_scoped_wide / search_messages_scoped_wide) -- asked BEFORE `_scoped_tile`, over which it wins: every searched handle
+        knows its span and the option "scope_wide" (0 = never, 2 = wherever the route serves the shape, 1 = where tavb_plan_scoped_wide
+        expects it to win) says so.  An engine without the call or the plan (an older library, a test double) keeps its routes.  Returns
+        the span (first, last) of the union of the searched scopes, or None."""
+        if not (hasattr(eng, call) and hasattr(eng, "plan_scoped_wide")) or any(handles[i].span is None for i in order):
+            return None
+        opts = eng.scope_wide_options() if hasattr(eng, "scope_wide_options") else tuple(
+            eng.get_option(n) for n in ("scope_wide", "mask_tile_min_bytes", "mask_tile_pct"))
+        mode, min_bytes, pct = opts
+        if mode == 0:
+            return None
+        first, last = min(handles[i].span[0] for i in order), max(handles[i].span[1] for i in order)
+        if mode == 2:  # (128 queries, no floors: yes exactly when the route serves the corpus, max_hits and the width)
+            yes = eng.plan_scoped_wide(128, max_hits, eng.dim, eng.dtype, 1, 1, 0, 0)
+        else:
+            gather = _native.scoped_gather_rows([handles[i].count for i in order], 4 if max_hits > 64 else 8)
+            yes = eng.plan_scoped_wide(len(order), max_hits, eng.dim, eng.dtype, gather, last + 1 - first // 256 * 256, min_bytes, pct)
+        return (first, last) if yes else None
+
     def fuzzy_lookup_embeddings_scoped(
         self,
         embeddings: NormalizedEmbeddings,
@@ -1206,10 +1228,16 @@ class VectorBase:
         `fuzzy_lookup_embeddings_masked` on its tile route: equal to the per-query calls except among float32 near-ties, scores within a
         few 1e-7, not bit for bit.  `engine.get_option("masked_route")` is then 5.
 
+        From 65 queries on an fp16 corpus (any width, 1 <= max_hits <= 256; engine option "scope_wide": where tavb_plan_scoped_wide says
+        so, and then in preference to the 32/64-query tile) dense scopes run on the 128/256-query filter tile with exact rescoring
+        (tavb_search_scoped_wide): the span is read once per 128 or 256 queries, each query's scope is tested in the filter's admission
+        path, and the candidates are scored again with the streaming kernels' arithmetic -- the answers of the row-list route BIT FOR
+        BIT, at max_hits up to 256.  `engine.get_option("masked_route")` is then 6.
+
         Everything else loops over `fuzzy_lookup_embedding_masked`: max_hits == 0 and max_hits > 256, device groups, `ShardedVectorBase`,
-        test doubles, and a handle without a device mask.  The tile route serves single-GPU engines only: device groups,
-        `ShardedVectorBase` and `FusedIndexQuery` do not take it, nor does max_hits > 64 (no 128/256-query tile form for per-query scopes),
-        and queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
+        test doubles, and a handle without a device mask.  The tile routes serve single-GPU engines only: device groups,
+        `ShardedVectorBase` and `FusedIndexQuery` do not take them; max_hits 65 .. 256 is served on the 128/256-query tile only (fp16
+        corpora), and queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
         if as_arrays and not (1 <= max_hits <= _PAGE):
             raise ValueError(f"as_arrays needs 1 <= max_hits <= {_PAGE}")
@@ -1223,8 +1251,12 @@ class VectorBase:
         eng = self._sync_device()
         if self._scoped_native(eng, "search_scoped_batch", handles, order, max_hits):
             t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
-            span = self._scoped_tile(eng, "search_scoped_tile", handles, order, max_hits)
-            if span is not None:
+            wide = self._scoped_wide(eng, "search_scoped_wide", handles, order, max_hits)
+            span = None if wide is not None else self._scoped_tile(eng, "search_scoped_tile", handles, order, max_hits)
+            if wide is not None:
+                o, s, c = eng.search_scoped_wide(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                 np.ascontiguousarray(t[order]), span=wide)
+            elif span is not None:
                 o, s, c = eng.search_scoped_tile(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
                                                  np.ascontiguousarray(t[order]), span=span)
             else:
@@ -1398,7 +1430,8 @@ class VectorBase:
         1 <= max_matches <= 256 whose scopes hold their packed mask on the device makes ONE submission (tavb_search_messages_scoped: the
         scoped batch, its key lists left on the device, one launch of the message aggregation, one copy back), bit for bit the per-query
         calls on the row list -- or, where `fuzzy_lookup_embeddings_scoped` would take the 32/64-query tile (option "scope_tile"),
-        tavb_search_messages_scoped_tile with the tile's contract: the same messages except among float32 near-ties; everything else (max_matches outside 1..256, device groups, test doubles, a handle without a device mask)
+        tavb_search_messages_scoped_tile with the tile's contract: the same messages except among float32 near-ties -- or, where it would take
+        the 128/256-query filter tile (option "scope_wide"), tavb_search_messages_scoped_wide, bit for bit again; everything else (max_matches outside 1..256, device groups, test doubles, a handle without a device mask)
         loops over `lookup_messages_by_embedding_masked`."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_matches, threshold_score)
         self._check_row_messages()
@@ -1412,8 +1445,12 @@ class VectorBase:
         eng = self._messages_engine()
         if eng is not None and self._scoped_native(eng, "search_messages_scoped", handles, order, max_hits):
             t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
-            span = self._scoped_tile(eng, "search_messages_scoped_tile", handles, order, max_hits)
-            if span is not None:
+            wide = self._scoped_wide(eng, "search_messages_scoped_wide", handles, order, max_hits)
+            span = None if wide is not None else self._scoped_tile(eng, "search_messages_scoped_tile", handles, order, max_hits)
+            if wide is not None:
+                m, s, c = eng.search_messages_scoped_wide(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                          np.ascontiguousarray(t[order]), max_hits, span=wide)
+            elif span is not None:
                 m, s, c = eng.search_messages_scoped_tile(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
                                                           np.ascontiguousarray(t[order]), max_hits, span=span)
             else:
