@@ -199,7 +199,12 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   32/64-query tile, 3 = the 128/256-query filter tile + rescoring (tavb_search_masked_wide), 4 = a scoped batch (one mask per
  *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped), 5 = a scoped batch on the 32/64-query tile
  *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile), 6 = a scoped batch on the 128/256-query filter tile +
- *                   rescoring (tavb_search_scoped_wide / _device, tavb_search_messages_scoped_wide)
+ *                   rescoring (tavb_search_scoped_wide / _device, tavb_search_messages_scoped_wide), 7 = a scoped batch on the large-k route
+ *                   (tavb_search_scoped_topk / _device), 8 = a scoped batch on the sorted route (tavb_search_scoped_sorted);
+ *                   tavb_search_subset_batch_sorted is the gather route: 1
+ *   "scope_large_k" (default 1; the binding reads it) 1 = a scoped batch at max_hits beyond TAVB_MAX_FUSED_K, or 0, is ONE call of
+ *                   tavb_search_scoped_topk / tavb_search_scoped_sorted (while "large_k" / "sort_all" are on); 0 = the binding loops over
+ *                   the per-query masked lookups, as before those calls existed
  *   "scope_wide"    scoped batches on fp16 corpora (the binding reads it; the rule is tavb_plan_scoped_wide, with "mask_tile_min_bytes" /
  *                   "mask_tile_pct"): 1 (default) = the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide) where
  *                   tavb_plan_scoped_wide says so -- it then wins over "scope_tile"; 0 = never; 2 = wherever that route serves the shape
@@ -582,6 +587,42 @@ int tavb_search_messages_scoped(tavb_ctx* ctx, const float* queries_host, int32_
                                 const float* min_scores, int32_t max_messages, int64_t* out_messages, float* out_scores, int32_t* out_counts);
 int tavb_mask_membership(tavb_ctx* ctx, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, const int32_t* dev_rows, int64_t n,
                          uint8_t* dev_member_out);
+
+/* ---- scoped and one-mask batches beyond TAVB_MAX_FUSED_K: the large-k and the sorted route under scopes ------------------------------------
+ * The same dev_masks / rows convention as tavb_search_scoped_batch; per query the result is what the single-query call over that mask's row
+ * list returns -- tavb_search_subset_topk / tavb_search_subset_sorted with the positions turned into corpus ordinals -- bit for bit:
+ * ordinals, float32 scores and counts.  Waves and passes as above (one synchronise per wave for the unions' sizes), a pass being min(8,
+ * the queries of one score pass) queries: eight bits of a membership byte.  Per pass, over the ascending row list of the union of its
+ * scopes: tavb_search_topk's score pass in its scoped form -- a row's score is written and counted for query j only when bit j of the
+ * row's membership byte is set, every other slot holds "no score" -- and then that route's own launches, unchanged: the histograms saw
+ * members only, so a query's need is min(k, survivors of ITS scope).  Keys carry union-list positions (the list is ascending, so equal
+ * scores leave by ascending row) and are turned into rows at the end.  "topk_scores_bytes" holds: where the score array of a whole pass
+ * (queries x union rows x 4 bytes) would exceed it, the pass' queries go in sub-groups over the same list (at least one query each).
+ *   tavb_search_scoped_topk: 1 <= k <= TAVB_MAX_LARGE_K.  Per pass: write pass, membership bytes, then per sub-group memset, score pass,
+ *     refinement rounds, compaction, finish; one remap.  Queries on the host, one more synchronise at the end; outputs [nq, k] / [nq] as
+ *     tavb_search_topk (ordinals carry ordinal_base).  "masked_route" reports 7, "last_topk_refine" the most rounds of any query.
+ *   tavb_search_scoped_topk_device: dev_queries device float32 [nq, dim]; out_keys [nq, k] sorted, zero-padded keys carrying ordinal_base +
+ *     row, device or device-writable pinned memory; waits only for the unions' sizes ("last_topk_refine" at the next tavb_synchronize).
+ *   tavb_search_scoped_sorted: k = 0 (every survivor of the query's scope) or ANY k >= 1.  Per sub-group the sorted route's group
+ *     (tavb_search_sorted): score pass, refinement only where k < the union's rows, counts, ONE synchronise, then per query compaction, sort
+ *     and decode -- the decode reads the row list.  max_total, the concatenated out_ordinals / out_scores, out_counts [nq] and *out_total
+ *     follow tavb_search_sorted; more than max_total results are TAVB_E_INVALID.  "masked_route" reports 8.
+ *   tavb_search_subset_batch_sorted: the one-mask batch on the sorted route -- nq queries over ONE resident row list (dev_rows device int32
+ *     [n_subset], valid corpus rows, e.g. tavb_mask_expand's), eight per pass; per query tavb_search_subset_sorted with out_ordinals =
+ *     ordinal_base + dev_rows[position].  "masked_route" reports 1 (the gather route).
+ * NULL arguments, rows != the corpus' rows, k out of range, max_total < 0 and a NULL mask pointer are TAVB_E_INVALID with a message.  nq == 0,
+ * an empty corpus or subset: zero counts / zero keys, nothing launched.  A query whose mask is empty gets an empty list.  Timed under
+ * TAVB_KERNEL_CONVERT (unions, lists, membership), TAVB_KERNEL_SCAN (score pass) and TAVB_KERNEL_TOPK (everything behind it). */
+int tavb_search_scoped_topk(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                            const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_scoped_topk_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                   const float* min_scores /*host*/, tavb_key* out_keys);
+int tavb_search_scoped_sorted(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t k,
+                              const float* min_scores, int64_t max_total, int64_t* out_ordinals, float* out_scores, int64_t* out_counts,
+                              int64_t* out_total);
+int tavb_search_subset_batch_sorted(tavb_ctx* ctx, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int64_t k,
+                                    const float* min_scores, int64_t max_total, int64_t* out_ordinals, float* out_scores, int64_t* out_counts,
+                                    int64_t* out_total);
 
 /* ---- scoped batches on the 32/64-query tile: one scope per query on the matrix cores ----------------------------------------------------
  * The scoped batch above reads, per pass of eight queries, the union of the pass' scopes; dense, independent or disjoint scopes make that

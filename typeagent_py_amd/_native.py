@@ -114,6 +114,12 @@ _SIGNATURES = [
     ("tavb_search_scoped_wide_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_search_messages_scoped_wide", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_scoped_topk", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_scoped_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_scoped_sorted", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    ("tavb_search_subset_batch_sorted", c_int,
+     [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -1174,6 +1180,65 @@ class Engine:
             rc = self.lib.tavb_search_scoped_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), k, _addr(t), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
+
+    def search_scoped_topk(self, queries, dev_bits_list, k: int, thrs):
+        """`search_scoped_batch` for any 1 <= k <= MAX_LARGE_K, in one submission (tavb_search_scoped_topk): the exact device top-k's
+        score pass over the union list of every pass of eight queries, a row scored for a query only inside that query's scope ->
+        (ordinals [nq, k], scores [nq, k], counts [nq]), per query `search_subset_batch_resident` over that mask's row list, bit for bit."""
+        a, nq, t, ords, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_topk(self._h, _addr(a), nq, ptrs, int(self.rows), k, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_scoped_topk_device(self, dev_queries, dev_bits_list, k: int, thrs, out_keys=None):
+        """`search_scoped_topk` with the queries on the device (tavb_search_scoped_topk_device) -> torch int64 [nq, k] sorted, zero-padded
+        keys carrying ordinal_base + row.  `out_keys`: a device tensor or a PINNED host tensor.  The call waits for the unions' sizes
+        only: `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_scoped_topk_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), k, _addr(t),
+                                                         c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def _sorted_batch(self, a, k: int, thrs, max_total: int, call):
+        """The arguments and outputs of a sorted batch of the queries a (`batch_queries`): `call(queries, nq, thresholds, max_total,
+        ordinals, scores, counts, total)` under the lock -> (ordinals int64 [total], scores float32 [total], counts int64 [nq]), query
+        q's results at counts[:q].sum() .. ."""
+        if k < 0 or max_total < 0:
+            raise ValueError("k and max_total must be >= 0")
+        nq = a.shape[0]
+        t = batch_thresholds(thrs, nq)
+        ords = np.empty(max(max_total, 1), dtype=np.int64)  # (lazy: only the pages the results touch are ever mapped)
+        scs = np.empty(max(max_total, 1), dtype=np.float32)
+        cnts = np.zeros(nq, dtype=np.int64)
+        total = c_int64(0)
+        with self._lock:
+            rc = call(_addr(a), nq, _addr(t), int(max_total), _addr(ords), _addr(scs), _addr(cnts), byref(total))
+        _check(self.lib, rc)
+        m = int(total.value)
+        return ords[:m], scs[:m], cnts
+
+    def search_scoped_sorted(self, queries, dev_bits_list, k: int, thrs, max_total: int):
+        """A scoped batch on the sorted route, in one submission (tavb_search_scoped_sorted): k = 0 (every survivor of the query's scope)
+        or any k; max_total: the most results the batch may have (more raise TavbError) -- the sum of min(k, rows of the scope) bounds
+        it.  -> `search_sorted`'s layout with corpus ordinals; per query `search_subset_sorted` over that mask's row list, bit for bit."""
+        a = batch_queries(queries, self.dim)
+        ptrs = self._mask_pointers(dev_bits_list, a.shape[0])
+        return self._sorted_batch(a, k, thrs, max_total, lambda qa, nq, t, bound, *out: self.lib.tavb_search_scoped_sorted(
+            self._h, qa, nq, ptrs, int(self.rows), int(k), t, bound, *out))
+
+    def search_subset_batch_sorted(self, queries, dev_rows, k: int, thrs):
+        """`search_subset_sorted` for a batch over ONE resident row list (tavb_search_subset_batch_sorted), with corpus ordinals
+        (dev_rows ascending: `mask_to_rows`) -> `search_sorted`'s layout."""
+        a = batch_queries(queries, self.dim)
+        rows_ptr, n = self._row_list(dev_rows)
+        bound = a.shape[0] * (n if k <= 0 else min(int(k), n))
+        return self._sorted_batch(a, k, thrs, bound, lambda qa, nq, t, bound, *out: self.lib.tavb_search_subset_batch_sorted(
+            self._h, qa, nq, rows_ptr, n, int(k), t, bound, *out))
 
     def search_messages_scoped(self, queries, dev_bits_list, k: int, thrs, max_messages: int):
         """`search_scoped_batch` aggregated to messages in one submission (tavb_search_messages_scoped) -> (message ordinals [nq, k], scores

@@ -184,6 +184,7 @@ struct tavb_ctx {
   Buffer d_scope_planes;
   int64_t scope_tile = 1;  // option: scoped batches on the 32/64-query tile: 1 = follow tavb_plan_scoped (with "mask_tile_min_bytes" / "mask_tile_pct"), 0 = never, 2 = always where supported
   int64_t scope_wide = 1;  // option: scoped batches on the 128/256-query filter tile (tavb_search_scoped_wide): 1 = follow tavb_plan_scoped_wide (same thresholds), 0 = never, 2 = always where supported
+  int64_t scope_large_k = 1;  // option: 1 = the binding sends scoped batches at max_hits 0 and beyond TAVB_MAX_FUSED_K through tavb_search_scoped_topk / tavb_search_scoped_sorted, 0 = it loops per query
   int64_t scope_wave_bytes = (int64_t)64 << 20;  // option: most bytes of membership planes one wave of tavb_search_scoped_wide builds (at least one query tile's are built whatever this says)
   Buffer h_sort_info{nullptr, 0, true};  // pinned: meta [nq][4] + per-block key counts [nq][blocks] of one group
   int64_t sort_all = 1;                   // option: 1 = the binding routes max_hits == 0 and max_hits > TAVB_MAX_LARGE_K through tavb_search_sorted
@@ -394,6 +395,21 @@ int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
 int search_scoped_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks, uint32_t index_base,
                        u64_t* work, u64_t* out);
 
+// What the row-list routes of a scoped batch share (search_scoped_impl, search_scoped_topk_impl, search_scoped_sorted_impl): a WAVE of
+// passes of per_pass (at most 8) queries.  scope_wave_unions enqueues the union of every pass' masks, synchronises ONCE for their sizes
+// and reserves d_scope_rows / d_scope_member for the wave (nothing when every union is empty: total == 0); scope_wave_lists then
+// enqueues, for a pass whose union is not empty, the write pass of its ascending row list and its membership bytes (bit j = query j of the
+// pass).  scoped_wave_queries: the queries of one wave -- at most 16 passes, fewer on corpora beyond 4M rows (the workspaces' bound).
+struct ScopeWave {
+  int nq, per_pass, passes;
+  std::vector<tavb::MaskOperands> ops;       // per pass: its masks
+  std::vector<int64_t> n_union, first_pos;  // per pass: rows of its union, where its list starts in the workspaces
+  int64_t total, most;                       // the unions' total and largest length
+};
+int scope_wave_unions(tavb_ctx* c, int nq, int per_pass, const uint32_t* const* masks, ScopeWave* w);
+int scope_wave_lists(tavb_ctx* c, const ScopeWave& w, int p, const int32_t** list_out, const uint8_t** member_out);
+int scoped_wave_queries(const tavb_ctx* c, int per_pass);
+
 // A scoped batch on the 32/64-query tile: the same masks; [first_row, last_row] holds every set bit of every mask.  Per wave of query tiles
 // the membership planes (c->d_scope_planes), then the tile ladder over the span with the per-query test in its admission path; keys carry
 // index_base + row -> d_out [nq, k].  Nothing is waited for.  The caller has checked skinny_supported and the bounds.
@@ -447,6 +463,16 @@ int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* 
 // carrying index_base + position -> out_keys (device or device-writable pinned memory); d_rows: a subset's rows (nq == 1), or null.
 int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
                       uint32_t index_base, u64_t* out_keys);
+
+// A scoped batch at 1 <= k <= TAVB_MAX_LARGE_K (masks as for search_scoped_impl): per pass of min(topk_queries_per_pass, 8) queries the
+// scoped score pass over the pass' union list, the refinement rounds, the compaction and the finish into `work` [nq, k], and the remap of
+// the positions to index_base + row on the way to `out` [nq, k] (`work` == `out`: in place; both device-writable); out_rounds [nq + 1]
+// device-writable and 8-byte aligned.  A pass whose score array would pass "topk_scores_bytes" goes in sub-groups of its queries over the
+// same list.  ONE synchronise per wave (the unions' sizes); everything else is enqueued and not waited for.
+int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
+                            uint32_t index_base, u64_t* work, u64_t* out, int32_t* out_rounds);
+// what the scoped entry points check after their own head: 1 <= k <= k_max, the masks; *empty: nothing to scan (tavb_lookup_masked.hip)
+int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, int32_t k_max, bool* empty);
 
 // ---- tavb_comm.hip
 int comm_wait_or_abort(tavb_ctx* c);

@@ -39,6 +39,9 @@ struct ScanParams {
   // scoped batch (launch_scan_scoped, plain form only): [n_pos] bytes, bit q of byte p = query q of the pass may take position p
   // (launch_scope_member); read by no other launch
   const uint8_t* scope_member;
+  // scoped score pass (launch_scan_topk_scoped): query q of the launch is bit scope_bit0 + q of a membership byte -- the launch's queries
+  // may be a sub-group of the pass the bytes were written for
+  int32_t scope_bit0;
 };
 
 struct ScanGeometry {
@@ -60,6 +63,10 @@ bool launch_scan_inline_query(const ScanParams& p, const ScanGeometry& g, hipStr
 // the score pass of a large-k lookup (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES) queries, index_base 0, the streaming kernels'
 // arithmetic row for row -- the scores are those the fused selection sees, bit for bit -- with ScanParams::topk_* as the output
 hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// the score pass of a scoped large-k or sorted batch (tavb_scan.hip): launch_scan_topk over p.row_ids, the ascending row list of the union of
+// the pass' scopes, with p.scope_member / p.scope_bit0 set (scope_bit0 + nq <= 8) -- a position whose member bit is clear gets kScoreNone
+// for that query and is counted nowhere; a member's score and bucket are launch_scan_topk's.  Vector tier for aligned rows, else scalar.
+hipError_t launch_scan_topk_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
 // one pass of a scoped batch (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES; 4 for k > 64) queries over p.row_ids, the ascending row
 // list of the union of their scopes, index_base 0; query q is offered position pos only when bit q of p.scope_member[pos] is set.
 // Otherwise launch_scan's plain form: the same lists at p.lists, the same per-row arithmetic on the vector or the scalar tier.
@@ -131,7 +138,9 @@ struct SortJob {
 size_t sort_workspace_bytes(int64_t n);
 hipError_t launch_sort_desc(SortJob& j, hipStream_t stream);
 // sorted keys [off, off + len) -> ords [0, len) (position + base) and scs [0, len) (score bits), e.g. pinned host memory
-hipError_t launch_sort_decode(const SortJob& j, int64_t off, int64_t len, int64_t base, int64_t* ords, float* scs, hipStream_t stream);
+// map (optional, map_len entries): the positions are those of a row list, and ords = map[position] + base
+hipError_t launch_sort_decode(const SortJob& j, int64_t off, int64_t len, int64_t base, int64_t* ords, float* scs, hipStream_t stream,
+                              const int32_t* map = nullptr, int64_t map_len = 0);
 hipError_t launch_sort_copy_back(const SortJob& j, hipStream_t stream);
 
 // every row with score >= min_score[0] (and key < key_bound), unsorted: out[0 .. *counter) (entries past `capacity` are dropped, still counted)

@@ -704,9 +704,11 @@ int tavb_search_messages_masked(tavb_ctx* c, const float* queries_host, int32_t 
 
 // ---- scoped batches: one mask per query (tavb_route.hip::search_scoped_impl)
 // what the three entry points check after their own head; *empty: nothing to scan (an empty corpus, no query)
-static int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, bool* empty) {
+}  // extern "C"
+// (shared with the scoped large-k and sorted entry points of tavb_lookup_topk.hip, whose k_max is TAVB_MAX_LARGE_K)
+int tavb::host::check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, int32_t k_max, bool* empty) {
   if (int rc = check_masked_head(c, nq, rows, k)) return rc;
-  if (k > TAVB_MAX_FUSED_K) return fail(TAVB_E_INVALID, "a scoped batch serves 1 <= k <= %d (got %d)", TAVB_MAX_FUSED_K, k);
+  if (k > k_max) return fail(TAVB_E_INVALID, "a scoped batch serves 1 <= k <= %d (got %d)", k_max, k);
   if (rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
   *empty = rows == 0 || nq == 0;
   if (*empty) return TAVB_OK;
@@ -716,6 +718,11 @@ static int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev
     if ((reinterpret_cast<uintptr_t>(dev_masks[q]) & 3) != 0) return fail(TAVB_E_INVALID, "the mask of query %d must be 4-byte aligned", q);
   }
   return TAVB_OK;
+}
+extern "C" {
+
+static int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, bool* empty) {
+  return check_scoped_args(c, nq, dev_masks, rows, k, TAVB_MAX_FUSED_K, empty);
 }
 
 static void note_scoped_route(tavb_ctx* c) {

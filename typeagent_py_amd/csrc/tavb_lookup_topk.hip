@@ -1,5 +1,6 @@
 // The large-k and sorted lookups of the C ABI (include/tavb.h): tavb_search_topk and its subset / device forms, tavb_search_sorted,
-// tavb_search_subset_sorted, tavb_sort_keys_device -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
+// tavb_search_subset_sorted, tavb_search_subset_batch_sorted, tavb_sort_keys_device, their scoped forms (one mask per query:
+// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
 // tavb_topk.hip and tavb_sort.hip, the staging in tavb_lookup.hip.
 
 #include <optional>
@@ -22,14 +23,13 @@ struct ScorePlan {
   tavb::ScanGeometry g;  // of the score pass
 };
 
-// Sizes the groups and reserves the score array of one; d_topk, the selection's workspace, is the caller's to reserve.
-int plan_score_pass(tavb_ctx* c, int nq, int64_t n_pos, bool refine, ScorePlan* s) {
+// Groups of at most `most` queries over n_pos positions, cut to what "topk_scores_bytes" lets one score array hold (at least one), and
+// the score array of one group reserved; d_topk, the selection's workspace, is the caller's to reserve.
+int shape_score_pass(tavb_ctx* c, int64_t most, int64_t n_pos, bool refine, ScorePlan* s) {
   s->n_pos = n_pos;
   s->nb = (int)c->topk_buckets;
   s->cap = (int)c->topk_boundary_keys;
-  s->per = tavb::topk_queries_per_pass(c->dim, c->dtype, s->nb);
-  s->per = std::min<int64_t>(s->per, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
-  s->per = std::min<int64_t>(s->per, nq);
+  s->per = std::min<int64_t>(most, std::max<int64_t>(1, c->topk_scores_bytes / (n_pos * (int64_t)sizeof(uint32_t))));
   s->rounds = refine ? tavb::topk_refine_rounds(n_pos, s->cap) : 0;
   if (int rc = c->d_topk_scores.reserve((size_t)s->per * n_pos * sizeof(uint32_t))) return rc;
   s->g = clamped_geometry(c);
@@ -39,17 +39,29 @@ int plan_score_pass(tavb_ctx* c, int nq, int64_t n_pos, bool refine, ScorePlan* 
   return TAVB_OK;
 }
 
+// the groups of an unscoped batch of nq queries: as many queries as the score pass takes
+int plan_score_pass(tavb_ctx* c, int nq, int64_t n_pos, bool refine, ScorePlan* s) {
+  return shape_score_pass(c, std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, (int)c->topk_buckets), nq), n_pos, refine, s);
+}
+
+// queries per pass of the scoped routes: the score pass' own, within the bits of a membership byte
+int scoped_topk_per_pass(const tavb_ctx* c) { return std::min(tavb::topk_queries_per_pass(c->dim, c->dtype, (int)c->topk_buckets), 8); }
+
 // The pass for the queries [q0, q0 + n) of the batch (d_q, min_scores: the whole batch's; d_rows: a subset's rows, or null).  *t arrives
 // with the caller's own members set (k, out_keys, out_rounds, index_base) and leaves filled in, ready for the caller's selection launches.
 // `what` names the caller in the messages.  *tm: the TAVB_KERNEL_TOPK interval, opened in front of the refinement rounds -- the caller's
 // launches of the group that follow belong to it, and the caller closes it.
+// member (optional): the scoped form -- d_rows is the union list of a scoped pass, member its membership bytes, and the n queries are its
+// member bits bit0 .. bit0 + n - 1 (launch_scan_topk_scoped).
 int run_score_pass(tavb_ctx* c, const ScorePlan& s, const char* what, const float* d_q, const float* min_scores /*host*/, const int32_t* d_rows, int q0, int n,
-                   tavb::TopkLaunch* t, std::optional<Timed>* tm) {
+                   tavb::TopkLaunch* t, std::optional<Timed>* tm, const uint8_t* member = nullptr, int bit0 = 0) {
   TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
   tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, s.n_pos, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
   p.topk_scores = reinterpret_cast<unsigned*>(c->d_topk_scores.ptr);
   p.topk_hist = reinterpret_cast<unsigned*>(c->d_topk.ptr);
   p.topk_buckets = s.nb;
+  p.scope_member = member;
+  p.scope_bit0 = bit0;
   for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
     const float ms = i < n ? min_scores[q0 + i] : INFINITY;
     float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
@@ -59,7 +71,7 @@ int run_score_pass(tavb_ctx* c, const ScorePlan& s, const char* what, const floa
   }
   {
     Timed scan(c, TAVB_KERNEL_SCAN);
-    hipError_t e = tavb::launch_scan_topk(p, s.g, c->stream, &c->last_tier);
+    hipError_t e = member ? tavb::launch_scan_topk_scoped(p, s.g, c->stream, &c->last_tier) : tavb::launch_scan_topk(p, s.g, c->stream, &c->last_tier);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "%s score pass launch failed: %s", what, hipGetErrorString(e));
   }
   t->scores = p.topk_scores;
@@ -103,6 +115,55 @@ int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* 
     hipError_t e = tavb::launch_topk_compact(t, c->stream);
     if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "top-k selection launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+// ---- the same under one scope per query (tavb_search_scoped_topk): waves of passes as in search_scoped_impl (tavb_route.hip).  Per pass
+// whose union is not empty: the write pass and the membership bytes, then per sub-group of its queries (one, unless the score array of the
+// whole pass would exceed "topk_scores_bytes") a memset, the scoped score pass, the refinement rounds, the compaction and the finish --
+// keys carrying union-list positions into `work` -- and ONE remap of the pass' keys to index_base + row into `out`.  The histograms saw
+// members only, so need = min(k, survivors of the query's own scope) falls out of the boundary search as it stands.
+// out_rounds: pinned host memory; the queries of empty unions get their zero from the host, after the wave's synchronise.
+int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
+                            uint32_t index_base, u64_t* work, u64_t* out, int32_t* out_rounds) {
+  const int per = scoped_topk_per_pass(c);
+  const int wave = scoped_wave_queries(c, per);
+  for (int w0 = 0; w0 < nq; w0 += wave) {
+    const int wn = std::min(wave, nq - w0);
+    ScopeWave w;
+    if (int rc = scope_wave_unions(c, wn, per, masks + w0, &w)) return rc;
+    for (int p = 0; p < w.passes; ++p) {
+      const int q0 = w0 + p * per, n = std::min(per, wn - p * per);
+      const int64_t n_pos = w.n_union[p];
+      if (n_pos == 0) {  // every scope of the pass is empty
+        for (int q = 0; q < n; ++q) out_rounds[q0 + q] = 0;
+        if (int rc = fill_empty_keys(c, out + (size_t)q0 * k, (int64_t)n * k)) return rc;
+        continue;
+      }
+      const int32_t* list;
+      const uint8_t* member;
+      if (int rc = scope_wave_lists(c, w, p, &list, &member)) return rc;
+      ScorePlan s;
+      if (int rc = shape_score_pass(c, n, n_pos, /*refine=*/true, &s)) return rc;
+      if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)s.per, k, s.nb, s.cap, s.rounds))) return rc;
+      for (int s0 = 0; s0 < n; s0 += (int)s.per) {
+        const int m = (int)std::min<int64_t>(s.per, n - s0);
+        tavb::TopkLaunch t{};
+        t.k = k;
+        t.out_keys = work + (size_t)(q0 + s0) * k;
+        t.out_rounds = out_rounds + q0 + s0;
+        t.index_base = 0u;
+        std::optional<Timed> tm;
+        if (int rc = run_score_pass(c, s, "scoped top-k", d_q, min_scores, list, q0 + s0, m, &t, &tm, member, s0)) return rc;
+        hipError_t e = tavb::launch_topk_compact(t, c->stream);
+        if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+        if (e != hipSuccess) return fail(TAVB_E_HIP, "scoped top-k selection launch failed: %s", hipGetErrorString(e));
+      }
+      Timed tm(c, TAVB_KERNEL_TOPK);
+      hipError_t e = tavb::launch_remap_positions(work + (size_t)q0 * k, out + (size_t)q0 * k, (int64_t)n * k, list, n_pos, index_base, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "scoped top-k remap launch failed: %s", hipGetErrorString(e));
+    }
   }
   return TAVB_OK;
 }
@@ -233,32 +294,59 @@ int flush_staged(tavb_ctx* c, SortedOut& o, int64_t cap) {
   o.staged = 0;
   return TAVB_OK;
 }
-}  // namespace
-
-static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /*1 .. n_pos*/, const float* min_scores /*host, nq*/,
-                              const int32_t* d_rows, int64_t n_pos, int64_t base, int64_t max_total, int64_t* out_ords, float* out_scores,
-                              int64_t* out_counts, int64_t* out_total) {
-  ScorePlan s;
-  if (int rc = plan_score_pass(c, nq, n_pos, /*refine=*/k < n_pos, &s)) return rc;  // (k = n_pos: every survivor, nothing to refine)
-  const int nb = s.nb, rounds = s.rounds;
-  int64_t chunk;
-  const int cblocks = tavb::sorted_blocks(n_pos, &chunk);
-  const size_t head = tavb::topk_head_bytes((int)s.per, nb, rounds);
-  if (int rc = c->d_topk.reserve(head + (size_t)s.per * cblocks * sizeof(unsigned))) return rc;
-  if (int rc = c->h_sort_info.reserve((size_t)s.per * (4 + cblocks) * sizeof(int32_t))) return rc;
-  const int64_t stage = c->sort_stage_keys;
-  if (int rc = c->h_out.reserve((size_t)stage * (sizeof(int64_t) + sizeof(float)))) return rc;
-  SortedOut o{out_ords, out_scores};
+// one sorted lookup, over all its groups: the caller's outputs, the totals so far, the staging
+struct SortedRun {
+  SortedOut o;
+  int64_t* out_counts;  // [nq] of the whole batch
+  int64_t max_total, stage;
   int64_t total = 0;
   int max_rounds = 0;
-  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
-    const int n = (int)std::min<int64_t>(s.per, nq - q0);
+};
+
+int start_sorted_run(tavb_ctx* c, int64_t max_total, int64_t* out_ords, float* out_scores, int64_t* out_counts, SortedRun* r) {
+  r->o = SortedOut{out_ords, out_scores};
+  r->out_counts = out_counts;
+  r->max_total = max_total;
+  r->stage = c->sort_stage_keys;
+  return c->h_out.reserve((size_t)r->stage * (sizeof(int64_t) + sizeof(float)));
+}
+
+int end_sorted_run(tavb_ctx* c, SortedRun& r, int64_t* out_total) {
+  if (int rc = flush_staged(c, r.o, r.stage)) return rc;
+  c->last_topk_refine = r.max_rounds;
+  *out_total = r.total;
+  return TAVB_OK;
+}
+
+// the selection workspace and the pinned words of one group of up to s.per queries
+int reserve_sorted_group(tavb_ctx* c, const ScorePlan& s) {
+  int64_t chunk;
+  const int cblocks = tavb::sorted_blocks(s.n_pos, &chunk);
+  if (int rc = c->d_topk.reserve(tavb::topk_head_bytes((int)s.per, s.nb, s.rounds) + (size_t)s.per * cblocks * sizeof(unsigned))) return rc;
+  return c->h_sort_info.reserve((size_t)s.per * (4 + cblocks) * sizeof(int32_t));
+}
+
+// One group of a sorted lookup: the queries [q0, q0 + n) of the batch, n <= s.per, best k each (k = s.n_pos: every survivor), over the
+// s.n_pos positions of d_rows (null: the corpus).  member / bit0: the scoped form of run_score_pass.  remap: the results are base +
+// d_rows[position] instead of base + position.
+int sorted_group(tavb_ctx* c, const ScorePlan& s, const float* d_q, const float* min_scores /*host*/, const int32_t* d_rows, const uint8_t* member, int bit0,
+                 int q0, int n, int64_t k, int64_t base, bool remap, SortedRun& r) {
+  const int nb = s.nb, rounds = s.rounds;
+  int64_t chunk;
+  const int cblocks = tavb::sorted_blocks(s.n_pos, &chunk);
+  const size_t head = tavb::topk_head_bytes((int)s.per, nb, rounds);
+  const int64_t stage = r.stage, max_total = r.max_total;
+  SortedOut& o = r.o;
+  int64_t* const out_counts = r.out_counts;
+  int64_t& total = r.total;
+  int& max_rounds = r.max_rounds;
+  {
     unsigned* d_counts = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(c->d_topk.ptr) + head);
     tavb::TopkLaunch t{};
     t.k = (int32_t)k;
     {
       std::optional<Timed> tm;
-      if (int rc = run_score_pass(c, s, "sorted", d_q, min_scores, d_rows, q0, n, &t, &tm)) return rc;
+      if (int rc = run_score_pass(c, s, "sorted", d_q, min_scores, d_rows, q0, n, &t, &tm, member, bit0)) return rc;
       hipError_t e = tavb::launch_sorted_count(t, d_counts, c->stream);
       if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted count launch failed: %s", hipGetErrorString(e));
     }
@@ -305,7 +393,8 @@ static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /
         char* hb = reinterpret_cast<char*>(c->h_out.ptr);
         Timed tm(c, TAVB_KERNEL_TOPK);
         hipError_t e = tavb::launch_sort_decode(j, off, len, base, reinterpret_cast<int64_t*>(hb) + o.staged,
-                                                reinterpret_cast<float*>(hb + (size_t)stage * sizeof(int64_t)) + o.staged, c->stream);
+                                                reinterpret_cast<float*>(hb + (size_t)stage * sizeof(int64_t)) + o.staged, c->stream,
+                                                remap ? d_rows : nullptr, remap ? s.n_pos : 0);
         if (e != hipSuccess) return fail(TAVB_E_HIP, "sorted decode launch failed: %s", hipGetErrorString(e));
         o.staged += len;
         off += len;
@@ -313,10 +402,56 @@ static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /
     }
     total += group_total;
   }
-  if (int rc = flush_staged(c, o, stage)) return rc;
-  c->last_topk_refine = max_rounds;
-  *out_total = total;
   return TAVB_OK;
+}
+}  // namespace
+
+// remap: the results are base + d_rows[position] (the one-mask batch: corpus ordinals) instead of base + position
+static int search_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k /*1 .. n_pos*/, const float* min_scores /*host, nq*/,
+                              const int32_t* d_rows, int64_t n_pos, int64_t base, int64_t max_total, int64_t* out_ords, float* out_scores,
+                              int64_t* out_counts, int64_t* out_total, bool remap = false) {
+  ScorePlan s;
+  if (int rc = plan_score_pass(c, nq, n_pos, /*refine=*/k < n_pos, &s)) return rc;  // (k = n_pos: every survivor, nothing to refine)
+  if (int rc = reserve_sorted_group(c, s)) return rc;
+  SortedRun r;
+  if (int rc = start_sorted_run(c, max_total, out_ords, out_scores, out_counts, &r)) return rc;
+  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
+    if (int rc = sorted_group(c, s, d_q, min_scores, d_rows, nullptr, 0, q0, (int)std::min<int64_t>(s.per, nq - q0), k, base, remap, r)) return rc;
+  }
+  return end_sorted_run(c, r, out_total);
+}
+
+// ---- the same under one scope per query (tavb_search_scoped_sorted): waves and passes as in search_scoped_topk_impl, each sub-group of a
+// pass one group of the sorted route over the pass' union list -- its own synchronise, max_total check, compactions, sorts and decodes,
+// the decode going through the list to ordinal base + row.  k: 0 = every survivor; per pass it is clamped to the union's length, and
+// need = min(k, survivors of the query's own scope) is the boundary search's as it stands.  out_counts arrives zeroed.
+static int search_scoped_sorted_impl(tavb_ctx* c, const float* d_q, int nq, int64_t k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
+                                     int64_t base, int64_t max_total, int64_t* out_ords, float* out_scores, int64_t* out_counts, int64_t* out_total) {
+  const int per = scoped_topk_per_pass(c);
+  const int wave = scoped_wave_queries(c, per);
+  SortedRun r;
+  if (int rc = start_sorted_run(c, max_total, out_ords, out_scores, out_counts, &r)) return rc;
+  for (int w0 = 0; w0 < nq; w0 += wave) {
+    const int wn = std::min(wave, nq - w0);
+    ScopeWave w;
+    if (int rc = scope_wave_unions(c, wn, per, masks + w0, &w)) return rc;
+    for (int p = 0; p < w.passes; ++p) {
+      const int q0 = w0 + p * per, n = std::min(per, wn - p * per);
+      const int64_t n_pos = w.n_union[p];
+      if (n_pos == 0) continue;  // every scope of the pass is empty
+      const int32_t* list;
+      const uint8_t* member;
+      if (int rc = scope_wave_lists(c, w, p, &list, &member)) return rc;
+      const int64_t kk = (k == 0 || k > n_pos) ? n_pos : k;
+      ScorePlan s;
+      if (int rc = shape_score_pass(c, n, n_pos, /*refine=*/kk < n_pos, &s)) return rc;
+      if (int rc = reserve_sorted_group(c, s)) return rc;
+      for (int s0 = 0; s0 < n; s0 += (int)s.per) {
+        if (int rc = sorted_group(c, s, d_q, min_scores, list, member, s0, q0 + s0, (int)std::min<int64_t>(s.per, n - s0), kk, base, /*remap=*/true, r)) return rc;
+      }
+    }
+  }
+  return end_sorted_run(c, r, out_total);
 }
 
 static int check_sorted_args(tavb_ctx* c, int64_t k, int64_t max_total, const void* out_total) {
@@ -364,6 +499,112 @@ int tavb_search_subset_sorted(tavb_ctx* c, const float* query_host, const int64_
   const int64_t kk = (k == 0 || k > n_subset) ? n_subset : k;
   int64_t count = 0;
   return search_sorted_impl(c, d_q, 1, kk, &min_score, d_rows, n_subset, 0, max_total, out_positions, out_scores, &count, out_count);
+}
+
+// ---- the one-mask batch, sorted: nq queries over one resident row list, corpus ordinals out (the gather route of a masked batch)
+int tavb_search_subset_batch_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int64_t k,
+                                    const float* min_scores, int64_t max_total, int64_t* out_ordinals, float* out_scores, int64_t* out_counts,
+                                    int64_t* out_total) {
+  if (int rc = check_sorted_args(c, k, max_total, out_total)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (n_subset < 0 || n_subset >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad subset length");
+  *out_total = 0;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->masked_route = 1;  // the gather route of a masked batch
+  for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+  if (n_subset == 0 || c->rows == 0) return TAVB_OK;
+  if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  const int64_t kk = (k == 0 || k > n_subset) ? n_subset : k;
+  return search_sorted_impl(c, d_q, nq, kk, min_scores, dev_rows, n_subset, c->ordinal_base, max_total, out_ordinals, out_scores, out_counts, out_total,
+                            /*remap=*/true);
+}
+
+// ---- scoped batches beyond the fused selection: one mask per query at any max_hits (search_scoped_topk_impl, search_scoped_sorted_impl)
+static void note_scoped_large_route(tavb_ctx* c, int route) {
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->last_graph = 0;
+  c->masked_route = route;  // 7 = a scoped batch on the large-k route, 8 = on the sorted route
+}
+
+int tavb_search_scoped_topk(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                            const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, TAVB_MAX_LARGE_K, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_large_route(c, 7);
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  // (up to 4096 keys the finish kernels write into pinned memory and the remaps run there in place; more go through device memory and are
+  //  copied out once -- the rounds behind the keys in h_out stay reserved either way)
+  u64_t* target = keys;
+  if (n_keys > 4096) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_scoped_topk_impl(c, d_q, nq, k, min_scores, dev_masks, 0u, target, target, rounds)) return rc;
+  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts)) return rc;
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_scoped_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                   const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, TAVB_MAX_LARGE_K, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
+  note_scoped_large_route(c, 7);
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  // (the finish kernels write positions into d_out and the remaps turn them into ordinal_base + row on the way to out_keys: a pinned
+  //  out_keys is written once and never read over PCIe)
+  if (int rc = c->d_out.reserve((size_t)nq * k * sizeof(u64_t))) return rc;
+  if (int rc = search_scoped_topk_impl(c, dev_queries, nq, k, min_scores, dev_masks, (uint32_t)c->ordinal_base, reinterpret_cast<u64_t*>(c->d_out.ptr), out,
+                                       reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr)))
+    return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+int tavb_search_scoped_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int64_t k,
+                              const float* min_scores, int64_t max_total, int64_t* out_ordinals, float* out_scores, int64_t* out_counts,
+                              int64_t* out_total) {
+  if (int rc = check_sorted_args(c, k, max_total, out_total)) return rc;
+  bool empty = false;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, /*k: checked above*/ 1, TAVB_MAX_LARGE_K, &empty)) return rc;
+  *out_total = 0;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_large_route(c, 8);
+  for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+  if (empty) return TAVB_OK;
+  DeviceGuard guard(c->device);
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  return search_scoped_sorted_impl(c, d_q, nq, k, min_scores, dev_masks, c->ordinal_base, max_total, out_ordinals, out_scores, out_counts, out_total);
 }
 
 int tavb_sort_keys_device(tavb_ctx* c, tavb_key* dev_keys, int64_t n) {

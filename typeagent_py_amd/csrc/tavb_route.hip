@@ -134,70 +134,99 @@ int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float
 constexpr int kScopedWavePasses = 16;
 constexpr int64_t kScopedWavePositions = (int64_t)64 << 20;
 
-// one wave: nq queries (at most kScopedWavePasses passes of per_pass), every pointer at the wave's first query
-static int scoped_wave(tavb_ctx* c, const float* d_q, int nq, int k, int per_pass, const float* min_scores, const uint32_t* const* masks, uint32_t index_base,
-                       u64_t* work, u64_t* out) {
+// The unions of one wave (nq queries, at most kScopedWavePasses passes of per_pass; masks at the wave's first query): one
+// mask_combine launch per pass, the ONE synchronise of the wave, the unions' sizes and -- unless every union is empty -- the two
+// workspaces of exactly their total length.
+int scope_wave_unions(tavb_ctx* c, int nq, int per_pass, const uint32_t* const* masks, ScopeWave* w) {
   static_assert(TAVB_MAX_STREAM_QUERIES <= TAVB_MAX_MASK_OPERANDS, "a pass' masks are the operands of one mask_combine launch and the bits of one membership byte");
   const int passes = (nq + per_pass - 1) / per_pass;
   const int64_t rows = c->rows, n_words = (rows + 31) >> 5;
   const int chunks = tavb::mask_blocks(rows);
+  w->nq = nq;
+  w->per_pass = per_pass;
+  w->passes = passes;
   if (int rc = c->d_scope_bits.reserve((size_t)passes * n_words * sizeof(uint32_t))) return rc;
   if (int rc = c->d_mask_counts.reserve((size_t)passes * chunks * sizeof(unsigned))) return rc;
   constexpr size_t info_at = kScopedWavePasses * sizeof(long long);  // (fixed: the totals of an earlier, longer wave never lie under this wave's infos)
   if (int rc = c->h_scope.reserve(info_at + (size_t)passes * chunks * sizeof(tavb::MaskChunkInfo))) return rc;
   uint32_t* const bits = reinterpret_cast<uint32_t*>(c->d_scope_bits.ptr);
   unsigned* const counts = reinterpret_cast<unsigned*>(c->d_mask_counts.ptr);
-  long long* const totals = reinterpret_cast<long long*>(c->h_scope.ptr);  // (the write passes leave their totals here; nothing reads them: a pass of
-                                                                            //  an earlier wave may still be writing its own)
   tavb::MaskChunkInfo* const info = reinterpret_cast<tavb::MaskChunkInfo*>(reinterpret_cast<char*>(c->h_scope.ptr) + info_at);
   for (int i = 0; i < passes * chunks; ++i) info[i].first = -1;  // (a chunk the kernel wrote holds a row or INT32_MAX here)
-  std::vector<tavb::MaskOperands> ops((size_t)passes);
+  w->ops.assign((size_t)passes, tavb::MaskOperands{});
   {
     Timed t(c, TAVB_KERNEL_CONVERT);
     for (int p = 0; p < passes; ++p) {
       const int q0 = p * per_pass, n = std::min(per_pass, nq - q0);
-      ops[p] = tavb::MaskOperands{};
-      ops[p].n = n;
-      ops[p].op = TAVB_MASK_OR;
-      for (int j = 0; j < n; ++j) ops[p].m[j] = masks[q0 + j];
-      hipError_t e = tavb::launch_mask_combine(ops[p], rows, bits + (size_t)p * n_words, counts + (size_t)p * chunks, info + (size_t)p * chunks, c->stream);
+      w->ops[p].n = n;
+      w->ops[p].op = TAVB_MASK_OR;
+      for (int j = 0; j < n; ++j) w->ops[p].m[j] = masks[q0 + j];
+      hipError_t e = tavb::launch_mask_combine(w->ops[p], rows, bits + (size_t)p * n_words, counts + (size_t)p * chunks, info + (size_t)p * chunks, c->stream);
       if (e != hipSuccess) return fail(TAVB_E_HIP, "scope union launch failed: %s", hipGetErrorString(e));
     }
   }
   TAVB_HIP(hipStreamSynchronize(c->stream));
-  std::vector<int64_t> n_union((size_t)passes, 0), first_pos((size_t)passes, 0);
-  int64_t total = 0, most = 0;
+  w->n_union.assign((size_t)passes, 0);
+  w->first_pos.assign((size_t)passes, 0);
+  w->total = w->most = 0;
   for (int p = 0; p < passes; ++p) {
     for (int b = 0; b < chunks; ++b) {
       const tavb::MaskChunkInfo ci = info[(size_t)p * chunks + b];
       if (ci.first < 0) return fail(TAVB_E_HIP, "chunk %d of the union of pass %d wrote no info (internal error)", b, p);
-      n_union[p] += ci.count;
+      w->n_union[p] += ci.count;
     }
-    if (n_union[p] > rows) return fail(TAVB_E_HIP, "the union of pass %d counted %lld of %lld rows (internal error)", p, (long long)n_union[p], (long long)rows);
-    first_pos[p] = total;
-    total += n_union[p];
-    most = std::max(most, n_union[p]);
+    if (w->n_union[p] > rows)
+      return fail(TAVB_E_HIP, "the union of pass %d counted %lld of %lld rows (internal error)", p, (long long)w->n_union[p], (long long)rows);
+    w->first_pos[p] = w->total;
+    w->total += w->n_union[p];
+    w->most = std::max(w->most, w->n_union[p]);
   }
-  if (total == 0) return fill_empty_keys(c, out, (int64_t)nq * k);
-  if (int rc = c->d_scope_rows.reserve((size_t)total * sizeof(int32_t))) return rc;
-  if (int rc = c->d_scope_member.reserve((size_t)total)) return rc;
+  if (w->total == 0) return TAVB_OK;
+  if (int rc = c->d_scope_rows.reserve((size_t)w->total * sizeof(int32_t))) return rc;
+  return c->d_scope_member.reserve((size_t)w->total);
+}
+
+// The row list and the membership bytes of pass p (its union is not empty): the write pass and scope_member, enqueued.
+int scope_wave_lists(tavb_ctx* c, const ScopeWave& w, int p, const int32_t** list_out, const uint8_t** member_out) {
+  const int64_t rows = c->rows, n_words = (rows + 31) >> 5;
+  const int chunks = tavb::mask_blocks(rows);
+  const uint32_t* const bits = reinterpret_cast<const uint32_t*>(c->d_scope_bits.ptr);
+  const unsigned* const counts = reinterpret_cast<const unsigned*>(c->d_mask_counts.ptr);
+  long long* const totals = reinterpret_cast<long long*>(c->h_scope.ptr);  // (the write passes leave their totals here; nothing reads them: a pass of
+                                                                            //  an earlier wave may still be writing its own)
+  int32_t* const list = reinterpret_cast<int32_t*>(c->d_scope_rows.ptr) + w.first_pos[p];
+  uint8_t* const member = reinterpret_cast<uint8_t*>(c->d_scope_member.ptr) + w.first_pos[p];
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  hipError_t e = tavb::launch_mask_write(bits + (size_t)p * n_words, rows, counts + (size_t)p * chunks, list, w.n_union[p], totals + p, c->stream);
+  if (e == hipSuccess) e = tavb::launch_scope_member(w.ops[p], list, w.n_union[p], rows, member, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "scope list launch failed: %s", hipGetErrorString(e));
+  *list_out = list;
+  *member_out = member;
+  return TAVB_OK;
+}
+
+int scoped_wave_queries(const tavb_ctx* c, int per_pass) {
+  return per_pass * (int)std::min<int64_t>(kScopedWavePasses, std::max<int64_t>(1, kScopedWavePositions / std::max<int64_t>(c->rows, 1)));
+}
+
+// one wave: nq queries (at most kScopedWavePasses passes of per_pass), every pointer at the wave's first query
+static int scoped_wave(tavb_ctx* c, const float* d_q, int nq, int k, int per_pass, const float* min_scores, const uint32_t* const* masks, uint32_t index_base,
+                       u64_t* work, u64_t* out) {
+  ScopeWave w;
+  if (int rc = scope_wave_unions(c, nq, per_pass, masks, &w)) return rc;
+  if (w.total == 0) return fill_empty_keys(c, out, (int64_t)nq * k);
   tavb::ScanGeometry g = clamped_geometry(c);
-  if (int rc = c->d_lists.reserve((size_t)per_pass * scan_blocks_for(c, most, g.waves, g.unroll) * k * sizeof(u64_t))) return rc;
-  for (int p = 0; p < passes; ++p) {
+  if (int rc = c->d_lists.reserve((size_t)per_pass * scan_blocks_for(c, w.most, g.waves, g.unroll) * k * sizeof(u64_t))) return rc;
+  for (int p = 0; p < w.passes; ++p) {
     const int q0 = p * per_pass, n = std::min(per_pass, nq - q0);
-    const int64_t n_pos = n_union[p];
+    const int64_t n_pos = w.n_union[p];
     if (n_pos == 0) {  // every scope of the pass is empty
       if (int rc = fill_empty_keys(c, out + (size_t)q0 * k, (int64_t)n * k)) return rc;
       continue;
     }
-    int32_t* const list = reinterpret_cast<int32_t*>(c->d_scope_rows.ptr) + first_pos[p];
-    uint8_t* const member = reinterpret_cast<uint8_t*>(c->d_scope_member.ptr) + first_pos[p];
-    {
-      Timed t(c, TAVB_KERNEL_CONVERT);
-      hipError_t e = tavb::launch_mask_write(bits + (size_t)p * n_words, rows, counts + (size_t)p * chunks, list, n_pos, totals + p, c->stream);
-      if (e == hipSuccess) e = tavb::launch_scope_member(ops[p], list, n_pos, rows, member, c->stream);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "scope list launch failed: %s", hipGetErrorString(e));
-    }
+    const int32_t* list;
+    const uint8_t* member;
+    if (int rc = scope_wave_lists(c, w, p, &list, &member)) return rc;
     g.blocks = scan_blocks_for(c, n_pos, g.waves, g.unroll);
     tavb::ScanParams sp = scan_params(c, d_q + (size_t)q0 * c->dim, list, n_pos, n, k, 0u, ~0ull, reinterpret_cast<u64_t*>(c->d_lists.ptr), min_scores + q0,
                                       TAVB_MAX_STREAM_QUERIES);
@@ -220,8 +249,7 @@ static int scoped_wave(tavb_ctx* c, const float* d_q, int nq, int k, int per_pas
 int search_scoped_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores, const uint32_t* const* masks, uint32_t index_base, u64_t* work,
                        u64_t* out) {
   const int per_pass = tavb::scoped_queries_per_pass(c->corpus, c->dim, c->dtype, k, clamped_geometry(c));
-  const int wave_passes = (int)std::min<int64_t>(kScopedWavePasses, std::max<int64_t>(1, kScopedWavePositions / std::max<int64_t>(c->rows, 1)));
-  const int wave = wave_passes * per_pass;
+  const int wave = scoped_wave_queries(c, per_pass);
   for (int q0 = 0; q0 < nq; q0 += wave) {
     if (int rc = scoped_wave(c, d_q + (size_t)q0 * c->dim, std::min(wave, nq - q0), k, per_pass, min_scores + q0, masks + q0, index_base, work + (size_t)q0 * k,
                              out + (size_t)q0 * k))

@@ -181,6 +181,29 @@ struct ScopedSelector : Selector<NQ, KPL> {
   }
 };
 
+// The epilogue of the score pass of a scoped large-k or sorted batch (launch_scan_topk_scoped): the ScoreSink over the union list of the pass,
+// with the ScopedSelector's test in front -- query q of the launch is member bit `bit0 + q` (the launch's queries may be a sub-group of the
+// pass whose membership bytes these are).  Bit set: the ScoreSink's own offer.  Bit clear: kScoreNone, nothing counted, no wave reduction.
+// Every (query, position) slot of the score array is written either way, so the passes over it see members only.
+template <int NQ>
+struct ScopedScoreSink : ScoreSink<NQ> {
+  static constexpr bool kScoped = true;
+  const uint8_t* member;  // [n_pos]
+  int bit0;
+
+  __device__ __forceinline__ void setup(const ScanParams& p, const QueryGroup& qg, void* lds) {
+    ScoreSink<NQ>::setup(p, qg, lds);
+    bit0 = p.scope_bit0;
+  }
+  __device__ __forceinline__ void offer(int q, float partial, uint32_t index, float min_score, int k, int lane, u64 bound) {
+    const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)member[index]) >> bit0;  // (index_base is 0: the index IS the position)
+    if ((m >> q) & 1u)  // wave-uniform
+      ScoreSink<NQ>::offer(q, partial, index, min_score, k, lane, bound);
+    else if (q < this->n_live && lane == 0)
+      this->scores[(size_t)q * this->n_pos + index] = kScoreNone;
+  }
+};
+
 template <int NQ, int KPL, typename SEL>
 __device__ __forceinline__ void start_epilogue(SEL& sel, const ScanParams& p, const QueryGroup& qg, void* lds) {
   if constexpr (SEL::kScorePass) sel.setup(p, qg, lds);
@@ -732,19 +755,19 @@ constexpr size_t kTopkLdsBudget = 150 * 1024;
 
 inline size_t topk_vec_lds(int nqt, int dim, int buckets) { return (((size_t)nqt * dim * sizeof(float)) + 15 & ~(size_t)15) + (size_t)nqt * buckets * 4; }
 
-template <typename T, int NQ>
+template <typename T, int NQ, typename SINK = ScoreSink<NQ>>
 hipError_t go_topk_vec(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
   const size_t lds = topk_vec_lds(NQ, p.dim, p.topk_buckets);
-  auto kern = scan_vec_kernel<T, NQ, 1, true, ScoreSink<NQ>>;
+  auto kern = scan_vec_kernel<T, NQ, 1, true, SINK>;
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
   hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
   return hipGetLastError();
 }
 
-template <typename T, int NQ>
+template <typename T, int NQ, typename SINK = ScoreSink<NQ>>
 hipError_t go_topk_scalar(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
   const size_t lds = (size_t)NQ * p.topk_buckets * 4;
-  auto kern = scan_scalar_kernel<T, NQ, 1, ScoreSink<NQ>>;
+  auto kern = scan_scalar_kernel<T, NQ, 1, SINK>;
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
   hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p);
   return hipGetLastError();
@@ -759,18 +782,18 @@ hipError_t go_topk_fixed(const ScanParams& p, const ScanGeometry& g, hipStream_t
   return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, template <int> class SINK = ScoreSink>
 hipError_t dispatch_topk(const ScanParams& p, const ScanGeometry& g, hipStream_t s, int tier, int nqt) {
   if (tier == 2) {
-    if (nqt == 1) return go_topk_vec<T, 1>(p, g, s);
-    if (nqt == 2) return go_topk_vec<T, 2>(p, g, s);
-    if (nqt == 4) return go_topk_vec<T, 4>(p, g, s);
-    return go_topk_vec<T, 8>(p, g, s);
+    if (nqt == 1) return go_topk_vec<T, 1, SINK<1>>(p, g, s);
+    if (nqt == 2) return go_topk_vec<T, 2, SINK<2>>(p, g, s);
+    if (nqt == 4) return go_topk_vec<T, 4, SINK<4>>(p, g, s);
+    return go_topk_vec<T, 8, SINK<8>>(p, g, s);
   }
-  if (nqt == 1) return go_topk_scalar<T, 1>(p, g, s);
-  if (nqt == 2) return go_topk_scalar<T, 2>(p, g, s);
-  if (nqt == 4) return go_topk_scalar<T, 4>(p, g, s);
-  return go_topk_scalar<T, 8>(p, g, s);
+  if (nqt == 1) return go_topk_scalar<T, 1, SINK<1>>(p, g, s);
+  if (nqt == 2) return go_topk_scalar<T, 2, SINK<2>>(p, g, s);
+  if (nqt == 4) return go_topk_scalar<T, 4, SINK<4>>(p, g, s);
+  return go_topk_scalar<T, 8, SINK<8>>(p, g, s);
 }
 
 }  // namespace
@@ -799,6 +822,25 @@ hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStrea
   if (tier_used) *tier_used = tier;
   if (tier == 1) return f16 ? go_topk_fixed<_Float16, 3>(p, g, stream) : go_topk_fixed<float, 6>(p, g, stream);
   return f16 ? dispatch_topk<_Float16>(p, g, stream, tier, nqt) : dispatch_topk<float>(p, g, stream, tier, nqt);
+}
+
+// The scoped form of that score pass (tavb_search_scoped_topk / _sorted): p.row_ids is the ascending union list of the pass, p.scope_member its
+// membership bytes, and the launch's queries are the member bits p.scope_bit0 .. p.scope_bit0 + p.nq - 1.  The vector tier for aligned rows,
+// the scalar tier otherwise -- launch_scan_topk's rule, except that ONE aligned 1536-wide query takes the vector tier as well (tier 1 has no
+// scoped form; the per-row arithmetic of tiers 1 and 2 is the same), so every member's score is the unscoped pass' score bit for bit.
+hipError_t launch_scan_topk_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used) {
+  if (p.nq < 1 || p.nq > TAVB_MAX_STREAM_QUERIES || p.group != 0 || p.dim < 1 || p.index_base != 0 || !p.topk_scores || !p.topk_hist ||
+      p.topk_buckets < 64 || p.topk_buckets % 64 != 0 || !p.row_ids || !p.scope_member || p.scope_bit0 < 0 || p.scope_bit0 + p.nq > 8)
+    return hipErrorInvalidValue;
+  const bool f16 = p.dtype == TAVB_F16;
+  const int epl = f16 ? 8 : 4;
+  const bool aligned = ((uintptr_t)p.corpus % 16) == 0 && (p.dim % epl) == 0;
+  const int nqt = p.nq <= 1 ? 1 : p.nq <= 2 ? 2 : p.nq <= 4 ? 4 : 8;
+  const int tier = aligned ? 2 : 3;
+  if (tier == 2 && topk_vec_lds(nqt, p.dim, p.topk_buckets) > kTopkLdsBudget) return hipErrorInvalidValue;  // (topk_queries_per_pass sizes the groups)
+  if (tier == 3 && (size_t)nqt * p.topk_buckets * 4 > kTopkLdsBudget) return hipErrorInvalidValue;
+  if (tier_used) *tier_used = tier;
+  return f16 ? dispatch_topk<_Float16, ScopedScoreSink>(p, g, stream, tier, nqt) : dispatch_topk<float, ScopedScoreSink>(p, g, stream, tier, nqt);
 }
 
 // ---------------------------------------------------------------------------

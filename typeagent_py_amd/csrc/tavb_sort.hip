@@ -193,11 +193,14 @@ __global__ void __launch_bounds__(1024) sort_small_kernel(u64* keys, int n) {
 
 // sorted keys [off, off + len) -> ordinal (position + base) and score of each, at ords / scs [0, len)
 __global__ void __launch_bounds__(256) sort_decode_kernel(const u64* b0, const u64* b1, const int* which, int64_t off, int64_t len, int64_t base,
-                                                          int64_t* __restrict__ ords, float* __restrict__ scs) {
+                                                          int64_t* __restrict__ ords, float* __restrict__ scs, const int32_t* __restrict__ map,
+                                                          int64_t map_len) {
   const u64* __restrict__ src = (which && *which) ? b1 : b0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x) {
     const u64 key = src[off + i];
-    ords[i] = (int64_t)(0xFFFFFFFFu - (uint32_t)key) + base;
+    int64_t pos = (int64_t)(0xFFFFFFFFu - (uint32_t)key);
+    if (map) pos = pos < map_len ? (int64_t)map[pos] : -1 - base;  // (a position outside the list: ordinal -1, never a read past it)
+    ords[i] = pos + base;
     scs[i] = __uint_as_float((uint32_t)(key >> 32));
   }
 }
@@ -273,7 +276,8 @@ hipError_t launch_sort_desc(SortJob& j, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_sort_decode(const SortJob& j, int64_t off, int64_t len, int64_t base, int64_t* ords, float* scs, hipStream_t stream) {
+hipError_t launch_sort_decode(const SortJob& j, int64_t off, int64_t len, int64_t base, int64_t* ords, float* scs, hipStream_t stream, const int32_t* map,
+                              int64_t map_len) {
   if (off < 0 || len < 1 || off + len > j.n || !ords || !scs) return hipErrorInvalidValue;
   const u64* alt = j.keys;
   const int* which = nullptr;
@@ -282,7 +286,7 @@ hipError_t launch_sort_decode(const SortJob& j, int64_t off, int64_t len, int64_
     alt = a.ws.alt;
     which = a.ws.plan + 8;
   }
-  hipLaunchKernelGGL(sort_decode_kernel, dim3(grid_for(len, 4 * 256)), dim3(256), 0, stream, j.keys, alt, which, off, len, base, ords, scs);
+  hipLaunchKernelGGL(sort_decode_kernel, dim3(grid_for(len, 4 * 256)), dim3(256), 0, stream, j.keys, alt, which, off, len, base, ords, scs, map, map_len);
   return hipGetLastError();
 }
 

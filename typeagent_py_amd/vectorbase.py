@@ -1063,8 +1063,10 @@ class VectorBase:
         for e in embeddings].  On a single-GPU engine with 1 <= max_hits <= 16384 (beyond 256: while the "large_k" option is on, as for
         every other lookup) it is one submission -- the queries go over the
         mask's resident row list eight per pass -- and with a `RowMask` only the queries travel; a device group does the same on every
-        shard that has allowed rows (one batched call per shard, merged on the host); everything else (max_hits == 0 or
-        beyond 16384, "large_k" off beyond 256, test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
+        shard that has allowed rows (one batched call per shard, merged on the host).  max_hits == 0 and beyond 16384 are one submission
+        on a single-GPU engine as well, on the device sort route over the same row list (tavb_search_subset_batch_sorted, while
+        "sort_all" is on); everything else ("large_k" off beyond 256, "sort_all" off, max_hits == 0 or beyond 16384 on a device group,
+        test doubles) loops over `fuzzy_lookup_embedding_in_subset`.  `min_score` may be a sequence with one
         threshold per query; `as_arrays=True` (1 <= max_hits <= 256) as in `fuzzy_lookup_embeddings`.
 
         A DENSE mask under a real batch (1 <= max_hits <= 64, rows of a multiple of 64 bytes; engine option "mask_tile": by default from
@@ -1097,6 +1099,9 @@ class VectorBase:
             else:
                 out = eng.search_subset_batch_resident(queries, mask.dev_rows, max_hits, thr, remap=True)
             return self._batch_result(*out, max_hits, as_arrays, base=eng.ordinal_base)
+        if self._masked_native(eng) and mask.dev_rows is not None and hasattr(eng, "search_subset_batch_sorted") and self._sort_all(eng, max_hits):
+            ords, scs, cnts = eng.search_subset_batch_sorted(queries, mask.dev_rows, max_hits, thr)
+            return _sorted_lists(ords - eng.ordinal_base, scs, cnts)
         if self._masked_group(eng) and mask.shards is not None and (1 <= max_hits <= _PAGE or self._large_k(eng, max_hits)):
             if mask.bounds != tuple(eng.bounds):
                 # the same index at the same length under other shard bounds (grown row by row, then re-uploaded from row 0): the
@@ -1150,6 +1155,18 @@ class VectorBase:
         packed mask on the device."""
         return (isinstance(eng, _native.Engine) and hasattr(eng, call) and 1 <= max_hits <= _PAGE
                 and all(handles[i].dev_bits is not None for i in order))
+
+    @classmethod
+    def _scoped_large(cls, eng, handles, order, max_hits: int):
+        """The one-call route of a scoped batch beyond the fused selection, by the name of its Engine method, or None (the loop over the
+        per-query masked lookups): "search_scoped_topk" for max_hits 257 .. 16384 where `_large_k` holds, "search_scoped_sorted" for
+        max_hits == 0 and beyond 16384 where `_sort_all` holds -- on a single-GPU engine that has the call, with the option
+        "scope_large_k" on and every searched scope holding its packed mask on the device."""
+        call = ("search_scoped_topk" if cls._large_k(eng, max_hits) else
+                "search_scoped_sorted" if cls._sort_all(eng, max_hits) else None)
+        if call is None or not hasattr(eng, call) or any(handles[i].dev_bits is None for i in order):
+            return None
+        return call if eng.get_option("scope_large_k") != 0 else None
 
     @staticmethod
     def _scoped_tile(eng, call: str, handles, order, max_hits: int):
@@ -1234,8 +1251,16 @@ class VectorBase:
         path, and the candidates are scored again with the streaming kernels' arithmetic -- the answers of the row-list route BIT FOR
         BIT, at max_hits up to 256.  `engine.get_option("masked_route")` is then 6.
 
-        Everything else loops over `fuzzy_lookup_embedding_masked`: max_hits == 0 and max_hits > 256, device groups, `ShardedVectorBase`,
-        test doubles, and a handle without a device mask.  The tile routes serve single-GPU engines only: device groups,
+        Beyond 256 the batch stays ONE submission on a single-GPU engine whose scopes all hold their device mask (engine option
+        "scope_large_k", default 1): max_hits 257 .. 16384 (while "large_k" is on) runs the exact device top-k under scopes
+        (tavb_search_scoped_topk) and max_hits == 0 or beyond 16384 (while "sort_all" is on) the device sort (tavb_search_scoped_sorted:
+        every survivor of the query's own scope, or its best max_hits) -- the same passes of eight queries over the union of their scopes,
+        a row scored for a query only inside that query's scope, answers bit for bit those of the per-query calls.
+        `engine.get_option("masked_route")` is then 7 and 8.
+
+        Everything else loops over `fuzzy_lookup_embedding_masked`: "scope_large_k", "large_k" or "sort_all" switched off, device groups,
+        `ShardedVectorBase`, `FusedIndexQuery`, test doubles, and a handle without a device mask; so does
+        `lookup_messages_by_embeddings_scoped` at max_matches above 256.  The tile routes serve single-GPU engines only: device groups,
         `ShardedVectorBase` and `FusedIndexQuery` do not take them; max_hits 65 .. 256 is served on the 128/256-query tile only (fp16
         corpora), and queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_hits, min_score)
@@ -1265,6 +1290,21 @@ class VectorBase:
             ords, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
             ords[order], scs[order], cnts[order] = o - eng.ordinal_base, s, c
             return (ords, scs, cnts) if as_arrays else _scored_lists(ords, scs, cnts, max_hits)
+        large = self._scoped_large(eng, handles, order, max_hits)
+        if large is not None:
+            t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
+            sub_q, sub_t, masks = np.ascontiguousarray(queries[order]), np.ascontiguousarray(t[order]), [handles[i].dev_bits for i in order]
+            if large == "search_scoped_topk":
+                o, s, c = eng.search_scoped_topk(sub_q, masks, max_hits, sub_t)
+                ords, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+                ords[order], scs[order], cnts[order] = o - eng.ordinal_base, s, c
+                return _scored_lists(ords, scs, cnts, max_hits)
+            bound = sum(handles[i].count if max_hits == 0 else min(max_hits, handles[i].count) for i in order)
+            o, s, c = eng.search_scoped_sorted(sub_q, masks, max_hits, sub_t, bound)
+            lists = [[] for _ in range(nq)]
+            for i, hits in zip(order, _sorted_lists(o - eng.ordinal_base, s, c)):
+                lists[i] = hits
+            return lists
         lists = [self.fuzzy_lookup_embedding_masked(q, handles[i], max_hits, min_score if per_query is None else per_query[i]) for i, q in enumerate(queries)]
         return self._lists_as_arrays(lists, max_hits) if as_arrays else lists
 
