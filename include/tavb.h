@@ -68,6 +68,10 @@ extern "C" {
 #define TAVB_MASK_OR 1
 #define TAVB_MASK_ANDNOT 2
 #define TAVB_SCOPE_LDS_RANGES 1024
+/* The edits tavb_mask_remap carries masks through. */
+#define TAVB_REMAP_REMOVE 0
+#define TAVB_REMAP_INSERT 1
+#define TAVB_REMAP_APPEND 2
 
 typedef struct tavb_ctx tavb_ctx;
 
@@ -548,6 +552,37 @@ int tavb_mask_from_ranges(tavb_ctx* ctx, const int64_t* ranges_host, const int32
                           int64_t rows, uint32_t* dev_bits_out, int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
 int tavb_mask_combine(tavb_ctx* ctx, int32_t op, const uint32_t* const* dev_masks, int32_t n_masks, int64_t rows, uint32_t* dev_bits_out,
                       int32_t* dev_rows_out, int64_t cap, tavb_mask_info* out_info);
+
+/* ---- masks carried through a row edit: np.delete / np.insert of packed masks under the edit's packed flags, on the device ------------------
+ * tavb_mask_remap pushes 1 <= n_masks <= TAVB_MAX_MASK_OPERANDS masks in the bit form above through ONE edit of the row space, in one
+ * submission on the context's stream.  dev_masks / dev_bits_out: HOST arrays of n_masks device pointers (tavb_mask_combine's convention);
+ * mask j is read from dev_masks[j] over old_rows rows and written to dev_bits_out[j] over new_rows rows.
+ *   TAVB_REMAP_REMOVE  dev_flags covers old_rows, a SET bit means the row goes (tavb_compact_rows' mask).  The kept rows are numbered
+ *                      k = 0, 1, .. in ascending order and output bit k is the input bit of the k-th kept row.  new_rows must equal the
+ *                      number of clear flag bits below old_rows, else TAVB_E_INVALID.
+ *   TAVB_REMAP_INSERT  dev_flags covers new_rows, a SET bit means a hole (tavb_expand_rows' mask).  Output bit p is `fill` (0 or non-zero)
+ *                      where flag p is set, else input bit p - popcount(flags[0, p)).  The clear bits must number old_rows, else
+ *                      TAVB_E_INVALID.
+ *   TAVB_REMAP_APPEND  no flags (dev_flags is ignored).  Output bits [0, old_rows) are the input's, bits [old_rows, new_rows) are `fill`.
+ * The flags are counted and checked first (the call's first synchronise): a mismatch returns before any output is written.  Input bits at
+ * or beyond old_rows are ignored (they may hold anything; with old_rows == 0 the input pointers may be NULL); every word of (new_rows +
+ * 31) / 32 of every output is written, the bits at or beyond new_rows ZERO.  An output overlaps neither the flags nor any input nor
+ * another output (TAVB_E_INVALID): the removal flags may be one of the carried masks, and tavb_compact_rows reads them afterwards.  The
+ * masks need not be the corpus' length -- the call does not look at the corpus, so it may run before or after the edit itself.  new_rows
+ * == 0 is legal: empty infos, nothing written.  The result is deterministic, and no workgroup waits for another: the popcount prefix over
+ * the flags is the per-chunk counts of tavb_compact_rows' count pass, made once per call and shared by all masks, and a workgroup sums
+ * the counts in front of its chunk itself.  A lane squeezes (REMOVE) or spreads (INSERT) its word of every mask under its flag word in
+ * registers.  REMOVE: a workgroup owns a chunk of input words; a lane's piece straddles at most two output words, the pieces of a chunk
+ * are assembled by OR in LDS and only the first and last word of a chunk's output -- the ones two chunks may share -- go through a
+ * global atomic OR on zeroed output.  INSERT / APPEND: a workgroup owns a chunk of output words and gathers its source bits; plain stores.
+ * Per output the call leaves what tavb_mask_combine leaves: out_info[j] = its count and span (an empty mask: 0, 0, -1), and the per-chunk
+ * counts tavb_mask_expand's write pass needs -- so with dev_rows_out != NULL, dev_rows_out[j] != NULL and caps[j] > 0 the set rows of output
+ * j follow in ascending order in dev_rows_out[j] [0, count) at the cost of ONE more launch; caps[j] bounds the count (REMOVE: at most the
+ * input's count; INSERT / APPEND: exactly the input's count, plus the number of new rows when fill is set), a smaller one returns
+ * TAVB_E_INVALID with out_info filled and nothing written at or beyond it.  Two synchronises in all; timed under TAVB_KERNEL_CONVERT. */
+int tavb_mask_remap(tavb_ctx* ctx, int32_t mode, const uint32_t* dev_flags, int64_t old_rows, int64_t new_rows, const uint32_t* const* dev_masks,
+                    uint32_t* const* dev_bits_out, int32_t n_masks, int32_t fill, int32_t* const* dev_rows_out, const int64_t* caps,
+                    tavb_mask_info* out_info);
 
 /* ---- scoped batches: one row mask PER QUERY in a single submission ----------------------------------------------------------------------
  * A compiled question is a handful of lookups, each under its own scope (a time range, a thread, a set of messages): query q searches the

@@ -28,6 +28,7 @@ MASK_ROWS_PER_WORKGROUP = 16384  # TAVB_MASK_ROWS_PER_WORKGROUP: rows of a mask 
 MAX_SCOPE_COLLECTIONS = 8
 MAX_MASK_OPERANDS = 8
 MASK_AND, MASK_OR, MASK_ANDNOT = 0, 1, 2
+REMAP_REMOVE, REMAP_INSERT, REMAP_APPEND = 0, 1, 2  # TAVB_REMAP_*: the edits tavb_mask_remap carries masks through
 SCOPE_LDS_RANGES = 1024
 MAX_SCOPE_RANGES = 1 << 20
 SCOPE_DOMAINS = {"rows": 0, "messages": 1}
@@ -101,6 +102,7 @@ _SIGNATURES = [
     ("tavb_search_messages_batch", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_mask_from_ranges", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_mask_combine", c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_mask_remap", c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_scoped_batch", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_scoped_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_search_messages_scoped", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -1127,6 +1129,59 @@ class Engine:
         bits_ptr = c_void_p(bits.data_ptr()) if rows else None
         return self._mask_algebra(lambda out_ptr, n, info: self.lib.tavb_mask_combine(self._h, int(op), ptrs, len(masks), rows, bits_ptr, out_ptr, n, info),
                                   bits, cap)
+
+    def mask_remap(self, mode: int, dev_flags, old_rows: int, new_rows: int, dev_bits_list, fill, counts=None):
+        """1 .. 8 packed masks carried through one row edit on the device (tavb_mask_remap) -> per mask the quadruple of `mask_combine`:
+        (dev_rows, count, dev_bits, span) over `new_rows` rows, in fresh tensors.  mode REMAP_REMOVE: `dev_flags` (torch int32 on this
+        device, the layout of `pack_mask_bits`) covers `old_rows`, a set bit removes the row -- np.delete of every mask; `new_rows` must be
+        the number of clear bits.  REMAP_INSERT: `dev_flags` covers `new_rows`, a set bit is a hole that takes `fill` -- np.insert; the
+        clear bits must number `old_rows`.  REMAP_APPEND: `dev_flags` is None, rows [old_rows, new_rows) take `fill`.  A mismatch raises
+        ValueError before anything is written.  Bits of the inputs at or beyond `old_rows` are ignored.  `counts`: the inputs' counts
+        when the caller knows them -- they bound the row lists; without them every list is allocated at `new_rows` first."""
+        torch = self._torch
+        masks = list(dev_bits_list)
+        mode, old_rows, new_rows, fill = int(mode), int(old_rows), int(new_rows), bool(fill)
+        if mode not in (REMAP_REMOVE, REMAP_INSERT, REMAP_APPEND):
+            raise ValueError(f"mode must be REMAP_REMOVE, REMAP_INSERT or REMAP_APPEND, got {mode}")
+        if not 1 <= len(masks) <= MAX_MASK_OPERANDS:
+            raise ValueError(f"a remap carries 1 .. {MAX_MASK_OPERANDS} masks (got {len(masks)})")
+        if old_rows < 0 or new_rows < 0 or (new_rows > old_rows if mode == REMAP_REMOVE else new_rows < old_rows):
+            raise ValueError(f"an edit of mode {mode} cannot take {old_rows} rows to {new_rows}")
+        if counts is not None and len(counts) != len(masks):
+            raise ValueError(f"{len(counts)} counts for {len(masks)} masks")
+        flag_rows = old_rows if mode == REMAP_REMOVE else new_rows if mode == REMAP_INSERT else 0
+        if flag_rows:
+            self._check_device_words(dev_flags, "the flags")
+            if dev_flags.numel() * 32 < flag_rows:
+                raise ValueError(f"the flags hold {dev_flags.numel()} words, {flag_rows} rows need {(flag_rows + 31) // 32}")
+        for i, m in enumerate(masks):
+            self._check_device_words(m, f"mask {i}")
+            if m.numel() * 32 < old_rows:
+                raise ValueError(f"mask {i} holds {m.numel()} words, {old_rows} rows need {(old_rows + 31) // 32}")
+        dev = torch.device("cuda", self.device)
+        n, grown = len(masks), (new_rows - old_rows if fill else 0)
+        if counts is None:
+            bounds = [new_rows] * n
+        else:  # a removal only takes rows away; an insertion adds exactly the new rows, where they are set
+            bounds = [min(int(c) + grown, new_rows) for c in counts]
+        outs = [torch.empty((new_rows + 31) // 32, dtype=torch.int32, device=dev) for _ in masks]
+        lists = [torch.empty(b, dtype=torch.int32, device=dev) for b in bounds]
+        in_ptrs = (c_void_p * n)(*[m.data_ptr() if m.numel() else None for m in masks])
+        out_ptrs = (c_void_p * n)(*[o.data_ptr() if o.numel() else None for o in outs])
+        list_ptrs = (c_void_p * n)(*[r.data_ptr() if r.numel() else None for r in lists])
+        caps = (c_int64 * n)(*bounds)
+        infos = (MaskInfo * n)()
+        torch.cuda.current_stream(self.device).synchronize()  # whatever produced the masks (and the allocations above) ran on torch's stream
+        with self._lock:
+            rc = self.lib.tavb_mask_remap(self._h, mode, c_void_p(dev_flags.data_ptr()) if flag_rows else None, old_rows, new_rows, in_ptrs, out_ptrs, n,
+                                          int(fill), list_ptrs, caps, infos)
+        _check(self.lib, rc)
+        result = []
+        for out, rows_out, bound, info in zip(outs, lists, bounds, infos):
+            cnt = int(info.count)
+            dev_rows = rows_out[:cnt].clone() if bound > 2 * cnt else rows_out[:cnt]
+            result.append((dev_rows, cnt, out, (int(info.first_row), int(info.last_row)) if cnt else None))
+        return result
 
     def search_messages_masked(self, queries, dev_bits, dev_rows, k: int, thrs, max_messages: int, route: int, span=None):
         """A masked batch aggregated to messages in one submission (tavb_search_messages_masked): the arguments of `search_masked_wide`

@@ -189,6 +189,22 @@ struct MaskOperands {
 hipError_t launch_mask_from_ranges(const int32_t* intervals, const ScopeCollections& cols, const int32_t* row_to_msg, int64_t n_messages, int64_t rows,
                                    uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
 hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* bits, unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
+// Masks carried through a row edit (tavb_mask.hip; tavb_mask_remap): operand j is read from in[j] (old_rows rows; bits at or beyond them may hold
+// anything; may be NULL when old_rows == 0) and written to out[j] (every word of new_rows rows, tail bits zero), which overlaps no input and not
+// the flags.  squeeze: REMOVE -- flags over old_rows, set = the row goes; kept_counts: launch_compact_count's over them, and the kept rows must
+// number new_rows (the caller has checked).  Memset + two launches.  spread: INSERT -- flags over new_rows, set = a hole that takes `fill`;
+// clear_counts: launch_compact_count's over them, and the clear bits must number old_rows -- or, flags == NULL, APPEND: the holes are the rows
+// [old_rows, new_rows).  One launch.  Both leave counts[j * mask_blocks(new_rows) + chunk] (launch_mask_write's input) and info[the same]
+// (device-writable memory) per output.  1 <= new_rows; nothing waits on another workgroup.
+struct RemapOperands {
+  const uint32_t* in[TAVB_MAX_MASK_OPERANDS];
+  uint32_t* out[TAVB_MAX_MASK_OPERANDS];
+  int32_t n;
+};
+hipError_t launch_mask_remap_squeeze(const RemapOperands& ops, const uint32_t* flags, const unsigned* kept_counts, int64_t old_rows, int64_t new_rows,
+                                     unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
+hipError_t launch_mask_remap_spread(const RemapOperands& ops, const uint32_t* flags, const unsigned* clear_counts, int64_t old_rows, int64_t new_rows, bool fill,
+                                    unsigned* counts, MaskChunkInfo* info, hipStream_t stream);
 // mask_expand's second launch alone, over counts one of the two kernels above (or its own count pass) wrote
 hipError_t launch_mask_write(const uint32_t* bits, int64_t rows, const unsigned* counts, int32_t* out, int64_t cap, long long* total_out,
                              hipStream_t stream);

@@ -631,6 +631,109 @@ int tavb_mask_combine(tavb_ctx* c, int32_t op, const uint32_t* const* dev_masks,
   return algebra_collect(c, o, dev_rows_out, cap, out_info);
 }
 
+// ---- masks carried through a row edit (the kernels are tavb_mask.hip's).  The count pass over the flags and ONE synchronise for the check
+// that they describe an edit from old_rows to new_rows -- before anything is written -- then the remap, one write pass per row list that is
+// asked for, and a second synchronise for the outputs' counts and spans.  Pinned (h_out): a total per mask, the flags' chunk infos, every
+// output's chunk infos.
+int tavb_mask_remap(tavb_ctx* c, int32_t mode, const uint32_t* dev_flags, int64_t old_rows, int64_t new_rows, const uint32_t* const* dev_masks,
+                    uint32_t* const* dev_bits_out, int32_t n_masks, int32_t fill, int32_t* const* dev_rows_out, const int64_t* caps, tavb_mask_info* out_info) {
+  if (int rc = check_ctx(c)) return rc;
+  if (n_masks < 1 || n_masks > TAVB_MAX_MASK_OPERANDS) return fail(TAVB_E_INVALID, "a remap carries 1 .. %d masks (got %d)", TAVB_MAX_MASK_OPERANDS, n_masks);
+  if (!out_info) return fail(TAVB_E_INVALID, "null argument");
+  for (int j = 0; j < n_masks; ++j) empty_mask_info(&out_info[j]);
+  if (mode < TAVB_REMAP_REMOVE || mode > TAVB_REMAP_APPEND) return fail(TAVB_E_INVALID, "mode must be 0 (remove), 1 (insert) or 2 (append), got %d", mode);
+  if (old_rows < 0 || old_rows >= 0x7FFFFFFFll || new_rows < 0 || new_rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "rows must be 0 .. 2^31 - 2");
+  if (mode == TAVB_REMAP_REMOVE ? new_rows > old_rows : new_rows < old_rows)
+    return fail(TAVB_E_INVALID, "%s %lld rows cannot leave %lld", mode == TAVB_REMAP_REMOVE ? "a removal from" : "an insertion into", (long long)old_rows, (long long)new_rows);
+  const int64_t flag_rows = mode == TAVB_REMAP_REMOVE ? old_rows : mode == TAVB_REMAP_INSERT ? new_rows : 0;
+  if (flag_rows > 0 && !dev_flags) return fail(TAVB_E_INVALID, "null dev_flags");
+  if ((reinterpret_cast<uintptr_t>(dev_flags) & 3) != 0) return fail(TAVB_E_INVALID, "dev_flags must be 4-byte aligned");
+  if (!dev_masks || !dev_bits_out) return fail(TAVB_E_INVALID, "null argument");
+  if (dev_rows_out && !caps) return fail(TAVB_E_INVALID, "row lists without capacities");
+  const size_t old_bytes = (size_t)((old_rows + 31) >> 5) * 4, new_bytes = (size_t)((new_rows + 31) >> 5) * 4, flag_bytes = (size_t)((flag_rows + 31) >> 5) * 4;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return na > 0 && nb > 0 && x < y + nb && y < x + na;
+  };
+  tavb::RemapOperands ops{};
+  ops.n = n_masks;
+  for (int j = 0; j < n_masks; ++j) {
+    if (old_rows > 0 && !dev_masks[j]) return fail(TAVB_E_INVALID, "mask %d is null", j);
+    if (new_rows > 0 && !dev_bits_out[j]) return fail(TAVB_E_INVALID, "output %d is null", j);
+    if (((reinterpret_cast<uintptr_t>(dev_masks[j]) | reinterpret_cast<uintptr_t>(dev_bits_out[j])) & 3) != 0) return fail(TAVB_E_INVALID, "mask %d must be 4-byte aligned", j);
+    if (dev_rows_out && caps[j] < 0) return fail(TAVB_E_INVALID, "bad capacity");
+    ops.in[j] = dev_masks[j];
+    ops.out[j] = dev_bits_out[j];
+  }
+  for (int j = 0; j < n_masks; ++j) {  // an output is nobody's input: the removal flags may be carried themselves, and are read again by the compaction
+    if (overlap(ops.out[j], new_bytes, dev_flags, flag_bytes)) return fail(TAVB_E_INVALID, "output %d overlaps the flags", j);
+    for (int i = 0; i < n_masks; ++i)
+      if (overlap(ops.out[j], new_bytes, ops.in[i], old_bytes) || (i != j && overlap(ops.out[j], new_bytes, ops.out[i], new_bytes)))
+        return fail(TAVB_E_INVALID, "output %d overlaps mask or output %d", j, i);
+  }
+  DeviceGuard guard(c->device);
+  const int flag_blocks = flag_rows > 0 ? tavb::mask_blocks(flag_rows) : 0, blocks = new_rows > 0 ? tavb::mask_blocks(new_rows) : 0;
+  const size_t totals_bytes = 64, n_infos = (size_t)flag_blocks + (size_t)n_masks * blocks;
+  if (int rc = c->d_mask_counts.reserve(n_infos * sizeof(unsigned))) return rc;
+  if (int rc = c->h_out.reserve(totals_bytes + n_infos * sizeof(tavb::MaskChunkInfo))) return rc;
+  static_assert(TAVB_MAX_MASK_OPERANDS * sizeof(long long) <= 64, "the totals come first");
+  unsigned* const flag_counts = reinterpret_cast<unsigned*>(c->d_mask_counts.ptr);
+  unsigned* const counts = flag_counts + flag_blocks;
+  long long* const totals = reinterpret_cast<long long*>(c->h_out.ptr);
+  tavb::MaskChunkInfo* const flag_info = reinterpret_cast<tavb::MaskChunkInfo*>(reinterpret_cast<char*>(c->h_out.ptr) + totals_bytes);
+  tavb::MaskChunkInfo* const info = flag_info + flag_blocks;
+  for (int j = 0; j < n_masks; ++j) totals[j] = -1;
+  for (size_t b = 0; b < n_infos; ++b) flag_info[b].first = -1;  // (a chunk a kernel wrote holds a row or INT32_MAX here)
+  Timed t(c, TAVB_KERNEL_CONVERT);
+  if (flag_blocks > 0) {
+    hipError_t e = tavb::launch_compact_count(dev_flags, flag_rows, flag_counts, flag_info, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "remap count launch failed: %s", hipGetErrorString(e));
+    TAVB_HIP(hipStreamSynchronize(c->stream));
+    int64_t clear = 0;
+    for (int b = 0; b < flag_blocks; ++b) {
+      if (flag_info[b].first < 0) return fail(TAVB_E_HIP, "chunk %d of the flags wrote no info (internal error)", b);
+      clear += flag_info[b].count;
+    }
+    const int64_t want = mode == TAVB_REMAP_REMOVE ? new_rows : old_rows;
+    if (clear != want)
+      return fail(TAVB_E_INVALID, "the flags have %lld clear bits among %lld rows, the edit needs %lld", (long long)clear, (long long)flag_rows, (long long)want);
+  }
+  if (new_rows == 0) return TAVB_OK;
+  hipError_t e = mode == TAVB_REMAP_REMOVE ? tavb::launch_mask_remap_squeeze(ops, dev_flags, flag_counts, old_rows, new_rows, counts, info, c->stream)
+                                           : tavb::launch_mask_remap_spread(ops, mode == TAVB_REMAP_INSERT ? dev_flags : nullptr, flag_counts, old_rows, new_rows, fill != 0,
+                                                                            counts, info, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "mask remap launch failed: %s", hipGetErrorString(e));
+  for (int j = 0; j < n_masks; ++j) {
+    if (!dev_rows_out || !dev_rows_out[j] || caps[j] == 0) continue;
+    e = tavb::launch_mask_write(ops.out[j], new_rows, counts + (size_t)j * blocks, dev_rows_out[j], caps[j], &totals[j], c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "mask write launch failed: %s", hipGetErrorString(e));
+  }
+  TAVB_HIP(hipStreamSynchronize(c->stream));
+  for (int j = 0; j < n_masks; ++j) {
+    int64_t count = 0, first = 0x7FFFFFFFll, last = -1;
+    for (int b = 0; b < blocks; ++b) {
+      const tavb::MaskChunkInfo ci = info[(size_t)j * blocks + b];
+      if (ci.first < 0) return fail(TAVB_E_HIP, "chunk %d of output %d wrote no info (internal error)", b, j);
+      count += ci.count;
+      first = std::min<int64_t>(first, ci.first);
+      last = std::max<int64_t>(last, ci.last);
+    }
+    if (count > 0) {
+      out_info[j].count = count;
+      out_info[j].first_row = first;
+      out_info[j].last_row = last;
+    }
+  }
+  for (int j = 0; j < n_masks; ++j) {
+    if (!dev_rows_out || !dev_rows_out[j] || caps[j] == 0) continue;
+    if (totals[j] != out_info[j].count)
+      return fail(TAVB_E_HIP, "the write pass of output %d counted %lld rows, the mask has %lld (internal error)", j, totals[j], (long long)out_info[j].count);
+    if (out_info[j].count > caps[j])
+      return fail(TAVB_E_INVALID, "output %d has %lld rows set, its row list holds %lld", j, (long long)out_info[j].count, (long long)caps[j]);
+  }
+  return TAVB_OK;
+}
+
 // ---- batched message lookups: nq key lists [nq, k] on the device (keys carrying index_base + row) -> ONE message_rerank_kernel launch of nq
 // workgroups -> ONE device-to-host copy -> the callers' arrays.  d_out holds both: the hits in its first nq * k keys, the message keys behind.
 static int rerank_batch_and_return(tavb_ctx* c, const u64_t* d_hits, int nq, int k, uint32_t index_base, const uint32_t* d_accept_bits, int32_t max_messages,

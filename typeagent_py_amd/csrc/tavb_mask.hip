@@ -4,6 +4,7 @@
 // Scope algebra (tavb_mask_from_ranges, tavb_mask_combine): the mask of a scope of range collections (mask_from_ranges_kernel) and AND /
 // OR / ANDNOT of masks (mask_combine_kernel), both of which also leave the counts mask_write_kernel needs and the mask's count and span.
 // Row compaction (tavb_compact_rows): the rows a mask names are removed and the others moved down, by the same per-chunk counts (further down).
+// Masks carried through such an edit (tavb_mask_remap): packed masks squeezed or spread under the edit's flags, by the same counts again.
 //
 // The mask is uint32 words, row r = bit (r & 31) of word (r >> 5).  Two launches, both grids fixed on the host:
 //   mask_count_kernel   workgroup b popcounts its kMaskWordsPerBlock words -> counts[b]
@@ -17,6 +18,7 @@
 
 #include "tavb_device.h"
 #include "tavb_internal.h"
+#include "tavb_remap_bits.h"
 
 namespace tavb {
 
@@ -508,6 +510,198 @@ __global__ void __launch_bounds__(kMaskThreads) expand_scatter_kernel(const char
   }
 }
 
+// ---- masks carried through a row edit (tavb_mask_remap): np.delete / np.insert of packed masks under the edit's packed flags, up to
+// TAVB_MAX_MASK_OPERANDS masks per launch.  The flags' per-chunk counts of clear bits (compact_count_kernel: kept rows of a removal, old
+// rows of an insertion) are made once per call; a workgroup sums the counts of the chunks before its own, scans its 512 flag words once,
+// works out the moves of every flag word once (tavb_remap_bits.h) and applies them to that word of every operand, in registers.
+//   mask_remap_squeeze_kernel  REMOVE.  The flags cover the OLD rows, so a workgroup owns a chunk of INPUT words: a lane squeezes its word of
+//                              an operand under the kept bits and ORs the piece -- it straddles at most two words -- into an LDS image of
+//                              the chunk's output bits [kept before the chunk, + kept in it).  The image's inner words are stored; its
+//                              first and last word, which the neighbouring chunks may share, go out through an atomic OR: the output
+//                              was zeroed by the launcher's memset, and an OR does not care about order, so the result is deterministic.
+//   mask_remap_info_kernel     the counts and infos of those outputs per chunk of NEW rows (the chunks of the two row spaces do not line up)
+//   mask_remap_spread_kernel   INSERT and APPEND.  The flags cover the NEW rows, so a workgroup owns a chunk of OUTPUT words: a lane's source
+//                              bits are the popcount(clear) bits from bit (clear bits before its word) of the input on -- two words through a
+//                              funnel shift -- spread under the clear bits; the holes take `fill`.  Plain stores, and the chunk's count and
+//                              info in the same launch.  APPEND has no flags: the holes are the bits [old_rows, new_rows).
+// No workgroup waits for another.  Inputs are read through mask_word (bits at or beyond old_rows may hold anything); output bits at or beyond
+// new_rows are zero.
+
+constexpr int kRemapRounds = kMaskWordsPerBlock / kMaskThreads;
+constexpr int kRemapPieceWords = kMaskWordsPerBlock + 2;  // a chunk's output bits start anywhere in a word: up to 31 bits in front, as many behind
+
+__device__ __forceinline__ uint32_t low_bits(int64_t k) { return k >= 32 ? 0xFFFFFFFFu : k <= 0 ? 0u : (1u << (int)k) - 1u; }
+
+// The exclusive prefix of `mine` over the workgroup in thread order, *total = the sum; every thread calls it.  wc: kMaskWaves LDS words,
+// free again on return.
+__device__ __forceinline__ unsigned block_prefix(unsigned mine, unsigned* wc, unsigned* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = mine;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned up = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += up;
+  }
+  if (lane == 63) wc[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+  for (int x = 0; x < kMaskWaves; ++x) {
+    before += x < wave ? wc[x] : 0u;
+    all += wc[x];
+  }
+  __syncthreads();
+  *total = all;
+  return before + (incl - mine);
+}
+
+// the sum of counts[0 .. blockIdx.x), the same value on every thread (all of them call it); sh: one LDS word, free again on return
+__device__ __forceinline__ unsigned counts_before(const unsigned* __restrict__ counts, unsigned* sh) {
+  if (threadIdx.x == 0) *sh = 0u;
+  __syncthreads();
+  unsigned part = 0;
+  for (unsigned b = threadIdx.x; b < blockIdx.x; b += kMaskThreads) part += counts[b];
+  if (part) atomicAdd(sh, part);
+  __syncthreads();
+  const unsigned all = *sh;
+  __syncthreads();
+  return all;
+}
+
+__global__ void __launch_bounds__(kMaskThreads) mask_remap_squeeze_kernel(RemapOperands ops, const uint32_t* __restrict__ flags,
+                                                                          const unsigned* __restrict__ kept_counts, int64_t old_rows,
+                                                                          int64_t old_words, int64_t new_words) {
+  __shared__ uint32_t piece[kRemapPieceWords];
+  __shared__ unsigned sh;
+  __shared__ unsigned wc[kMaskWaves];
+  const unsigned kept = kept_counts[blockIdx.x];
+  if (kept == 0) return;  // (block-uniform) the chunk leaves no bit
+  const int64_t base = counts_before(kept_counts, &sh);  // the chunk's first output bit
+  const unsigned head = (unsigned)(base & 31);
+  const int64_t word0 = base >> 5;
+  const int n_piece = (int)((head + kept + 31u) >> 5);
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock + threadIdx.x;
+  uint32_t kw[kRemapRounds];
+  unsigned off[kRemapRounds];  // where the lane's piece starts, in bits of the image
+  BitMoves mv[kRemapRounds];
+  unsigned run = head;
+#pragma unroll
+  for (int r = 0; r < kRemapRounds; ++r) {
+    kw[r] = kept_word(flags, w0 + r * kMaskThreads, old_words, old_rows);
+    unsigned all;
+    off[r] = run + block_prefix((unsigned)__popc(kw[r]), wc, &all);
+    run += all;
+    mv[r] = bit_moves(kw[r]);
+  }
+  for (int j = 0; j < ops.n; ++j) {  // (block-uniform)
+    for (int i = threadIdx.x; i < n_piece; i += kMaskThreads) piece[i] = 0u;
+    __syncthreads();
+    const uint32_t* __restrict__ in = ops.in[j];
+#pragma unroll
+    for (int r = 0; r < kRemapRounds; ++r) {
+      if (kw[r] == 0u) continue;
+      const uint32_t x = squeeze_bits(mask_word(in, w0 + r * kMaskThreads, old_words, old_rows), kw[r], mv[r]);
+      if (x == 0u) continue;
+      const unsigned lo = off[r] >> 5, s = off[r] & 31u;
+      atomicOr(&piece[lo], x << s);
+      if (s != 0u && (x >> (32u - s)) != 0u) atomicOr(&piece[lo + 1], x >> (32u - s));
+    }
+    __syncthreads();
+    uint32_t* out = ops.out[j];
+    for (int i = threadIdx.x; i < n_piece; i += kMaskThreads) {
+      const uint32_t v = piece[i];
+      const int64_t gw = word0 + i;
+      if (gw >= new_words) continue;  // (never: the host has checked that the kept rows number new_rows)
+      const bool shared = (i == 0 && head != 0u) || (i == n_piece - 1 && ((head + kept) & 31u) != 0u);
+      if (!shared) out[gw] = v;
+      else if (v != 0u) atomicOr(&out[gw], v);
+    }
+    __syncthreads();  // the image is zeroed again for the next operand
+  }
+}
+
+// counts[j * chunks + b], info[j * chunks + b] of output j (blockIdx.y) over its chunk b of NEW rows
+__global__ void __launch_bounds__(kMaskThreads) mask_remap_info_kernel(RemapOperands ops, int64_t rows, int64_t n_words, unsigned* __restrict__ counts,
+                                                                       MaskChunkInfo* __restrict__ info) {
+  const uint32_t* __restrict__ bits = ops.out[blockIdx.y];
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock;
+  unsigned n = 0;
+  int first = 0x7FFFFFFF, last = -1;
+  for (int i = threadIdx.x; i < kMaskWordsPerBlock; i += kMaskThreads) {
+    const int64_t w = w0 + i;
+    if (w >= n_words) break;
+    const uint32_t v = mask_word(bits, w, n_words, rows);
+    if (v) {
+      n += (unsigned)__popc(v);
+      first = min(first, (int)(w << 5) + __ffs((int)v) - 1);
+      last = max(last, (int)(w << 5) + 31 - __clz((int)v));
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    n += __shfl_down(n, d, 64);
+    first = min(first, __shfl_down(first, d, 64));
+    last = max(last, __shfl_down(last, d, 64));
+  }
+  const size_t at = (size_t)blockIdx.y * gridDim.x;
+  mask_chunk_reduce(n, first, last, counts + at, info + at);
+}
+
+__global__ void __launch_bounds__(kMaskThreads) mask_remap_spread_kernel(RemapOperands ops, const uint32_t* __restrict__ flags,
+                                                                         const unsigned* __restrict__ clear_counts, int64_t old_rows,
+                                                                         int64_t old_words, int64_t new_rows, int64_t new_words, int fill,
+                                                                         unsigned* __restrict__ counts, MaskChunkInfo* __restrict__ info) {
+  __shared__ unsigned sh;
+  __shared__ unsigned wc[kMaskWaves];
+  // the chunk's first source bit: the clear bits in front of it
+  const int64_t chunk0 = (int64_t)blockIdx.x * TAVB_MASK_ROWS_PER_WORKGROUP;
+  const int64_t base = flags ? (int64_t)counts_before(clear_counts, &sh) : (chunk0 < old_rows ? chunk0 : old_rows);
+  const int64_t w0 = (int64_t)blockIdx.x * kMaskWordsPerBlock + threadIdx.x;
+  uint32_t hole[kRemapRounds], clear[kRemapRounds];
+  int64_t src[kRemapRounds];  // the lane's first source bit
+  BitMoves mv[kRemapRounds];
+  int64_t run = base;
+#pragma unroll
+  for (int r = 0; r < kRemapRounds; ++r) {
+    const int64_t w = w0 + r * kMaskThreads;
+    const uint32_t valid = w < new_words ? low_bits(new_rows - (w << 5)) : 0u;
+    hole[r] = flags ? mask_word(flags, w, new_words, new_rows) : valid & ~low_bits(old_rows - (w << 5));
+    clear[r] = valid & ~hole[r];
+    unsigned all;
+    src[r] = run + block_prefix((unsigned)__popc(clear[r]), wc, &all);
+    run += all;
+    mv[r] = bit_moves(clear[r]);
+  }
+  for (int j = 0; j < ops.n; ++j) {  // (block-uniform)
+    const uint32_t* __restrict__ in = ops.in[j];
+    uint32_t* __restrict__ out = ops.out[j];
+    unsigned n = 0;
+    int first = 0x7FFFFFFF, last = -1;
+#pragma unroll
+    for (int r = 0; r < kRemapRounds; ++r) {
+      const int64_t w = w0 + r * kMaskThreads;
+      if (w >= new_words) continue;
+      uint32_t v = fill ? hole[r] : 0u;
+      if (clear[r] != 0u) {
+        const int64_t lo = src[r] >> 5;
+        const uint32_t x = funnel_bits(mask_word(in, lo, old_words, old_rows), mask_word(in, lo + 1, old_words, old_rows), (int)(src[r] & 31));
+        v |= spread_bits(x & low_bits(__popc(clear[r])), clear[r], mv[r]);
+      }
+      out[w] = v;
+      if (v) {
+        n += (unsigned)__popc(v);
+        first = min(first, (int)(w << 5) + __ffs((int)v) - 1);
+        last = max(last, (int)(w << 5) + 31 - __clz((int)v));
+      }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+      n += __shfl_down(n, d, 64);
+      first = min(first, __shfl_down(first, d, 64));
+      last = max(last, __shfl_down(last, d, 64));
+    }
+    const size_t at = (size_t)j * gridDim.x;
+    mask_chunk_reduce(n, first, last, counts + at, info + at);
+    __syncthreads();  // (the reduction's LDS words are written again for the next operand)
+  }
+}
+
 // ---- scattered row writes (tavb_scatter_rows): n staged fp32 rows -> corpus rows positions[j], converted to the corpus' dtype as the load
 // path converts them ((_Float16)x: v_cvt_f16_f32, round to nearest even), so a row written here equals the same row uploaded.
 //   scatter_check_kernel   *bad = 1 when a position lies outside [0, rows) (host memory the device writes; the host zeroes it first)
@@ -790,6 +984,37 @@ hipError_t launch_mask_combine(const MaskOperands& ops, int64_t rows, uint32_t* 
   for (int j = 0; j < ops.n; ++j)
     if (!ops.m[j]) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mask_combine_kernel, dim3(mask_blocks(rows)), dim3(kMaskThreads), 0, stream, ops, rows, (rows + 31) >> 5, bits, counts, info);
+  return hipGetLastError();
+}
+
+static bool remap_operands_ok(const RemapOperands& ops, int64_t old_rows, int64_t new_rows) {
+  if (ops.n < 1 || ops.n > TAVB_MAX_MASK_OPERANDS || old_rows < 0 || old_rows >= 0x7FFFFFFFll || new_rows < 1 || new_rows >= 0x7FFFFFFFll) return false;
+  for (int j = 0; j < ops.n; ++j)
+    if (!ops.out[j] || (old_rows > 0 && !ops.in[j])) return false;
+  return true;
+}
+
+hipError_t launch_mask_remap_squeeze(const RemapOperands& ops, const uint32_t* flags, const unsigned* kept_counts, int64_t old_rows, int64_t new_rows,
+                                     unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
+  if (!remap_operands_ok(ops, old_rows, new_rows) || !flags || !kept_counts || !counts || !info || new_rows > old_rows) return hipErrorInvalidValue;
+  const int64_t new_words = (new_rows + 31) >> 5;
+  for (int j = 0; j < ops.n; ++j) {  // the kernel ORs into the words two chunks share
+    hipError_t e = hipMemsetAsync(ops.out[j], 0, (size_t)new_words * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(mask_remap_squeeze_kernel, dim3(mask_blocks(old_rows)), dim3(kMaskThreads), 0, stream, ops, flags, kept_counts, old_rows, (old_rows + 31) >> 5,
+                     new_words);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mask_remap_info_kernel, dim3(mask_blocks(new_rows), ops.n), dim3(kMaskThreads), 0, stream, ops, new_rows, new_words, counts, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_remap_spread(const RemapOperands& ops, const uint32_t* flags, const unsigned* clear_counts, int64_t old_rows, int64_t new_rows, bool fill,
+                                    unsigned* counts, MaskChunkInfo* info, hipStream_t stream) {
+  if (!remap_operands_ok(ops, old_rows, new_rows) || (flags && !clear_counts) || !counts || !info || new_rows < old_rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_remap_spread_kernel, dim3(mask_blocks(new_rows)), dim3(kMaskThreads), 0, stream, ops, flags, clear_counts, old_rows, (old_rows + 31) >> 5,
+                     new_rows, (new_rows + 31) >> 5, fill ? 1 : 0, counts, info);
   return hipGetLastError();
 }
 

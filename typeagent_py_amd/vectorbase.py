@@ -1541,6 +1541,85 @@ class VectorBase:
         embedding = await self.get_embedding(key)
         return self.fuzzy_lookup_embedding(embedding, max_hits=max_hits, min_score=min_score, predicate=predicate)
 
+    # ------------------------------------------------------------------ masks carried through row edits (additive)
+    def _carried(self, carry) -> list[RowMask]:
+        """`carry=` of an edit -> its handles, each once, refused as `_resolve_mask` refuses them -- before anything is edited."""
+        out: list[RowMask] = []
+        for h in (carry,) if isinstance(carry, RowMask) else tuple(carry):
+            if not isinstance(h, RowMask):
+                raise TypeError(f"carry takes RowMask handles of this index, got {type(h).__name__}")
+            self._resolve_mask(h)
+            if not any(h is x for x in out):
+                out.append(h)
+        return out
+
+    def _carry_on_device(self, eng, handles) -> bool:
+        """The device route of a carried edit: a single-GPU engine with tavb_mask_remap, and every handle holds its packed mask there."""
+        return bool(handles) and self._masked_native(eng) and hasattr(eng, "mask_remap") and all(h.dev_bits is not None for h in handles)
+
+    @staticmethod
+    def _remap_on_device(eng, mode: int, dev_flags, old: int, new: int, handles, fill: bool) -> list[tuple]:
+        """The handles' packed masks through one edit, 8 per call of tavb_mask_remap -> a quadruple (dev_rows, count, dev_bits, span) each.
+        Nothing of the index or the handles is touched: the caller adopts the results once the edit itself is done."""
+        most = _native.MAX_MASK_OPERANDS
+        out: list[tuple] = []
+        for i in range(0, len(handles), most):
+            group = handles[i:i + most]
+            out += eng.mask_remap(mode, dev_flags, old, new, [h.dev_bits for h in group], fill, counts=[h.count for h in group])
+        return out
+
+    def _fresh_mask(self, bools: np.ndarray) -> RowMask:
+        """The host route's new handle: `row_mask`, or -- on an index that never reached a device -- the host list alone."""
+        if self._engine is None:
+            flat = np.flatnonzero(bools)
+            return RowMask(self, len(bools), len(flat), flat=flat)
+        return self.row_mask(bools)
+
+    def _adopt_masks(self, handles, fresh) -> None:
+        """Every handle takes over what its fresh twin -- a `RowMask`, or a quadruple of `_remap_on_device` -- holds, in place: the
+        length, the count, the epoch, the lists, the packed mask and the span; its route plans are emptied with them."""
+        for h, f in zip(handles, fresh):
+            if not isinstance(f, RowMask):
+                dev_rows, count, dev_bits, span = f
+                f = RowMask(self, self._count, count, dev_rows=dev_rows, dev_bits=dev_bits, span=span)
+            for slot in RowMask.__slots__:
+                if slot != "_owner":
+                    setattr(h, slot, getattr(f, slot))
+
+    def extend_masks(self, *masks, new: bool = False) -> None:
+        """Bring `RowMask` handles that were built at a smaller length -- before rows were appended by `add_embedding(s)` / `add_key(s)` --
+        to len(self), IN PLACE: the rows they name stay, the appended rows are clear, or set with `new=True`; equals
+        row_mask(np.concatenate([bools, np.full(len(self) - len(bools), new)])).  A handle already at the current length is left alone.
+        Handles of another index, handles made before a removal or an insertion that was not handed them (`carry=`), and handles longer
+        than the index raise ValueError, before any handle changes.  On a single-GPU engine handles that hold their packed mask on the
+        device are extended there (tavb_mask_remap, 8 per call; only `new` and the two lengths travel); everything else goes through
+        the host bool array and `row_mask`."""
+        n = self._count
+        todo: list[RowMask] = []
+        for h in masks:
+            if not isinstance(h, RowMask):
+                raise TypeError(f"extend_masks takes RowMask handles of this index, got {type(h).__name__}")
+            if h._owner() is not self:
+                raise ValueError("this RowMask was built by another index")
+            if h.epoch != self._removal_epoch:
+                raise ValueError(f"this RowMask was built before rows were {self._epoch_change} the index: build it again")
+            if h.rows > n:
+                raise ValueError(f"mask covers {h.rows} rows, the index has {n}")
+            if h.rows < n and not any(h is x for x in todo):
+                todo.append(h)
+        eng = self._engine
+        for old in sorted({h.rows for h in todo}):
+            group = [h for h in todo if h.rows == old]
+            if self._carry_on_device(eng, group):
+                fresh = self._remap_on_device(eng, _native.REMAP_APPEND, None, old, n, group, bool(new))
+            else:
+                fresh = []
+                for h in group:
+                    b = np.zeros(old, dtype=bool)
+                    b[h.flat()] = True
+                    fresh.append(self._fresh_mask(np.concatenate([b, np.full(n - old, bool(new))])))
+            self._adopt_masks(group, fresh)
+
     # ------------------------------------------------------------------ removal (additive)
     def _removal_flags(self, which) -> tuple[np.ndarray | None, RowMask | None, int]:
         """What `remove_rows` was handed -> (bool [len(self)] of the rows to remove, or None when a RowMask's packed mask on the device says
@@ -1568,7 +1647,7 @@ class VectorBase:
         flags[a] = True  # (negatives wrap, duplicates fall together: np.delete's rules)
         return flags, None, int(np.count_nonzero(flags))
 
-    def remove_rows(self, which) -> int:
+    def remove_rows(self, which, carry=()) -> int:
         """Remove rows -> how many went.  `which`: integer ordinals with np.delete's rules (duplicates allowed, negatives wrap, out of range
         raises IndexError), a bool array of length len(self), or a `RowMask` of this index.  Defined as the reference class with
         `_vectors = np.delete(_vectors, which, axis=0)`: later ordinals shift down -- the removal the reference leaves as a TODO
@@ -1577,7 +1656,14 @@ class VectorBase:
         mask is used where it is; ordinals and bool arrays travel as rows / 8 bytes.  The host matrix, when there is one, is compacted in
         its growth buffer -- unless somebody else holds it (a matrix adopted by deserialize(), a view handed out by serialize()): then the
         index moves to a buffer of its own, as np.delete would.  The row -> message map loses the same rows.  Every `RowMask` built before
-        the call raises ValueError from then on.  A device group (`devices=[...]`) removes on the host and uploads again."""
+        the call raises ValueError from then on -- except the handles named in `carry`: they are updated IN PLACE and name the same
+        vectors afterwards as before, minus the removed ones (row_mask(np.delete(bools, which)); a handle that is also `which` becomes the
+        empty mask).  On a single-GPU engine carried handles that hold their packed mask on the device are remapped there, under the
+        removal flags the compaction reads (tavb_mask_remap, 8 per call): nothing of them visits the host but their counts and spans.
+        Everything else -- device groups, handles with a host list only -- goes through the host bool arrays and `row_mask`.  With no
+        row to remove nothing changes and every handle stays as it is.  A device group (`devices=[...]`) removes on the host and
+        uploads again."""
+        carried = self._carried(carry)
         flags, mask, removed = self._removal_flags(which)
         if removed == 0:
             return 0
@@ -1589,10 +1675,14 @@ class VectorBase:
         if native and self._device_only is None:
             eng = self._sync_device()  # rows appended or edited since the last lookup reach the mirror first
         need_host_list = self._device_only is None or self._row_messages is not None
-        if flags is None and (need_host_list or not native):
+        on_device = native and self._carry_on_device(eng, carried)
+        if flags is None and (need_host_list or not native or (carried and not on_device)):
             flags = self._mask_bools(mask)
+        held = [] if on_device else [self._mask_bools(h) for h in carried]  # (read before the count changes)
         if native:
             dev_bits = mask.dev_bits if mask is not None else eng.mask_bits_to_device(_native.pack_mask_bits(flags))
+            if on_device:  # (fresh tensors: neither the handles nor the flags change before the rows have moved)
+                remapped = self._remap_on_device(eng, _native.REMAP_REMOVE, dev_bits, n, n - removed, carried, False)
             kept = eng.compact_rows(dev_bits)
             if kept != n - removed:
                 raise RuntimeError(f"the device kept {kept} rows of {n}, expected {n - removed}")
@@ -1634,6 +1724,8 @@ class VectorBase:
         self._subset_cache = None
         self._removal_epoch += 1
         self._epoch_change = "removed from"
+        if carried:
+            self._adopt_masks(carried, remapped if on_device else [self._fresh_mask(b[~flags]) for b in held])
         return removed
 
     def remove_at(self, pos: int) -> None:
@@ -1677,7 +1769,7 @@ class VectorBase:
         idx[order] += np.arange(m, dtype=np.int64)
         return idx
 
-    def insert_rows(self, at, embeddings, row_messages=None) -> int:
+    def insert_rows(self, at, embeddings, row_messages=None, carry=(), carry_new: bool = False) -> int:
         """Insert rows -> how many went in.  Defined as the reference class with `_vectors = np.insert(_vectors, at, embeddings, axis=0)`:
         `embeddings` is one row [dim] or [m, dim]; `at` one integer (all m rows go in front of old row `at`; `at == len(self)` appends) or
         a sequence of m integers (row j goes in front of old row at[j]; equal positions keep their order; one row and many positions
@@ -1688,7 +1780,12 @@ class VectorBase:
         is one, is opened up in its growth buffer, from the tail -- unless somebody else holds it (a matrix adopted by deserialize(), a
         view handed out by serialize()): then the index moves to a buffer of its own, as np.insert would.  The row -> message map gets
         `row_messages` (one int, or one per new row) at the same positions, -1 where none is given.  Every `RowMask` built before the
-        call raises ValueError from then on.  A device group (`devices=[...]`) inserts on the host and uploads from the first new row."""
+        call raises ValueError from then on -- except the handles named in `carry`: they are updated IN PLACE, keep the vectors they
+        named and get `carry_new` (clear by default) at the new rows: row_mask(np.insert(bools, at, carry_new)) under the position rule
+        of the rows.  On a single-GPU engine carried handles that hold their packed mask on the device are remapped there, under the
+        hole flags the expansion reads (tavb_mask_remap, 8 per call); everything else goes through the host bool arrays and `row_mask`.
+        A device group (`devices=[...]`) inserts on the host and uploads from the first new row."""
+        carried = self._carried(carry)
         n = self._count
         new = self._rows_argument(embeddings)
         a = np.asarray(at)
@@ -1710,6 +1807,8 @@ class VectorBase:
         first = int(pos.min())
         eng = self._engine
         native = eng is not None and hasattr(eng, "expand_rows") and hasattr(eng, "scatter_rows")  # (a device group has neither: the host route)
+        on_device = native and n > 0 and self._carry_on_device(eng, carried)
+        held = [] if on_device else [self._mask_bools(h) for h in carried]  # (read before the count changes)
         if n == 0:
             ordered = np.empty_like(new)
             ordered[pos] = new  # into an empty index: an append, in np.insert's order
@@ -1722,7 +1821,10 @@ class VectorBase:
             if self._device_only is None:
                 self._open_host_rows(flags, pos, new)
             if native:
-                eng.expand_rows(eng.mask_bits_to_device(_native.pack_mask_bits(flags)), n + m)
+                dev_flags = eng.mask_bits_to_device(_native.pack_mask_bits(flags))
+                if on_device:  # (fresh tensors: the handles do not change before the rows have moved)
+                    remapped = self._remap_on_device(eng, _native.REMAP_INSERT, dev_flags, n, n + m, carried, bool(carry_new))
+                eng.expand_rows(dev_flags, n + m)
                 eng.scatter_rows(new, pos.astype(np.int32))
                 if self._device_only is not None:
                     self._device_only = eng.corpus
@@ -1744,6 +1846,16 @@ class VectorBase:
         self._subset_cache = None
         self._removal_epoch += 1
         self._epoch_change = "inserted into"
+        if carried and on_device:
+            self._adopt_masks(carried, remapped)
+        elif carried:
+            fresh = []
+            for b in held:
+                grown = np.empty(n + m, dtype=bool)
+                grown[~flags] = b
+                grown[pos] = bool(carry_new)
+                fresh.append(self._fresh_mask(grown))
+            self._adopt_masks(carried, fresh)
         return m
 
     _host_block_bytes = 64 << 20  # the host matrix is opened up in blocks of about this size
