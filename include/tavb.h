@@ -209,6 +209,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "scope_large_k" (default 1; the binding reads it) 1 = a scoped batch at max_hits beyond TAVB_MAX_FUSED_K, or 0, is ONE call of
  *                   tavb_search_scoped_topk / tavb_search_scoped_sorted (while "large_k" / "sort_all" are on); 0 = the binding loops over
  *                   the per-query masked lookups, as before those calls existed
+ *   "top_messages"  (default 1; the binding reads it) 1 = lookup_top_messages_by_embedding(s) is ONE call of tavb_search_top_messages (1 <=
+ *                   max_messages <= TAVB_MAX_LARGE_K); 0 = the binding takes the all-survivor lookup and collapses rows to messages on the host
  *   "scope_wide"    scoped batches on fp16 corpora (the binding reads it; the rule is tavb_plan_scoped_wide, with "mask_tile_min_bytes" /
  *                   "mask_tile_pct"): 1 (default) = the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide) where
  *                   tavb_plan_scoped_wide says so -- it then wins over "scope_tile"; 0 = never; 2 = wherever that route serves the shape
@@ -658,6 +660,31 @@ int tavb_search_scoped_sorted(tavb_ctx* ctx, const float* queries_host, int32_t 
 int tavb_search_subset_batch_sorted(tavb_ctx* ctx, const float* queries_host, int32_t nq, const int32_t* dev_rows, int64_t n_subset, int64_t k,
                                     const float* min_scores, int64_t max_total, int64_t* out_ordinals, float* out_scores, int64_t* out_counts,
                                     int64_t* out_total);
+
+/* ---- the best k MESSAGES: per-message best score and top-k on the device ("collapsing") ----------------------------------------------------
+ * The message lookups above take the best k chunk ROWS and then collapse them to messages: possibly far fewer than k messages.  These calls
+ * return, per query, the k messages with the highest best(m) = max score(r) over the rows r of message m (tavb_set_row_messages) that pass
+ * score(r) >= min_score (NaN never passes) and, with dev_rows, are in that list -- min(k, messages with a passing row) of them, sorted by
+ * best descending, ties by ascending message ordinal.  Rows whose map value is below 0 or at or beyond n_messages belong to no message.
+ * Scores are tavb_search's float32 scores bit for bit.  1 <= k <= TAVB_MAX_LARGE_K; dev_rows == NULL (n_rows 0): the whole corpus; dev_rows:
+ * device int32 [n_rows], valid corpus rows (e.g. tavb_mask_expand's list; order and repeats do not matter), any nq.
+ * On the device, per group of up to TAVB_MAX_STREAM_QUERIES queries: ONE pass over the corpus or the list with the streaming scan's
+ * arithmetic that writes nothing per row -- a passing row does one atomic max on its message's slot of a [queries][n_messages] array
+ * (zeroed first; 4 bytes per query and message, cut to groups of at least one query by "topk_scores_bytes") -- then one pass over that
+ * array that counts the messages into tavb_search_topk's histograms, then tavb_search_topk's boundary search, refinement, compaction and
+ * sort with the message ordinals as positions ("topk_buckets", "topk_boundary_keys"; "last_topk_refine" reports the rounds).  A max does not
+ * depend on the order of its operands: the result is deterministic.  No host round trip before the results.
+ *   tavb_search_top_messages: queries on the host, one synchronise; out_messages / out_scores [nq, k], out_counts [nq] as tavb_search_batch,
+ *     the ordinals being MESSAGE ordinals (no ordinal_base).
+ *   tavb_search_top_messages_device: dev_queries device float32 [nq, dim], nq >= 1; out_keys [nq, k] sorted, zero-padded keys carrying message
+ *     ordinals, device or device-writable pinned memory; nothing waited for ("last_topk_refine" at the next tavb_synchronize).
+ * No map set: TAVB_E_NO_CORPUS; a map that does not cover exactly the corpus' rows, NULL arguments, k out of range, a bad row list length:
+ * TAVB_E_INVALID; n_messages >= 2^31 - 1: TAVB_E_UNSUPPORTED -- each with a message.  nq == 0, an empty corpus, n_messages == 0 or an empty
+ * list: zero counts / zero keys, nothing launched.  Timed under TAVB_KERNEL_SCAN (score pass) and TAVB_KERNEL_TOPK (everything behind it). */
+int tavb_search_top_messages(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                             int64_t n_rows, int64_t* out_messages, float* out_scores, int32_t* out_counts);
+int tavb_search_top_messages_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores /*host*/,
+                                    const int32_t* dev_rows, int64_t n_rows, tavb_key* out_keys);
 
 /* ---- scoped batches on the 32/64-query tile: one scope per query on the matrix cores ----------------------------------------------------
  * The scoped batch above reads, per pass of eight queries, the union of the pass' scopes; dense, independent or disjoint scopes make that

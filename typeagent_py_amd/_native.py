@@ -122,6 +122,8 @@ _SIGNATURES = [
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     ("tavb_search_subset_batch_sorted", c_int,
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    ("tavb_search_top_messages", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_top_messages_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -1294,6 +1296,37 @@ class Engine:
         bound = a.shape[0] * (n if k <= 0 else min(int(k), n))
         return self._sorted_batch(a, k, thrs, bound, lambda qa, nq, t, bound, *out: self.lib.tavb_search_subset_batch_sorted(
             self._h, qa, nq, rows_ptr, n, int(k), t, bound, *out))
+
+    def search_top_messages(self, queries, k: int, thrs, dev_rows=None):
+        """The best k MESSAGES of every query -- per message the best score of its rows that pass the threshold, then the top k, all on the
+        device (tavb_search_top_messages): queries f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K; dev_rows: a
+        resident row list (torch int32 [S], valid corpus rows, e.g. `mask_to_rows`) to search instead of the whole corpus -> (message
+        ordinals [nq, k], scores [nq, k], counts [nq]).  Needs `set_row_messages` over exactly the corpus' rows."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        rows_ptr, n = (None, 0) if dev_rows is None else self._row_list(dev_rows)
+        if dev_rows is not None and n == 0:  # (an empty tensor has no address to name "a list" by)
+            return msgs, scs, cnts
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages(self._h, _addr(a), nq, k, _addr(t), rows_ptr, n, _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def search_top_messages_device(self, dev_queries, k: int, thrs, out_keys=None, dev_rows=None):
+        """`search_top_messages` with the queries on the device and nothing waited for (tavb_search_top_messages_device): dev_queries torch
+        f32 [nq, dim] -> torch int64 [nq, k] sorted, zero-padded keys carrying MESSAGE ordinals (`decode_keys`).  `out_keys`: a device
+        tensor or a PINNED host tensor.  Async: `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        rows_ptr, n = (None, 0) if dev_rows is None else self._row_list(dev_rows)
+        if dev_rows is not None and n == 0:
+            self.synchronize()
+            out_keys.view(-1)[: nq * k].zero_()
+            self._torch.cuda.current_stream(self.device).synchronize()
+            return out_keys
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), rows_ptr, n,
+                                                          c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
 
     def search_messages_scoped(self, queries, dev_bits_list, k: int, thrs, max_messages: int):
         """`search_scoped_batch` aggregated to messages in one submission (tavb_search_messages_scoped) -> (message ordinals [nq, k], scores

@@ -339,6 +339,34 @@ def lookup_messages_in_scope(
     return lists if max_matches is None else [out[:max_matches] for out in lists]
 
 
+def lookup_top_messages(
+    vector_base: VectorBase,
+    embedding_or_embeddings,
+    row_to_message,
+    max_messages: int | None = None,
+    threshold_score=None,
+    scope=None,
+):
+    """The best `max_messages` DISTINCT messages (None -> 10) -- what a caller who asks a `MessageTextIndex` for "25 messages" means, and
+    what the providers' lookups above do not give: they collapse the best `max_matches` chunk rows, often to a handful of messages.  Per
+    message the best score of its chunks that reach `threshold_score`, then the messages with the highest such score, sorted by it, ties
+    by ascending message ordinal (`VectorBase.lookup_top_messages_by_embeddings`: on a single-GPU engine ONE device submission).
+    `scope` restricts the search as in `lookup_messages_in_scope`: None (every chunk), a collection of message ordinals, a `RowMask`
+    (`vector_base.message_mask`, `row_mask`, mask algebra), a `TextRangesInScope`, a `TextRangeCollection` or a list of either.  A 1-D
+    embedding returns one list of ScoredInt(message, score), a 2-D array one list per embedding, all under the ONE scope (one scope per
+    query: loop over this call); `threshold_score` may then be a sequence.  `row_to_message`: message ordinal per index position (-1: none)."""
+    if callable(row_to_message):
+        raise TypeError("lookup_top_messages needs row_to_message as a sequence (the map is searched on the device)")
+    _ensure_row_messages(vector_base, row_to_message)
+    mask = None if scope is None else _scope_mask(vector_base, scope)
+    queries = np.asarray(embedding_or_embeddings, dtype=np.float32)
+    if queries.ndim == 1:
+        return vector_base.lookup_top_messages_by_embedding(queries, max_messages, threshold_score, mask)
+    if queries.ndim != 2:
+        raise ValueError(f"Expected a 1D embedding or a 2D array of embeddings, got {queries.ndim}D")
+    return vector_base.lookup_top_messages_by_embeddings(queries, max_messages, threshold_score, mask)
+
+
 def load_sqlite_embeddings(
     db,
     vector_base: VectorBase,

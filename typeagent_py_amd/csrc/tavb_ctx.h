@@ -163,6 +163,10 @@ struct tavb_ctx {
   int64_t topk_buckets = 1024;               // option: histogram buckets of the score pass
   int64_t topk_boundary_keys = 16384;        // option: capacity of a query's boundary list (more keys in the boundary bucket: refinement)
   int64_t topk_scores_bytes = (int64_t)1 << 30;  // option: most bytes of one group's score array (queries per corpus pass are cut to fit)
+  // top-messages lookups (tavb_search_top_messages): per query of a group and message, the best passing score of the message's rows
+  // ([queries of a group][n_messages] x 4 bytes: what d_topk_scores is to rows; the selection's workspace is d_topk as well)
+  Buffer d_msg_best;
+  int64_t top_messages = 1;                  // option: 1 = the binding sends lookup_top_messages_* through tavb_search_top_messages, 0 = through the all-survivor lookup and a collapse on the host
   int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
   // the asynchronous forms (tavb_search_topk_device, tavb_search_topk_allgather): the finish kernel writes every query's rounds here, and
   // the next tavb_synchronize folds the first topk_rounds_pending of them into last_topk_refine
@@ -279,7 +283,7 @@ struct tavb_ctx {
   template <class F>
   void for_each_buffer(F&& f) {
     for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
-                      &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk,
+                      &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk, &d_msg_best,
                       &d_sort_keys, &d_sort_ws, &d_mask_counts, &d_compact, &d_scope, &d_scope_bits, &d_scope_rows, &d_scope_member, &d_scope_planes, &h_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
                       &d_local, &d_xlocal, &d_gather})
       f(*b);
@@ -463,6 +467,14 @@ int search_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* 
 // carrying index_base + position -> out_keys (device or device-writable pinned memory); d_rows: a subset's rows (nq == 1), or null.
 int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_pos,
                       uint32_t index_base, u64_t* out_keys);
+
+// The best k MESSAGES of every query (tavb_search_top_messages): queries on the device over the corpus (d_rows null) or over n_rows valid
+// rows at d_rows; the caller has checked the row -> message map (it covers the corpus, 1 <= n_messages < 2^31 - 1), 1 <= k <=
+// TAVB_MAX_LARGE_K and that there is something to scan.  Per group of queries: two memsets, the score pass with the MessageMaxSink, the
+// histogram pass over [queries][n_messages], then search_topk_impl's launches with the message ordinals as positions -> out_keys [nq][k]
+// sorted, zero-filled keys carrying MESSAGE ordinals, + out_rounds [nq], both device-writable; nothing is waited for.
+int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_rows,
+                             u64_t* out_keys, int32_t* out_rounds);
 
 // A scoped batch at 1 <= k <= TAVB_MAX_LARGE_K (masks as for search_scoped_impl): per pass of min(topk_queries_per_pass, 8) queries the
 // scoped score pass over the pass' union list, the refinement rounds, the compaction and the finish into `work` [nq, k], and the remap of

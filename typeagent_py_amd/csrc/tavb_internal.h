@@ -42,6 +42,10 @@ struct ScanParams {
   // scoped score pass (launch_scan_topk_scoped): query q of the launch is bit scope_bit0 + q of a membership byte -- the launch's queries
   // may be a sub-group of the pass the bytes were written for
   int32_t scope_bit0;
+  // score pass of a top-messages lookup (launch_scan_top_messages, plain form only): topk_scores is msg_best [nq][n_messages], zeroed by the
+  // caller; a passing row whose message row_to_msg[row] lies in [0, n_messages) raises that message's slot (MessageMaxSink, tavb_scan.hip)
+  const int32_t* row_to_msg;
+  int64_t n_messages;
 };
 
 struct ScanGeometry {
@@ -67,6 +71,11 @@ hipError_t launch_scan_topk(const ScanParams& p, const ScanGeometry& g, hipStrea
 // the pass' scopes, with p.scope_member / p.scope_bit0 set (scope_bit0 + nq <= 8) -- a position whose member bit is clear gets kScoreNone
 // for that query and is counted nowhere; a member's score and bucket are launch_scan_topk's.  Vector tier for aligned rows, else scalar.
 hipError_t launch_scan_topk_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// the score pass of a top-messages lookup (tavb_scan.hip): launch_scan_topk's kernels, tiers and per-row arithmetic over the corpus or over
+// p.row_ids (n_pos positions), with the MessageMaxSink in place of the ScoreSink -- nothing is written per row; p.topk_scores [nq][n_messages]
+// (zero when the pass starts) ends with, per query and message, 1 + the score bits of the message's best passing row, 0 where no row of
+// it passed.  p.row_to_msg covers every row the pass visits; p.topk_hist / p.topk_buckets are unused (0): launch_message_hist counts afterwards.
+hipError_t launch_scan_top_messages(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
 // one pass of a scoped batch (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES; 4 for k > 64) queries over p.row_ids, the ascending row
 // list of the union of their scopes, index_base 0; query q is offered position pos only when bit q of p.scope_member[pos] is set.
 // Otherwise launch_scan's plain form: the same lists at p.lists, the same per-row arithmetic on the vector or the scalar tier.
@@ -100,6 +109,10 @@ int topk_refine_rounds(int64_t n_pos, int cap);
 hipError_t launch_topk_refine(const TopkLaunch& t, int round, hipStream_t stream);
 hipError_t launch_topk_compact(const TopkLaunch& t, hipStream_t stream);
 hipError_t launch_topk_finish(const TopkLaunch& t, hipStream_t stream);
+// Between launch_scan_top_messages and the launches above (t.n_pos = n_messages, positions = message ordinals): best [nq][n_pos], the
+// array t.scores names, is decoded in place -- 1 + score bits -> score bits, 0 -> kScoreNone -- and every message that has a score is counted
+// in the workspace's histograms with topk_bucket over t.lo / t.scale, as the ScoreSink counts rows.  One launch; t.buckets <= 4096.
+hipError_t launch_message_hist(const TopkLaunch& t, unsigned* best, hipStream_t stream);
 
 // Merge of LONG sorted lists (any k up to TAVB_MAX_LARGE_K; launch_merge stops at TAVB_MAX_FUSED_K): n_lists (1 .. 64) lists of k keys per
 // query, sorted descending and zero-padded, [n_lists, nq, k] or query-major [nq, n_lists, k] -> out [nq, k], the best k of their union,

@@ -1,6 +1,6 @@
 // The large-k and sorted lookups of the C ABI (include/tavb.h): tavb_search_topk and its subset / device forms, tavb_search_sorted,
 // tavb_search_subset_sorted, tavb_search_subset_batch_sorted, tavb_sort_keys_device, their scoped forms (one mask per query:
-// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
+// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted), the top-messages lookups (tavb_search_top_messages / _device) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
 // tavb_topk.hip and tavb_sort.hip, the staging in tavb_lookup.hip.
 
 #include <optional>
@@ -47,6 +47,17 @@ int plan_score_pass(tavb_ctx* c, int nq, int64_t n_pos, bool refine, ScorePlan* 
 // queries per pass of the scoped routes: the score pass' own, within the bits of a membership byte
 int scoped_topk_per_pass(const tavb_ctx* c) { return std::min(tavb::topk_queries_per_pass(c->dim, c->dtype, (int)c->topk_buckets), 8); }
 
+// the bucket maps of n queries (topk_bucket, tavb_device.h): lo = the threshold brought into [0, 1], scale = nb / (1 - lo); slots from n on: nothing passes
+void bucket_maps(const float* min_scores /*host, n*/, int n, int nb, tavb::TopkLaunch* t) {
+  for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
+    const float ms = i < n ? min_scores[i] : INFINITY;
+    float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
+    if (lo > 1.0f) lo = 1.0f;
+    t->lo[i] = lo;
+    t->scale[i] = lo < 1.0f ? (float)nb / (1.0f - lo) : 0.0f;
+  }
+}
+
 // The pass for the queries [q0, q0 + n) of the batch (d_q, min_scores: the whole batch's; d_rows: a subset's rows, or null).  *t arrives
 // with the caller's own members set (k, out_keys, out_rounds, index_base) and leaves filled in, ready for the caller's selection launches.
 // `what` names the caller in the messages.  *tm: the TAVB_KERNEL_TOPK interval, opened in front of the refinement rounds -- the caller's
@@ -62,12 +73,10 @@ int run_score_pass(tavb_ctx* c, const ScorePlan& s, const char* what, const floa
   p.topk_buckets = s.nb;
   p.scope_member = member;
   p.scope_bit0 = bit0;
+  bucket_maps(min_scores + q0, n, s.nb, t);
   for (int i = 0; i < TAVB_MAX_STREAM_QUERIES; ++i) {
-    const float ms = i < n ? min_scores[q0 + i] : INFINITY;
-    float lo = ms > 0.0f ? ms : 0.0f;  // (NaN: nothing passes; the bucket map is never used)
-    if (lo > 1.0f) lo = 1.0f;
-    p.topk_lo[i] = t->lo[i] = lo;
-    p.topk_scale[i] = t->scale[i] = lo < 1.0f ? (float)s.nb / (1.0f - lo) : 0.0f;
+    p.topk_lo[i] = t->lo[i];
+    p.topk_scale[i] = t->scale[i];
   }
   {
     Timed scan(c, TAVB_KERNEL_SCAN);
@@ -166,6 +175,86 @@ int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const 
     }
   }
   return TAVB_OK;
+}
+
+// ---- the best k messages (tavb_search_top_messages): the group-by-message step between the score pass and the selection.  Groups of
+// queries as in search_topk_impl, sized by the queries' LDS alone (the MessageMaxSink keeps no histogram there) and by "topk_scores_bytes"
+// over [queries][n_messages].  Per group: the head of d_topk and the group's slots of d_msg_best zeroed, ONE pass over the corpus or the row
+// list, the histogram pass over the messages, then the refinement rounds, the compaction and the finish with n_pos = n_messages.
+int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_rows,
+                             u64_t* out_keys, int32_t* out_rounds) {
+  const int64_t n_scan = d_rows ? n_rows : c->rows;
+  const int64_t nm = c->n_messages;
+  ScorePlan s;
+  s.n_pos = nm;
+  s.nb = (int)c->topk_buckets;
+  s.cap = (int)c->topk_boundary_keys;
+  s.per = std::min<int64_t>(std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, 0), nq),
+                            std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
+  s.rounds = tavb::topk_refine_rounds(nm, s.cap);
+  s.g = clamped_geometry(c);
+  s.g.blocks = scan_blocks_for(c, n_scan, s.g.waves, 2);
+  s.sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nm + 2047) / 2048), std::max<int64_t>(1, 2048 / s.per));
+  if (int rc = c->d_msg_best.reserve((size_t)s.per * nm * sizeof(uint32_t))) return rc;
+  if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)s.per, k, s.nb, s.cap, s.rounds))) return rc;
+  unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
+  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
+    const int n = (int)std::min<int64_t>(s.per, nq - q0);
+    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
+    TAVB_HIP(hipMemsetAsync(best, 0, (size_t)n * nm * sizeof(uint32_t), c->stream));
+    tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, n_scan, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
+    p.topk_scores = best;
+    p.row_to_msg = c->row_to_msg;
+    p.n_messages = nm;
+    {
+      Timed scan(c, TAVB_KERNEL_SCAN);
+      hipError_t e = tavb::launch_scan_top_messages(p, s.g, c->stream, &c->last_tier);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages score pass launch failed: %s", hipGetErrorString(e));
+    }
+    tavb::TopkLaunch t{};
+    bucket_maps(min_scores + q0, n, s.nb, &t);
+    t.scores = best;
+    t.workspace = c->d_topk.ptr;
+    t.n_pos = nm;
+    t.nq = n;
+    t.k = k;
+    t.buckets = s.nb;
+    t.cap = s.cap;
+    t.rounds = s.rounds;
+    t.blocks = s.sel_blocks;
+    t.out_keys = out_keys + (size_t)q0 * k;
+    t.out_rounds = out_rounds + q0;
+    t.index_base = 0u;
+    Timed tm(c, TAVB_KERNEL_TOPK);
+    hipError_t e = tavb::launch_message_hist(t, best, c->stream);
+    for (int r = 0; r < s.rounds && e == hipSuccess; ++r) e = tavb::launch_topk_refine(t, r, c->stream);
+    if (e == hipSuccess) e = tavb::launch_topk_compact(t, c->stream);
+    if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages selection launch failed: %s", hipGetErrorString(e));
+  }
+  return TAVB_OK;
+}
+
+// what both top-messages entry points check: context, corpus, 1 <= k <= TAVB_MAX_LARGE_K, the row list's shape, and a row -> message map
+// that covers exactly the corpus and whose ordinals fit a key's position.  *empty: nothing to scan -- every list is empty.
+int check_top_messages_args(tavb_ctx* c, int k, const int32_t* dev_rows, int64_t n_rows, bool* empty) {
+  if (int rc = check_topk_args(c, k)) return rc;
+  if (n_rows < 0 || n_rows >= 0x7FFFFFFFll) return fail(TAVB_E_INVALID, "bad row list length");
+  if (!dev_rows && n_rows != 0) return fail(TAVB_E_INVALID, "null dev_rows");
+  if (!c->row_to_msg && c->rows > 0) return fail(TAVB_E_NO_CORPUS, "no row -> message map set (call tavb_set_row_messages first)");
+  if (c->row_to_msg_rows != c->rows)
+    return fail(TAVB_E_INVALID, "the row -> message map covers %lld rows, the corpus has %lld", (long long)c->row_to_msg_rows, (long long)c->rows);
+  if (c->n_messages >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "top-messages keys hold message ordinals: n_messages must be < 2^31 - 1");
+  if (c->rows >= 0xFFFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "the score pass indexes rows in 32 bits: rows must be < 2^32 - 1");
+  *empty = c->rows == 0 || c->n_messages == 0 || (dev_rows && n_rows == 0);
+  return TAVB_OK;
+}
+
+void note_top_messages(tavb_ctx* c) {
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  c->last_graph = 0;
 }
 
 int check_topk_args(tavb_ctx* c, int k) {
@@ -605,6 +694,55 @@ int tavb_search_scoped_sorted(tavb_ctx* c, const float* queries_host, int32_t nq
   const float* d_q;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   return search_scoped_sorted_impl(c, d_q, nq, k, min_scores, dev_masks, c->ordinal_base, max_total, out_ordinals, out_scores, out_counts, out_total);
+}
+
+// ---- the best k messages: per-message best score and top-k on the device (search_top_messages_impl)
+int tavb_search_top_messages(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                             int64_t n_rows, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_top_messages_args(c, k, dev_rows, n_rows, &empty)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_top_messages(c);
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
+  u64_t* target = keys;
+  if (n_keys > 4096) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_top_messages_impl(c, d_q, nq, k, min_scores, dev_rows, n_rows, target, rounds)) return rc;
+  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                                    int64_t n_rows, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_top_messages_args(c, k, dev_rows, n_rows, &empty)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  note_top_messages(c);
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (int rc = search_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
 }
 
 int tavb_sort_keys_device(tavb_ctx* c, tavb_key* dev_keys, int64_t n) {

@@ -165,6 +165,50 @@ struct ScoreSink {
   }
 };
 
+// The epilogue of the score pass of a top-messages lookup (launch_scan_top_messages): the ScoreSink's score of the same row and the same
+// test, but nothing is stored per row -- a passing row raises its MESSAGE's slot, best[q][row_to_msg[row]], with one atomicMax from lane 0.
+// `row` is the index itself on the whole corpus and row_ids[index] on a row list (index_base is 0; both wave-uniform); a row without a
+// message (a map value outside [0, n_messages)) is skipped.  Scores are non-negative floats, so unsigned order on their bits is score
+// order.  Encoding: the slot holds bits + 1 over an array the caller zeroed -- 0 means "no passing row yet", which 0.0f (bits 0, a
+// legitimate passing score) could not mean and kScoreNone (0xFFFFFFFF) cannot as the empty value of a max; bits <= 0x3F800000, so the + 1
+// never wraps, and launch_message_hist's `slot - 1` gives the bits back and turns 0 into kScoreNone.  A max does not depend on the order of
+// its operands: the array, and with it the whole lookup, is deterministic.  The plain load in front skips the atomic where the slot holds
+// as much already (the chunks of one message are often neighbours and hit one address); slots only ever rise, so a stale value can only
+// cost an atomic that changes nothing.  No LDS, no histogram: a message's value keeps rising during the pass, so the counting waits.
+template <int NQ>
+struct MessageMaxSink {
+  static constexpr bool kScorePass = true;
+  static constexpr bool kScoped = false;
+  unsigned* best;             // [nq][n_messages]
+  const int32_t* row_ids;     // position -> row, or null
+  const int32_t* row_to_msg;  // [rows]
+  int64_t n_messages;
+  int n_live;
+
+  __device__ __forceinline__ void setup(const ScanParams& p, const QueryGroup& qg, void*) {
+    best = p.topk_scores;
+    row_ids = p.row_ids;
+    row_to_msg = p.row_to_msg;
+    n_messages = p.n_messages;
+    n_live = qg.n;
+  }
+  __device__ __forceinline__ void clear() {}
+  __device__ __forceinline__ void offer(int q, float partial, uint32_t index, float min_score, int, int lane, u64) {
+    const float dot = wave_sum(partial);
+    const float s = wave_uniform(cosine_to_score(dot));
+    if (q < n_live && s >= min_score && lane == 0) {  // NaN never passes, like numpy's >=
+      const int64_t row = row_ids ? (int64_t)row_ids[index] : (int64_t)index;
+      const int64_t m = row_to_msg[row];
+      if (m >= 0 && m < n_messages) {
+        unsigned* slot = best + (size_t)q * n_messages + m;
+        const unsigned v = __float_as_uint(s) + 1u;
+        if (*slot < v) atomicMax(slot, v);
+      }
+    }
+  }
+  __device__ __forceinline__ void flush() {}
+};
+
 // The Selector of a scoped batch (launch_scan_scoped): every query of the pass has a scope of its own, the scan runs over the ascending row
 // list of the scopes' UNION, and member[position] says which queries' scopes hold that row (bit q = query q of the pass;
 // scope_member_kernel, tavb_mask.hip).  A row is offered to query q only when its bit is set -- the score, the threshold test, the key and the
@@ -773,10 +817,10 @@ hipError_t go_topk_scalar(const ScanParams& p, const ScanGeometry& g, hipStream_
   return hipGetLastError();
 }
 
-template <typename T, int CH>
+template <typename T, int CH, typename SINK = ScoreSink<1>>
 hipError_t go_topk_fixed(const ScanParams& p, const ScanGeometry& g, hipStream_t s) {
   const size_t lds = (size_t)p.topk_buckets * 4;
-  auto kern = scan_fixed_kernel<T, CH, 1, 1, 2, true, false, 1024, NoInlineQuery, ScoreSink<1>>;
+  auto kern = scan_fixed_kernel<T, CH, 1, 1, 2, true, false, 1024, NoInlineQuery, SINK>;
   if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return e;
   hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.waves * 64), lds, s, p, NoInlineQuery{});
   return hipGetLastError();
@@ -841,6 +885,24 @@ hipError_t launch_scan_topk_scoped(const ScanParams& p, const ScanGeometry& g, h
   if (tier == 3 && (size_t)nqt * p.topk_buckets * 4 > kTopkLdsBudget) return hipErrorInvalidValue;
   if (tier_used) *tier_used = tier;
   return f16 ? dispatch_topk<_Float16, ScopedScoreSink>(p, g, stream, tier, nqt) : dispatch_topk<float, ScopedScoreSink>(p, g, stream, tier, nqt);
+}
+
+// The score pass of a top-messages lookup (tavb_search_top_messages): launch_scan_topk's tiers by launch_scan_topk's rule -- over the corpus or
+// over a row list -- with the MessageMaxSink, so every row's score is the single-query lookup's bit for bit.  The sink keeps nothing in LDS
+// (p.topk_buckets is 0: topk_queries_per_pass(dim, dtype, 0) sizes the groups by the queries alone).
+hipError_t launch_scan_top_messages(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used) {
+  if (p.nq < 1 || p.nq > TAVB_MAX_STREAM_QUERIES || p.group != 0 || p.dim < 1 || p.index_base != 0 || !p.topk_scores || p.topk_buckets != 0 ||
+      !p.row_to_msg || p.n_messages < 1 || p.n_pos < 1)
+    return hipErrorInvalidValue;
+  const bool f16 = p.dtype == TAVB_F16;
+  const int epl = f16 ? 8 : 4;
+  const bool aligned = ((uintptr_t)p.corpus % 16) == 0 && (p.dim % epl) == 0;
+  const int nqt = p.nq <= 1 ? 1 : p.nq <= 2 ? 2 : p.nq <= 4 ? 4 : 8;
+  const int tier = (aligned && p.dim == 1536 && nqt == 1) ? 1 : aligned ? 2 : 3;
+  if (tier == 2 && topk_vec_lds(nqt, p.dim, 0) > kTopkLdsBudget) return hipErrorInvalidValue;  // (topk_queries_per_pass sizes the groups)
+  if (tier_used) *tier_used = tier;
+  if (tier == 1) return f16 ? go_topk_fixed<_Float16, 3, MessageMaxSink<1>>(p, g, stream) : go_topk_fixed<float, 6, MessageMaxSink<1>>(p, g, stream);
+  return f16 ? dispatch_topk<_Float16, MessageMaxSink>(p, g, stream, tier, nqt) : dispatch_topk<float, MessageMaxSink>(p, g, stream, tier, nqt);
 }
 
 // ---------------------------------------------------------------------------

@@ -187,6 +187,37 @@ __global__ void __launch_bounds__(256) topk_refine_kernel(const TopkLaunch t, in
   }
 }
 
+// ---- top-messages lookups (tavb_search_top_messages): the score pass left best [nq][n_pos] -- n_pos = n_messages, position = message ordinal
+// -- holding 1 + the score bits of each message's best passing row, 0 for a message none of whose rows passed (MessageMaxSink,
+// tavb_scan.hip).  The pass could not count: a message's value kept rising.  This one decodes every slot in place (`slot - 1`: the bits, and
+// 0 becomes kScoreNone) and counts the messages that have a score into the workspace's histograms -- LDS histogram, nonzero buckets flushed
+// with atomics, topk_bucket over the same lo / scale a score pass would use -- so that what follows (resolve, refine, compact, finish) finds
+// what the ScoreSink leaves over rows, and runs unchanged.
+constexpr int kMessageHistBuckets = 4096;  // the most "topk_buckets" allows
+
+__global__ void __launch_bounds__(256) message_hist_kernel(const TopkLaunch t, unsigned* __restrict__ best) {
+  __shared__ unsigned lh[kMessageHistBuckets];
+  const Layout l = layout(t);
+  const int q = blockIdx.y;
+  const int nb = t.buckets;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) lh[i] = 0u;
+  __syncthreads();
+  const float lo = t.lo[q], scale = t.scale[q];
+  unsigned* __restrict__ sc = best + (size_t)q * t.n_pos;
+  for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < t.n_pos; pos += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned v = sc[pos];
+    const uint32_t bits = v - 1u;  // (0 -> kScoreNone)
+    sc[pos] = bits;
+    if (v) atomicAdd(&lh[topk_bucket(__uint_as_float(bits), lo, scale, nb)], 1u);
+  }
+  __syncthreads();
+  unsigned* gh = l.hist + (size_t)q * nb;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) {
+    const unsigned v = lh[i];
+    if (v) atomicAdd(&gh[i], v);
+  }
+}
+
 // append `key` (where `flag`) to list[0 .. limit) through *counter: one atomic per wave (all 64 lanes must be here)
 __device__ __forceinline__ void wave_append(bool flag, u64 key, unsigned* counter, u64* list, unsigned limit, int lane) {
   const unsigned long long m = __ballot(flag);
@@ -468,6 +499,12 @@ int topk_refine_rounds(int64_t n_pos, int cap) {
     ++r;
   }
   return r;
+}
+
+hipError_t launch_message_hist(const TopkLaunch& t, unsigned* best, hipStream_t stream) {
+  if (!valid_head(t) || !best || best != t.scores || t.buckets > kMessageHistBuckets) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(message_hist_kernel, dim3(t.blocks, t.nq), dim3(256), 0, stream, t, best);
+  return hipGetLastError();
 }
 
 hipError_t launch_topk_refine(const TopkLaunch& t, int round, hipStream_t stream) {

@@ -1527,6 +1527,77 @@ class VectorBase:
         msgs, scs, cnts = eng.search_messages_batch(queries, max_hits, thr, cut, accept=acc)
         return _scored_lists(msgs, scs, cnts, max_hits)
 
+    # ------------------------------------------------------------------ top-k distinct messages (additive)
+    def _collapse_to_messages(self, hits, max_messages: int) -> list[ScoredInt]:
+        """Row hits (every survivor of a lookup) -> the best `max_messages` MESSAGES (0: all of them): per message the best score of its
+        rows, rows without a message (-1) dropped, sorted by (score descending, message ordinal ascending)."""
+        if not hits:
+            return []
+        n = len(hits)
+        rows = np.fromiter((h.item for h in hits), dtype=np.int64, count=n)
+        scs = np.fromiter((h.score for h in hits), dtype=np.float64, count=n)
+        msgs = self._row_messages[rows]
+        keep = msgs >= 0
+        msgs, scs = msgs[keep], scs[keep]
+        order = np.lexsort((msgs, -scs))
+        msgs, scs = msgs[order], scs[order]
+        first = np.sort(np.unique(msgs, return_index=True)[1])  # a message's first entry in that order carries its best score
+        if max_messages:
+            first = first[:max_messages]
+        return list(map(ScoredInt, msgs[first].tolist(), scs[first].tolist()))
+
+    @staticmethod
+    def _top_messages_native(eng, max_messages: int) -> bool:
+        """A single-GPU engine with the call, its "top_messages" option on (the default) and 1 <= max_messages <= 16384; device groups,
+        test doubles, the option at 0 and every other max_messages take the all-survivor lookup and the host collapse."""
+        return (isinstance(eng, _native.Engine) and hasattr(eng, "search_top_messages") and 1 <= max_messages <= _native.MAX_LARGE_K
+                and eng.get_option("top_messages") != 0)
+
+    def lookup_top_messages_by_embedding(
+        self,
+        embedding: NormalizedEmbedding,
+        max_messages: int | None = None,
+        threshold_score: float | None = None,
+        allowed=None,
+    ) -> list[ScoredInt]:
+        """The best `max_messages` MESSAGES (None -> 10): see `lookup_top_messages_by_embeddings`, of which this is the one-query form."""
+        return self.lookup_top_messages_by_embeddings(self._batch_of_one(embedding), max_messages, threshold_score, allowed)[0]
+
+    def lookup_top_messages_by_embeddings(
+        self,
+        embeddings: NormalizedEmbeddings,
+        max_messages: int | None = None,
+        threshold_score: float | None = None,
+        allowed=None,
+    ) -> list[list[ScoredInt]]:
+        """Top-k DISTINCT messages ("collapsing"), per query: of every row that is inside `allowed` (a mask, see `row_mask`, or a `RowMask`
+        from `row_mask`, `message_mask`, `range_mask` or mask algebra; None: every row), has a message (`set_row_messages`, not -1) and
+        scores >= `threshold_score` (NaN never passes), each message gets the best score of its rows; the `max_messages` (None -> 10)
+        messages with the highest best score are returned, sorted by that score descending, ties by ascending message ordinal -- always
+        min(max_messages, messages with a passing row) of them.  `lookup_messages_by_embedding` instead collapses the best `max_matches`
+        chunk ROWS and may return far fewer messages.  Scores are `fuzzy_lookup_embedding`'s float32 scores bit for bit;
+        `threshold_score` may be a sequence with one threshold per query.
+
+        On a single-GPU engine with 1 <= max_messages <= 16384 (and a mask that holds its row list on the device) it is ONE submission
+        (tavb_search_top_messages, engine option "top_messages", default 1): per eight queries one corpus pass that keeps one maximum per
+        message on the device, then the exact device top-k over the messages.  Everything else -- max_messages 0 (every message) or
+        beyond 16384, device groups, test doubles, "top_messages" = 0 -- takes the all-survivor lookup (`fuzzy_lookup_embedding(s)` /
+        `_masked` at max_hits = 0) and collapses on the host, with the same result.  Not served here: one scope per query in one
+        submission (loop over this call), `FusedIndexQuery`, the MFMA tiles."""
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_messages, threshold_score)
+        self._check_row_messages()
+        mask = None if allowed is None else self._resolve_mask(allowed)
+        nq = len(queries)
+        if self._count == 0 or nq == 0 or (mask is not None and mask.count == 0):
+            return [[] for _ in range(nq)]
+        eng = self._messages_engine()
+        if eng is not None and self._top_messages_native(eng, max_hits) and (mask is None or (self._masked_native(eng) and mask.dev_rows is not None)):
+            msgs, scs, cnts = eng.search_top_messages(queries, max_hits, thr, dev_rows=None if mask is None else mask.dev_rows)
+            return _scored_lists(msgs, scs, cnts, max_hits)
+        min_score = threshold_score if per_query is None else per_query
+        lists = self.fuzzy_lookup_embeddings(queries, 0, min_score) if mask is None else self.fuzzy_lookup_embeddings_masked(queries, mask, 0, min_score)
+        return [self._collapse_to_messages(hits, max_hits) for hits in lists]
+
     async def fuzzy_lookup(
         self,
         key: str,
