@@ -204,13 +204,17 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   query: tavb_search_scoped_batch / _device, tavb_search_messages_scoped), 5 = a scoped batch on the 32/64-query tile
  *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile), 6 = a scoped batch on the 128/256-query filter tile +
  *                   rescoring (tavb_search_scoped_wide / _device, tavb_search_messages_scoped_wide), 7 = a scoped batch on the large-k route
- *                   (tavb_search_scoped_topk / _device), 8 = a scoped batch on the sorted route (tavb_search_scoped_sorted);
+ *                   (tavb_search_scoped_topk / _device), 8 = a scoped batch on the sorted route (tavb_search_scoped_sorted),
+ *                   9 = a scoped top-messages batch (tavb_search_top_messages_scoped / _device);
  *                   tavb_search_subset_batch_sorted is the gather route: 1
  *   "scope_large_k" (default 1; the binding reads it) 1 = a scoped batch at max_hits beyond TAVB_MAX_FUSED_K, or 0, is ONE call of
  *                   tavb_search_scoped_topk / tavb_search_scoped_sorted (while "large_k" / "sort_all" are on); 0 = the binding loops over
  *                   the per-query masked lookups, as before those calls existed
  *   "top_messages"  (default 1; the binding reads it) 1 = lookup_top_messages_by_embedding(s) is ONE call of tavb_search_top_messages (1 <=
  *                   max_messages <= TAVB_MAX_LARGE_K); 0 = the binding takes the all-survivor lookup and collapses rows to messages on the host
+ *   "top_messages_scoped"  (default 1; the binding reads it) 1 = lookup_top_messages_by_embeddings_scoped (one scope per query) is ONE call
+ *                   of tavb_search_top_messages_scoped (while "top_messages" is on, 1 <= max_messages <= TAVB_MAX_LARGE_K); 0 = the binding
+ *                   loops over the one-mask lookup, as before that call existed
  *   "scope_wide"    scoped batches on fp16 corpora (the binding reads it; the rule is tavb_plan_scoped_wide, with "mask_tile_min_bytes" /
  *                   "mask_tile_pct"): 1 (default) = the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide) where
  *                   tavb_plan_scoped_wide says so -- it then wins over "scope_tile"; 0 = never; 2 = wherever that route serves the shape
@@ -685,6 +689,33 @@ int tavb_search_top_messages(tavb_ctx* ctx, const float* queries_host, int32_t n
                              int64_t n_rows, int64_t* out_messages, float* out_scores, int32_t* out_counts);
 int tavb_search_top_messages_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores /*host*/,
                                     const int32_t* dev_rows, int64_t n_rows, tavb_key* out_keys);
+
+/* ---- the best k MESSAGES under one scope PER QUERY, in one submission ---------------------------------------------------------------------
+ * tavb_search_top_messages takes one row list for the whole batch; these calls take one mask per query -- the lookups of one compiled
+ * question, each under its own `when` filter.  Per query the result is tavb_search_top_messages' over that mask's row list
+ * (tavb_mask_expand), bit for bit: message ordinals, float32 scores and counts.  dev_masks / rows follow tavb_search_scoped_batch (HOST array
+ * of nq device pointers to packed masks over the corpus' rows, none NULL, 4-byte aligned, repeats allowed; rows = the corpus' rows), waves
+ * and passes follow tavb_search_scoped_topk: one synchronise per wave for the unions' sizes, a pass being min(8, the queries of one score
+ * pass) queries -- eight bits of a membership byte.  Per pass, over the ascending row list of the union of its scopes: the top-messages
+ * score pass in its scoped form -- a passing row raises its message's slot for query j only when bit j of the row's membership byte is
+ * set, a clear bit does nothing -- so a message whose chunks lie in several queries' scopes gets, for each query, the best score among
+ * the rows of THAT query's scope.  Then tavb_search_top_messages' own launches, unchanged: the histogram pass over [queries][n_messages],
+ * boundary search, refinement, compaction and sort with the message ordinals as positions.  "topk_scores_bytes" holds: where
+ * [queries of a pass][n_messages] x 4 bytes would exceed it the pass' queries go in sub-groups over the same list (at least one query
+ * each).  A row several scopes of a pass share is read once per pass.
+ *   tavb_search_top_messages_scoped: queries on the host, one more synchronise at the end; out_messages / out_scores [nq, k], out_counts
+ *     [nq] as tavb_search_top_messages: MESSAGE ordinals, no ordinal_base.  "masked_route" reports 9, "last_topk_refine" the most rounds
+ *     of any query.
+ *   tavb_search_top_messages_scoped_device: dev_queries device float32 [nq, dim]; out_keys [nq, k] sorted, zero-padded keys carrying message
+ *     ordinals, device or device-writable pinned memory; waits only for the unions' sizes ("last_topk_refine" at the next tavb_synchronize).
+ * 1 <= k <= TAVB_MAX_LARGE_K.  Errors are tavb_search_top_messages' (no map, a map that does not cover the corpus, k out of range, NULL
+ * arguments) and the scoped calls' (rows != the corpus' rows, a NULL or misaligned mask pointer), each with a message.  nq == 0, an empty
+ * corpus or n_messages == 0: zero counts / zero keys, nothing launched.  A query whose mask is empty gets an empty list.  Timed under
+ * TAVB_KERNEL_CONVERT (unions, lists, membership), TAVB_KERNEL_SCAN (score pass) and TAVB_KERNEL_TOPK (everything behind it). */
+int tavb_search_top_messages_scoped(tavb_ctx* ctx, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                    const float* min_scores, int64_t* out_messages, float* out_scores, int32_t* out_counts);
+int tavb_search_top_messages_scoped_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows,
+                                           int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
 
 /* ---- scoped batches on the 32/64-query tile: one scope per query on the matrix cores ----------------------------------------------------
  * The scoped batch above reads, per pass of eight queries, the union of the pass' scopes; dense, independent or disjoint scopes make that

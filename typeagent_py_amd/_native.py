@@ -124,6 +124,8 @@ _SIGNATURES = [
      [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     ("tavb_search_top_messages", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_top_messages_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_search_top_messages_scoped", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_top_messages_scoped_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -1325,6 +1327,30 @@ class Engine:
         with self._lock:
             rc = self.lib.tavb_search_top_messages_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), rows_ptr, n,
                                                           c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def search_top_messages_scoped(self, queries, dev_bits_list, k: int, thrs):
+        """`search_top_messages` under one scope PER QUERY, in one submission (tavb_search_top_messages_scoped): dev_bits_list: nq packed
+        masks on this device, one per query; per pass of eight queries one scan of the union of their scopes that raises a message's
+        best score for a query only inside that query's scope -> (message ordinals [nq, k], scores [nq, k], counts [nq]), per query
+        `search_top_messages` over that mask's row list, bit for bit."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_scoped(self._h, _addr(a), nq, ptrs, int(self.rows), k, _addr(t), _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def search_top_messages_scoped_device(self, dev_queries, dev_bits_list, k: int, thrs, out_keys=None):
+        """`search_top_messages_scoped` with the queries on the device (tavb_search_top_messages_scoped_device) -> torch int64 [nq, k]
+        sorted, zero-padded keys carrying MESSAGE ordinals (`decode_keys`).  `out_keys`: a device tensor or a PINNED host tensor.  The
+        call waits for the unions' sizes only: `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        ptrs = self._mask_pointers(dev_bits_list, nq)
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_scoped_device(self._h, c_void_p(dev_queries.data_ptr()), nq, ptrs, int(self.rows), k, _addr(t),
+                                                                 c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 

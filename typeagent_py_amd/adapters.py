@@ -276,6 +276,17 @@ def _scope_mask(vector_base: VectorBase, scope) -> RowMask:
     return vector_base.message_mask(scope)
 
 
+def _scope_masks(vector_base: VectorBase, scopes) -> list[RowMask]:
+    """One scope per query -> their `RowMask`s, one `_scope_mask` per distinct scope OBJECT."""
+    made: dict[int, RowMask] = {}
+    masks = []
+    for s in scopes:
+        if id(s) not in made:
+            made[id(s)] = _scope_mask(vector_base, s)
+        masks.append(made[id(s)])
+    return masks
+
+
 def lookup_messages_in_scopes(
     vector_base: VectorBase,
     embeddings,
@@ -299,13 +310,7 @@ def lookup_messages_in_scopes(
     if len(scopes) != len(queries):
         raise ValueError(f"Number of scopes {len(scopes)} does not match number of embeddings {len(queries)}")
     _ensure_row_messages(vector_base, row_to_message)
-    made: dict[int, RowMask] = {}
-    masks = []
-    for s in scopes:
-        if id(s) not in made:
-            made[id(s)] = _scope_mask(vector_base, s)
-        masks.append(made[id(s)])
-    lists = vector_base.lookup_messages_by_embeddings_scoped(queries, masks, max_matches, threshold_score)
+    lists = vector_base.lookup_messages_by_embeddings_scoped(queries, _scope_masks(vector_base, scopes), max_matches, threshold_score)
     return lists if max_matches is None else [out[:max_matches] for out in lists]
 
 
@@ -354,7 +359,7 @@ def lookup_top_messages(
     `scope` restricts the search as in `lookup_messages_in_scope`: None (every chunk), a collection of message ordinals, a `RowMask`
     (`vector_base.message_mask`, `row_mask`, mask algebra), a `TextRangesInScope`, a `TextRangeCollection` or a list of either.  A 1-D
     embedding returns one list of ScoredInt(message, score), a 2-D array one list per embedding, all under the ONE scope (one scope per
-    query: loop over this call); `threshold_score` may then be a sequence.  `row_to_message`: message ordinal per index position (-1: none)."""
+    query: `lookup_top_messages_in_scopes`); `threshold_score` may then be a sequence.  `row_to_message`: message ordinal per index position (-1: none)."""
     if callable(row_to_message):
         raise TypeError("lookup_top_messages needs row_to_message as a sequence (the map is searched on the device)")
     _ensure_row_messages(vector_base, row_to_message)
@@ -365,6 +370,33 @@ def lookup_top_messages(
     if queries.ndim != 2:
         raise ValueError(f"Expected a 1D embedding or a 2D array of embeddings, got {queries.ndim}D")
     return vector_base.lookup_top_messages_by_embeddings(queries, max_messages, threshold_score, mask)
+
+
+def lookup_top_messages_in_scopes(
+    vector_base: VectorBase,
+    embeddings,
+    row_to_message,
+    scopes,
+    max_messages: int | None = None,
+    threshold_score=None,
+):
+    """`lookup_top_messages` for the lookups of one compiled question, each under its own `when` filter: `embeddings` is a 2-D array and
+    `scopes` a sequence with one scope per embedding, each of the kinds `lookup_messages_in_scope` takes (a collection of message ordinals,
+    a `RowMask`, a `TextRangesInScope`, a `TextRangeCollection` or a list of either).  Returns one list of ScoredInt(message, score) per
+    embedding: per query what `lookup_top_messages(vector_base, e, row_to_message, max_messages, threshold_score_i, scope)` returns -- the
+    best `max_messages` DISTINCT messages of that query's scope.  A scope object that appears several times becomes one mask.  The lookup
+    is `VectorBase.lookup_top_messages_by_embeddings_scoped`: on a single-GPU engine ONE device submission, whatever the scopes.
+    `threshold_score` may be a sequence with one threshold per query."""
+    if callable(row_to_message):
+        raise TypeError("lookup_top_messages_in_scopes needs row_to_message as a sequence (the map is searched on the device)")
+    queries = np.asarray(embeddings, dtype=np.float32)
+    if queries.ndim != 2:
+        raise ValueError(f"Expected a 2D array of embeddings, got {queries.ndim}D")
+    scopes = list(scopes)
+    if len(scopes) != len(queries):
+        raise ValueError(f"Number of scopes {len(scopes)} does not match number of embeddings {len(queries)}")
+    _ensure_row_messages(vector_base, row_to_message)
+    return vector_base.lookup_top_messages_by_embeddings_scoped(queries, _scope_masks(vector_base, scopes), max_messages, threshold_score)
 
 
 def load_sqlite_embeddings(

@@ -258,6 +258,7 @@ const Option kOptions[] = {
     RANGE("scope_wide", scope_wide, 0, 2),
     SWITCH("scope_large_k", scope_large_k),
     SWITCH("top_messages", top_messages),
+    SWITCH("top_messages_scoped", top_messages_scoped),
     RANGE("scope_wave_bytes", scope_wave_bytes, 1, (int64_t)1 << 40),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
     READ_ONLY("norm_rows", norm_rows),

@@ -167,6 +167,7 @@ struct tavb_ctx {
   // ([queries of a group][n_messages] x 4 bytes: what d_topk_scores is to rows; the selection's workspace is d_topk as well)
   Buffer d_msg_best;
   int64_t top_messages = 1;                  // option: 1 = the binding sends lookup_top_messages_* through tavb_search_top_messages, 0 = through the all-survivor lookup and a collapse on the host
+  int64_t top_messages_scoped = 1;           // option: 1 = the binding sends lookup_top_messages_by_embeddings_scoped through tavb_search_top_messages_scoped (while "top_messages" is on), 0 = it loops over the one-mask call
   int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
   // the asynchronous forms (tavb_search_topk_device, tavb_search_topk_allgather): the finish kernel writes every query's rounds here, and
   // the next tavb_synchronize folds the first topk_rounds_pending of them into last_topk_refine
@@ -213,7 +214,7 @@ struct tavb_ctx {
   int64_t mask_tile = 1;                            // option: 1 = follow tavb_plan_masked, 0 = never the tile, 2 = always where supported
   int64_t mask_tile_min_bytes = (int64_t)128 << 20;  // option: allowed rows x row bytes below which the gather route (one launch there) is kept; the default of small_direct_bytes
   int64_t mask_tile_pct = 100;                      // option: the tile when the gather route's bytes are at least this many % of the tile's (100 = byte parity)
-  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile, 6 = a scoped batch on the 128/256-query filter tile + rescoring
+  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile, 6 = a scoped batch on the 128/256-query filter tile + rescoring, 7 / 8 = a scoped batch on the large-k / sorted route, 9 = a scoped top-messages batch
   int64_t mask_wide = 1;                            // option: masked batches on the 128/256-query filter tile (tavb_search_masked_wide): 1 = follow tavb_plan_masked_wide, 0 = never, 2 = always where supported
   int64_t last_skinny_kernel = 0;  // option "last_skinny_kernel" (get): what the last launch of the 32/64-query tile instantiated, tavb::skinny_kernel_id (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
@@ -475,6 +476,14 @@ int search_topk_async(tavb_ctx* c, const float* d_q, int nq, int k, const float*
 // sorted, zero-filled keys carrying MESSAGE ordinals, + out_rounds [nq], both device-writable; nothing is waited for.
 int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_rows,
                              u64_t* out_keys, int32_t* out_rounds);
+// The same under one scope per query (tavb_search_top_messages_scoped; masks as for search_scoped_impl, the caller's checks as above plus
+// 0 < rows < 2^31 - 1): waves and passes as in search_scoped_topk_impl, a pass being min(topk_queries_per_pass, 8) queries over the
+// ascending row list of the union of its scopes; per sub-group of a pass (one, unless [queries][n_messages] would pass
+// "topk_scores_bytes") the group above with the scoped score pass -- a row raises its message's slot for query j only when bit j of its
+// membership byte is set.  Keys carry message ordinals: no remap.  out_rounds: pinned host memory (the queries of empty unions get their
+// zero from the host).  ONE synchronise per wave (the unions' sizes); everything else is enqueued and not waited for.
+int search_scoped_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
+                                    u64_t* out_keys, int32_t* out_rounds);
 
 // A scoped batch at 1 <= k <= TAVB_MAX_LARGE_K (masks as for search_scoped_impl): per pass of min(topk_queries_per_pass, 8) queries the
 // scoped score pass over the pass' union list, the refinement rounds, the compaction and the finish into `work` [nq, k], and the remap of

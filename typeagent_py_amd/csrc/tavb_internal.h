@@ -39,7 +39,7 @@ struct ScanParams {
   // scoped batch (launch_scan_scoped, plain form only): [n_pos] bytes, bit q of byte p = query q of the pass may take position p
   // (launch_scope_member); read by no other launch
   const uint8_t* scope_member;
-  // scoped score pass (launch_scan_topk_scoped): query q of the launch is bit scope_bit0 + q of a membership byte -- the launch's queries
+  // scoped score pass (launch_scan_topk_scoped, launch_scan_top_messages_scoped): query q of the launch is bit scope_bit0 + q of a membership byte -- the launch's queries
   // may be a sub-group of the pass the bytes were written for
   int32_t scope_bit0;
   // score pass of a top-messages lookup (launch_scan_top_messages, plain form only): topk_scores is msg_best [nq][n_messages], zeroed by the
@@ -76,6 +76,10 @@ hipError_t launch_scan_topk_scoped(const ScanParams& p, const ScanGeometry& g, h
 // (zero when the pass starts) ends with, per query and message, 1 + the score bits of the message's best passing row, 0 where no row of
 // it passed.  p.row_to_msg covers every row the pass visits; p.topk_hist / p.topk_buckets are unused (0): launch_message_hist counts afterwards.
 hipError_t launch_scan_top_messages(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
+// the score pass of a scoped top-messages batch (tavb_scan.hip): launch_scan_top_messages over p.row_ids, the ascending row list of the
+// union of the pass' scopes, with p.scope_member / p.scope_bit0 set (scope_bit0 + nq <= 8) -- a position whose member bit is clear does
+// nothing for that query; a member raises its message's slot as launch_scan_top_messages does.  Vector tier for aligned rows, else scalar.
+hipError_t launch_scan_top_messages_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used);
 // one pass of a scoped batch (tavb_scan.hip): p.nq (1 .. TAVB_MAX_STREAM_QUERIES; 4 for k > 64) queries over p.row_ids, the ascending row
 // list of the union of their scopes, index_base 0; query q is offered position pos only when bit q of p.scope_member[pos] is set.
 // Otherwise launch_scan's plain form: the same lists at p.lists, the same per-row arithmetic on the vector or the scalar tier.

@@ -1,6 +1,7 @@
 // The large-k and sorted lookups of the C ABI (include/tavb.h): tavb_search_topk and its subset / device forms, tavb_search_sorted,
 // tavb_search_subset_sorted, tavb_search_subset_batch_sorted, tavb_sort_keys_device, their scoped forms (one mask per query:
-// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted), the top-messages lookups (tavb_search_top_messages / _device) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
+// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted), the top-messages lookups (tavb_search_top_messages / _device) and their scoped forms
+// (tavb_search_top_messages_scoped / _device) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
 // tavb_topk.hip and tavb_sort.hip, the staging in tavb_lookup.hip.
 
 #include <optional>
@@ -181,56 +182,114 @@ int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const 
 // queries as in search_topk_impl, sized by the queries' LDS alone (the MessageMaxSink keeps no histogram there) and by "topk_scores_bytes"
 // over [queries][n_messages].  Per group: the head of d_topk and the group's slots of d_msg_best zeroed, ONE pass over the corpus or the row
 // list, the histogram pass over the messages, then the refinement rounds, the compaction and the finish with n_pos = n_messages.
+namespace {
+
+// Groups of at most `most` queries over the n_messages slots, cut to what "topk_scores_bytes" lets [queries][n_messages] hold (at least
+// one), with d_msg_best and the selection's workspace reserved for one group at depth k.  s->g.blocks is the caller's to set per pass.
+int plan_top_messages(tavb_ctx* c, int64_t most, int k, ScorePlan* s) {
+  const int64_t nm = c->n_messages;
+  s->n_pos = nm;
+  s->nb = (int)c->topk_buckets;
+  s->cap = (int)c->topk_boundary_keys;
+  s->per = std::min<int64_t>(most, std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
+  s->rounds = tavb::topk_refine_rounds(nm, s->cap);
+  s->g = clamped_geometry(c);
+  s->sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nm + 2047) / 2048), std::max<int64_t>(1, 2048 / s->per));
+  if (int rc = c->d_msg_best.reserve((size_t)s->per * nm * sizeof(uint32_t))) return rc;
+  return c->d_topk.reserve(tavb::topk_workspace_bytes((int)s->per, k, s->nb, s->cap, s->rounds));
+}
+
+// One group: the queries [q0, q0 + n) of the batch, n <= s.per, over the n_scan positions of d_rows (null: the corpus) -> out_keys [n][k]
+// and out_rounds [n], both at the group's first query.  member (optional): the scoped form -- d_rows is the union list of a scoped pass,
+// member its membership bytes, and the n queries are its member bits bit0 .. bit0 + n - 1 (launch_scan_top_messages_scoped).
+int top_messages_group(tavb_ctx* c, const ScorePlan& s, const float* d_q, const float* min_scores /*host*/, const int32_t* d_rows, int64_t n_scan, int q0,
+                       int n, int k, u64_t* out_keys, int32_t* out_rounds, const uint8_t* member = nullptr, int bit0 = 0) {
+  const int64_t nm = s.n_pos;
+  unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
+  TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
+  TAVB_HIP(hipMemsetAsync(best, 0, (size_t)n * nm * sizeof(uint32_t), c->stream));
+  tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, n_scan, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
+  p.topk_scores = best;
+  p.row_to_msg = c->row_to_msg;
+  p.n_messages = nm;
+  p.scope_member = member;
+  p.scope_bit0 = bit0;
+  {
+    Timed scan(c, TAVB_KERNEL_SCAN);
+    hipError_t e = member ? tavb::launch_scan_top_messages_scoped(p, s.g, c->stream, &c->last_tier) : tavb::launch_scan_top_messages(p, s.g, c->stream, &c->last_tier);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages score pass launch failed: %s", hipGetErrorString(e));
+  }
+  tavb::TopkLaunch t{};
+  bucket_maps(min_scores + q0, n, s.nb, &t);
+  t.scores = best;
+  t.workspace = c->d_topk.ptr;
+  t.n_pos = nm;
+  t.nq = n;
+  t.k = k;
+  t.buckets = s.nb;
+  t.cap = s.cap;
+  t.rounds = s.rounds;
+  t.blocks = s.sel_blocks;
+  t.out_keys = out_keys;
+  t.out_rounds = out_rounds;
+  t.index_base = 0u;
+  Timed tm(c, TAVB_KERNEL_TOPK);
+  hipError_t e = tavb::launch_message_hist(t, best, c->stream);
+  for (int r = 0; r < s.rounds && e == hipSuccess; ++r) e = tavb::launch_topk_refine(t, r, c->stream);
+  if (e == hipSuccess) e = tavb::launch_topk_compact(t, c->stream);
+  if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages selection launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
+}  // namespace
+
 int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_rows, int64_t n_rows,
                              u64_t* out_keys, int32_t* out_rounds) {
   const int64_t n_scan = d_rows ? n_rows : c->rows;
-  const int64_t nm = c->n_messages;
   ScorePlan s;
-  s.n_pos = nm;
-  s.nb = (int)c->topk_buckets;
-  s.cap = (int)c->topk_boundary_keys;
-  s.per = std::min<int64_t>(std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, 0), nq),
-                            std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
-  s.rounds = tavb::topk_refine_rounds(nm, s.cap);
-  s.g = clamped_geometry(c);
+  if (int rc = plan_top_messages(c, std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, 0), nq), k, &s)) return rc;
   s.g.blocks = scan_blocks_for(c, n_scan, s.g.waves, 2);
-  s.sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nm + 2047) / 2048), std::max<int64_t>(1, 2048 / s.per));
-  if (int rc = c->d_msg_best.reserve((size_t)s.per * nm * sizeof(uint32_t))) return rc;
-  if (int rc = c->d_topk.reserve(tavb::topk_workspace_bytes((int)s.per, k, s.nb, s.cap, s.rounds))) return rc;
-  unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
   for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
     const int n = (int)std::min<int64_t>(s.per, nq - q0);
-    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
-    TAVB_HIP(hipMemsetAsync(best, 0, (size_t)n * nm * sizeof(uint32_t), c->stream));
-    tavb::ScanParams p = scan_params(c, d_q + (size_t)q0 * c->dim, d_rows, n_scan, n, 1, 0u, ~0ull, nullptr, min_scores + q0, TAVB_MAX_GROUPED_QUERIES);
-    p.topk_scores = best;
-    p.row_to_msg = c->row_to_msg;
-    p.n_messages = nm;
-    {
-      Timed scan(c, TAVB_KERNEL_SCAN);
-      hipError_t e = tavb::launch_scan_top_messages(p, s.g, c->stream, &c->last_tier);
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages score pass launch failed: %s", hipGetErrorString(e));
+    if (int rc = top_messages_group(c, s, d_q, min_scores, d_rows, n_scan, q0, n, k, out_keys + (size_t)q0 * k, out_rounds + q0)) return rc;
+  }
+  return TAVB_OK;
+}
+
+// ---- the same under one scope per query (tavb_search_top_messages_scoped): the waves and passes of search_scoped_topk_impl around the
+// group above.  Per pass whose union is not empty: the write pass and the membership bytes, then per sub-group of its queries (one, unless
+// [queries][n_messages] would exceed "topk_scores_bytes") the two memsets, the scoped score pass over the union list with bit0 = the
+// sub-group's first query of the pass, the histogram pass and the selection.  Keys carry message ordinals, not union positions: nothing
+// is remapped.  out_rounds: pinned host memory; the queries of empty unions get their zero from the host, after the wave's synchronise.
+int search_scoped_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
+                                    u64_t* out_keys, int32_t* out_rounds) {
+  const int per = scoped_topk_per_pass(c);
+  const int wave = scoped_wave_queries(c, per);
+  ScorePlan s;
+  if (int rc = plan_top_messages(c, std::min(per, nq), k, &s)) return rc;
+  for (int w0 = 0; w0 < nq; w0 += wave) {
+    const int wn = std::min(wave, nq - w0);
+    ScopeWave w;
+    if (int rc = scope_wave_unions(c, wn, per, masks + w0, &w)) return rc;
+    for (int p = 0; p < w.passes; ++p) {
+      const int q0 = w0 + p * per, n = std::min(per, wn - p * per);
+      const int64_t n_pos = w.n_union[p];
+      if (n_pos == 0) {  // every scope of the pass is empty
+        for (int q = 0; q < n; ++q) out_rounds[q0 + q] = 0;
+        if (int rc = fill_empty_keys(c, out_keys + (size_t)q0 * k, (int64_t)n * k)) return rc;
+        continue;
+      }
+      const int32_t* list;
+      const uint8_t* member;
+      if (int rc = scope_wave_lists(c, w, p, &list, &member)) return rc;
+      s.g.blocks = scan_blocks_for(c, n_pos, s.g.waves, 2);
+      for (int s0 = 0; s0 < n; s0 += (int)s.per) {
+        const int m = (int)std::min<int64_t>(s.per, n - s0);
+        if (int rc = top_messages_group(c, s, d_q, min_scores, list, n_pos, q0 + s0, m, k, out_keys + (size_t)(q0 + s0) * k, out_rounds + q0 + s0, member, s0))
+          return rc;
+      }
     }
-    tavb::TopkLaunch t{};
-    bucket_maps(min_scores + q0, n, s.nb, &t);
-    t.scores = best;
-    t.workspace = c->d_topk.ptr;
-    t.n_pos = nm;
-    t.nq = n;
-    t.k = k;
-    t.buckets = s.nb;
-    t.cap = s.cap;
-    t.rounds = s.rounds;
-    t.blocks = s.sel_blocks;
-    t.out_keys = out_keys + (size_t)q0 * k;
-    t.out_rounds = out_rounds + q0;
-    t.index_base = 0u;
-    Timed tm(c, TAVB_KERNEL_TOPK);
-    hipError_t e = tavb::launch_message_hist(t, best, c->stream);
-    for (int r = 0; r < s.rounds && e == hipSuccess; ++r) e = tavb::launch_topk_refine(t, r, c->stream);
-    if (e == hipSuccess) e = tavb::launch_topk_compact(t, c->stream);
-    if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
-    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages selection launch failed: %s", hipGetErrorString(e));
   }
   return TAVB_OK;
 }
@@ -741,6 +800,68 @@ int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
   if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
   if (int rc = search_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+// ---- the best k messages under one scope per query (search_scoped_top_messages_impl)
+// check_top_messages_args (no row list) and check_scoped_args; *empty: nothing to scan
+static int check_scoped_top_messages_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, bool* empty) {
+  bool no_messages = false, no_rows = false;
+  if (int rc = check_top_messages_args(c, k, nullptr, 0, &no_messages)) return rc;
+  if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, TAVB_MAX_LARGE_K, &no_rows)) return rc;
+  *empty = no_messages || no_rows;
+  return TAVB_OK;
+}
+
+static void note_scoped_top_messages(tavb_ctx* c) {
+  note_top_messages(c);
+  c->masked_route = 9;  // a scoped top-messages batch
+}
+
+int tavb_search_top_messages_scoped(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                    const float* min_scores, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_scoped_top_messages_args(c, nq, dev_masks, rows, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_top_messages(c);
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
+  u64_t* target = keys;
+  if (n_keys > 4096) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_scoped_top_messages_impl(c, d_q, nq, k, min_scores, dev_masks, target, rounds)) return rc;
+  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_top_messages_scoped_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
+                                           const float* min_scores, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_scoped_top_messages_args(c, nq, dev_masks, rows, k, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  note_scoped_top_messages(c);
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (int rc = search_scoped_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_masks, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
   c->topk_rounds_pending = nq;
   return TAVB_OK;
 }

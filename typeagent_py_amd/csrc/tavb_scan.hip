@@ -248,6 +248,27 @@ struct ScopedScoreSink : ScoreSink<NQ> {
   }
 };
 
+// The epilogue of the score pass of a scoped top-messages batch (launch_scan_top_messages_scoped): the MessageMaxSink over the union list of
+// the pass (p.row_ids: the row a position stands for is row_ids[index], as on any row list), with the ScopedScoreSink's test in front --
+// query q of the launch is member bit `bit0 + q`.  Bit set: the MessageMaxSink's own offer.  Bit clear: nothing -- no wave reduction, no
+// store; the slots start at zero, which already means "no passing row".  A message whose chunks lie in several queries' scopes so gets,
+// for query q, the max over the rows of q's own scope only.
+template <int NQ>
+struct ScopedMessageMaxSink : MessageMaxSink<NQ> {
+  static constexpr bool kScoped = true;
+  const uint8_t* member;  // [n_pos]
+  int bit0;
+
+  __device__ __forceinline__ void setup(const ScanParams& p, const QueryGroup& qg, void* lds) {
+    MessageMaxSink<NQ>::setup(p, qg, lds);
+    bit0 = p.scope_bit0;
+  }
+  __device__ __forceinline__ void offer(int q, float partial, uint32_t index, float min_score, int k, int lane, u64 bound) {
+    const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)member[index]) >> bit0;  // (index_base is 0: the index IS the position)
+    if ((m >> q) & 1u) MessageMaxSink<NQ>::offer(q, partial, index, min_score, k, lane, bound);  // wave-uniform
+  }
+};
+
 template <int NQ, int KPL, typename SEL>
 __device__ __forceinline__ void start_epilogue(SEL& sel, const ScanParams& p, const QueryGroup& qg, void* lds) {
   if constexpr (SEL::kScorePass) sel.setup(p, qg, lds);
@@ -903,6 +924,24 @@ hipError_t launch_scan_top_messages(const ScanParams& p, const ScanGeometry& g, 
   if (tier_used) *tier_used = tier;
   if (tier == 1) return f16 ? go_topk_fixed<_Float16, 3, MessageMaxSink<1>>(p, g, stream) : go_topk_fixed<float, 6, MessageMaxSink<1>>(p, g, stream);
   return f16 ? dispatch_topk<_Float16, MessageMaxSink>(p, g, stream, tier, nqt) : dispatch_topk<float, MessageMaxSink>(p, g, stream, tier, nqt);
+}
+
+// The scoped form of that score pass (tavb_search_top_messages_scoped): p.row_ids is the ascending union list of the pass, p.scope_member its
+// membership bytes, and the launch's queries are the member bits p.scope_bit0 .. p.scope_bit0 + p.nq - 1.  Tiers by launch_scan_topk_scoped's
+// rule -- the vector tier for aligned rows (ONE aligned 1536-wide query as well: tier 1 has no scoped form, and its per-row arithmetic is
+// the vector tier's), the scalar tier otherwise -- so every member's score is the single-query lookup's bit for bit.
+hipError_t launch_scan_top_messages_scoped(const ScanParams& p, const ScanGeometry& g, hipStream_t stream, int* tier_used) {
+  if (p.nq < 1 || p.nq > TAVB_MAX_STREAM_QUERIES || p.group != 0 || p.dim < 1 || p.index_base != 0 || !p.topk_scores || p.topk_buckets != 0 ||
+      !p.row_to_msg || p.n_messages < 1 || p.n_pos < 1 || !p.row_ids || !p.scope_member || p.scope_bit0 < 0 || p.scope_bit0 + p.nq > 8)
+    return hipErrorInvalidValue;
+  const bool f16 = p.dtype == TAVB_F16;
+  const int epl = f16 ? 8 : 4;
+  const bool aligned = ((uintptr_t)p.corpus % 16) == 0 && (p.dim % epl) == 0;
+  const int nqt = p.nq <= 1 ? 1 : p.nq <= 2 ? 2 : p.nq <= 4 ? 4 : 8;
+  const int tier = aligned ? 2 : 3;
+  if (tier == 2 && topk_vec_lds(nqt, p.dim, 0) > kTopkLdsBudget) return hipErrorInvalidValue;  // (topk_queries_per_pass sizes the groups)
+  if (tier_used) *tier_used = tier;
+  return f16 ? dispatch_topk<_Float16, ScopedMessageMaxSink>(p, g, stream, tier, nqt) : dispatch_topk<float, ScopedMessageMaxSink>(p, g, stream, tier, nqt);
 }
 
 // ---------------------------------------------------------------------------

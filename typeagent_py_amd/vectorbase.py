@@ -1582,8 +1582,8 @@ class VectorBase:
         (tavb_search_top_messages, engine option "top_messages", default 1): per eight queries one corpus pass that keeps one maximum per
         message on the device, then the exact device top-k over the messages.  Everything else -- max_messages 0 (every message) or
         beyond 16384, device groups, test doubles, "top_messages" = 0 -- takes the all-survivor lookup (`fuzzy_lookup_embedding(s)` /
-        `_masked` at max_hits = 0) and collapses on the host, with the same result.  Not served here: one scope per query in one
-        submission (loop over this call), `FusedIndexQuery`, the MFMA tiles."""
+        `_masked` at max_hits = 0) and collapses on the host, with the same result.  One scope per query in one submission is
+        `lookup_top_messages_by_embeddings_scoped`.  Not served here: `FusedIndexQuery`, the MFMA tiles."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_messages, threshold_score)
         self._check_row_messages()
         mask = None if allowed is None else self._resolve_mask(allowed)
@@ -1597,6 +1597,60 @@ class VectorBase:
         min_score = threshold_score if per_query is None else per_query
         lists = self.fuzzy_lookup_embeddings(queries, 0, min_score) if mask is None else self.fuzzy_lookup_embeddings_masked(queries, mask, 0, min_score)
         return [self._collapse_to_messages(hits, max_hits) for hits in lists]
+
+    @classmethod
+    def _top_messages_scoped_native(cls, eng, handles, order, max_messages: int) -> bool:
+        """The one-call route of a scoped top-messages batch: `_top_messages_native` on an engine that has the scoped call, the option
+        "top_messages_scoped" on (the default) and every searched scope holding its packed mask on the device."""
+        return (eng is not None and hasattr(eng, "search_top_messages_scoped") and cls._top_messages_native(eng, max_messages)
+                and eng.get_option("top_messages_scoped") != 0 and all(handles[i].dev_bits is not None for i in order))
+
+    def lookup_top_messages_by_embeddings_scoped(
+        self,
+        embeddings: NormalizedEmbeddings,
+        scopes,
+        max_messages: int | None = None,
+        threshold_score: float | None = None,
+    ) -> list[list[ScoredInt]]:
+        """`lookup_top_messages_by_embeddings` for queries that carry their OWN scopes -- the lookups of one compiled question, each under
+        its `when` filter: `scopes` is a sequence with one entry per query, each anything `allowed` takes there (a `RowMask` of this index
+        from `row_mask`, `message_mask`, `range_mask` or mask algebra, a bool array, a bool tensor).  Equals
+        [lookup_top_messages_by_embedding(e, max_messages, threshold_score_i, s) for e, s in zip(embeddings, scopes)]: a message whose
+        chunks lie in several queries' scopes gets, for each query, the best score among the rows of THAT query's scope.
+        `threshold_score` may be a sequence with one threshold per query.  A different number of scopes and embeddings raises ValueError;
+        a handle of another index, another length or from before an edit raises what the masked lookups raise.
+
+        When every scope is the same handle this IS `lookup_top_messages_by_embeddings` over it.  Otherwise, on a single-GPU engine with
+        1 <= max_messages <= 16384 whose scopes all hold their packed mask on the device (engine options "top_messages" and
+        "top_messages_scoped", both default 1), the batch is ONE submission (tavb_search_top_messages_scoped): the queries are ordered so
+        that identical handles sit next to each other and go in passes of eight over the UNION of the pass' scopes -- built, listed and
+        tested on the device; a row several scopes share is read once per pass -- and the answers come back in the caller's order, bit
+        for bit those of the per-query calls: message ordinals, float32 scores and counts.  A query whose scope is empty gets an empty
+        answer and takes no slot.  `engine.get_option("masked_route")` is then 9.
+
+        Everything else loops over `lookup_top_messages_by_embedding`: max_messages 0 or beyond 16384 (the host collapse), device groups,
+        `ShardedVectorBase`, test doubles, either option at 0, and a handle without a device mask.  Not served here: `FusedIndexQuery`,
+        the MFMA tiles; queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
+        queries, max_hits, thr, per_query = self._batch_args(embeddings, max_messages, threshold_score)
+        self._check_row_messages()
+        nq = len(queries)
+        handles = self._resolve_scopes(scopes, nq)
+        min_score = threshold_score if per_query is None else per_query
+        if nq and all(h is handles[0] for h in handles):
+            return self.lookup_top_messages_by_embeddings(queries, max_messages, min_score, allowed=handles[0])
+        order = self._scoped_order(handles)
+        if self._count == 0 or not order:
+            return [[] for _ in range(nq)]
+        eng = self._messages_engine()
+        if self._top_messages_scoped_native(eng, handles, order, max_hits):
+            t = np.broadcast_to(np.asarray(thr, dtype=np.float32), (nq,))
+            m, s, c = eng.search_top_messages_scoped(np.ascontiguousarray(queries[order]), [handles[i].dev_bits for i in order], max_hits,
+                                                     np.ascontiguousarray(t[order]))
+            msgs, scs, cnts = np.zeros((nq, max_hits), np.int64), np.zeros((nq, max_hits), np.float32), np.zeros(nq, np.int32)
+            msgs[order], scs[order], cnts[order] = m, s, c
+            return _scored_lists(msgs, scs, cnts, max_hits)
+        return [self.lookup_top_messages_by_embedding(q, max_messages, min_score if per_query is None else per_query[i], handles[i])
+                for i, q in enumerate(queries)]
 
     async def fuzzy_lookup(
         self,
