@@ -205,7 +205,8 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   (tavb_search_scoped_tile / _device, tavb_search_messages_scoped_tile), 6 = a scoped batch on the 128/256-query filter tile +
  *                   rescoring (tavb_search_scoped_wide / _device, tavb_search_messages_scoped_wide), 7 = a scoped batch on the large-k route
  *                   (tavb_search_scoped_topk / _device), 8 = a scoped batch on the sorted route (tavb_search_scoped_sorted),
- *                   9 = a scoped top-messages batch (tavb_search_top_messages_scoped / _device);
+ *                   9 = a scoped top-messages batch (tavb_search_top_messages_scoped / _device), 10 = a top-messages batch on the
+ *                   32/64-query tile (tavb_search_top_messages_tile / _device);
  *                   tavb_search_subset_batch_sorted is the gather route: 1
  *   "scope_large_k" (default 1; the binding reads it) 1 = a scoped batch at max_hits beyond TAVB_MAX_FUSED_K, or 0, is ONE call of
  *                   tavb_search_scoped_topk / tavb_search_scoped_sorted (while "large_k" / "sort_all" are on); 0 = the binding loops over
@@ -215,6 +216,11 @@ int tavb_synchronize(tavb_ctx* ctx);
  *   "top_messages_scoped"  (default 1; the binding reads it) 1 = lookup_top_messages_by_embeddings_scoped (one scope per query) is ONE call
  *                   of tavb_search_top_messages_scoped (while "top_messages" is on, 1 <= max_messages <= TAVB_MAX_LARGE_K); 0 = the binding
  *                   loops over the one-mask lookup, as before that call existed
+ *   "top_messages_tile"  (default 0; the binding reads it) lookup_top_messages_by_embedding(s), unmasked or under one mask that holds its
+ *                   packed bits, on the 32/64-query tile (tavb_search_top_messages_tile): 0 = never -- scores stay tavb_search's bit for bit;
+ *                   1 = where tavb_plan_top_messages_tile says so (with "top_messages_tile_min_batch", "mask_tile_min_bytes" /
+ *                   "mask_tile_pct"); 2 = wherever the tile serves the shape.  1 and 2 trade the bit-for-bit scores for the tile's own
+ *   "top_messages_tile_min_batch"  (default 8, >= 1) fewest queries the plan sends to the tile: the smallest batch measured (profiles/r27_top_messages_tile.md)
  *   "scope_wide"    scoped batches on fp16 corpora (the binding reads it; the rule is tavb_plan_scoped_wide, with "mask_tile_min_bytes" /
  *                   "mask_tile_pct"): 1 (default) = the 128/256-query filter tile + exact rescoring (tavb_search_scoped_wide) where
  *                   tavb_plan_scoped_wide says so -- it then wins over "scope_tile"; 0 = never; 2 = wherever that route serves the shape
@@ -716,6 +722,39 @@ int tavb_search_top_messages_scoped(tavb_ctx* ctx, const float* queries_host, in
                                     const float* min_scores, int64_t* out_messages, float* out_scores, int32_t* out_counts);
 int tavb_search_top_messages_scoped_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows,
                                            int32_t k, const float* min_scores /*host*/, tavb_key* out_keys);
+
+/* ---- the best k MESSAGES on the 32/64-query tile: one corpus pass per 64 queries -----------------------------------------------------------
+ * tavb_search_top_messages reads the corpus once per eight queries.  These calls read it -- or the span of ONE packed mask -- once per 64, on
+ * the 32/64-query MFMA tile in its top-messages form: the tile's own admission test on its own score (score > the float just below the
+ * query's min_score; NaN or a threshold above 1 admits nothing), then ONE unsigned atomic max per admitted (row, query) pair on the same
+ * zeroed [queries][n_messages] array, in the same encoding, that tavb_search_top_messages' score pass writes.  The tile keeps no candidate
+ * lists here, so its k <= 64 bound does not apply: 1 <= k <= TAVB_MAX_LARGE_K.  Behind the tile launch come tavb_search_top_messages' own
+ * launches, unchanged, eight queries at a time: the histogram pass over [queries][n_messages], boundary search, refinement, compaction and
+ * sort with the message ordinals as positions.  Groups are up to 64 queries, cut further by "topk_scores_bytes" over [queries][n_messages]
+ * (at least one query); per group two memsets and one tile launch over the span -- no sample pass and no phases: no threshold ever rises.
+ * SCORES ARE THE TILE'S OWN (fp32 rows: v_mfma_f32_32x32x2_f32 in the tile's summation order; fp16 rows: the fp32 query split into an fp16
+ * high and low plane), as on every other route of the 32/64-query tile: within a few ulp of tavb_search_top_messages', not bit for bit --
+ * which is why the binding's option "top_messages_tile" defaults to 0.  The fp16 shadow of an fp32 corpus is not used.
+ * dev_bits / rows / first_row / last_row follow tavb_search_masked_batch (packed mask over the corpus' rows, 4-byte aligned, rows = the
+ * corpus' rows, [first_row, last_row] holds every set bit; first_row > last_row: nothing to scan); dev_bits == NULL: the whole corpus (rows,
+ * first_row and last_row are then not read).  The row -> message map must be 64-byte aligned (the tile reads 16 entries per scalar load).
+ *   tavb_search_top_messages_tile: queries on the host, one synchronise; outputs as tavb_search_top_messages.
+ *   tavb_search_top_messages_tile_device: dev_queries device float32 [nq, dim], nq >= 1; out_keys as tavb_search_top_messages_device; nothing
+ *     waited for unless the thresholds differ between the queries (their upload is waited for, as on the masked tile).
+ * "masked_route" reports 10, "last_tier" 5, "last_skinny_kernel" the instantiation (one of the four ring variants: 12832, 12864, 6432, 6464).
+ * Errors are tavb_search_top_messages' (no map, a map that does not cover the corpus, k out of range, NULL arguments) plus the tile's own:
+ * rows that are not a multiple of 64 bytes, or a map that is not 64-byte aligned: TAVB_E_UNSUPPORTED; a misaligned mask, rows != the corpus'
+ * rows, a span outside the corpus: TAVB_E_INVALID -- each with a message.  Timed under TAVB_KERNEL_SKINNY (the tile) and TAVB_KERNEL_TOPK.
+ * tavb_plan_top_messages_tile: the binding's rule under "top_messages_tile" = 1, a pure function: 1 = the tile, 0 = tavb_search_top_messages
+ * (negative: an error).  allowed == span == the corpus' rows for an unmasked lookup.  The tile where the row size is a multiple of 64 bytes,
+ * nq >= min_batch ("top_messages_tile_min_batch") and -- under a mask -- allowed x row bytes >= min_bytes and the row list's bytes
+ * (ceil(nq / 8) x allowed) are at least pct % of the tile's (ceil(nq / 64) x span): "mask_tile_min_bytes" / "mask_tile_pct". */
+int tavb_search_top_messages_tile(tavb_ctx* ctx, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const uint32_t* dev_bits,
+                                  int64_t rows, int64_t first_row, int64_t last_row, int64_t* out_messages, float* out_scores, int32_t* out_counts);
+int tavb_search_top_messages_tile_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores /*host*/,
+                                         const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, tavb_key* out_keys);
+int tavb_plan_top_messages_tile(int32_t nq, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_batch, int64_t min_bytes,
+                                int64_t pct);
 
 /* ---- scoped batches on the 32/64-query tile: one scope per query on the matrix cores ----------------------------------------------------
  * The scoped batch above reads, per pass of eight queries, the union of the pass' scopes; dense, independent or disjoint scopes make that

@@ -126,6 +126,9 @@ _SIGNATURES = [
     ("tavb_search_top_messages_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_search_top_messages_scoped", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_top_messages_scoped_device", c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("tavb_search_top_messages_tile", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_top_messages_tile_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    ("tavb_plan_top_messages_tile", c_int, [c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64, c_int64]),
     ("tavb_compact_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_expand_rows", c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64)]),
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -255,6 +258,20 @@ def plan_masked(nq: int, k: int, dim: int, dtype: int, allowed: int, span: int, 
     "mask_tile" = 1, False: the gather route (tavb_plan_masked; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
     lib = load_library(preload_torch=False)
     r = lib.tavb_plan_masked(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
+
+
+TOP_MESSAGES_TILE_MIN_BATCH = 8  # the default of the option "top_messages_tile_min_batch"
+
+
+def plan_top_messages_tile(nq: int, dim: int, dtype: int, allowed: int, span: int, min_batch: int = TOP_MESSAGES_TILE_MIN_BATCH,
+                           min_bytes: int = MASK_TILE_MIN_BYTES, pct: int = MASK_TILE_PCT) -> bool:
+    """True: a top-messages batch of `nq` queries with `allowed` allowed rows inside a span of `span` rows (both the corpus' rows for an
+    unmasked lookup) takes the 32/64-query tile under option "top_messages_tile" = 1, False: the row scan of `search_top_messages`
+    (tavb_plan_top_messages_tile; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_top_messages_tile(int(nq), int(dim), int(dtype), int(allowed), int(span), int(min_batch), int(min_bytes), int(pct))
     _check(lib, r if r < 0 else 0)
     return bool(r)
 
@@ -476,6 +493,15 @@ class Engine:
         self.__dict__.pop("_mask_wide_opts", None)
         self.__dict__.pop("_scope_tile_opts", None)
         self.__dict__.pop("_scope_wide_opts", None)
+        self.__dict__.pop("_top_messages_tile_opts", None)
+
+    def top_messages_tile_options(self) -> tuple[int, int, int, int]:
+        """("top_messages_tile", "top_messages_tile_min_batch", "mask_tile_min_bytes", "mask_tile_pct"), cached like `mask_tile_options`."""
+        opts = self.__dict__.get("_top_messages_tile_opts")
+        if opts is None:
+            opts = self._top_messages_tile_opts = tuple(
+                self.get_option(n) for n in ("top_messages_tile", "top_messages_tile_min_batch", "mask_tile_min_bytes", "mask_tile_pct"))
+        return opts
 
     def mask_tile_options(self) -> tuple[int, int, int]:
         """("mask_tile", "mask_tile_min_bytes", "mask_tile_pct") as the library holds them, read once and again after any `set_option`: a
@@ -1327,6 +1353,40 @@ class Engine:
         with self._lock:
             rc = self.lib.tavb_search_top_messages_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), rows_ptr, n,
                                                           c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    plan_top_messages_tile = staticmethod(plan_top_messages_tile)
+
+    def _tile_mask_args(self, dev_bits, span):
+        """(dev_bits pointer or None, rows, first, last) of the top-messages tile calls: None = the whole corpus."""
+        if dev_bits is None:
+            return None, int(self.rows), 0, int(self.rows) - 1
+        bits, first, last = self._masked_args(dev_bits, span)
+        return bits, int(self.rows), first, last
+
+    def search_top_messages_tile(self, queries, k: int, thrs, dev_bits=None, span=None):
+        """`search_top_messages` on the 32/64-query MFMA tile (tavb_search_top_messages_tile): one corpus pass per 64 queries instead of one
+        per eight; dev_bits: ONE packed mask (torch int32 [(rows + 31) // 32] on this device, `mask_to_rows_bits`) with span = (first,
+        last) allowed row, or None for the whole corpus; 1 <= k <= MAX_LARGE_K -> (message ordinals [nq, k], scores [nq, k], counts
+        [nq]).  Scores are the tile's own -- within a few ulp of `search_top_messages`', not bit for bit.  Raises TavbError
+        (TAVB_E_UNSUPPORTED) for rows that are not a multiple of 64 bytes."""
+        a, nq, t, msgs, scs, cnts = self._host_batch(queries, k, thrs)
+        bits, rows, first, last = self._tile_mask_args(dev_bits, span)
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_tile(self._h, _addr(a), nq, k, _addr(t), bits, rows, first, last, _addr(msgs), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return msgs, scs, cnts
+
+    def search_top_messages_tile_device(self, dev_queries, k: int, thrs, out_keys=None, dev_bits=None, span=None):
+        """`search_top_messages_tile` with the queries on the device (tavb_search_top_messages_tile_device) -> torch int64 [nq, k] sorted,
+        zero-padded keys carrying MESSAGE ordinals (`decode_keys`).  `out_keys`: a device tensor or a PINNED host tensor.  Async:
+        `synchronize()` before reading."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        bits, rows, first, last = self._tile_mask_args(dev_bits, span)
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_tile_device(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), bits, rows, first, last,
+                                                               c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 

@@ -259,6 +259,8 @@ const Option kOptions[] = {
     SWITCH("scope_large_k", scope_large_k),
     SWITCH("top_messages", top_messages),
     SWITCH("top_messages_scoped", top_messages_scoped),
+    RANGE("top_messages_tile", top_messages_tile, 0, 2),
+    RANGE("top_messages_tile_min_batch", top_messages_tile_min_batch, 1, 1 << 20),
     RANGE("scope_wave_bytes", scope_wave_bytes, 1, (int64_t)1 << 40),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
     READ_ONLY("norm_rows", norm_rows),

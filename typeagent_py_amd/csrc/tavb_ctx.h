@@ -84,6 +84,10 @@ constexpr int64_t kSkinnyMinBatchF32 = 5, kSkinnyMinBatchF16 = 3;
 // the default of mfma_min_batch (the unmasked dispatcher's own bound for the 128/256-query tile on fp16 corpora) and the compute units the
 // planning functions that have no context assume (MI355X); tavb_plan_masked_wide uses both as they ship
 constexpr int64_t kMfmaMinBatch = 65;
+// fewest queries tavb_plan_top_messages_tile sends to the 32/64-query tile (option "top_messages_tile_min_batch"): the smallest batch
+// measured -- at 8 queries over 1M x 1536 rows no cell loses, threshold 0 (every pair an atomic) included: 1.08 .. 3.2 x
+// (profiles/r27_top_messages_tile.md); smaller batches were not measured
+constexpr int64_t kTopMessagesTileMinBatch = 8;
 constexpr int kPlanComputeUnits = 256;
 
 struct PendingTiming {
@@ -168,6 +172,8 @@ struct tavb_ctx {
   Buffer d_msg_best;
   int64_t top_messages = 1;                  // option: 1 = the binding sends lookup_top_messages_* through tavb_search_top_messages, 0 = through the all-survivor lookup and a collapse on the host
   int64_t top_messages_scoped = 1;           // option: 1 = the binding sends lookup_top_messages_by_embeddings_scoped through tavb_search_top_messages_scoped (while "top_messages" is on), 0 = it loops over the one-mask call
+  int64_t top_messages_tile = 0;             // option: lookup_top_messages_* on the 32/64-query tile (tavb_search_top_messages_tile): 0 = never (the default: scores stay the row scan's bit for bit), 1 = follow tavb_plan_top_messages_tile, 2 = always where supported
+  int64_t top_messages_tile_min_batch = tavb::host::kTopMessagesTileMinBatch;  // option: fewest queries tavb_plan_top_messages_tile sends to the tile
   int64_t last_topk_refine = 0;              // option "last_topk_refine" (get): refinement rounds the last large-k lookup needed (most of any query)
   // the asynchronous forms (tavb_search_topk_device, tavb_search_topk_allgather): the finish kernel writes every query's rounds here, and
   // the next tavb_synchronize folds the first topk_rounds_pending of them into last_topk_refine
@@ -214,7 +220,7 @@ struct tavb_ctx {
   int64_t mask_tile = 1;                            // option: 1 = follow tavb_plan_masked, 0 = never the tile, 2 = always where supported
   int64_t mask_tile_min_bytes = (int64_t)128 << 20;  // option: allowed rows x row bytes below which the gather route (one launch there) is kept; the default of small_direct_bytes
   int64_t mask_tile_pct = 100;                      // option: the tile when the gather route's bytes are at least this many % of the tile's (100 = byte parity)
-  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile, 6 = a scoped batch on the 128/256-query filter tile + rescoring, 7 / 8 = a scoped batch on the large-k / sorted route, 9 = a scoped top-messages batch
+  int64_t masked_route = 0;                         // option "masked_route" (get): 0 before the first masked lookup, 1 = gather, 2 = tile, 3 = the wide filter tile + rescoring, 4 = a scoped batch (one mask per query), 5 = a scoped batch on the 32/64-query tile, 6 = a scoped batch on the 128/256-query filter tile + rescoring, 7 / 8 = a scoped batch on the large-k / sorted route, 9 = a scoped top-messages batch, 10 = a top-messages batch on the 32/64-query tile
   int64_t mask_wide = 1;                            // option: masked batches on the 128/256-query filter tile (tavb_search_masked_wide): 1 = follow tavb_plan_masked_wide, 0 = never, 2 = always where supported
   int64_t last_skinny_kernel = 0;  // option "last_skinny_kernel" (get): what the last launch of the 32/64-query tile instantiated, tavb::skinny_kernel_id (0: none yet)
   int64_t mfma_bdirect = 0;  // option (measurement for now): the 256-query tile takes its query operand straight from L2 (fragment-major layout), not through LDS
@@ -484,6 +490,17 @@ int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const
 // zero from the host).  ONE synchronise per wave (the unions' sizes); everything else is enqueued and not waited for.
 int search_scoped_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
                                     u64_t* out_keys, int32_t* out_rounds);
+// The same on the 32/64-query tile (tavb_search_top_messages_tile): groups of up to 64 queries, cut by "topk_scores_bytes" over
+// [queries][n_messages]; per group the memset of its slots of d_msg_best and top_messages_tile_pass, then per eight queries the memset of the
+// selection's head and search_top_messages_impl's histogram pass, refinement, compaction and finish.  dev_bits (optional): ONE packed mask
+// over the corpus' rows whose set bits lie in [first_row, last_row].  The caller has checked what search_top_messages_impl's has, that rows
+// are a multiple of 64 bytes and the alignment of the mask and the map.  Nothing is waited for unless the thresholds differ (their upload).
+int search_top_messages_tile_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits,
+                                  int64_t first_row, int64_t last_row, u64_t* out_keys, int32_t* out_rounds);
+// tavb_route.hip: ONE launch of the 32/64-query tile in its top-messages form for n <= 64 queries at d_q over the mask's span (dev_bits
+// null: the corpus) -> best [n][n_messages] (zeroed by the caller).  Sets last_tier, last_skinny_kernel and masked_route.
+int top_messages_tile_pass(tavb_ctx* c, const float* d_q, int n, const float* min_scores /*host, n*/, const uint32_t* dev_bits, int64_t first_row,
+                           int64_t last_row, unsigned* best);
 
 // A scoped batch at 1 <= k <= TAVB_MAX_LARGE_K (masks as for search_scoped_impl): per pass of min(topk_queries_per_pass, 8) queries the
 // scoped score pass over the pass' union list, the refinement rounds, the compaction and the finish into `work` [nq, k], and the remap of

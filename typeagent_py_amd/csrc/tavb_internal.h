@@ -354,6 +354,15 @@ struct MfmaParams {
   // where bit q & 31 of its word in plane q >> 5 is set.
   const uint32_t* scope_planes;
   int64_t scope_stride;
+  // optional (the skinny kernel's four ring variants; with `mask` or without, never with scope_planes or a work list): the TOP-MESSAGES form --
+  // msg_best [nq_padded or more][n_messages], zero when the launch starts: an admitted (row, query) pair raises the slot of the row's message to
+  // 1 + the bits of its clamped score (MessageMaxSink's encoding; launch_message_hist follows).  msg_map: the map entry of row 0 of `corpus`
+  // (64-byte aligned), msg_map_rows (>= rows) entries readable from there; entries outside [0, n_messages) are skipped.  No candidates and no
+  // lists: workspace, lists and k are unused; thresholds never rise (min_score and thr_in as given).
+  const int32_t* msg_map;
+  unsigned* msg_best;
+  int64_t msg_map_rows;
+  int64_t n_messages;
 };
 hipError_t launch_mfma_scan(const MfmaParams& p, hipStream_t stream);
 int mfma_tile_shape(const MfmaParams& p);  // M = N of the MFMA the 128/256-query kernel launch_mfma_scan picks for p runs on: 16 or 32

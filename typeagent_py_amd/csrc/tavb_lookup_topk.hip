@@ -1,7 +1,7 @@
 // The large-k and sorted lookups of the C ABI (include/tavb.h): tavb_search_topk and its subset / device forms, tavb_search_sorted,
 // tavb_search_subset_sorted, tavb_search_subset_batch_sorted, tavb_sort_keys_device, their scoped forms (one mask per query:
-// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted), the top-messages lookups (tavb_search_top_messages / _device) and their scoped forms
-// (tavb_search_top_messages_scoped / _device) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
+// tavb_search_scoped_topk / _device, tavb_search_scoped_sorted), the top-messages lookups (tavb_search_top_messages / _device), their scoped forms
+// (tavb_search_top_messages_scoped / _device) and their forms on the 32/64-query tile (tavb_search_top_messages_tile / _device) -- and the score pass they share.  Host code only: the kernels live in tavb_scan.hip,
 // tavb_topk.hip and tavb_sort.hip, the staging in tavb_lookup.hip.
 
 #include <optional>
@@ -199,6 +199,33 @@ int plan_top_messages(tavb_ctx* c, int64_t most, int k, ScorePlan* s) {
   return c->d_topk.reserve(tavb::topk_workspace_bytes((int)s->per, k, s->nb, s->cap, s->rounds));
 }
 
+// The second half of a group, shared with the tile route: best [n][n_messages] as a top-messages score pass left it (n <= s.per <= 8 queries
+// whose thresholds are min_scores[0 .. n)) and the zeroed head of d_topk -> the histogram pass, the refinement rounds, the compaction and the
+// finish -> out_keys [n][k] and out_rounds [n].
+int top_messages_select(tavb_ctx* c, const ScorePlan& s, unsigned* best, const float* min_scores /*host, n*/, int n, int k, u64_t* out_keys, int32_t* out_rounds) {
+  tavb::TopkLaunch t{};
+  bucket_maps(min_scores, n, s.nb, &t);
+  t.scores = best;
+  t.workspace = c->d_topk.ptr;
+  t.n_pos = s.n_pos;
+  t.nq = n;
+  t.k = k;
+  t.buckets = s.nb;
+  t.cap = s.cap;
+  t.rounds = s.rounds;
+  t.blocks = s.sel_blocks;
+  t.out_keys = out_keys;
+  t.out_rounds = out_rounds;
+  t.index_base = 0u;
+  Timed tm(c, TAVB_KERNEL_TOPK);
+  hipError_t e = tavb::launch_message_hist(t, best, c->stream);
+  for (int r = 0; r < s.rounds && e == hipSuccess; ++r) e = tavb::launch_topk_refine(t, r, c->stream);
+  if (e == hipSuccess) e = tavb::launch_topk_compact(t, c->stream);
+  if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages selection launch failed: %s", hipGetErrorString(e));
+  return TAVB_OK;
+}
+
 // One group: the queries [q0, q0 + n) of the batch, n <= s.per, over the n_scan positions of d_rows (null: the corpus) -> out_keys [n][k]
 // and out_rounds [n], both at the group's first query.  member (optional): the scoped form -- d_rows is the union list of a scoped pass,
 // member its membership bytes, and the n queries are its member bits bit0 .. bit0 + n - 1 (launch_scan_top_messages_scoped).
@@ -219,27 +246,7 @@ int top_messages_group(tavb_ctx* c, const ScorePlan& s, const float* d_q, const 
     hipError_t e = member ? tavb::launch_scan_top_messages_scoped(p, s.g, c->stream, &c->last_tier) : tavb::launch_scan_top_messages(p, s.g, c->stream, &c->last_tier);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages score pass launch failed: %s", hipGetErrorString(e));
   }
-  tavb::TopkLaunch t{};
-  bucket_maps(min_scores + q0, n, s.nb, &t);
-  t.scores = best;
-  t.workspace = c->d_topk.ptr;
-  t.n_pos = nm;
-  t.nq = n;
-  t.k = k;
-  t.buckets = s.nb;
-  t.cap = s.cap;
-  t.rounds = s.rounds;
-  t.blocks = s.sel_blocks;
-  t.out_keys = out_keys;
-  t.out_rounds = out_rounds;
-  t.index_base = 0u;
-  Timed tm(c, TAVB_KERNEL_TOPK);
-  hipError_t e = tavb::launch_message_hist(t, best, c->stream);
-  for (int r = 0; r < s.rounds && e == hipSuccess; ++r) e = tavb::launch_topk_refine(t, r, c->stream);
-  if (e == hipSuccess) e = tavb::launch_topk_compact(t, c->stream);
-  if (e == hipSuccess) e = tavb::launch_topk_finish(t, c->stream);
-  if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages selection launch failed: %s", hipGetErrorString(e));
-  return TAVB_OK;
+  return top_messages_select(c, s, best, min_scores + q0, n, k, out_keys, out_rounds);
 }
 
 }  // namespace
@@ -253,6 +260,31 @@ int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const
   for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
     const int n = (int)std::min<int64_t>(s.per, nq - q0);
     if (int rc = top_messages_group(c, s, d_q, min_scores, d_rows, n_scan, q0, n, k, out_keys + (size_t)q0 * k, out_rounds + q0)) return rc;
+  }
+  return TAVB_OK;
+}
+
+// ---- the same on the 32/64-query tile (tavb_search_top_messages_tile): groups of up to 64 queries -- fewer where [queries][n_messages]
+// would pass "topk_scores_bytes" -- each ONE tile launch over the corpus or the span of the one mask (top_messages_tile_pass, tavb_route.hip)
+// into the group's zeroed slots of d_msg_best; then, eight queries at a time (the selection's launches take no more), the zeroed head of d_topk
+// and the second half of the group above over those queries' slots.
+int search_top_messages_tile_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits,
+                                  int64_t first_row, int64_t last_row, u64_t* out_keys, int32_t* out_rounds) {
+  const int64_t nm = c->n_messages;
+  const int per_tile = (int)std::min<int64_t>(std::min(64, nq), std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
+  ScorePlan s;
+  if (int rc = plan_top_messages(c, std::min(TAVB_MAX_STREAM_QUERIES, per_tile), k, &s)) return rc;
+  if (int rc = c->d_msg_best.reserve((size_t)per_tile * nm * sizeof(uint32_t))) return rc;
+  unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
+  for (int q0 = 0; q0 < nq; q0 += per_tile) {
+    const int n = std::min(per_tile, nq - q0);
+    TAVB_HIP(hipMemsetAsync(best, 0, (size_t)n * nm * sizeof(uint32_t), c->stream));
+    if (int rc = top_messages_tile_pass(c, d_q + (size_t)q0 * c->dim, n, min_scores + q0, dev_bits, first_row, last_row, best)) return rc;
+    for (int s0 = 0; s0 < n; s0 += (int)s.per) {
+      const int m = (int)std::min<int64_t>(s.per, n - s0);
+      TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(m, s.nb, s.rounds), c->stream));
+      if (int rc = top_messages_select(c, s, best + (size_t)s0 * nm, min_scores + q0 + s0, m, k, out_keys + (size_t)(q0 + s0) * k, out_rounds + q0 + s0)) return rc;
+    }
   }
   return TAVB_OK;
 }
@@ -800,6 +832,75 @@ int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
   if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
   if (int rc = search_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+// ---- the best k messages on the 32/64-query tile (search_top_messages_tile_impl)
+// check_top_messages_args (no row list), the one mask's shape as tavb_search_masked_batch checks it, and the tile's own refusals
+static int check_top_messages_tile_args(tavb_ctx* c, int32_t nq, int32_t k, const uint32_t* dev_bits, int64_t rows, int64_t first_row, int64_t last_row, bool* empty) {
+  if (int rc = check_top_messages_args(c, k, nullptr, 0, empty)) return rc;
+  if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
+  const int row_bytes = c->dim * (c->dtype == TAVB_F16 ? 2 : 4);
+  if (row_bytes % 64 != 0)
+    return fail(TAVB_E_UNSUPPORTED, "the top-messages tile serves rows of a multiple of 64 bytes (%d bytes): use tavb_search_top_messages", row_bytes);
+  if ((reinterpret_cast<uintptr_t>(c->row_to_msg) & 63) != 0)
+    return fail(TAVB_E_UNSUPPORTED, "the top-messages tile reads the row -> message map 16 entries at a time: the map must be 64-byte aligned");
+  if (dev_bits) {
+    if ((reinterpret_cast<uintptr_t>(dev_bits) & 3) != 0) return fail(TAVB_E_INVALID, "misaligned mask (dev_bits must be 4-byte aligned)");
+    if (rows != c->rows) return fail(TAVB_E_INVALID, "the mask covers %lld rows, the corpus has %lld", (long long)rows, (long long)c->rows);
+    if (first_row > last_row) *empty = true;
+    else if (first_row < 0 || last_row >= rows) return fail(TAVB_E_INVALID, "mask span [%lld, %lld] outside the corpus", (long long)first_row, (long long)last_row);
+  }
+  return TAVB_OK;
+}
+
+int tavb_search_top_messages_tile(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t k, const float* min_scores, const uint32_t* dev_bits, int64_t rows,
+                                  int64_t first_row, int64_t last_row, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
+  bool empty = false;
+  if (int rc = check_top_messages_tile_args(c, nq, k, dev_bits, rows, first_row, last_row, &empty)) return rc;
+  if (nq == 0) return TAVB_OK;
+  if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
+  note_top_messages(c);
+  c->masked_route = 10;  // a top-messages batch on the 32/64-query tile
+  if (empty) {
+    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
+    return TAVB_OK;
+  }
+  DeviceGuard guard(c->device);
+  const size_t n_keys = (size_t)nq * k;
+  u64_t* keys;
+  int32_t* rounds;
+  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
+  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
+  u64_t* target = keys;
+  if (n_keys > 4096) {
+    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  }
+  const float* d_q;
+  if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
+  if (int rc = search_top_messages_tile_impl(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, target, rounds)) return rc;
+  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
+  note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int tavb_search_top_messages_tile_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const uint32_t* dev_bits,
+                                         int64_t rows, int64_t first_row, int64_t last_row, tavb_key* out_keys) {
+  bool empty = false;
+  if (int rc = check_top_messages_tile_args(c, nq, k, dev_bits, rows, first_row, last_row, &empty)) return rc;
+  if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  note_top_messages(c);
+  c->masked_route = 10;
+  DeviceGuard guard(c->device);
+  u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
+  if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (int rc = search_top_messages_tile_impl(c, dev_queries, nq, k, min_scores, dev_bits, first_row, last_row, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr)))
+    return rc;
   c->topk_rounds_pending = nq;
   return TAVB_OK;
 }

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "tavb_tile.h"
@@ -111,10 +112,29 @@ struct ScopePlanes {
 };
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(4))) u32x16 const_u32x16;
+// TOPMSG: the top-messages form (tavb.h "top messages on the tile") -- the epilogue keeps no candidates: an admitted (row, query) pair raises
+// best[query][message of the row] to 1 + the bits of its clamped score (MessageMaxSink's encoding, tavb_scan.hip, over the same zeroed array;
+// message_hist_kernel and the selection run behind it unchanged).  Like SCOPED the mode is the TYPE of an extra argument, the LAST one (after
+// the one mask of a MASKED instantiation) -- the pack is empty by default, so every other instantiation keeps its name and compiles to what it
+// compiled to before the mode existed (a template parameter in front of the pack would be part of every mangled name).  `map` names the entry
+// of the launch's first row (64-byte aligned: the launcher checks); map_rows entries from there on are readable.  The 32 entries of an
+// admitting block are wave-uniform and come through the scalar data path like the SCOPED form's plane words (two 16-word loads, lgkmcnt), only
+// behind a non-zero ballot; a block that reaches behind map_rows loads its entries one by one.  Thresholds never rise: no k-th best, no
+// cnt_lds, no need_compact, no candidate buffer, no lists -- p.cand and p.lists may be null.  Never together with SCOPED.
+struct TopMessages {
+  const int32_t* map;
+  unsigned* best;      // [nq_padded or more][n_messages], zero when the launch starts
+  int64_t map_rows;
+  int64_t n_messages;
+};
 template <typename T, int NI, int STEP, bool DEEP = false, int DR = 0, bool HALF = false, bool MASKED = false, typename... MaskArg>
 __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) == 2)) ? 1 : 2)) skinny_scan_kernel(const MfmaDeviceParams p, MaskArg... mask_arg) {
-  static_assert(sizeof...(MaskArg) == (MASKED ? 1 : 0), "the mask is an argument of the masked instantiations only");
+  constexpr bool TOPMSG = (std::is_same_v<MaskArg, TopMessages> || ...);  // the top-messages form: the LAST argument is the message map and the best array
+  static_assert(sizeof...(MaskArg) == (MASKED ? 1 : 0) + (TOPMSG ? 1 : 0), "the mask is an argument of the masked instantiations only");
   constexpr bool SCOPED = (std::is_same_v<MaskArg, ScopePlanes> || ...);  // per-query scopes: the argument is the membership planes
+  static_assert(!(SCOPED && TOPMSG), "no top-messages form of the scoped tile");
+  // the one mask of a MASKED instantiation: its first extra argument (the top-messages form has one more behind it)
+  [[maybe_unused]] const auto mask_of = [](auto a, auto...) { return a; };
   using G = SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>;
   constexpr int BMT = G::BMT, RW = G::RW, MI = G::MI;
   constexpr int SQ = G::SQ;
@@ -148,7 +168,7 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
   const int64_t r_begin = (int64_t)split * p.rows_per_split;
   const int64_t r_end = (r_begin + p.rows_per_split < p.rows) ? r_begin + p.rows_per_split : p.rows;
   const int logical_block = split * p.n_qtiles + qtile;
-  u64* my_cand = p.cand + (size_t)logical_block * SQ * CAP;
+  [[maybe_unused]] u64* my_cand = TOPMSG ? nullptr : p.cand + (size_t)logical_block * SQ * CAP;
 
   const float thr0 = (p.min_score > 0.0f) ? __uint_as_float(__float_as_uint(p.min_score) - 1u) : -__builtin_inff();
   if (tid < SQ) {  // SQ <= 64 < S_THREADS
@@ -157,9 +177,10 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
     if (qg0 >= live_q) t0 = __builtin_inff();  // padding queries (and unused work-list slots) admit nothing
     else if (p.thr_in && p.thr_in[qg0] > t0) t0 = p.thr_in[qg0];  // k-th best so far: a valid lower bound
     thr_lds[tid] = t0;
-    cnt_lds[tid] = 0;
+    if constexpr (!TOPMSG) cnt_lds[tid] = 0;
   }
-  if (tid == 0) *need_compact = 0;
+  if constexpr (!TOPMSG)
+    if (tid == 0) *need_compact = 0;
 
   const size_t row_bytes = (size_t)p.dim * sizeof(T);
   const int steps_per_tile = (int)(row_bytes / STEP);
@@ -168,6 +189,7 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
   const size_t plane_bytes = (size_t)p.n_qtiles * SQ * row_bytes;  // fp16: the low plane follows the high plane
   const int n_tiles = (r_end > r_begin) ? (int)((r_end - r_begin + BMT - 1) / BMT) : 0;
   if (n_tiles == 0) {
+    if constexpr (TOPMSG) return;  // (no lists to zero)
     for (int q = wave; q < SQ; q += S_THREADS / 64) {
       const int qg = qtile * SQ + q;
       if (qg < p.nq && lane < p.k) p.lists[((size_t)qg * p.list_stride + split) * (size_t)p.k + lane] = 0ull;
@@ -414,9 +436,28 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
           } else if constexpr (MASKED) {
             const int64_t block_row = row0 + wave * RW + mi * 32;  // (a multiple of 32, as r_begin and the tile are)
             if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range has no word (and admits nothing either way)
-            const char* word = sgpr_ptr(reinterpret_cast<const char*>((mask_arg, ...)) + (size_t)(block_row >> 5) * sizeof(uint32_t));
+            const char* word = sgpr_ptr(reinterpret_cast<const char*>(mask_of(mask_arg...)) + (size_t)(block_row >> 5) * sizeof(uint32_t));
             allow = *(const const_u32*)(uintptr_t)word;  // s_load_dword: lgkmcnt, not vmcnt
             if (allow == 0u) continue;  // nothing of this block is allowed
+          }
+          [[maybe_unused]] u32x16 msgw[2];  // TOPMSG: the message of each of this block's 32 rows
+          [[maybe_unused]] TopMessages tm{};
+          if constexpr (TOPMSG) {
+            tm = std::get<sizeof...(MaskArg) - 1>(std::tuple<MaskArg...>(mask_arg...));  // the last argument
+            const int64_t block_row = row0 + wave * RW + mi * 32;  // (a multiple of 32, as r_begin and the tile are)
+            if (block_row >= r_end) continue;  // wave-uniform: a block behind the row range admits nothing (and may lie behind the map)
+            const char* words = sgpr_ptr(reinterpret_cast<const char*>(tm.map) + (size_t)block_row * sizeof(int32_t));
+            if (block_row + 32 <= tm.map_rows) {
+              msgw[0] = *(const const_u32x16*)(uintptr_t)words;  // s_load_dwordx16 x 2: lgkmcnt, not vmcnt
+              msgw[1] = *(const const_u32x16*)(uintptr_t)(words + 16 * sizeof(int32_t));
+            } else {  // the last block of a map whose length is no multiple of 32: entry by entry, nothing behind the map's end is read
+#pragma unroll
+              for (int w = 0; w < 32; ++w) {
+                uint32_t m = 0xFFFFFFFFu;  // (no message)
+                if (block_row + w < tm.map_rows) m = *(const const_u32*)(uintptr_t)(words + w * sizeof(int32_t));
+                msgw[w >> 4][w & 15] = m;
+              }
+            }
           }
           // (the admission path of the 256-query tile: wave masks in scalar registers, four rows at a time, one LDS atomic per admitted row)
           const int64_t row_base = row0 + wave * RW + mi * 32 + 4 * (lane >> 5);
@@ -443,6 +484,20 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
               // (MASKED: bits at or beyond `rows` in the last word may hold anything -- rows_left cuts those rows.  SCOPED: m[j] is already cut
               //  to the lanes whose query holds the row; the planes are zero behind the corpus, rows_left cuts the rows of a later phase)
               if (((m[j] >> lane) & 1ull) != 0ull && r_off < rows_left && (!MASKED || SCOPED || ((allow >> (r_off + 4 * (lane >> 5))) & 1u) != 0u)) {
+                if constexpr (TOPMSG) {
+                  float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
+                  s1 = (s1 > 1.0f) ? 1.0f : s1;
+                  // rows 8g .. 8g + 7 are entries 8 (g & 1) .. of half g >> 1: lanes 0-31 test row r_off, lanes 32-63 row r_off + 4 -- a select
+                  // between two scalars
+                  const uint32_t msg = (lane >> 5) ? msgw[g >> 1][8 * (g & 1) + j + 4] : msgw[g >> 1][8 * (g & 1) + j];
+                  if ((u64)msg < (u64)tm.n_messages) {  // (-1 = no message, and whatever else lies outside [0, n_messages))
+                    unsigned* slot = tm.best + (size_t)(qtile * SQ + ql) * (size_t)tm.n_messages + msg;
+                    const uint32_t v = __float_as_uint(s1) + 1u;
+                    // no return value, and behind the compiler's back like the candidate store below, for the same reason
+                    asm volatile("global_atomic_umax %0, %1, off" ::"v"(slot), "v"(v) : "memory");
+                  }
+                  continue;
+                }
                 const int pos = lds_add_rtn(&cnt_lds[ql], 1);
                 if (pos + 1 > CAP - BMT) lds_store_i32(need_compact, 1);  // this buffer could overflow on the next tile
                 float s1 = (sc[j] > 0.0f) ? sc[j] : 0.0f;
@@ -464,6 +519,7 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TAVB_BARRIER();
+    if constexpr (TOPMSG) continue;  // (no buffer to compact; the barrier stays: the waves enter the next tile together, as in every other form)
     if (*need_compact != 0) {  // workgroup-uniform: read after the barrier
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), through the builtin: the compiler's wait-count pass sees the queue empty from here on
       TAVB_BARRIER();
@@ -490,6 +546,7 @@ __global__ void __launch_bounds__(S_THREADS, ((DR >= 4 || (DR == 3 && sizeof(T) 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the run-ahead LDS-DMA before the block retires
   __syncthreads();
+  if constexpr (TOPMSG) return;  // (no lists: p.cand and p.lists are never touched)
 
   for (int q = wave; q < SQ; q += S_THREADS / 64) {
     const int qg = qtile * SQ + q;
@@ -564,7 +621,13 @@ int skinny_pick_splits(int64_t rows, int nq_padded, int tile, int n_cu, int dim,
 hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
   const bool f32 = p.f32 != 0;
   const int tile = p.skinny_tile == 64 ? 64 : 32;
-  if (!skinny_supported(p.dim, p.k, f32) || p.nq_padded % tile != 0 || p.n_splits < 1 || !p.workspace) return hipErrorInvalidValue;
+  const bool topmsg = p.msg_best != nullptr;  // the top-messages form: no candidates, no lists, any k
+  if (!skinny_supported(p.dim, topmsg ? 1 : p.k, f32) || p.nq_padded % tile != 0 || p.n_splits < 1 || (!topmsg && !p.workspace)) return hipErrorInvalidValue;
+  // top messages: a map aligned for the 16-word scalar loads that covers the launch's rows; one mask or none; the four ring variants only
+  if (topmsg && (!p.msg_map || (reinterpret_cast<uintptr_t>(p.msg_map) & 63) != 0 || p.msg_map_rows < p.rows || p.n_messages < 1 || p.scope_planes || p.active ||
+                 skinny_variant(p.dim, f32, tile, p.sched) != 0))
+    return hipErrorInvalidValue;
+  const TopMessages tmsg{p.msg_map, p.msg_best, p.msg_map_rows, p.n_messages};
   if (p.mask && (p.active || (reinterpret_cast<uintptr_t>(p.mask) & 3) != 0)) return hipErrorInvalidValue;  // (no work-list form of the masked tile)
   // per-query scopes: 64-byte aligned plane words (the 16-word scalar loads), whole 32-row blocks per plane, never together with one mask
   if (p.scope_planes && (p.mask || p.active || (reinterpret_cast<uintptr_t>(p.scope_planes) & 63) != 0 || p.scope_stride % 32 != 0 || p.scope_stride < ((p.rows + 31) & ~(int64_t)31)))
@@ -586,6 +649,22 @@ hipError_t launch_skinny_scan(const MfmaParams& p, hipStream_t stream) {
    : p.mask ? go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF, true, const uint32_t*>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS, p.mask) \
           : go(skinny_scan_kernel<T, NI, STEP, DEEP, DR, HALF>, SkinnyGeom<T, NI, STEP, DEEP, DR, HALF>::LDS))
 #define TAVB_SKINNY(NI, STEP, DEEP, DR, HALF) (f32 ? TAVB_SKINNY_T(float, NI, STEP, DEEP, DR, HALF) : TAVB_SKINNY_T(_Float16, NI, STEP, DEEP, DR, HALF))
+  // (top messages: the four ring variants in their unmasked and one-mask form, the map and the best array as their last argument)
+#define TAVB_SKINNY_TM_T(T, NI, STEP)                                                                                                                   \
+  (p.mask ? go(skinny_scan_kernel<T, NI, STEP, false, 0, false, true, const uint32_t*, TopMessages>, SkinnyGeom<T, NI, STEP>::LDS, p.mask, tmsg) \
+          : go(skinny_scan_kernel<T, NI, STEP, false, 0, false, false, TopMessages>, SkinnyGeom<T, NI, STEP>::LDS, tmsg))
+#define TAVB_SKINNY_TM(NI, STEP) (f32 ? TAVB_SKINNY_TM_T(float, NI, STEP) : TAVB_SKINNY_TM_T(_Float16, NI, STEP))
+  if (topmsg) {
+    switch (skinny_kernel_id(p)) {
+      case 12832: return TAVB_SKINNY_TM(1, 128);
+      case 12864: return TAVB_SKINNY_TM(2, 128);
+      case 6432: return TAVB_SKINNY_TM(1, 64);
+      case 6464: return TAVB_SKINNY_TM(2, 64);
+      default: return hipErrorInvalidValue;
+    }
+  }
+#undef TAVB_SKINNY_TM
+#undef TAVB_SKINNY_TM_T
   switch (skinny_kernel_id(p)) {
     case 12832: return TAVB_SKINNY(1, 128, false, 0, false);
     case 12864: return TAVB_SKINNY(2, 128, false, 0, false);

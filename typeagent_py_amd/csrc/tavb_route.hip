@@ -1092,6 +1092,67 @@ int search_scoped_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
   return TAVB_OK;
 }
 
+// Top messages on the 32/64-query tile (tavb_search_top_messages_tile; search_top_messages_tile_impl groups the queries and runs the
+// selection): the queries staged as run_skinny_tile stages them (fp32 rows: as they are; fp16 rows: split into a high and a low plane), the
+// per-query thresholds as exclusive admission floors, ONE launch over the span of the mask -- launch_skinny_scan's row ranges and XCD mapping;
+// no sample pass and no phases, there is no threshold to hand on.  The measurement variants of "mfma_sched" have no top-messages form: only
+// 9 (64-byte K steps) is passed on.
+int top_messages_tile_pass(tavb_ctx* c, const float* d_q, int n, const float* min_scores, const uint32_t* dev_bits, int64_t first_row, int64_t last_row,
+                           unsigned* best) {
+  const bool q32 = c->dtype != TAVB_F16;
+  const int qt = tavb::skinny_query_tile(n);
+  const int nq_pad = ((n + qt - 1) / qt) * qt;
+  const size_t plane = (size_t)nq_pad * c->dim * (q32 ? 4 : 2);
+  const size_t qbytes = plane * (q32 ? 1 : 2);
+  if (int rc = c->d_queries_f16.reserve(qbytes)) return rc;
+  const bool uniform_thr = uniform_min_scores(min_scores, n);
+  float *d_ms = nullptr, *d_ms_floor = nullptr;
+  if (!uniform_thr) {
+    bool uni = false;
+    if (int rc = upload_min_scores(c, min_scores, n, nq_pad, &d_ms, &d_ms_floor, &uni)) return rc;
+  }
+  TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, qbytes, c->stream));
+  if (q32) {
+    TAVB_HIP(hipMemcpyAsync(c->d_queries_f16.ptr, d_q, (size_t)n * c->dim * 4, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    hipError_t e = tavb::launch_f32_split_f16(d_q, c->d_queries_f16.ptr, reinterpret_cast<char*>(c->d_queries_f16.ptr) + plane, (int64_t)n * c->dim, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "query split launch failed: %s", hipGetErrorString(e));
+  }
+  const int64_t span_begin = dev_bits ? first_row / 256 * 256 : 0, span_end = dev_bits ? last_row + 1 : c->rows;
+  if (span_begin < 0 || span_end > c->rows || span_end <= span_begin) return fail(TAVB_E_INVALID, "bad top-messages tile span (internal error)");
+  const int sched = c->mfma_sched == 9 ? 9 : 0;
+  tavb::MfmaParams p{};
+  p.corpus = reinterpret_cast<const char*>(c->corpus) + (size_t)span_begin * c->dim * (q32 ? 4 : 2);
+  p.queries = c->d_queries_f16.ptr;
+  p.rows = span_end - span_begin;
+  p.dim = c->dim;
+  p.nq = n;
+  p.nq_padded = nq_pad;
+  p.k = 1;  // (unused: the form keeps no lists)
+  p.min_score = uniform_thr ? min_scores[0] : lowest_min_score(min_scores, n);
+  p.thr_in = d_ms_floor;
+  p.n_splits = c->mfma_splits > 0 ? (int)c->mfma_splits : tavb::skinny_pick_splits(p.rows, nq_pad, qt, c->n_cu, c->dim, q32, sched);
+  p.sched = sched;
+  p.f32 = q32 ? 1 : 0;
+  p.skinny_tile = qt;
+  p.mask = dev_bits ? dev_bits + (span_begin >> 5) : nullptr;
+  p.msg_map = c->row_to_msg + span_begin;
+  p.msg_best = best;
+  p.msg_map_rows = c->rows - span_begin;
+  p.n_messages = c->n_messages;
+  c->last_tier = 5;
+  c->last_shadow = 0;
+  c->last_direct = 0;
+  c->masked_route = 10;
+  Timed t(c, TAVB_KERNEL_SKINNY);
+  hipError_t e = tavb::launch_skinny_scan(p, c->stream);
+  if (e != hipSuccess)
+    return fail(TAVB_E_HIP, "top-messages tile launch failed: %s (kernel %d, %lld rows in %d ranges, %d of %d queries)", hipGetErrorString(e), tavb::skinny_kernel_id(p),
+                (long long)p.rows, p.n_splits, p.nq, p.nq_padded);
+  c->last_skinny_kernel = tavb::skinny_kernel_id(p);
+  return TAVB_OK;
+}
+
 // fp16 corpora of any width (one that is no multiple of 64 filters on the zero-padded copy of the rows, as the unmasked route does), every k the
 // filter's band and the rescoring serve
 bool masked_wide_supported(const tavb_ctx* c, int k) {
@@ -1175,6 +1236,21 @@ extern "C" int tavb_plan_masked(int32_t nq, int32_t k, int32_t dim, int32_t dtyp
   if ((__int128)allowed * row_bytes < (__int128)min_bytes) return 0;
   // the gather route reads the allowed rows once per 8 queries, the tile the span once per 64: the tile when the gather's bytes are at least
   // pct % of the tile's
+  const __int128 gather = (__int128)((nq + 7) / 8) * allowed * 100;
+  const __int128 tile = (__int128)((nq + 63) / 64) * span * pct;
+  return gather >= tile ? 1 : 0;
+}
+
+extern "C" int tavb_plan_top_messages_tile(int32_t nq, int32_t dim, int32_t dtype, int64_t allowed, int64_t span, int64_t min_batch, int64_t min_bytes,
+                                           int64_t pct) {
+  if (dtype != TAVB_F32 && dtype != TAVB_F16) return fail(TAVB_E_INVALID, "dtype must be TAVB_F32 or TAVB_F16");
+  if (nq < 0 || allowed < 0 || span < allowed || min_batch < 0 || min_bytes < 0 || pct < 0) return fail(TAVB_E_INVALID, "bad shape");
+  const bool f32 = dtype == TAVB_F32;
+  if (dim <= 0 || !tavb::skinny_supported(dim, 1, f32)) return 0;  // (rows of a multiple of 64 bytes; the form keeps no lists: any k)
+  if (nq < 1 || nq < min_batch) return 0;
+  if (allowed == span) return 1;  // every row of the span is allowed (an unmasked lookup): one pass per 64 queries against one per eight
+  // under a mask the row scan reads the allowed rows once per 8 queries, the tile the span once per 64: tavb_plan_masked's rule and floor
+  if ((__int128)allowed * dim * (f32 ? 4 : 2) < (__int128)min_bytes) return 0;
   const __int128 gather = (__int128)((nq + 7) / 8) * allowed * 100;
   const __int128 tile = (__int128)((nq + 63) / 64) * span * pct;
   return gather >= tile ? 1 : 0;

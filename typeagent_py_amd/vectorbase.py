@@ -1553,6 +1553,27 @@ class VectorBase:
         return (isinstance(eng, _native.Engine) and hasattr(eng, "search_top_messages") and 1 <= max_messages <= _native.MAX_LARGE_K
                 and eng.get_option("top_messages") != 0)
 
+    @staticmethod
+    def _top_messages_tile(eng, mask, nq: int) -> bool:
+        """Whether a top-messages batch that `_top_messages_native` serves takes the 32/64-query tile (Engine.search_top_messages_tile)
+        instead of the row scan: the engine has the call, the mask (if any) holds its packed bits and its span, and the option
+        "top_messages_tile" (0 = never, the default; 2 = wherever the tile serves the shape; 1 = where tavb_plan_top_messages_tile
+        expects it to win) says so."""
+        if not (hasattr(eng, "search_top_messages_tile") and hasattr(eng, "plan_top_messages_tile")):
+            return False
+        if mask is not None and (mask.dev_bits is None or mask.span is None):
+            return False
+        opts = (eng.top_messages_tile_options() if hasattr(eng, "top_messages_tile_options") else
+                tuple(eng.get_option(n) for n in ("top_messages_tile", "top_messages_tile_min_batch", "mask_tile_min_bytes", "mask_tile_pct")))
+        mode, min_batch, min_bytes, pct = opts
+        if mode == 0:
+            return False
+        if mode == 2:  # (one allowed row in a span of one, no floors: yes exactly when the tile serves the width)
+            return bool(eng.plan_top_messages_tile(64, eng.dim, eng.dtype, 1, 1, 0, 0, 0))
+        if mask is None:
+            return bool(eng.plan_top_messages_tile(nq, eng.dim, eng.dtype, eng.rows, eng.rows, min_batch, min_bytes, pct))
+        return bool(eng.plan_top_messages_tile(nq, eng.dim, eng.dtype, mask.count, mask.span[1] + 1 - mask.span[0] // 256 * 256, min_batch, min_bytes, pct))
+
     def lookup_top_messages_by_embedding(
         self,
         embedding: NormalizedEmbedding,
@@ -1583,7 +1604,13 @@ class VectorBase:
         message on the device, then the exact device top-k over the messages.  Everything else -- max_messages 0 (every message) or
         beyond 16384, device groups, test doubles, "top_messages" = 0 -- takes the all-survivor lookup (`fuzzy_lookup_embedding(s)` /
         `_masked` at max_hits = 0) and collapses on the host, with the same result.  One scope per query in one submission is
-        `lookup_top_messages_by_embeddings_scoped`.  Not served here: `FusedIndexQuery`, the MFMA tiles."""
+        `lookup_top_messages_by_embeddings_scoped`.  Not served here: `FusedIndexQuery`.
+
+        Engine option "top_messages_tile" (default 0) moves the native route onto the 32/64-query MFMA tile
+        (tavb_search_top_messages_tile: one corpus pass per 64 queries instead of one per eight; rows of a multiple of 64 bytes; a mask
+        must hold its packed bits): 1 = where tavb_plan_top_messages_tile expects it to win, 2 = wherever the tile serves the shape.
+        Scores are then the tile's own -- within a few ulp of `fuzzy_lookup_embedding`'s, NOT bit for bit, as on every other route of that
+        tile -- which is why the switch is off unless a deployment flips it."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_messages, threshold_score)
         self._check_row_messages()
         mask = None if allowed is None else self._resolve_mask(allowed)
@@ -1591,6 +1618,10 @@ class VectorBase:
         if self._count == 0 or nq == 0 or (mask is not None and mask.count == 0):
             return [[] for _ in range(nq)]
         eng = self._messages_engine()
+        if eng is not None and self._top_messages_native(eng, max_hits) and self._top_messages_tile(eng, mask, nq):
+            msgs, scs, cnts = eng.search_top_messages_tile(queries, max_hits, thr, dev_bits=None if mask is None else mask.dev_bits,
+                                                           span=None if mask is None else mask.span)
+            return _scored_lists(msgs, scs, cnts, max_hits)
         if eng is not None and self._top_messages_native(eng, max_hits) and (mask is None or (self._masked_native(eng) and mask.dev_rows is not None)):
             msgs, scs, cnts = eng.search_top_messages(queries, max_hits, thr, dev_rows=None if mask is None else mask.dev_rows)
             return _scored_lists(msgs, scs, cnts, max_hits)
