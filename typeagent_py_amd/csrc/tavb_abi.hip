@@ -1,6 +1,6 @@
 // C ABI of libtavb.so (declared in include/tavb.h), the part that is not a lookup: version and error string, the context and its options,
-// corpus, load path, normalise / convert / merge / remap, profiling.  Host code only -- the lookups are in tavb_lookup.hip / tavb_lookup_topk.hip / tavb_lookup_masked.hip, their routing
-// in tavb_route.hip, the RCCL binding in tavb_comm.hip, the kernels in tavb_scan.hip / tavb_misc.hip / tavb_mfma_wide.hip / ...
+// corpus, load path, normalise / convert / merge / remap, profiling.  Host code only -- the lookups are in tavb_lookup.hip / tavb_lookup_topk.hip / tavb_lookup_masked.hip, the row
+// edits in tavb_row_edits.hip, the row masks in tavb_mask_entry.hip, the routing in tavb_route.hip, the RCCL binding in tavb_comm.hip, the kernels in tavb_scan.hip / tavb_misc.hip / tavb_mfma_wide.hip / ...
 
 #include <cstdarg>
 #include <cstdio>

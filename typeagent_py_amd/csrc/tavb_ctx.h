@@ -1,6 +1,7 @@
 // What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the fused-k lookups and the
-// staging), tavb_lookup_topk.hip (the large-k and sorted lookups), tavb_lookup_masked.hip (the batched resident subset, the masked batches,
-// the row masks), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
+// staging), tavb_lookup_topk.hip (the large-k and sorted lookups), tavb_lookup_masked.hip (the batched resident subset, the masked and
+// scoped batches), tavb_row_edits.hip (row compaction, expansion and scattered writes), tavb_mask_entry.hip (the row masks and the scope
+// algebra), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
 // context itself and the internal functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
 // tavb_search_device_dispatch lives in tavb::host, whose symbols stay inside the library.
 #pragma once
@@ -453,6 +454,34 @@ int check_key_ordinals(const tavb_ctx* c, bool device_resident);
 int fill_empty_keys(tavb_ctx* c, u64_t* out, int64_t n);
 // the tail of a host-synchronous lookup whose last kernel wrote [nq, k] keys into h_out: ONE synchronise, the keys decoded into the caller's arrays
 int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts);
+// Where the keys of a batched host-synchronous lookup land: up to kPinnedKeysMax of them in pinned host memory (h_out: the last kernel
+// writes them there, as in the single-query forms -- a remap of a few KiB runs on them in place); more are written in device memory (d_out)
+// and copied out once -- no merge writes megabytes over PCIe.  rounds (optional): the rounds [nq] of a large-k lookup stay reserved
+// behind the keys in h_out either way (reserve_topk_out).
+constexpr size_t kPinnedKeysMax = 4096;
+int reserve_key_target(tavb_ctx* c, int nq, int k, u64_t** target, int32_t** rounds = nullptr);
+// the keys at `target` -> h_out (when they are not there already), ONE synchronise, the caller's arrays; rounds (optional): reported
+// after the synchronise (note_rounds)
+int collect_keys(tavb_ctx* c, const u64_t* target, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts,
+                 const int32_t* rounds = nullptr);
+// the empty answer of a host form: every count zero, nothing launched
+inline int empty_counts(int32_t* counts, int nq) {
+  for (int q = 0; q < nq; ++q) counts[q] = 0;
+  return TAVB_OK;
+}
+// What a lookup that is no plain fused-k lookup resets before it runs: the large-k rounds, "last_direct", "last_graph" (not where
+// clear_graph is false: the gather route of a masked batch leaves it as it was) -- and "masked_route" = route.
+inline void note_route(tavb_ctx* c, int64_t route, bool clear_graph = true) {
+  c->last_topk_refine = 0;
+  c->topk_rounds_pending = 0;
+  c->last_direct = 0;
+  if (clear_graph) c->last_graph = 0;
+  c->masked_route = route;
+}
+// every mask of a list present and 4-byte aligned; `who` names one in the texts ("the mask of query", "mask")
+int check_mask_list(const uint32_t* const* masks, int n, const char* who);
+// positions -> base + rows[position] over n keys (launch_remap_positions; in == out: in place)
+int remap_key_rows(tavb_ctx* c, const u64_t* in, u64_t* out, int64_t n, const int32_t* rows, int64_t n_rows, uint32_t base);
 // the message lookups: the row -> message map is set and covers the corpus (check_message_map); that, plus context, corpus, 1 <= k <=
 // TAVB_MAX_FUSED_K and max_messages >= 0 (check_message_args)
 int check_message_map(const tavb_ctx* c);
@@ -509,8 +538,22 @@ int top_messages_tile_pass(tavb_ctx* c, const float* d_q, int n, const float* mi
 // same list.  ONE synchronise per wave (the unions' sizes); everything else is enqueued and not waited for.
 int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
                             uint32_t index_base, u64_t* work, u64_t* out, int32_t* out_rounds);
-// what the scoped entry points check after their own head: 1 <= k <= k_max, the masks; *empty: nothing to scan (tavb_lookup_masked.hip)
+
+// ---- tavb_lookup_masked.hip
+// what the scoped entry points check after their own head: 1 <= k <= k_max, the masks; *empty: nothing to scan
 int check_scoped_args(tavb_ctx* c, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k, int32_t k_max, bool* empty);
+// the span of a masked lookup that has something to scan
+int check_masked_span(bool empty, int64_t rows, int64_t first_row, int64_t last_row);
+
+// ---- tavb_mask_entry.hip: the chunk infos a count pass leaves in pinned memory
+// before the launch: every info unwritten (a chunk the kernel wrote holds a row or INT32_MAX in `first`)
+void mark_chunk_infos(tavb::MaskChunkInfo* info, size_t n);
+// after the synchronise: a chunk that wrote nothing is an internal error ("chunk %d of <what> wrote no info"); the counts' sum, the least
+// first and the greatest last
+struct ChunkSum {
+  int64_t count = 0, first = 0x7FFFFFFFll, last = -1;
+};
+int sum_chunk_infos(const tavb::MaskChunkInfo* info, int blocks, const char* what, ChunkSum* sum);
 
 // ---- tavb_comm.hip
 int comm_wait_or_abort(tavb_ctx* c);

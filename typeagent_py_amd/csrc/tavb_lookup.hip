@@ -1,8 +1,9 @@
 // The fused-k lookups of the C ABI (include/tavb.h): the host-synchronous and device-resident tavb_search_* entry points up to
 // TAVB_MAX_FUSED_K keys per query, the one-launch form and the captured graph of a small corpus, the host merges, the message re-rank -- and
 // the staging and the small helpers every lookup file shares (declared in tavb_ctx.h).  The large-k and sorted forms are in
-// tavb_lookup_topk.hip, the batched resident subset, the masked batches and the row masks in tavb_lookup_masked.hip.  Host code only -- a
-// device-resident batch is routed by tavb_route.hip, the kernels live in tavb_scan.hip / tavb_misc.hip.
+// tavb_lookup_topk.hip, the batched resident subset and the masked and scoped batches in tavb_lookup_masked.hip, the row edits in
+// tavb_row_edits.hip, the row masks in tavb_mask_entry.hip.  Host code only -- a device-resident batch is routed by tavb_route.hip, the
+// kernels live in tavb_scan.hip / tavb_misc.hip.
 
 #include <functional>
 
@@ -97,6 +98,41 @@ int fill_empty_keys(tavb_ctx* c, u64_t* out, int64_t n) {
 int sync_decode(tavb_ctx* c, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts) {
   TAVB_HIP(hipStreamSynchronize(c->stream));
   decode(reinterpret_cast<const u64_t*>(c->h_out.ptr), nq, k, base, ordinals, scores, counts);
+  return TAVB_OK;
+}
+
+int reserve_key_target(tavb_ctx* c, int nq, int k, u64_t** target, int32_t** rounds) {
+  const size_t n_keys = (size_t)nq * k;
+  if (rounds) {
+    if (int rc = reserve_topk_out(c, nq, k, target, rounds)) return rc;
+  } else {
+    if (int rc = c->h_out.reserve(n_keys * sizeof(u64_t))) return rc;
+    *target = reinterpret_cast<u64_t*>(c->h_out.ptr);
+  }
+  if (n_keys <= kPinnedKeysMax) return TAVB_OK;
+  if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
+  *target = reinterpret_cast<u64_t*>(c->d_out.ptr);
+  return TAVB_OK;
+}
+
+int collect_keys(tavb_ctx* c, const u64_t* target, int nq, int k, int64_t base, int64_t* ordinals, float* scores, int32_t* counts, const int32_t* rounds) {
+  if (target != c->h_out.ptr) TAVB_HIP(hipMemcpyAsync(c->h_out.ptr, target, (size_t)nq * k * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = sync_decode(c, nq, k, base, ordinals, scores, counts)) return rc;
+  if (rounds) note_rounds(c, rounds, nq);
+  return TAVB_OK;
+}
+
+int check_mask_list(const uint32_t* const* masks, int n, const char* who) {
+  for (int j = 0; j < n; ++j) {
+    if (!masks[j]) return fail(TAVB_E_INVALID, "%s %d is null", who, j);
+    if ((reinterpret_cast<uintptr_t>(masks[j]) & 3) != 0) return fail(TAVB_E_INVALID, "%s %d must be 4-byte aligned", who, j);
+  }
+  return TAVB_OK;
+}
+
+int remap_key_rows(tavb_ctx* c, const u64_t* in, u64_t* out, int64_t n, const int32_t* rows, int64_t n_rows, uint32_t base) {
+  const hipError_t e = tavb::launch_remap_positions(in, out, n, rows, n_rows, base, c->stream);
+  if (e != hipSuccess) return fail(TAVB_E_HIP, "remap launch failed: %s", hipGetErrorString(e));
   return TAVB_OK;
 }
 

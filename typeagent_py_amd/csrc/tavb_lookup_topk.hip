@@ -341,13 +341,6 @@ int check_top_messages_args(tavb_ctx* c, int k, const int32_t* dev_rows, int64_t
   return TAVB_OK;
 }
 
-void note_top_messages(tavb_ctx* c) {
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  c->last_direct = 0;
-  c->last_graph = 0;
-}
-
 int check_topk_args(tavb_ctx* c, int k) {
   if (int rc = check_ctx(c)) return rc;
   if (int rc = require_corpus(c)) return rc;
@@ -396,10 +389,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
-  if (c->rows == 0) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
+  if (c->rows == 0) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
   const float* d_q;
   u64_t* keys;
@@ -407,9 +397,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   if (int rc = search_topk_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, 0u, keys, rounds)) return rc;
-  if (int rc = sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts)) return rc;
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
+  return collect_keys(c, keys, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts, rounds);
 }
 
 int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, int32_t k, float min_score,
@@ -433,9 +421,7 @@ int tavb_search_subset_topk(tavb_ctx* c, const float* query_host, const int64_t*
   if (int rc = reserve_topk_out(c, 1, k, &keys, &rounds)) return rc;
   if (int rc = stage_subset(c, query_host, rows_host, n_subset, &d_q, &d_rows)) return rc;
   if (int rc = search_topk_impl(c, d_q, 1, k, &min_score, d_rows, n_subset, 0u, keys, rounds)) return rc;
-  if (int rc = sync_decode(c, 1, k, 0, out_positions, out_scores, out_count)) return rc;
-  note_rounds(c, rounds, 1);
-  return TAVB_OK;
+  return collect_keys(c, keys, 1, k, 0, out_positions, out_scores, out_count, rounds);
 }
 
 int tavb_search_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
@@ -691,10 +677,7 @@ int tavb_search_subset_batch_sorted(tavb_ctx* c, const float* queries_host, int3
   *out_total = 0;
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  c->last_direct = 0;
-  c->masked_route = 1;  // the gather route of a masked batch
+  note_route(c, 1, /*clear_graph=*/false);  // the gather route of a masked batch
   for (int q = 0; q < nq; ++q) out_counts[q] = 0;
   if (n_subset == 0 || c->rows == 0) return TAVB_OK;
   if (!dev_rows) return fail(TAVB_E_INVALID, "null dev_rows");
@@ -706,45 +689,24 @@ int tavb_search_subset_batch_sorted(tavb_ctx* c, const float* queries_host, int3
                             /*remap=*/true);
 }
 
-// ---- scoped batches beyond the fused selection: one mask per query at any max_hits (search_scoped_topk_impl, search_scoped_sorted_impl)
-static void note_scoped_large_route(tavb_ctx* c, int route) {
-  c->last_topk_refine = 0;
-  c->topk_rounds_pending = 0;
-  c->last_direct = 0;
-  c->last_graph = 0;
-  c->masked_route = route;  // 7 = a scoped batch on the large-k route, 8 = on the sorted route
-}
-
+// ---- scoped batches beyond the fused selection: one mask per query at any max_hits (search_scoped_topk_impl, search_scoped_sorted_impl);
+// "masked_route" = 7 on the large-k route, 8 on the sorted route
 int tavb_search_scoped_topk(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
                             const float* min_scores, int64_t* out_ordinals, float* out_scores, int32_t* out_counts) {
   bool empty = false;
   if (int rc = check_scoped_args(c, nq, dev_masks, rows, k, TAVB_MAX_LARGE_K, &empty)) return rc;
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  note_scoped_large_route(c, 7);
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
+  note_route(c, 7);
+  if (empty) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
-  const size_t n_keys = (size_t)nq * k;
-  u64_t* keys;
+  u64_t* target;
   int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  // (up to 4096 keys the finish kernels write into pinned memory and the remaps run there in place; more go through device memory and are
-  //  copied out once -- the rounds behind the keys in h_out stay reserved either way)
-  u64_t* target = keys;
-  if (n_keys > 4096) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
+  if (int rc = reserve_key_target(c, nq, k, &target, &rounds)) return rc;
   const float* d_q;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   if (int rc = search_scoped_topk_impl(c, d_q, nq, k, min_scores, dev_masks, 0u, target, target, rounds)) return rc;
-  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  if (int rc = sync_decode(c, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts)) return rc;
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
+  return collect_keys(c, target, nq, k, c->ordinal_base, out_ordinals, out_scores, out_counts, rounds);
 }
 
 int tavb_search_scoped_topk_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
@@ -754,7 +716,7 @@ int tavb_search_scoped_topk_device(tavb_ctx* c, const float* dev_queries, int32_
   if (nq == 0) return TAVB_OK;
   if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
   if (int rc = check_key_ordinals(c, /*device_resident=*/true)) return rc;
-  note_scoped_large_route(c, 7);
+  note_route(c, 7);
   DeviceGuard guard(c->device);
   u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
@@ -778,7 +740,7 @@ int tavb_search_scoped_sorted(tavb_ctx* c, const float* queries_host, int32_t nq
   *out_total = 0;
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
-  note_scoped_large_route(c, 8);
+  note_route(c, 8);
   for (int q = 0; q < nq; ++q) out_counts[q] = 0;
   if (empty) return TAVB_OK;
   DeviceGuard guard(c->device);
@@ -795,29 +757,16 @@ int tavb_search_top_messages(tavb_ctx* c, const float* queries_host, int32_t nq,
   if (nq < 0) return fail(TAVB_E_INVALID, "nq must be >= 0");
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  note_top_messages(c);
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
+  note_route(c, c->masked_route);  // ("masked_route" stays: this is no masked lookup)
+  if (empty) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
-  const size_t n_keys = (size_t)nq * k;
-  u64_t* keys;
+  u64_t* target;
   int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
-  u64_t* target = keys;
-  if (n_keys > 4096) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
+  if (int rc = reserve_key_target(c, nq, k, &target, &rounds)) return rc;
   const float* d_q;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   if (int rc = search_top_messages_impl(c, d_q, nq, k, min_scores, dev_rows, n_rows, target, rounds)) return rc;
-  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
+  return collect_keys(c, target, nq, k, 0, out_messages, out_scores, out_counts, rounds);
 }
 
 int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
@@ -826,7 +775,7 @@ int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32
   if (int rc = check_top_messages_args(c, k, dev_rows, n_rows, &empty)) return rc;
   if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
   if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  note_top_messages(c);
+  note_route(c, c->masked_route);  // ("masked_route" stays: this is no masked lookup)
   DeviceGuard guard(c->device);
   u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
@@ -861,30 +810,16 @@ int tavb_search_top_messages_tile(tavb_ctx* c, const float* queries_host, int32_
   if (int rc = check_top_messages_tile_args(c, nq, k, dev_bits, rows, first_row, last_row, &empty)) return rc;
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  note_top_messages(c);
-  c->masked_route = 10;  // a top-messages batch on the 32/64-query tile
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
+  note_route(c, 10);  // a top-messages batch on the 32/64-query tile
+  if (empty) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
-  const size_t n_keys = (size_t)nq * k;
-  u64_t* keys;
+  u64_t* target;
   int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
-  u64_t* target = keys;
-  if (n_keys > 4096) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
+  if (int rc = reserve_key_target(c, nq, k, &target, &rounds)) return rc;
   const float* d_q;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   if (int rc = search_top_messages_tile_impl(c, d_q, nq, k, min_scores, dev_bits, first_row, last_row, target, rounds)) return rc;
-  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
+  return collect_keys(c, target, nq, k, 0, out_messages, out_scores, out_counts, rounds);
 }
 
 int tavb_search_top_messages_tile_device(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const uint32_t* dev_bits,
@@ -893,8 +828,7 @@ int tavb_search_top_messages_tile_device(tavb_ctx* c, const float* dev_queries, 
   if (int rc = check_top_messages_tile_args(c, nq, k, dev_bits, rows, first_row, last_row, &empty)) return rc;
   if (nq < 1) return fail(TAVB_E_INVALID, "nq must be >= 1");
   if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  note_top_messages(c);
-  c->masked_route = 10;
+  note_route(c, 10);
   DeviceGuard guard(c->device);
   u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
@@ -915,40 +849,22 @@ static int check_scoped_top_messages_args(tavb_ctx* c, int32_t nq, const uint32_
   return TAVB_OK;
 }
 
-static void note_scoped_top_messages(tavb_ctx* c) {
-  note_top_messages(c);
-  c->masked_route = 9;  // a scoped top-messages batch
-}
-
 int tavb_search_top_messages_scoped(tavb_ctx* c, const float* queries_host, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
                                     const float* min_scores, int64_t* out_messages, float* out_scores, int32_t* out_counts) {
   bool empty = false;
   if (int rc = check_scoped_top_messages_args(c, nq, dev_masks, rows, k, &empty)) return rc;
   if (nq == 0) return TAVB_OK;
   if (!queries_host || !min_scores || !out_messages || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
-  note_scoped_top_messages(c);
-  if (empty) {
-    for (int q = 0; q < nq; ++q) out_counts[q] = 0;
-    return TAVB_OK;
-  }
+  note_route(c, 9);  // a scoped top-messages batch
+  if (empty) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
-  const size_t n_keys = (size_t)nq * k;
-  u64_t* keys;
+  u64_t* target;
   int32_t* rounds;
-  if (int rc = reserve_topk_out(c, nq, k, &keys, &rounds)) return rc;
-  // (up to 4096 keys the finish kernel writes into pinned memory; more go through device memory and are copied out once)
-  u64_t* target = keys;
-  if (n_keys > 4096) {
-    if (int rc = c->d_out.reserve(n_keys * sizeof(u64_t))) return rc;
-    target = reinterpret_cast<u64_t*>(c->d_out.ptr);
-  }
+  if (int rc = reserve_key_target(c, nq, k, &target, &rounds)) return rc;
   const float* d_q;
   if (int rc = stage_queries(c, queries_host, nq, &d_q)) return rc;
   if (int rc = search_scoped_top_messages_impl(c, d_q, nq, k, min_scores, dev_masks, target, rounds)) return rc;
-  if (target != keys) TAVB_HIP(hipMemcpyAsync(keys, target, n_keys * sizeof(u64_t), hipMemcpyDeviceToHost, c->stream));
-  if (int rc = sync_decode(c, nq, k, 0, out_messages, out_scores, out_counts)) return rc;
-  note_rounds(c, rounds, nq);
-  return TAVB_OK;
+  return collect_keys(c, target, nq, k, 0, out_messages, out_scores, out_counts, rounds);
 }
 
 int tavb_search_top_messages_scoped_device(tavb_ctx* c, const float* dev_queries, int32_t nq, const uint32_t* const* dev_masks, int64_t rows, int32_t k,
@@ -957,7 +873,7 @@ int tavb_search_top_messages_scoped_device(tavb_ctx* c, const float* dev_queries
   if (int rc = check_scoped_top_messages_args(c, nq, dev_masks, rows, k, &empty)) return rc;
   if (nq == 0) return TAVB_OK;
   if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
-  note_scoped_top_messages(c);
+  note_route(c, 9);  // a scoped top-messages batch
   DeviceGuard guard(c->device);
   u64_t* const out = reinterpret_cast<u64_t*>(out_keys);
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
