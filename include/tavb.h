@@ -337,6 +337,14 @@ int tavb_merge_keys_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int
  * keys must be unique (they carry global ordinals or positions).  A query one of whose lists leads with TAVB_KEY_PEER_FAILED comes back as
  * that key in every slot.  A pure host helper: no context, no GPU. */
 int tavb_merge_topk_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out);
+/* tavb_merge_topk_host for lists whose keys carry MESSAGE ordinals (the lists of tavb_search_top_messages_device, one per shard): a message
+ * whose chunks lie on several shards stands in several lists, with several scores, so the keys are NOT unique in their low half.  n_lists
+ * (1 .. 64) sorted, zero-padded lists per query, [n_lists, nq, k], 1 <= k <= TAVB_MAX_LARGE_K -> out [nq, k]: per message its largest key,
+ * the best min(k, distinct messages) of those, sorted descending and zero-padded.  With every shard's own top k as input this is the
+ * whole-corpus answer of tavb_search_top_messages: a message of the global top k is in the top k of the shard that holds its best row, with
+ * that score.  A query one of whose lists leads with TAVB_KEY_PEER_FAILED comes back as that key in every slot.  A pure host helper: no
+ * context, no GPU, no n_messages. */
+int tavb_merge_top_messages_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out);
 
 /* Every row with score >= min_score in ONE pass -- the reference's `np.flatnonzero(scores >= min_score)`
  * (vectorbase.py:179, 219) -- sorted best first on the host; the first min(total, max_out) are returned, *out_total is the
@@ -874,6 +882,19 @@ int tavb_merge_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists,
  * Asynchronous; timed under TAVB_KERNEL_MERGE. */
 int tavb_merge_topk_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out_keys);
 
+/* tavb_merge_topk_device for lists whose keys carry MESSAGE ordinals below n_messages (1 <= n_messages < 2^31 - 1): the same shapes and the
+ * two layouts (n_lists negative: query-major), up to 65535 queries -> out_keys [nq, k] (device or device-writable pinned memory), what
+ * tavb_merge_top_messages_host returns for the same lists, the rule for TAVB_KEY_PEER_FAILED included; a key whose message is at or beyond
+ * n_messages is dropped.  Per group of up to TAVB_MAX_STREAM_QUERIES queries (cut by "topk_scores_bytes" over [queries][n_messages], at
+ * least one): the [queries][n_messages] array of tavb_search_top_messages zeroed, ONE launch in which every key does one atomic max on its
+ * message's slot (tavb_topk.hip), then that lookup's histogram pass, boundary search, refinement, compaction and sort unchanged
+ * ("last_topk_refine" reports the rounds at the next tavb_synchronize).  A max does not depend on the order of its operands: the result is
+ * deterministic.  The cost is a pass over n_messages slots per query, whatever n_lists x k is.  Uses the workspaces of
+ * tavb_search_top_messages; needs no row -> message map.  Asynchronous; the scatter and the failure fill are timed under
+ * TAVB_KERNEL_MERGE, the selection under TAVB_KERNEL_TOPK. */
+int tavb_merge_top_messages_device(tavb_ctx* ctx, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k, int64_t n_messages,
+                                   tavb_key* out_keys);
+
 /* Decode host copies of keys into ordinals/scores/counts (pure host helper). */
 int tavb_decode_keys(const tavb_key* keys_host, int32_t nq, int32_t k, int64_t* out_ordinals, float* out_scores,
                      int32_t* out_counts);
@@ -920,6 +941,21 @@ int tavb_allgather_merge(tavb_ctx* ctx, const tavb_key* dev_local_keys, int32_t 
  * act as they do there.  Without a communicator: tavb_search_topk_device / a copy. */
 int tavb_search_topk_allgather(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, tavb_key* out_keys);
 int tavb_allgather_merge_topk(tavb_ctx* ctx, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys);
+/* The two calls above for the best k MESSAGES (1 <= k <= TAVB_MAX_LARGE_K): tavb_search_top_messages_device on every rank over its shard
+ * -- dev_rows NULL (n_rows 0): the whole shard; dev_rows: this rank's part of a mask as shard-local rows, and a non-NULL dev_rows with
+ * n_rows 0 (or a shard without rows) joins with zero lists -- then the all-gather, then the merge of tavb_merge_top_messages_device over the
+ * context's n_messages.  Message ordinals are global: every rank sets its slice of ONE map with the SAME n_messages (tavb_set_row_messages;
+ * a rank without rows too), and every shard's own top k suffices for the whole-corpus answer (tavb_merge_top_messages_host).  The protocol
+ * is that of tavb_search_topk_allgather step by step: argument errors every rank makes alike return at once -- k out of range, NULL
+ * pointers, a k above "comm_reserve_keys", more than 64 ranks, n_messages 0 (no map: TAVB_E_NO_CORPUS) or >= 2^31 - 1; whatever fails on
+ * one rank -- a map that does not cover its shard, a bad row list, the workspaces of its lookup -- still joins every chunk of the exchange
+ * with TAVB_KEY_PEER_FAILED lists; the merge's own workspaces (no larger than the rank's lookup reserved) are reserved behind a chunk's
+ * all-gather, and a rank whose merge fails still joins the all-gathers of every later chunk before it returns its error; chunks, "comm_fail_rank",
+ * "comm_fail_alloc", "comm_stall_ms", "comm_force" and "comm_timeout_ms" act as they do there.  The all-gather is timed under
+ * TAVB_KERNEL_EXCHANGE.  Without a communicator: tavb_search_top_messages_device / a copy. */
+int tavb_search_top_messages_allgather(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores /*host*/,
+                                       const int32_t* dev_rows, int64_t n_rows, tavb_key* out_keys);
+int tavb_allgather_merge_top_messages(tavb_ctx* ctx, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys);
 /* keys [count] that carry POSITIONS into a list -> the same keys carrying dev_map[position] (int32 [map_len]): a rank's subset search
  * (tavb_search_subset_device) numbers the part of the caller's subset that lies in its shard; the map leads back to the positions in the
  * caller's whole list.  In place, asynchronous.  The map must be monotonic for the lists to stay sorted among equal scores. */

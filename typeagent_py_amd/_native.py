@@ -67,6 +67,7 @@ _SIGNATURES = [
     ("tavb_search_end", c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_merge_keys_host", c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_host", c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    ("tavb_merge_top_messages_host", c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_search_all", c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     ("tavb_search_subset_all", c_int,
      [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
@@ -134,6 +135,7 @@ _SIGNATURES = [
     ("tavb_scatter_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     ("tavb_merge_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     ("tavb_merge_topk_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    ("tavb_merge_top_messages_device", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
     ("tavb_decode_keys", c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_comm_unique_id", c_int, [c_void_p]),
     ("tavb_comm_init", c_int, [c_void_p, c_void_p, c_int32, c_int32]),
@@ -142,6 +144,8 @@ _SIGNATURES = [
     ("tavb_allgather_merge", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_search_topk_allgather", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     ("tavb_allgather_merge_topk", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    ("tavb_search_top_messages_allgather", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_allgather_merge_top_messages", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_remap_key_positions", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64]),
     ("tavb_profile_enable", c_int, [c_void_p, c_int32]),
     ("tavb_profile_reset", c_int, [c_void_p]),
@@ -1057,15 +1061,19 @@ class Engine:
         _check(self.lib, rc)
 
     # message re-rank on the device ---------------------------------------------
-    def set_row_messages(self, row_to_message: np.ndarray) -> None:
-        """int array [rows]: chunk row -> message ordinal (-1 = none); kept on the device next to the corpus."""
+    def set_row_messages(self, row_to_message: np.ndarray, n_messages: int | None = None) -> None:
+        """int array [rows]: chunk row -> message ordinal (-1 = none); kept on the device next to the corpus.  n_messages: the number of
+        messages when the rows are one shard of a larger corpus -- message ordinals are global, so every shard sets the same one (None:
+        the map's largest ordinal + 1)."""
         torch = self._torch
         m = np.ascontiguousarray(row_to_message, dtype=np.int32)
         if m.ndim != 1:
             raise ValueError("row_to_message must be 1-D")
         self.row_messages = torch.from_numpy(m).to(torch.device("cuda", self.device))
         torch.cuda.current_stream(self.device).synchronize()
-        n_messages = int(m.max()) + 1 if m.size else 0
+        if n_messages is None:
+            n_messages = int(m.max()) + 1 if m.size else 0
+        self.n_messages = max(int(n_messages), 0)
         _check(self.lib, self.lib.tavb_set_row_messages(self._h, c_void_p(self.row_messages.data_ptr()), m.shape[0], max(n_messages, 0)))
 
     def search_messages(self, q, k: int, thr: np.float32, max_messages: int, accept=None, subset_rows=None):
@@ -1709,6 +1717,34 @@ class Engine:
         _check(self.lib, rc)
         return out_keys
 
+    def search_top_messages_allgather(self, dev_queries, k: int, thrs, out_keys=None, dev_rows=None):
+        """Collective `search_top_messages_device` (tavb_search_top_messages_allgather): every rank passes the same queries and thresholds
+        and gets the merged whole-corpus lists [nq, k] of keys carrying MESSAGE ordinals, 1 <= k <= MAX_LARGE_K.  dev_rows: None -- this
+        rank's whole shard -- or this rank's part of a mask as shard-local rows (torch int32 [S]; an EMPTY tensor: this rank joins with
+        zero lists).  Needs `set_row_messages` with the same n_messages on every rank.  `out_keys`: a device tensor or a PINNED host tensor.
+        Async."""
+        nq, t, out_keys = self._device_batch(dev_queries, k, thrs, out_keys)
+        rows_ptr, n = (None, 0) if dev_rows is None else self._row_list(dev_rows)
+        if dev_rows is not None and n == 0:  # (an empty tensor has no address: any non-null pointer names "an empty part of a mask")
+            rows_ptr = c_void_p(dev_queries.data_ptr())
+        with self._lock:
+            rc = self.lib.tavb_search_top_messages_allgather(self._h, c_void_p(dev_queries.data_ptr()), nq, k, _addr(t), rows_ptr, n,
+                                                             c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def allgather_merge_top_messages(self, dev_local_keys, out_keys=None):
+        """`allgather_merge_topk` for lists whose keys carry MESSAGE ordinals (tavb_allgather_merge_top_messages): per message the largest
+        key over all ranks, then the best k.  Async; collective."""
+        torch = self._torch
+        assert dev_local_keys.dtype == torch.int64 and dev_local_keys.is_contiguous() and dev_local_keys.dim() == 2
+        nq, k = dev_local_keys.shape
+        out_keys = self._out_keys(out_keys, nq, k, dev_local_keys.device)
+        with self._lock:
+            rc = self.lib.tavb_allgather_merge_top_messages(self._h, c_void_p(dev_local_keys.data_ptr()), nq, k, c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
     def remap_key_positions(self, dev_keys, dev_map) -> None:
         """In place: keys carrying list positions -> keys carrying dev_map[position] (int32 device tensor).  Async."""
         torch = self._torch
@@ -1741,6 +1777,22 @@ class Engine:
         with self._lock:
             rc = self.lib.tavb_merge_topk_device(self._h, c_void_p(dev_lists.data_ptr()), -n_lists if query_major else n_lists, nq, k,
                                                  c_void_p(out_keys.data_ptr()))
+        _check(self.lib, rc)
+        return out_keys
+
+    def merge_top_messages_device(self, dev_lists, n_messages: int, out_keys=None, query_major: bool = False):
+        """`merge_topk_device` for lists whose keys carry MESSAGE ordinals below n_messages (tavb_merge_top_messages_device): a message may
+        stand in several lists -> [nq, k], per message its largest key, the best k, what `merge_top_messages_keys` returns (async)."""
+        torch = self._torch
+        assert dev_lists.dtype == torch.int64 and dev_lists.is_contiguous() and dev_lists.dim() == 3
+        if query_major:
+            nq, n_lists, k = dev_lists.shape
+        else:
+            n_lists, nq, k = dev_lists.shape
+        out_keys = self._out_keys(out_keys, nq, k, dev_lists.device)
+        with self._lock:
+            rc = self.lib.tavb_merge_top_messages_device(self._h, c_void_p(dev_lists.data_ptr()), -n_lists if query_major else n_lists, nq, k,
+                                                         int(n_messages), c_void_p(out_keys.data_ptr()))
         _check(self.lib, rc)
         return out_keys
 
@@ -1779,6 +1831,20 @@ def merge_topk_keys(lists: np.ndarray) -> np.ndarray:
     n_lists, nq, k = a.shape
     out = np.empty((nq, k), dtype=np.uint64)
     _check(lib, lib.tavb_merge_topk_host(_addr(a), n_lists, nq, k, _addr(out)))
+    return out
+
+
+def merge_top_messages_keys(lists: np.ndarray) -> np.ndarray:
+    """`merge_topk_keys` for lists whose keys carry MESSAGE ordinals (tavb_merge_top_messages_host): uint64 [n_lists <= 64, nq, k] sorted,
+    zero-padded lists in which one message may stand several times -> uint64 [nq, k]: per message its largest key, the best k, sorted and
+    zero-padded; a query one of whose lists leads with the failure key comes back as that key in every slot.  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    a = np.ascontiguousarray(lists).view(np.uint64)
+    if a.ndim != 3:
+        raise ValueError("lists must be [n_lists, nq, k]")
+    n_lists, nq, k = a.shape
+    out = np.empty((nq, k), dtype=np.uint64)
+    _check(lib, lib.tavb_merge_top_messages_host(_addr(a), n_lists, nq, k, _addr(out)))
     return out
 
 

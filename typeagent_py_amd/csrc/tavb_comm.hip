@@ -1,5 +1,6 @@
 // Row-sharded corpora: the RCCL binding of libtavb.so -- tavb_comm_*, tavb_search_allgather, tavb_allgather_merge and their large-k
-// forms tavb_search_topk_allgather, tavb_allgather_merge_topk.  The only file that
+// forms tavb_search_topk_allgather, tavb_allgather_merge_topk, and the top-messages forms tavb_search_top_messages_allgather,
+// tavb_allgather_merge_top_messages.  The only file that
 // includes RCCL's header (the context holds the communicator as an opaque pointer).  Host code only.
 
 #include <dlfcn.h>
@@ -143,11 +144,17 @@ int tavb_comm_destroy(tavb_ctx* c) {
 }  // extern "C"
 
 // local [nq, k] lists (device; nullptr = this rank FAILED: it sends TAVB_KEY_PEER_FAILED in every slot) -> ncclAllGather on the context's
-// stream -> merge kernel -> out_keys [nq, k].  Nothing here allocates: the lists travel through the buffers tavb_comm_init reserved, in chunks
+// stream -> merge kernel -> out_keys [nq, k].  Nothing in front of an all-gather allocates: the lists travel through the buffers tavb_comm_init reserved, in chunks
 // of whole queries when they hold more than comm_reserve_keys keys.  Every rank makes the same call and cuts by the value tavb_comm_init
-// stored (comm_chunk_keys), so every rank cuts the same chunks.  long_lists: the merge of tavb_topk.hip (any k up to TAVB_MAX_LARGE_K, up to
-// 64 ranks) instead of the register merge (k up to TAVB_MAX_FUSED_K) -- the one difference between the two families of collective calls.
-static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys) {
+// stored (comm_chunk_keys), so every rank cuts the same chunks.  The merge is the one difference between the families of collective calls:
+// kMergeFused, the register merge (k up to TAVB_MAX_FUSED_K); kMergeLong, the merge of tavb_topk.hip (any k up to TAVB_MAX_LARGE_K, up to 64
+// ranks); kMergeMessages, the same shapes for keys that carry MESSAGE ordinals -- one maximum per message, then the top-messages selection
+// (merge_top_messages_impl over the context's n_messages).  That merge has workspaces of its own (d_msg_best, d_topk: no larger than the
+// rank's own lookup reserved, plan_top_messages), reserved behind the chunk's all-gather; a rank whose merge fails all the same stops
+// merging but still joins the all-gathers of EVERY later chunk -- the peers are never left waiting -- and returns its error at the end.
+enum MergeKind { kMergeFused, kMergeLong, kMergeMessages };
+
+static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32_t k, MergeKind merge, tavb_key* out_keys) {
   const int qc = (int)std::min<int64_t>(nq, std::max<int64_t>(1, c->comm_chunk_keys / k));  // queries per chunk
   if ((size_t)qc * k * sizeof(u64_t) * c->comm_world > c->d_gather.cap || (size_t)qc * k * sizeof(u64_t) > c->d_xlocal.cap)
     return fail(TAVB_E_INVALID, "the exchange buffers of this communicator are gone (tavb_comm_init reserves them)");
@@ -158,6 +165,8 @@ static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32
     c->comm_stall_ms = 0;
   }
   c->comm_inflight = true;
+  int rc_merge = TAVB_OK;
+  std::string merge_error;
   for (int q0 = 0; q0 < nq; q0 += qc) {
     const int qn = std::min(qc, nq - q0);
     const u64_t* src = local ? local + (size_t)q0 * k : reinterpret_cast<const u64_t*>(c->d_xlocal.ptr);
@@ -165,12 +174,25 @@ static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32
       Timed t(c, TAVB_KERNEL_EXCHANGE);
       TAVB_RCCL(g_rccl.AllGather(src, gathered, (size_t)qn * k, ncclUint64, comm_of(c), c->stream));
     }
-    Timed t(c, TAVB_KERNEL_MERGE);
     u64_t* out = reinterpret_cast<u64_t*>(out_keys) + (size_t)q0 * k;
-    hipError_t e = long_lists ? tavb::launch_merge_topk(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream)
-                              : tavb::launch_merge(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream);
+    if (merge == kMergeMessages) {
+      if (rc_merge != TAVB_OK) continue;  // (this rank's merge has failed: it only keeps the collectives company)
+      if ((rc_merge = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) == TAVB_OK)
+        rc_merge = merge_top_messages_impl(c, gathered, c->comm_world, qn, k, /*query_major=*/false, c->n_messages, out,
+                                           reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr) + q0);
+      if (rc_merge != TAVB_OK) merge_error = g_last_error;
+      continue;
+    }
+    Timed t(c, TAVB_KERNEL_MERGE);
+    hipError_t e = merge == kMergeLong ? tavb::launch_merge_topk(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream)
+                                       : tavb::launch_merge(gathered, c->comm_world, qn, k, /*query_major=*/false, out, c->stream);
     if (e != hipSuccess) return fail(TAVB_E_HIP, "merge launch failed: %s", hipGetErrorString(e));
   }
+  if (rc_merge != TAVB_OK) {
+    g_last_error = merge_error;
+    return rc_merge;
+  }
+  if (merge == kMergeMessages) c->topk_rounds_pending = nq;  // ("last_topk_refine": the merge's rounds, at the next tavb_synchronize)
   return TAVB_OK;
 }
 
@@ -180,7 +202,7 @@ static int exchange_and_merge(tavb_ctx* c, const u64_t* local, int32_t nq, int32
 // allocation between here and the all-gather.  `search(local)` enqueues this shard's lookup into local [nq, k] and returns its status -- the
 // workspaces it reserves on the way are part of it: a failure there joins the exchange like any other.
 template <class Search>
-static int search_exchange_merge(tavb_ctx* c, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys, Search&& search) {
+static int search_exchange_merge(tavb_ctx* c, int32_t nq, int32_t k, MergeKind merge, tavb_key* out_keys, Search&& search) {
   DeviceGuard guard(c->device);
   const size_t list_keys = (size_t)nq * k;
   int rc_local = TAVB_OK;
@@ -202,7 +224,7 @@ static int search_exchange_merge(tavb_ctx* c, int32_t nq, int32_t k, bool long_l
   // a failed rank's lists = TAVB_KEY_PEER_FAILED (all bits set) in every slot: it sorts above every real key, so it leads every merged list on
   // EVERY rank -- the peers' answers would silently miss this shard otherwise; tavb_decode_keys turns it into TAVB_E_PEER
   const std::string local_error = rc_local != TAVB_OK ? g_last_error : std::string();
-  const int rc_x = exchange_and_merge(c, rc_local == TAVB_OK ? local : nullptr, nq, k, long_lists, out_keys);
+  const int rc_x = exchange_and_merge(c, rc_local == TAVB_OK ? local : nullptr, nq, k, merge, out_keys);
   if (rc_local != TAVB_OK) {
     g_last_error = local_error;
     return rc_local;
@@ -236,7 +258,7 @@ int tavb_search_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int
   if (!collective(c)) return tavb_search_device(c, dev_queries, nq, k, min_score, out_keys);
   // ... everything else joins the exchange (search_exchange_merge)
   const std::vector<float> ms((size_t)nq, min_score);
-  return search_exchange_merge(c, nq, k, /*long_lists=*/false, out_keys, [&](u64_t* local) {
+  return search_exchange_merge(c, nq, k, kMergeFused, out_keys, [&](u64_t* local) {
     return tavb_search_device_dispatch(c, dev_queries, nq, k, ms.data(), (uint32_t)c->ordinal_base, local);
   });
 }
@@ -246,12 +268,12 @@ int tavb_search_topk_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq
   if (int rc = check_long_lists(c, nq, k)) return rc;
   if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
   if (!collective(c)) return tavb_search_topk_device(c, dev_queries, nq, k, min_scores, nullptr, 0, out_keys);
-  return search_exchange_merge(c, nq, k, /*long_lists=*/true, out_keys, [&](u64_t* local) {
+  return search_exchange_merge(c, nq, k, kMergeLong, out_keys, [&](u64_t* local) {
     return search_topk_async(c, dev_queries, nq, k, min_scores, nullptr, c->rows, (uint32_t)c->ordinal_base, local);
   });
 }
 
-static int allgather_merge_impl(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, bool long_lists, tavb_key* out_keys) {
+static int allgather_merge_impl(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, MergeKind merge, tavb_key* out_keys) {
   if (!dev_local_keys || !out_keys) return fail(TAVB_E_INVALID, "null argument");
   DeviceGuard guard(c->device);
   if (!collective(c)) {
@@ -259,19 +281,52 @@ static int allgather_merge_impl(tavb_ctx* c, const tavb_key* dev_local_keys, int
       TAVB_HIP(hipMemcpyAsync(out_keys, dev_local_keys, (size_t)nq * k * sizeof(u64_t), hipMemcpyDefault, c->stream));
     return TAVB_OK;
   }
-  return exchange_and_merge(c, reinterpret_cast<const u64_t*>(dev_local_keys), nq, k, long_lists, out_keys);
+  return exchange_and_merge(c, reinterpret_cast<const u64_t*>(dev_local_keys), nq, k, merge, out_keys);
 }
 
 int tavb_allgather_merge(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
   if (int rc = check_ctx(c)) return rc;
   if (nq < 1 || k < 1 || k > TAVB_MAX_FUSED_K) return fail(TAVB_E_INVALID, "bad list shape");
-  return allgather_merge_impl(c, dev_local_keys, nq, k, /*long_lists=*/false, out_keys);
+  return allgather_merge_impl(c, dev_local_keys, nq, k, kMergeFused, out_keys);
 }
 
 int tavb_allgather_merge_topk(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
   if (int rc = check_ctx(c)) return rc;
   if (int rc = check_long_lists(c, nq, k)) return rc;
-  return allgather_merge_impl(c, dev_local_keys, nq, k, /*long_lists=*/true, out_keys);
+  return allgather_merge_impl(c, dev_local_keys, nq, k, kMergeLong, out_keys);
+}
+
+// argument errors of the top-messages collectives that every rank makes alike: check_long_lists, and the context's n_messages -- every rank
+// sets the same one (tavb_set_row_messages), a rank without rows included; 0 means no map was ever set
+static int check_message_lists(const tavb_ctx* c, int32_t nq, int32_t k) {
+  if (int rc = check_long_lists(c, nq, k)) return rc;
+  if (c->n_messages == 0) return fail(TAVB_E_NO_CORPUS, "no row -> message map set (call tavb_set_row_messages first, with the same n_messages on every rank)");
+  if (c->n_messages >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "top-messages keys hold message ordinals: n_messages must be < 2^31 - 1");
+  return TAVB_OK;
+}
+
+int tavb_search_top_messages_allgather(tavb_ctx* c, const float* dev_queries, int32_t nq, int32_t k, const float* min_scores, const int32_t* dev_rows,
+                                       int64_t n_rows, tavb_key* out_keys) {
+  // argument errors every rank makes alike return at once ...
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = check_message_lists(c, nq, k)) return rc;
+  if (!dev_queries || !min_scores || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  if (!collective(c)) return tavb_search_top_messages_device(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, out_keys);
+  // ... everything else -- the row list's shape and a map that does not cover this rank's shard among it -- joins the exchange
+  return search_exchange_merge(c, nq, k, kMergeMessages, out_keys, [&](u64_t* local) {
+    bool empty = false;
+    if (int rc = check_top_messages_args(c, k, dev_rows, n_rows, &empty)) return rc;
+    c->topk_rounds_pending = 0;
+    if (empty) return fill_empty_keys(c, local, (int64_t)nq * k);  // (this rank's part of the mask holds no row)
+    if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+    return search_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, local, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr));
+  });
+}
+
+int tavb_allgather_merge_top_messages(tavb_ctx* c, const tavb_key* dev_local_keys, int32_t nq, int32_t k, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  if (int rc = check_message_lists(c, nq, k)) return rc;
+  return allgather_merge_impl(c, dev_local_keys, nq, k, kMergeMessages, out_keys);
 }
 
 }  // extern "C"

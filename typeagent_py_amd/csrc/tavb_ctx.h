@@ -492,6 +492,13 @@ int stage_accept_bitmap(tavb_ctx* c, const int32_t* accept_msgs_host, int64_t n_
 
 // ---- tavb_lookup_topk.hip
 int check_topk_args(tavb_ctx* c, int k);  // context, corpus, 1 <= k <= TAVB_MAX_LARGE_K
+// check_topk_args, the row list's shape and a row -> message map that covers exactly the corpus; *empty: nothing to scan
+int check_top_messages_args(tavb_ctx* c, int k, const int32_t* dev_rows, int64_t n_rows, bool* empty);
+// The merge of top-messages lists (tavb_merge_top_messages_device): n_lists (1 .. 64) sorted, zero-padded device lists of k keys per query
+// carrying MESSAGE ordinals below nm, laid out as launch_merge_topk takes them -> out_keys [nq][k], per message its largest key, the best k,
+// sorted and zero-padded, + out_rounds [nq]; both device-writable.  A query one of whose lists leads with TAVB_KEY_PEER_FAILED is that key
+// in every slot.  Uses d_msg_best and d_topk, not the row -> message map; nothing is waited for.  The caller has checked the shape.
+int merge_top_messages_impl(tavb_ctx* c, const u64_t* lists, int n_lists, int nq, int k, bool query_major, int64_t nm, u64_t* out_keys, int32_t* out_rounds);
 // the pinned keys [nq][k] + rounds [nq] of a large-k lookup (h_out), and what tavb_search_topk reports of the rounds ("last_topk_refine")
 int reserve_topk_out(tavb_ctx* c, int nq, int k, u64_t** keys, int32_t** rounds);
 void note_rounds(tavb_ctx* c, const int32_t* rounds, int nq);

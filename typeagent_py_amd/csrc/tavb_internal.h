@@ -126,6 +126,15 @@ hipError_t launch_merge_topk(const unsigned long long* lists, int n_lists, int n
                              hipStream_t stream);
 // out[0 .. n) = value, with vector stores (out: device or device-writable pinned memory)
 hipError_t launch_fill_keys(unsigned long long* out, int64_t n, unsigned long long value, hipStream_t stream);
+// the rows [q * k, (q + 1) * k) of out [nq][k] whose flags[q] (device) is set = value; the other rows stay as they are
+hipError_t launch_fill_flagged_rows(unsigned long long* out, int nq, int k, unsigned long long value, const unsigned* flags, hipStream_t stream);
+// First half of the merge of TOP-MESSAGES lists (keys carrying message ordinals, one list per shard: a message may stand in several): for the
+// queries [q0, q0 + n) of lists laid out as launch_merge_topk takes them (nq queries in all; n <= TAVB_MAX_STREAM_QUERIES), every non-zero
+// key raises best [n][n_messages] (zeroed by the caller) at its message to 1 + its score bits -- what launch_scan_top_messages leaves, so
+// that launch_message_hist and the selection follow unchanged.  Keys whose message is >= n_messages are dropped.  flags [n] (device; written
+// for every query): 1 where a list of the query leads with TAVB_KEY_PEER_FAILED -- such a query raises nothing.  tavb_topk.hip
+hipError_t launch_message_keys_max(const unsigned long long* lists, int n_lists, int nq, int k, bool query_major, int q0, int n, int64_t n_messages,
+                                   unsigned* best, unsigned* flags, hipStream_t stream);
 
 // The sorted route (tavb_search_sorted) over the same score pass and workspace head, after the refinement rounds (t.k: any 1 .. n_pos,
 // n_pos = every survivor; t.out_keys / t.out_rounds unused): sorted_count writes, per query and block of positions, how many keys lie at

@@ -486,6 +486,38 @@ int tavb_merge_topk_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int
   return TAVB_OK;
 }
 
+// Lists whose keys carry MESSAGE ordinals: a message may stand in several lists, with several scores.  Per query: every real key, grouped by
+// message (the low half) with the largest first, one key per message kept, the best k of those sorted descending.  The rule of the device
+// merge (merge_top_messages_impl) for the failure key.
+int tavb_merge_top_messages_host(const tavb_key* lists, int32_t n_lists, int32_t nq, int32_t k, tavb_key* out) {
+  if (n_lists < 1 || n_lists > 64 || nq < 0 || k < 1 || k > TAVB_MAX_LARGE_K)
+    return fail(TAVB_E_INVALID, "bad merge shape (1 .. 64 lists of 1 .. %d keys)", TAVB_MAX_LARGE_K);
+  if (nq == 0) return TAVB_OK;
+  if (!lists || !out) return fail(TAVB_E_INVALID, "null argument");
+  std::vector<u64_t> pool;
+  for (int q = 0; q < nq; ++q) {
+    tavb_key* o = out + (size_t)q * k;
+    bool failed = false;
+    pool.clear();
+    for (int l = 0; l < n_lists; ++l) {
+      const tavb_key* list = lists + ((size_t)l * nq + q) * k;
+      failed = failed || list[0] == TAVB_KEY_PEER_FAILED;
+      for (int i = 0; i < k && list[i] != 0; ++i) pool.push_back(list[i]);  // (sorted, zero-padded: nothing behind the first zero)
+    }
+    if (failed) {
+      std::fill(o, o + k, TAVB_KEY_PEER_FAILED);
+      continue;
+    }
+    std::sort(pool.begin(), pool.end(), [](u64_t a, u64_t b) { return (uint32_t)a != (uint32_t)b ? (uint32_t)a < (uint32_t)b : a > b; });
+    pool.erase(std::unique(pool.begin(), pool.end(), [](u64_t a, u64_t b) { return (uint32_t)a == (uint32_t)b; }), pool.end());
+    const size_t n = std::min<size_t>((size_t)k, pool.size());
+    std::partial_sort(pool.begin(), pool.begin() + n, pool.end(), std::greater<u64_t>());
+    std::copy(pool.begin(), pool.begin() + n, o);
+    std::fill(o + n, o + k, (tavb_key)0);
+  }
+  return TAVB_OK;
+}
+
 int tavb_search(tavb_ctx* c, const float* query_host, int32_t k, float min_score, int64_t* out_ordinals,
                 float* out_scores, int32_t* out_count) {
   return tavb_search_batch(c, query_host, 1, k, &min_score, out_ordinals, out_scores, out_count);

@@ -184,10 +184,11 @@ int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const 
 // list, the histogram pass over the messages, then the refinement rounds, the compaction and the finish with n_pos = n_messages.
 namespace {
 
-// Groups of at most `most` queries over the n_messages slots, cut to what "topk_scores_bytes" lets [queries][n_messages] hold (at least
-// one), with d_msg_best and the selection's workspace reserved for one group at depth k.  s->g.blocks is the caller's to set per pass.
-int plan_top_messages(tavb_ctx* c, int64_t most, int k, ScorePlan* s) {
-  const int64_t nm = c->n_messages;
+// Groups of at most `most` queries over nm = n_messages slots, cut to what "topk_scores_bytes" lets [queries][n_messages] hold (at least
+// one), with d_msg_best and the selection's workspace reserved for one group at depth k -- d_msg_best with TAVB_MAX_STREAM_QUERIES words
+// behind the group's slots (the per-query failure flags of merge_top_messages_impl), so that the merge of a lookup's lists never asks for
+// more than the lookup itself did.  s->g.blocks is the caller's to set per pass.
+int plan_top_messages(tavb_ctx* c, int64_t nm, int64_t most, int k, ScorePlan* s) {
   s->n_pos = nm;
   s->nb = (int)c->topk_buckets;
   s->cap = (int)c->topk_boundary_keys;
@@ -195,7 +196,7 @@ int plan_top_messages(tavb_ctx* c, int64_t most, int k, ScorePlan* s) {
   s->rounds = tavb::topk_refine_rounds(nm, s->cap);
   s->g = clamped_geometry(c);
   s->sel_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nm + 2047) / 2048), std::max<int64_t>(1, 2048 / s->per));
-  if (int rc = c->d_msg_best.reserve((size_t)s->per * nm * sizeof(uint32_t))) return rc;
+  if (int rc = c->d_msg_best.reserve(((size_t)s->per * nm + TAVB_MAX_STREAM_QUERIES) * sizeof(uint32_t))) return rc;
   return c->d_topk.reserve(tavb::topk_workspace_bytes((int)s->per, k, s->nb, s->cap, s->rounds));
 }
 
@@ -255,11 +256,40 @@ int search_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k, const
                              u64_t* out_keys, int32_t* out_rounds) {
   const int64_t n_scan = d_rows ? n_rows : c->rows;
   ScorePlan s;
-  if (int rc = plan_top_messages(c, std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, 0), nq), k, &s)) return rc;
+  if (int rc = plan_top_messages(c, c->n_messages, std::min<int64_t>(tavb::topk_queries_per_pass(c->dim, c->dtype, 0), nq), k, &s)) return rc;
   s.g.blocks = scan_blocks_for(c, n_scan, s.g.waves, 2);
   for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
     const int n = (int)std::min<int64_t>(s.per, nq - q0);
     if (int rc = top_messages_group(c, s, d_q, min_scores, d_rows, n_scan, q0, n, k, out_keys + (size_t)q0 * k, out_rounds + q0)) return rc;
+  }
+  return TAVB_OK;
+}
+
+// ---- the merge of the top-messages lists of several shards (tavb_merge_top_messages_device): groups of up to TAVB_MAX_STREAM_QUERIES queries,
+// cut by "topk_scores_bytes" over [queries][nm] as above.  Per group: the two memsets, ONE launch that raises every key's message slot to
+// its score (launch_message_keys_max -- the score pass' place), then the second half of the group above.  Thresholds: 0 -- the keys have
+// passed theirs on their shards, and a bucket map only has to be monotone.  A query one of whose lists leads with the failure key raises
+// nothing, its selection leaves an empty row, and the flagged fill behind it writes the failure key into every slot.  The flags of a group
+// live behind its slots of d_msg_best (plan_top_messages reserves them).
+int merge_top_messages_impl(tavb_ctx* c, const u64_t* lists, int n_lists, int nq, int k, bool query_major, int64_t nm, u64_t* out_keys, int32_t* out_rounds) {
+  ScorePlan s;
+  if (int rc = plan_top_messages(c, nm, std::min(TAVB_MAX_STREAM_QUERIES, nq), k, &s)) return rc;
+  unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
+  unsigned* const flags = best + (size_t)s.per * nm;
+  const float zeros[TAVB_MAX_STREAM_QUERIES] = {};
+  for (int q0 = 0; q0 < nq; q0 += (int)s.per) {
+    const int n = (int)std::min<int64_t>(s.per, nq - q0);
+    TAVB_HIP(hipMemsetAsync(c->d_topk.ptr, 0, tavb::topk_head_bytes(n, s.nb, s.rounds), c->stream));
+    TAVB_HIP(hipMemsetAsync(best, 0, (size_t)n * nm * sizeof(uint32_t), c->stream));
+    {
+      Timed tm(c, TAVB_KERNEL_MERGE);
+      hipError_t e = tavb::launch_message_keys_max(lists, n_lists, nq, k, query_major, q0, n, nm, best, flags, c->stream);
+      if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages merge launch failed: %s", hipGetErrorString(e));
+    }
+    if (int rc = top_messages_select(c, s, best, zeros, n, k, out_keys + (size_t)q0 * k, out_rounds + q0)) return rc;
+    Timed tm(c, TAVB_KERNEL_MERGE);
+    hipError_t e = tavb::launch_fill_flagged_rows(out_keys + (size_t)q0 * k, n, k, TAVB_KEY_PEER_FAILED, flags, c->stream);
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "top-messages merge fill launch failed: %s", hipGetErrorString(e));
   }
   return TAVB_OK;
 }
@@ -273,7 +303,7 @@ int search_top_messages_tile_impl(tavb_ctx* c, const float* d_q, int nq, int k, 
   const int64_t nm = c->n_messages;
   const int per_tile = (int)std::min<int64_t>(std::min(64, nq), std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
   ScorePlan s;
-  if (int rc = plan_top_messages(c, std::min(TAVB_MAX_STREAM_QUERIES, per_tile), k, &s)) return rc;
+  if (int rc = plan_top_messages(c, nm, std::min(TAVB_MAX_STREAM_QUERIES, per_tile), k, &s)) return rc;
   if (int rc = c->d_msg_best.reserve((size_t)per_tile * nm * sizeof(uint32_t))) return rc;
   unsigned* const best = reinterpret_cast<unsigned*>(c->d_msg_best.ptr);
   for (int q0 = 0; q0 < nq; q0 += per_tile) {
@@ -299,7 +329,7 @@ int search_scoped_top_messages_impl(tavb_ctx* c, const float* d_q, int nq, int k
   const int per = scoped_topk_per_pass(c);
   const int wave = scoped_wave_queries(c, per);
   ScorePlan s;
-  if (int rc = plan_top_messages(c, std::min(per, nq), k, &s)) return rc;
+  if (int rc = plan_top_messages(c, c->n_messages, std::min(per, nq), k, &s)) return rc;
   for (int w0 = 0; w0 < nq; w0 += wave) {
     const int wn = std::min(wave, nq - w0);
     ScopeWave w;
@@ -781,6 +811,26 @@ int tavb_search_top_messages_device(tavb_ctx* c, const float* dev_queries, int32
   if (empty) return fill_empty_keys(c, out, (int64_t)nq * k);
   if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
   if (int rc = search_top_messages_impl(c, dev_queries, nq, k, min_scores, dev_rows, n_rows, out, reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr))) return rc;
+  c->topk_rounds_pending = nq;
+  return TAVB_OK;
+}
+
+// ---- the top-messages lists of several shards -> one list per query (merge_top_messages_impl)
+int tavb_merge_top_messages_device(tavb_ctx* c, const tavb_key* dev_lists, int32_t n_lists, int32_t nq, int32_t k, int64_t n_messages, tavb_key* out_keys) {
+  if (int rc = check_ctx(c)) return rc;
+  const bool query_major = n_lists < 0;
+  if (query_major) n_lists = -n_lists;
+  if (n_lists < 1 || n_lists > 64 || nq < 1 || nq > 65535 || k < 1 || k > TAVB_MAX_LARGE_K)
+    return fail(TAVB_E_INVALID, "bad merge shape (1 .. 64 lists of 1 .. %d keys, 1 .. 65535 queries)", TAVB_MAX_LARGE_K);
+  if (n_messages < 1) return fail(TAVB_E_INVALID, "n_messages must be >= 1");
+  if (n_messages >= 0x7FFFFFFFll) return fail(TAVB_E_UNSUPPORTED, "top-messages keys hold message ordinals: n_messages must be < 2^31 - 1");
+  if (!dev_lists || !out_keys) return fail(TAVB_E_INVALID, "null argument");
+  DeviceGuard guard(c->device);
+  c->topk_rounds_pending = 0;
+  if (int rc = c->h_topk_rounds.reserve((size_t)nq * sizeof(int32_t))) return rc;
+  if (int rc = merge_top_messages_impl(c, reinterpret_cast<const u64_t*>(dev_lists), n_lists, nq, k, query_major, n_messages, reinterpret_cast<u64_t*>(out_keys),
+                                       reinterpret_cast<int32_t*>(c->h_topk_rounds.ptr)))
+    return rc;
   c->topk_rounds_pending = nq;
   return TAVB_OK;
 }

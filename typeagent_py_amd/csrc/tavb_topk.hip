@@ -17,7 +17,8 @@
 // ascending position, as everywhere in this library.
 //
 // Also here: the merge of long sorted lists (merge_topk_kernel), which puts the lists of several shards -- each the output of the passes
-// above -- together for k beyond what the register merge of tavb_misc.hip holds.
+// above -- together for k beyond what the register merge of tavb_misc.hip holds, and the first half of the merge of top-messages lists
+// (message_keys_max_kernel), whose keys are not unique across shards: one maximum per message, then the selection above.
 
 #include "tavb_device.h"
 #include "tavb_internal.h"
@@ -462,8 +463,55 @@ __global__ void __launch_bounds__(256) merge_topk_kernel(const u64* __restrict__
   }
 }
 
-__global__ void __launch_bounds__(256) fill_keys_kernel(u64* __restrict__ out, int64_t n, u64 value) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = value;
+// ---- merge of top-messages lists (launch_message_keys_max + the selection of a top-messages lookup): the lists of several shards carry
+// MESSAGE ordinals, and a message whose chunks lie on two shards stands in two lists with two scores -- the rank arithmetic above does not
+// hold.  Every non-zero key instead raises best[q][message] to its score, in the MessageMaxSink's encoding (1 + score bits over an array the
+// caller zeroed; a plain load in front skips the atomic where the slot holds as much already: slots only rise), and what follows is the
+// second half of a top-messages lookup as it stands (message_hist_kernel, refinement, compaction, finish).  A max does not depend on the
+// order of its operands: the result is deterministic.  A key whose message is at or beyond n_messages, or whose score bits exceed 1.0f's,
+// is dropped -- nothing is ever written outside [0, n_messages).  The first wave of every workgroup works out whether a list of the query
+// leads with TAVB_KEY_PEER_FAILED: such a query scatters nothing (its selection finds no message) and block 0 raises flags[q], by which
+// fill_keys_kernel writes the failure key into every slot of its row afterwards; flags[q] is written for every query, 0 or 1.
+// Query q of the launch is query q0 + q of the lists.
+__global__ void __launch_bounds__(256) message_keys_max_kernel(const u64* __restrict__ lists, int n_lists, int nq, int k, int query_major, int q0,
+                                                               int64_t n_messages, unsigned* __restrict__ best, unsigned* __restrict__ flags) {
+  __shared__ int failed_sh;
+  const int q = blockIdx.y;
+  const int gq = q0 + q;
+  const size_t stride = query_major ? (size_t)k : (size_t)nq * k;  // from one list of this query to the next
+  const u64* __restrict__ base = lists + (query_major ? (size_t)gq * n_lists * k : (size_t)gq * k);
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const u64 head = lane < n_lists ? base[(size_t)lane * stride] : 0ull;
+    const unsigned long long failed = __ballot(head == kPeerFailed);
+    if (lane == 0) {
+      failed_sh = failed != 0ull;
+      if (blockIdx.x == 0) flags[q] = failed != 0ull ? 1u : 0u;
+    }
+  }
+  __syncthreads();
+  if (failed_sh) return;  // (the whole workgroup)
+  const int n_keys = n_lists * k;
+  unsigned* __restrict__ b = best + (size_t)q * n_messages;
+#pragma unroll
+  for (int r = 0; r < kMergeTopkPerThread; ++r) {
+    const int e = (blockIdx.x * kMergeTopkPerThread + r) * 256 + threadIdx.x;
+    if (e >= n_keys) break;
+    const int l = e / k, i = e - l * k;
+    const u64 key = base[(size_t)l * stride + i];
+    if (key == 0ull) continue;  // padding
+    const uint32_t bits = (uint32_t)(key >> 32);
+    const int64_t m = (int64_t)(0xFFFFFFFFu - (uint32_t)key);
+    if (bits > kOneBits || m >= n_messages) continue;
+    const unsigned v = bits + 1u;
+    if (b[m] < v) atomicMax(&b[m], v);
+  }
+}
+
+// out[0 .. n) = value; with flags: only the rows [q * k, (q + 1) * k) whose flags[q] is set
+__global__ void __launch_bounds__(256) fill_keys_kernel(u64* __restrict__ out, int64_t n, u64 value, const unsigned* __restrict__ flags, int k) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    if (!flags || flags[i / k]) out[i] = value;
 }
 
 int pow2_at_least(int n) {
@@ -536,10 +584,29 @@ hipError_t launch_merge_topk(const unsigned long long* lists, int n_lists, int n
   return hipGetLastError();
 }
 
+hipError_t launch_message_keys_max(const unsigned long long* lists, int n_lists, int nq, int k, bool query_major, int q0, int n, int64_t n_messages,
+                                   unsigned* best, unsigned* flags, hipStream_t stream) {
+  if (!lists || !best || !flags || n_lists < 1 || n_lists > 64 || nq < 1 || k < 1 || k > TAVB_MAX_LARGE_K || q0 < 0 || n < 1 ||
+      n > TAVB_MAX_STREAM_QUERIES || q0 + n > nq || n_messages < 1 || n_messages >= 0x7FFFFFFFll)
+    return hipErrorInvalidValue;
+  const int per_block = 256 * kMergeTopkPerThread;
+  const int blocks = (n_lists * k + per_block - 1) / per_block;
+  hipLaunchKernelGGL(message_keys_max_kernel, dim3(blocks, n), dim3(256), 0, stream, lists, n_lists, nq, k, query_major ? 1 : 0, q0, n_messages, best, flags);
+  return hipGetLastError();
+}
+
 hipError_t launch_fill_keys(unsigned long long* out, int64_t n, unsigned long long value, hipStream_t stream) {
   if (!out || n < 1) return hipErrorInvalidValue;
   const int blocks = n > 1024 * 256 ? 1024 : (int)((n + 255) / 256);
-  hipLaunchKernelGGL(fill_keys_kernel, dim3(blocks), dim3(256), 0, stream, out, n, value);
+  hipLaunchKernelGGL(fill_keys_kernel, dim3(blocks), dim3(256), 0, stream, out, n, value, static_cast<const unsigned*>(nullptr), 1);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_flagged_rows(unsigned long long* out, int nq, int k, unsigned long long value, const unsigned* flags, hipStream_t stream) {
+  if (!out || !flags || nq < 1 || k < 1) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)nq * k;
+  const int blocks = n > 1024 * 256 ? 1024 : (int)((n + 255) / 256);
+  hipLaunchKernelGGL(fill_keys_kernel, dim3(blocks), dim3(256), 0, stream, out, n, value, flags, k);
   return hipGetLastError();
 }
 

@@ -18,6 +18,10 @@ on all shards before anything is waited for) into one reused pinned buffer, merg
 Masked lookups (`mask_to_rows`, `search_masked`): the mask is cut at the shard bounds, every slice is expanded on its shard's device
 (`tavb_mask_expand`) into shard-local rows that stay there, and a batch of queries is ONE `tavb_search_subset_batch_device` per shard --
 keys carrying global ordinals into the same pinned buffer, enqueued everywhere before anything is waited for -- merged on the host.
+
+Top-k distinct messages (`set_row_messages`, `search_top_messages`): every shard holds its slice of the row -> message map with the global
+message count, a batch is ONE `tavb_search_top_messages_device` per shard -- the shard's own best k messages, keys carrying global message
+ordinals -- and the lists are merged on the host by `tavb_merge_top_messages_host`: one maximum per message, then the best k.
 """
 
 from __future__ import annotations
@@ -337,6 +341,48 @@ class DeviceGroup:
         if len(parts) == 1:
             return _native.decode_keys(keys[0])
         return _native.decode_keys(_native.merge_keys(keys) if k <= _native.MAX_FUSED_K else _native.merge_topk_keys(keys))
+
+    # -- top-k distinct messages (tavb_search_top_messages_device per shard + tavb_merge_top_messages_host) ---------------------------
+    @_locked
+    def set_row_messages(self, row_to_message: np.ndarray, n_messages: int | None = None) -> None:
+        """chunk row -> message ordinal for every row of the index (-1: none): every active shard gets its slice under the current
+        `bounds` with the GLOBAL n_messages (None: the map's largest ordinal + 1) -- message ordinals stay global, nothing is remapped.
+        The caller sets it again whenever the bounds change (`row_messages_bounds` says which bounds the slices were cut by)."""
+        m = np.ascontiguousarray(row_to_message, dtype=np.int64).reshape(-1)
+        if len(m) < self.rows:
+            raise ValueError(f"the row -> message map covers {len(m)} rows, the index has {self.rows}")
+        if n_messages is None:
+            n_messages = int(m[: self.rows].max()) + 1 if self.rows else 0
+        self.n_messages = max(int(n_messages), 0)
+        for e, lo, hi in self._active():
+            e.set_row_messages(m[lo:hi], self.n_messages)
+        self.row_messages_bounds = tuple(self.bounds)
+
+    def top_messages_capable(self) -> bool:
+        """Every engine is a real `_native.Engine` (has the device-resident top-messages call) with the "top_messages" option on."""
+        return all(hasattr(e, "search_top_messages_device") and e.get_option("top_messages") != 0 for e in self.engines)
+
+    @_locked
+    def search_top_messages(self, queries, k: int, thrs, handles=None):
+        """`Engine.search_top_messages` over the shards: queries f32 [nq, dim]; thrs float32 [nq] (or one for all); 1 <= k <= MAX_LARGE_K;
+        handles: None, or `mask_to_rows` under the current bounds -> (message ordinals [nq,k], scores [nq,k], counts [nq]).  Every shard
+        returns its own best k messages (ONE tavb_search_top_messages_device per shard, all enqueued before any is waited for; under a
+        mask only the shards with a handle are visited): a message of the whole-corpus top k is in the top k of the shard that holds its
+        best row, with that score, so one maximum per message over the lists and the best k of those (tavb_merge_top_messages_host) is
+        the whole-corpus answer.  Needs `set_row_messages` under the current bounds."""
+        a = _native.batch_queries(queries, self.dim)
+        nq = a.shape[0]
+        t = _native.batch_thresholds(thrs, nq)
+        if handles is None:
+            parts = [(g, e, None) for g, e in enumerate(self.engines) if self.bounds[g + 1] > self.bounds[g]]
+        else:
+            if len(handles) != len(self.engines):
+                raise ValueError("one handle (or None) per device")
+            parts = [(g, e, handles[g]) for g, e in enumerate(self.engines) if handles[g] is not None and self.bounds[g + 1] > self.bounds[g]]
+        if not parts or nq == 0:
+            return np.zeros((nq, k), np.int64), np.zeros((nq, k), np.float32), np.zeros(nq, np.int32)
+        keys = self._on_all_parts(parts, a, k, lambda part, dq, out: part[1].search_top_messages_device(dq, k, t, out_keys=out, dev_rows=part[2]))
+        return _native.decode_keys(keys[0] if len(parts) == 1 else _native.merge_top_messages_keys(keys))
 
     @_locked
     def search_all(self, q, thr: np.float32, max_out: int | None = None, subset_rows=None):

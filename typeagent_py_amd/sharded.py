@@ -33,6 +33,10 @@ a `VectorBase(devices=[...])` device group serves them through its emit-all rout
 
 Masked lookups: every rank expands ITS slice of the mask on its device once (`DeviceShardBackend.mask_to_device`, tavb_mask_expand), a
 batch of queries is one `tavb_search_subset_batch_device` per rank -- keys carrying global ordinals -- and ONE exchange of the [nq, k] lists.
+
+Top-k distinct messages (`set_row_messages`, `lookup_top_messages_by_embedding(s)`): every rank holds its slice of ONE global row -> message
+map with the global message count, a batch is `tavb_search_top_messages_allgather` -- the rank's own best k messages, the all-gather, one
+maximum per message and the best k of those -- and every rank returns the whole-corpus answer.
 """
 
 from __future__ import annotations
@@ -280,6 +284,68 @@ class DeviceShardBackend:
         self._keep = (dq, handle, keys)  # alive until the next call (the kernels run asynchronously)
         return keys
 
+    # -- top-k distinct messages: this rank's slice of the global row -> message map, and its own best k messages -------------------------
+    def set_row_messages(self, local_map: np.ndarray, n_messages: int) -> None:
+        """This rank's slice of the row -> message map (message ordinals are global: no remap) with the GLOBAL n_messages."""
+        with self.torch.cuda.stream(self.stream):
+            self.engine.set_row_messages(local_map, n_messages)
+        self.n_messages = int(n_messages)
+
+    def _empty_rows(self):
+        buf = getattr(self, "_no_rows", None)
+        if buf is None:
+            with self.torch.cuda.stream(self.stream):
+                buf = self._no_rows = self.torch.empty(0, dtype=self.torch.int32, device=self.torch.device("cuda", self.device))
+        return buf
+
+    def local_top_messages(self, queries: np.ndarray, k: int, thrs, handle=None, masked: bool = False):
+        """A batch of queries (host float32 [nq, dim]; thrs: one threshold per query) over this rank's shard, or, with `masked`, over a
+        handle of `mask_to_device` (None: this rank's part of the mask is empty -> zero keys): ONE tavb_search_top_messages_device on
+        the backend's stream -> keys [nq, k] carrying GLOBAL message ordinals.  Asynchronous."""
+        torch = self.torch
+        nq = int(np.shape(queries)[0])
+        if (masked and handle is None) or self.engine.rows == 0:
+            with torch.cuda.stream(self.stream):
+                return torch.zeros((nq, k), dtype=torch.int64, device=torch.device("cuda", self.device))
+        dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
+        with torch.cuda.stream(self.stream):
+            keys = self.engine.search_top_messages_device(dq, k, thrs, dev_rows=handle if masked else None)
+        self._keep = (dq, handle, keys)  # alive until the next call (the kernels run asynchronously)
+        return keys
+
+    def merge_top_messages(self, gathered):
+        """tensor int64 [world, nq, k] of top-messages lists -> [nq, k]: one maximum per message, then the best k (tavb_merge_top_messages_device)"""
+        if not getattr(self, "n_messages", 0):
+            raise RuntimeError("set_row_messages() first")
+        with self.torch.cuda.stream(self.stream):
+            return self.engine.merge_top_messages_device(gathered, self.n_messages)
+
+    def search_top_messages_allgather(self, queries: np.ndarray, k: int, thrs, handle=None, masked: bool = False):
+        """This rank's best k messages -> ncclAllGather -> the top-messages merge inside libtavb (tavb_search_top_messages_allgather), merged
+        keys written into a reused pinned host buffer: -> int64 [nq, k] (host view, valid until the next call)."""
+        dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
+        shape = (int(dq.shape[0]), int(k))
+        pinned = self._pinned.get(shape)
+        if pinned is None:
+            pinned = self._pinned[shape] = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
+        rows = None if not masked else (self._empty_rows() if handle is None else handle)
+        with self.torch.cuda.stream(self.stream):
+            self.engine.search_top_messages_allgather(dq, k, thrs, out_keys=pinned, dev_rows=rows)
+        self.engine.synchronize()
+        return pinned.numpy()
+
+    def join_failed_top_messages(self, nq: int, k: int, n_messages: int) -> None:
+        """What a rank does whose preparation of `search_top_messages_allgather` raised: the same collectives with failure lists.  The
+        library refuses the call, before anything collective, on a context that was never told the message count (an error every rank
+        makes alike there); a rank whose upload of its slice of the map is what failed has none yet, so it sets an empty map with the
+        global count first -- the next lookup uploads the slice again."""
+        with self.torch.cuda.stream(self.stream):
+            if getattr(self, "n_messages", 0) != int(n_messages):
+                self.engine.set_row_messages(np.zeros(0, dtype=np.int32), int(n_messages))
+                self.n_messages = int(n_messages)
+            self.engine.allgather_merge_top_messages(self.failed_lists(nq, k))
+        self.engine.synchronize()
+
     def local_survivors(self, query: np.ndarray, thr: float):
         """every row of this shard with score >= thr -> (global ordinals int64, scores float32), unsorted (one emit-all pass)."""
         return self.engine.search_all(np.ascontiguousarray(query, dtype=np.float32), np.float32(thr), None)
@@ -404,8 +470,27 @@ class ShardedSearcher:
             raise failure
         return merged
 
-    def exchange(self, local_keys):
-        """this rank's sorted lists [nq, k] (global ordinals / positions) -> the lists merged over all ranks, on every rank."""
+    def _merge_top_messages(self, gathered):
+        """[world, nq, k] top-messages lists -> [nq, k] on the backend's device: the backend's own merge, or the host merge of libtavb"""
+        if hasattr(self.backend, "merge_top_messages"):
+            return self.backend.merge_top_messages(gathered)
+        host = np.ascontiguousarray(self.backend.to_host(gathered)).view(np.uint64)
+        return self.backend.keys_to_device(_native.merge_top_messages_keys(host))
+
+    def exchange(self, local_keys, messages: bool = False):
+        """this rank's sorted lists [nq, k] (global ordinals / positions) -> the lists merged over all ranks, on every rank.  messages: the
+        keys carry MESSAGE ordinals -- one message may stand in several ranks' lists: one maximum per message, then the best k."""
+        if messages:
+            if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
+                return self.backend.engine.allgather_merge_top_messages(local_keys)
+            if self.gather_fn is not None:
+                return self._merge_top_messages(self.gather_fn(local_keys))
+            if self.world == 1 and not (self.always_collective and self.dist.is_initialized()):
+                return local_keys
+            nq, k = local_keys.shape
+            gathered = self.backend.empty_gather(self.world, nq, k)
+            self.dist.all_gather_into_tensor(gathered.view(-1), local_keys.contiguous().view(-1), group=self.group)
+            return self._merge_top_messages(gathered)
         if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
             if local_keys.shape[1] <= _native.MAX_FUSED_K:
                 return self.backend.engine.allgather_merge(local_keys)
@@ -447,6 +532,8 @@ class ShardedVectorBase:
         self.searcher = ShardedSearcher(backend, group=group)
         self._storage_dtype = backend.storage_dtype() if hasattr(backend, "storage_dtype") else "fp32"
         self._subset_cache = None  # (caller's subset object, private copy, total rows, ordinals int64, the backend's handle) of the last subset lookup
+        self._row_messages = None  # the GLOBAL chunk row -> message map (set_row_messages), identical on every rank
+        self._row_messages_layout = None  # the (total, offset, local) this rank's slice of it was last uploaded under
 
     def __len__(self) -> int:
         return self.total_rows
@@ -612,7 +699,7 @@ class ShardedVectorBase:
         ords, sc, cnt = self._exchange_or_fail(local_lists, 1, k)
         return [ScoredInt(int(o), float(s_)) for o, s_ in zip(ords[0, : cnt[0]].tolist(), sc[0, : cnt[0]].tolist())]
 
-    def _exchange_or_fail(self, local_lists, nq: int, k: int):
+    def _exchange_or_fail(self, local_lists, nq: int, k: int, messages: bool = False):
         """The collective forms beside the plain lookup (subset, predicate): `local_lists()` -> this rank's [nq, k] keys -> exchange -> decoded
         merged lists.  The failure protocol of `ShardedSearcher.search_keys` / tavb_search_allgather: a rank whose local part raises -- the
         caller's predicate included -- still joins the exchange, with PEER_FAILED_KEY lists, then raises ITS error; the others raise
@@ -625,7 +712,7 @@ class ShardedVectorBase:
                 raise
             failure = exc
             local = self.backend.failed_lists(nq, k)
-        merged = self.backend.to_host(self.searcher.exchange(local))
+        merged = self.backend.to_host(self.searcher.exchange(local, messages=True) if messages else self.searcher.exchange(local))
         if failure is not None:
             raise failure
         if merged.size and (np.asarray(merged).reshape(merged.shape[0], -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
@@ -736,6 +823,18 @@ class ShardedVectorBase:
             raise ValueError(f"mask covers {allowed.rows} rows, the index has {self.total_rows}")
         return allowed
 
+    def _mask_part(self, mask, backend):
+        """This rank's part of a device-backed mask as the backend's handle (None: an empty part).  A handle cut under another layout
+        (the rows were re-dealt since) is cut again from its packed bits: this rank's slice, expanded on its device.  May raise on ONE
+        rank: call it inside the local part of a collective."""
+        layout = (self.total_rows, self.row_offset, self.local_rows)
+        if mask.layout != layout:
+            lo, n = self.row_offset, self.local_rows
+            part = np.unpackbits(mask.bits.view(np.uint8)[lo // 8 : (lo + n + 7) // 8], bitorder="little")[lo % 8 : lo % 8 + n]
+            mask.dev_rows = backend.mask_to_device(part.astype(np.bool_))
+            mask.layout = layout
+        return mask.dev_rows
+
     def fuzzy_lookup_embeddings_masked(self, embeddings, allowed, max_hits: int | None = None, min_score=None):
         """≡ [fuzzy_lookup_embedding_in_subset(e, np.flatnonzero(allowed), max_hits, min_score) for e in embeddings] (`min_score`: one
         threshold, or one per query); `allowed`: a mask or the `RowMask` made from one.  With a backend that offers the masked route the
@@ -758,15 +857,9 @@ class ShardedVectorBase:
             if mask.bits is not None:
                 if mask.count == 0 or nq == 0 or self.total_rows == 0:
                     return [[] for _ in range(nq)]  # (the global count is the same on every rank: nobody waits in an exchange)
-                layout = (self.total_rows, self.row_offset, self.local_rows)
 
                 def local_lists():
-                    if mask.layout != layout:  # the rows were re-dealt since: this rank's slice of the packed mask, expanded again
-                        lo, n = self.row_offset, self.local_rows
-                        part = np.unpackbits(mask.bits.view(np.uint8)[lo // 8 : (lo + n + 7) // 8], bitorder="little")[lo % 8 : lo % 8 + n]
-                        mask.dev_rows = backend.mask_to_device(part.astype(np.bool_))
-                        mask.layout = layout
-                    return backend.local_search_masked(q, mask.dev_rows, k, thr)
+                    return backend.local_search_masked(q, self._mask_part(mask, backend), k, thr)
 
                 from .vectorbase import _scored_lists
 
@@ -780,6 +873,120 @@ class ShardedVectorBase:
         if e.ndim != 1:
             raise ValueError(f"Expected 1D embedding, got {e.ndim}D")
         return self.fuzzy_lookup_embeddings_masked(e[None, :], allowed, max_hits, min_score)[0]
+
+    # ---- top-k distinct messages ------------------------------------------------------------------------------------------------------
+    def set_row_messages(self, row_to_message) -> None:
+        """The GLOBAL chunk row -> message ordinal map (-1: none), identical on every rank; n_messages = its largest ordinal + 1 over the
+        index' rows.  With a backend that has an engine this rank's slice is uploaded before the next top-messages lookup, and again
+        whenever the layout changes (`rebalance`, appends).  No collective."""
+        self._row_messages = np.array(row_to_message, dtype=np.int64).reshape(-1)  # a snapshot: never an alias of the caller's array
+        self._row_messages_layout = None
+
+    def _n_messages(self) -> int:
+        held = self._row_messages[: self.total_rows]
+        return max(int(held.max()) + 1, 0) if len(held) else 0
+
+    def _sync_row_messages(self) -> None:
+        """this rank's slice of the map on its device, under the current layout (may raise on ONE rank: call it inside the local part)"""
+        layout = (self.total_rows, self.row_offset, self.local_rows)
+        if self._row_messages_layout != layout and hasattr(self.backend, "set_row_messages"):
+            self.backend.set_row_messages(self._row_messages[self.row_offset : self.row_offset + self.local_rows], self._n_messages())
+        self._row_messages_layout = layout
+
+    @staticmethod
+    def _message_keys(msgs: np.ndarray, scs: np.ndarray, k: int) -> np.ndarray:
+        """(message ordinal, float32 score) pairs -> the sorted, zero-padded top-messages list uint64 [k]: per message its best score"""
+        keep = msgs >= 0
+        keys = (scs[keep].astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - msgs[keep].astype(np.uint64))
+        keys = np.sort(keys)[::-1]
+        _, first = np.unique(keys & np.uint64(0xFFFFFFFF), return_index=True)  # a message's first key in that order is its largest
+        best = keys[np.sort(first)][:k]
+        out = np.zeros(k, dtype=np.uint64)
+        out[: len(best)] = best
+        return out
+
+    def lookup_top_messages_by_embeddings(self, embeddings, max_messages: int | None = None, threshold_score=None, allowed=None):
+        """`VectorBase.lookup_top_messages_by_embeddings` over the row-sharded corpus (collective: every rank passes the same arguments and
+        gets the same lists): per query the `max_messages` (None -> 10; 1 .. 16384) messages with the highest best score among the rows
+        that pass `threshold_score` (one, or one per query) and lie inside `allowed` (a mask or a `RowMask` of this index; None: every
+        row), sorted by (score descending, message ordinal ascending).  Needs `set_row_messages`.  Every rank returns ITS best
+        `max_messages` messages -- a message of the whole-corpus answer is among those of the rank that holds its best row, with that
+        score -- and ONE exchange per batch merges them: one maximum per message, then the best `max_messages`.  With the library's own
+        communicator that is one C call (tavb_search_top_messages_allgather); with `gather_fn` or torch.distributed the backend's
+        `local_top_messages` / `merge_top_messages` around the exchange; a backend without them: `local_survivors` and a collapse on the
+        host.  A rank whose local part raises joins the exchange with failure lists and raises its own error; the others raise
+        `PeerFailedError`."""
+        from .vectorbase import _scored_lists
+
+        q = np.asarray(embeddings, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
+        nq = len(q)
+        per_query = threshold_score is not None and not np.isscalar(threshold_score) and np.ndim(threshold_score) == 1
+        if per_query and len(threshold_score) != nq:
+            raise ValueError(f"Number of thresholds {len(threshold_score)} does not match number of embeddings {nq}")
+        k = 10 if max_messages is None else int(max_messages)
+        _check_k(k, "max_messages")  # (before anything collective: every rank makes the same call)
+        if self._row_messages is None:
+            raise RuntimeError("set_row_messages() first")
+        if len(self._row_messages) < self.total_rows:
+            raise ValueError(f"the row -> message map covers {len(self._row_messages)} rows, the index has {self.total_rows}")
+        mask = None if allowed is None else self._resolve_mask(allowed)
+        # (global quantities only: every rank decides alike, nobody waits in an exchange)
+        if nq == 0 or self.total_rows == 0 or self._n_messages() == 0 or (mask is not None and mask.count == 0):
+            return [[] for _ in range(nq)]
+        each = list(threshold_score) if per_query else [threshold_score] * nq
+        thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in each], dtype=np.float32)
+        backend = self.backend
+        on_device = hasattr(backend, "local_top_messages") and (mask is None or mask.bits is not None)
+
+        def handle():
+            return None if mask is None else self._mask_part(mask, backend)
+
+        if on_device and getattr(backend, "native_comm", False) and self.searcher.gather_fn is None and hasattr(backend, "search_top_messages_allgather"):
+            try:  # the product path: one C call; what can fail on ONE rank before it still joins the collectives
+                self._sync_row_messages()
+                rows = handle()
+            except Exception:  # noqa: BLE001
+                self._row_messages_layout = None
+                backend.join_failed_top_messages(nq, k, self._n_messages())
+                raise
+            keys = backend.search_top_messages_allgather(q, k, thr, rows, masked=mask is not None)
+            if keys.size and (np.asarray(keys).reshape(nq, -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
+                raise PeerFailedError("a rank of the collective lookup failed in its local search: the merged lists are missing its shard")
+            return _scored_lists(*_native.decode_keys(keys), k)
+
+        if on_device:
+            def local_lists():
+                self._sync_row_messages()
+                return backend.local_top_messages(q, k, thr, handle(), masked=mask is not None)
+        else:
+            flat = None if mask is None else mask.flat()
+
+            def local_lists():
+                lo, hi = self.row_offset, self.row_offset + self.local_rows
+                allowed_rows = None if flat is None else flat[(flat >= lo) & (flat < hi)]
+                local = np.zeros((nq, k), dtype=np.uint64)
+                for i in range(nq):
+                    if self.local_rows == 0 or (allowed_rows is not None and len(allowed_rows) == 0):
+                        continue
+                    ids, scs = backend.local_survivors(q[i], thr[i])
+                    ids, scs = np.asarray(ids, dtype=np.int64), np.asarray(scs, dtype=np.float32)
+                    if allowed_rows is not None:
+                        keep = np.isin(ids, allowed_rows)
+                        ids, scs = ids[keep], scs[keep]
+                    local[i] = self._message_keys(self._row_messages[ids], scs, k)
+                return backend.keys_to_device(local)
+
+        msgs, scs, cnts = self._exchange_or_fail(local_lists, nq, k, messages=True)
+        return _scored_lists(msgs, scs, cnts, k)
+
+    def lookup_top_messages_by_embedding(self, embedding, max_messages: int | None = None, threshold_score: float | None = None, allowed=None):
+        """The one-query form of `lookup_top_messages_by_embeddings`."""
+        e = np.asarray(embedding, dtype=np.float32)
+        if e.ndim != 1:
+            raise ValueError(f"Expected 1D embedding, got {e.ndim}D")
+        return self.lookup_top_messages_by_embeddings(e[None, :], max_messages, threshold_score, allowed)[0]
 
     def lookup_messages_by_embedding(self, embedding, row_to_message, max_matches: int | None = None, threshold_score: float | None = None, accept=None):
         """`SqliteMessageTextIndex.lookup_by_embedding` / `lookup_in_subset_by_embedding` (storage/sqlite/messageindex.py:296-326, 182-257)

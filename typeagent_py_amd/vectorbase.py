@@ -1335,6 +1335,18 @@ class VectorBase:
             self._row_messages_rows = self._count
         return eng
 
+    def _messages_group(self, eng, max_messages: int):
+        """The device group `eng` with the map's slices synced to its current bounds, when it serves top-messages lookups itself
+        (`DeviceGroup.search_top_messages`: every engine real, option "top_messages" on, 1 <= max_messages <= 16384); else None."""
+        if not (hasattr(eng, "top_messages_capable") and hasattr(eng, "search_top_messages") and 1 <= max_messages <= _native.MAX_LARGE_K
+                and eng.top_messages_capable()):
+            return None
+        if self._row_messages_rows != self._count or getattr(eng, "row_messages_bounds", None) != tuple(eng.bounds):
+            held = self._row_messages[: self._count]
+            eng.set_row_messages(held, int(held.max()) + 1 if self._count else 0)
+            self._row_messages_rows = self._count
+        return eng
+
     def _host_rerank(self, hits, max_matches, accept=None) -> list[ScoredInt]:
         best: dict[int, float] = {}
         for h in hits:
@@ -1601,10 +1613,14 @@ class VectorBase:
 
         On a single-GPU engine with 1 <= max_messages <= 16384 (and a mask that holds its row list on the device) it is ONE submission
         (tavb_search_top_messages, engine option "top_messages", default 1): per eight queries one corpus pass that keeps one maximum per
-        message on the device, then the exact device top-k over the messages.  Everything else -- max_messages 0 (every message) or
-        beyond 16384, device groups, test doubles, "top_messages" = 0 -- takes the all-survivor lookup (`fuzzy_lookup_embedding(s)` /
-        `_masked` at max_hits = 0) and collapses on the host, with the same result.  One scope per query in one submission is
-        `lookup_top_messages_by_embeddings_scoped`.  Not served here: `FusedIndexQuery`.
+        message on the device, then the exact device top-k over the messages.  On a device group (`devices=[...]`) under the same
+        conditions every shard runs that call over its rows (or its part of the mask) and returns its own best `max_messages` messages
+        with global message ordinals; the lists are merged on the host, one maximum per message and then the best `max_messages`
+        (`DeviceGroup.search_top_messages`, tavb_merge_top_messages_host) -- the single-GPU answer, bit for bit where the shards' rows
+        are a multiple of 16 bytes.  Everything else -- max_messages 0 (every message) or beyond 16384, test doubles, "top_messages" = 0
+        -- takes the all-survivor lookup (`fuzzy_lookup_embedding(s)` / `_masked` at max_hits = 0) and collapses on the host, with the
+        same result.  One scope per query in one submission is `lookup_top_messages_by_embeddings_scoped`.  Not served here:
+        `FusedIndexQuery`.
 
         Engine option "top_messages_tile" (default 0) moves the native route onto the 32/64-query MFMA tile
         (tavb_search_top_messages_tile: one corpus pass per 64 queries instead of one per eight; rows of a multiple of 64 bytes; a mask
@@ -1625,6 +1641,13 @@ class VectorBase:
         if eng is not None and self._top_messages_native(eng, max_hits) and (mask is None or (self._masked_native(eng) and mask.dev_rows is not None)):
             msgs, scs, cnts = eng.search_top_messages(queries, max_hits, thr, dev_rows=None if mask is None else mask.dev_rows)
             return _scored_lists(msgs, scs, cnts, max_hits)
+        if eng is None and (mask is None or mask.shards is not None):
+            group = self._sync_device()
+            if (mask is None or self._masked_group(group)) and self._messages_group(group, max_hits) is not None:
+                if mask is not None and mask.bounds != tuple(group.bounds):  # (as `fuzzy_lookup_embeddings_masked` cuts a handle again)
+                    mask.shards, _, mask.bounds = group._rows_to_handles(mask.flat())
+                msgs, scs, cnts = group.search_top_messages(queries, max_hits, thr, handles=None if mask is None else mask.shards)
+                return _scored_lists(msgs, scs, cnts, max_hits)
         min_score = threshold_score if per_query is None else per_query
         lists = self.fuzzy_lookup_embeddings(queries, 0, min_score) if mask is None else self.fuzzy_lookup_embeddings_masked(queries, mask, 0, min_score)
         return [self._collapse_to_messages(hits, max_hits) for hits in lists]
@@ -1659,8 +1682,9 @@ class VectorBase:
         for bit those of the per-query calls: message ordinals, float32 scores and counts.  A query whose scope is empty gets an empty
         answer and takes no slot.  `engine.get_option("masked_route")` is then 9.
 
-        Everything else loops over `lookup_top_messages_by_embedding`: max_messages 0 or beyond 16384 (the host collapse), device groups,
-        `ShardedVectorBase`, test doubles, either option at 0, and a handle without a device mask.  Not served here: `FusedIndexQuery`,
+        Everything else loops over `lookup_top_messages_by_embedding`: max_messages 0 or beyond 16384 (the host collapse), device groups
+        (every iteration then takes the group's own top-messages route), test doubles, either option at 0, and a handle without a
+        device mask.  Not served here: `FusedIndexQuery`,
         the MFMA tiles; queries are not reordered by how much their scopes overlap -- only identical handles are grouped."""
         queries, max_hits, thr, per_query = self._batch_args(embeddings, max_messages, threshold_score)
         self._check_row_messages()
