@@ -403,7 +403,17 @@ int tavb_search_subset_after(tavb_ctx* ctx, const float* query_host, const int64
 /* ---- asynchronous device-resident lookups (sharding, benchmarking) -------------- */
 /* Queries already on the device (float32 [nq, dim]); writes nq sorted lists of k keys to
  * dev_out_keys [nq, k] on the context's stream and returns without synchronising.
- * Keys carry ordinal_base + row (must stay below 2^32 - 1). */
+ * Keys carry ordinal_base + row (must stay below 2^32 - 1).
+ *
+ * PRECONDITION on the queries of EVERY *_device entry point that can take an MFMA tile route (tavb_search_device, tavb_search_allgather,
+ * tavb_search_masked_device, tavb_search_masked_wide_device, tavb_search_scoped_tile_device, tavb_search_scoped_wide_device,
+ * tavb_search_top_messages_tile_device): every element must round to a FINITE fp16 value, i.e. be finite with magnitude < 65520.  The
+ * tiles see a query through fp16 planes; an element beyond that becomes an infinity there and that query's answer is unspecified (rows
+ * may be missing).  The library never sees device-resident queries on the host and does not check this.  The host-synchronous entry
+ * points (queries_host) do check, while they stage the queries, and run a batch that holds such an element -- or +-inf / NaN -- on the
+ * streaming kernels: their answers are the fp32 answers for every query.  The *_device forms that only run the streaming kernels
+ * (tavb_search_topk_device, tavb_search_subset_batch_device, tavb_search_scoped_device, tavb_search_top_messages_device) multiply fp32
+ * queries and have no such precondition. */
 int tavb_search_device(tavb_ctx* ctx, const float* dev_queries, int32_t nq, int32_t k, float min_score,
                        tavb_key* dev_out_keys);
 

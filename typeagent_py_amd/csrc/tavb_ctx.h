@@ -236,6 +236,7 @@ struct tavb_ctx {
   int64_t direct_group_max_nq = TAVB_MAX_GROUPED_QUERIES;  // option: biggest batch that may take it (0 / 1 = never: batches of up to 8 keep the plain form, bigger ones the tiles)
   int64_t direct_group = 0;                         // option: queries per group, 1 / 2 / 4 / 8, taken whatever the cost model says (0 = plan_direct_group)
   int64_t direct_group_wgs = 0;                     // option: most workgroups of such a launch (row workgroups x groups); 0 = plan_direct_group (256 or 512)
+  bool staged_overflow = false;                     // set by stage_queries_host: a staged query holds an element whose fp16 rounding is not finite (staged_overflow())
   bool dispatch_no_group = false;                   // set by tavb_search_batch around its fall-through: the host-synchronous cost model already said no
   int64_t direct_group_keys = 32768;                // option: most keys the lists of such a launch may hold (nq x workgroups-per-group x k; 256 KiB over PCIe)
 
@@ -445,6 +446,19 @@ int search_scoped_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
 // does both.  stage_subset: one query and a subset's rows (int64 on the host, checked against the corpus; int32 at *d_rows), both copies enqueued;
 // the caller has checked 0 < n_subset < 2^31 - 1.
 int stage_queries_host(tavb_ctx* c, const float* queries_host, int nq, const float** d_q);
+// Queries the tiles must not multiply.  The 32/64-query tile on fp16 rows, both exact fallbacks and the filter see a query through fp16
+// planes (hi = fp16(q), lo = fp16(q - hi)): a finite element of magnitude 65520 or more becomes an infinite high part, and two of them,
+// or one over a zero of a row, make a NaN where the fp32 dot product is finite.  A query that holds +-inf or NaN itself leaves the tiles
+// too: a dot product of -inf clips to the score 0.0, which passes min_score 0, but never passes the tiles' admission test on the raw dot
+// product.  stage_queries_host looks at every element while it copies
+// (the only place the host sees the queries; no launch, no synchronise) and the routes ask here: true when d_q points into the staging
+// buffer of a batch that holds such a query -- the whole batch then runs on the streaming kernels, whose answer is the definition.
+// Queries a caller keeps on the device are never seen: their elements must round to finite fp16 values (include/tavb.h).
+inline bool staged_overflow(const tavb_ctx* c, const float* d_q) {
+  const char* const p = reinterpret_cast<const char*>(d_q);
+  const char* const b = reinterpret_cast<const char*>(c->d_queries.ptr);
+  return c->staged_overflow && b != nullptr && p >= b && p < b + c->d_queries.cap;
+}
 hipError_t submit_queries(tavb_ctx* c, int nq);
 int stage_queries(tavb_ctx* c, const float* queries_host, int nq, const float** d_q);
 int stage_subset(tavb_ctx* c, const float* query_host, const int64_t* rows_host, int64_t n_subset, const float** d_q, const int32_t** d_rows);

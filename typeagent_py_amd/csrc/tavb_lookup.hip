@@ -44,6 +44,16 @@ int stage_queries_host(tavb_ctx* c, const float* queries_host, int nq, const flo
   if (int rc = c->h_stage.reserve(qbytes)) return rc;
   if (int rc = c->d_queries.reserve(qbytes)) return rc;
   parallel_copy(c->h_stage.ptr, queries_host, qbytes);  // (a 1024 x 1536 batch is 6 MiB: 0.6 ms on one core, a few threads from 4 MiB up)
+  // staged_overflow (tavb_ctx.h): an element of magnitude >= 65520 rounds to an fp16 infinity; +-inf and NaN lie above it.  One compare
+  // per element on the bits without the sign, right behind the copy; an OR reduction with no branch, so the compiler may vectorise it.
+  const uint32_t* const bits = reinterpret_cast<const uint32_t*>(c->h_stage.ptr);
+  const size_t n = (size_t)nq * c->dim;
+  uint32_t over = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t a = bits[i] & 0x7FFFFFFFu;
+    over |= (uint32_t)(a >= 0x477FF000u);  // 65520.0f and beyond
+  }
+  c->staged_overflow = over != 0;
   *d_q = reinterpret_cast<const float*>(c->d_queries.ptr);
   return TAVB_OK;
 }
@@ -76,6 +86,7 @@ int stage_subset(tavb_ctx* c, const float* query_host, const int64_t* rows_host,
   }
   char* q_stage = reinterpret_cast<char*>(c->h_stage.ptr) + qoff;
   memcpy(q_stage, query_host, qbytes);
+  c->staged_overflow = false;  // (one query over a row list: the streaming kernels, fp32 throughout)
   TAVB_HIP(hipMemcpyAsync(c->d_rows.ptr, c->h_stage.ptr, rbytes, hipMemcpyHostToDevice, c->stream));
   TAVB_HIP(hipMemcpyAsync(c->d_queries.ptr, q_stage, qbytes, hipMemcpyHostToDevice, c->stream));
   *d_q = reinterpret_cast<const float*>(c->d_queries.ptr);

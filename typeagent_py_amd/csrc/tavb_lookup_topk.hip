@@ -301,6 +301,11 @@ int merge_top_messages_impl(tavb_ctx* c, const u64_t* lists, int n_lists, int nq
 int search_top_messages_tile_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* dev_bits,
                                   int64_t first_row, int64_t last_row, u64_t* out_keys, int32_t* out_rounds) {
   const int64_t nm = c->n_messages;
+  if (staged_overflow(c, d_q)) {  // (tavb_ctx.h) the row scan's forms: every query under the one mask, or over the whole corpus
+    if (!dev_bits) return search_top_messages_impl(c, d_q, nq, k, min_scores, nullptr, 0, out_keys, out_rounds);
+    const std::vector<const uint32_t*> masks((size_t)nq, dev_bits);
+    return search_scoped_top_messages_impl(c, d_q, nq, k, min_scores, masks.data(), out_keys, out_rounds);
+  }
   const int per_tile = (int)std::min<int64_t>(std::min(64, nq), std::max<int64_t>(1, c->topk_scores_bytes / (nm * (int64_t)sizeof(uint32_t))));
   ScorePlan s;
   if (int rc = plan_top_messages(c, nm, std::min(TAVB_MAX_STREAM_QUERIES, per_tile), k, &s)) return rc;

@@ -979,6 +979,15 @@ int tavb_search_device_dispatch(tavb_ctx* c, const float* d_q, int nq, int k, co
       }
     }
   }
+  // A staged query the tiles cannot serve (tavb_ctx.h): the WHOLE batch on the streaming kernels.  Behind the grouped scan, which is fp32
+  // throughout.  Whole batch, not a re-run of the marked queries in groups of 8: that needs the per-query scatter of rerun_flagged on
+  // every tile route (masked, scoped and top-messages included) for inputs no embedding produces; the price is nq / 8 corpus passes for
+  // such a batch.  fp32 rows too: their tile multiplies fp32 queries, but its admission test on the raw dot product drops the rows an
+  // infinite query scores 0.0, and one rule for both dtypes keeps the answer the scan's wherever the flag is up.
+  if (staged_overflow(c, d_q)) {
+    c->last_shadow = 0;
+    return search_device_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, index_base, d_out);
+  }
   // the wide tile keeps a band below the k-th best (any k the fused selections serve: the reference's max_matches = 50, convsettings.py:61-63,
   // included).  Its flagged queries need an exact tile: the 64-query one up to k = 64, beyond that the wide split-plane form (fp16 corpora).
   // A width that is not a multiple of 64 (the tile's K step) rides the wide tile on a zero-padded copy of the rows (search_wide_exact): any
@@ -1035,6 +1044,10 @@ int search_masked_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
   c->last_shadow = 0;
   c->last_direct = 0;
   c->masked_route = 2;
+  if (staged_overflow(c, d_q)) {  // (tavb_ctx.h) the row-list scoped route, every query under the one mask
+    const std::vector<const uint32_t*> masks((size_t)nq, dev_bits);
+    return search_scoped_impl(c, d_q, nq, k, min_scores, masks.data(), index_base, d_out, d_out);
+  }
   return run_skinny_tile(c, d_q, nq, k, min_scores, index_base, d_out, dev_bits, first_row / 256 * 256, last_row + 1);
 }
 
@@ -1077,6 +1090,7 @@ int search_scoped_tile(tavb_ctx* c, const float* d_q, int nq, int k, const float
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
   c->masked_route = 5;
+  if (staged_overflow(c, d_q)) return search_scoped_impl(c, d_q, nq, k, min_scores, masks, index_base, d_out, d_out);  // (tavb_ctx.h)
   const int64_t stride = scope_plane_stride(first_row, last_row);
   const int64_t tile_bytes = 2 * stride * (int64_t)sizeof(uint32_t);
   const int wave = 64 * (int)std::max<int64_t>(1, std::min<int64_t>(kScopeWavePlaneBytes / tile_bytes, 1 << 20));
@@ -1166,6 +1180,10 @@ int search_masked_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
   c->last_tier = 4;
   c->last_direct = 0;
   c->masked_route = 3;
+  if (staged_overflow(c, d_q)) {  // (tavb_ctx.h) the gather route over the mask's row list, as for a flagged query
+    if (int rc = search_device_impl(c, d_q, nq, k, min_scores, dev_rows, n_allowed, 0u, d_out)) return rc;
+    return remap_key_rows(c, d_out, d_out, (int64_t)nq * k, dev_rows, n_allowed, index_base);
+  }
   const MaskedWide mw{dev_bits, first_row / 256 * 256, last_row + 1, dev_rows, n_allowed};
   return search_wide_exact(c, d_q, nq, k, min_scores, index_base, d_out, /*small=*/false, &mw);
 }
@@ -1188,6 +1206,7 @@ int search_scoped_wide(tavb_ctx* c, const float* d_q, int nq, int k, const float
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
   c->masked_route = 6;
+  if (staged_overflow(c, d_q)) return search_scoped_impl(c, d_q, nq, k, min_scores, masks, index_base, d_out, d_out);  // (tavb_ctx.h)
   const int64_t stride = scope_plane_stride(first_row, last_row);
   const int qt_all = c->mfma_tile > 0 ? (int)c->mfma_tile : tavb::mfma_query_tile_for(nq, stride, c->n_cu);
   const int64_t fit256 = c->scope_wave_bytes / (8 * stride * (int64_t)sizeof(uint32_t));  // whole 256-query tiles in the budget
