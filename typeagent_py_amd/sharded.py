@@ -37,10 +37,16 @@ batch of queries is one `tavb_search_subset_batch_device` per rank -- keys carry
 Top-k distinct messages (`set_row_messages`, `lookup_top_messages_by_embedding(s)`): every rank holds its slice of ONE global row -> message
 map with the global message count, a batch is `tavb_search_top_messages_allgather` -- the rank's own best k messages, the all-gather, one
 maximum per message and the best k of those -- and every rank returns the whole-corpus answer.
+
+One copy of each step: `ShardedSearcher.collective` answers "does this call exchange", `ShardedSearcher.exchange` is the only exchange (the
+library's communicator -> `gather_fn` -> a single rank -> torch.distributed) and `ShardedSearcher.lookup_keys` the only failure protocol
+(the local part, failure lists in its place when it raises, the exchange, the rank's own error, `_raise_if_peer_failed`): every lookup
+form of `ShardedVectorBase` hands it its local part.  The library's one-call paths run the protocol inside libtavb and share the last step.
 """
 
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Protocol
 
@@ -93,6 +99,33 @@ class ShardBackend(Protocol):
     def rows_to_host(self) -> np.ndarray:  # this rank's rows as float32 [n, dim]
         ...
 
+    # Optional capabilities, probed with hasattr / getattr (test doubles leave them out on purpose) and what each unlocks:
+    #   native_comm (attribute)                the library's own communicator: `search_allgather` serves the plain lookup in one C call and
+    #                                          the engine's allgather_merge* calls serve every other exchange (unless `gather_fn` is set)
+    #   stage_queries(q)                       host queries -> device through a reused pinned buffer (else a plain torch copy)
+    #   subset_to_device(local_rows, positions) + local_search_subset_resident(query, handle, k, thr)
+    #                                          this shard's part of a caller's subset stays on the device while the same list comes back
+    #   mask_to_device(local_mask) + local_search_masked(queries, handle, k, thrs)
+    #                                          masked batches as ONE local call and ONE exchange (else the subset lookup per query)
+    #   local_top_messages(queries, k, thrs, handle, masked)
+    #                                          this rank's best k messages on the device (else `local_survivors` and a collapse on the host)
+    #   merge_top_messages(gathered)           the top-messages merge on the device (else libtavb's host merge)
+    #   search_top_messages_allgather(...) + join_failed_top_messages(nq, k, n_messages)
+    #                                          with native_comm: a top-messages batch in one C call
+    #   set_row_messages(local_map, n_messages) this rank's slice of the row -> message map on its device
+    #   storage_dtype()                        what `rebalance()` keeps the shard stored as
+    #   stream, torch (attributes)             the stream the backend's kernels run on: the torch.distributed all-gather is issued on it
+
+
+def _fused_k(k: int) -> bool:
+    """the fused selection family of the library (k <= 256) or, False, its large-k family: the one place that decides from k"""
+    return k <= _native.MAX_FUSED_K
+
+
+def _pack_keys(scores: np.ndarray, ordinals: np.ndarray) -> np.ndarray:
+    """(float32 scores, ordinals) -> uint64 result keys: (score bits << 32) | (0xFFFFFFFF - ordinal)"""
+    return (scores.astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - ordinals.astype(np.uint64))
+
 
 def _check_k(k: int, what: str) -> None:
     if not (1 <= k <= _native.MAX_LARGE_K):
@@ -115,6 +148,14 @@ class PeerFailedError(RuntimeError):
     """Another rank's local search failed during a collective lookup: the merged lists would be missing its shard."""
 
 
+def _raise_if_peer_failed(keys: np.ndarray) -> np.ndarray:
+    """merged host keys [nq, k] -> the same keys, unless a list leads with the failure key (it sorts above every real key, so a failed rank's
+    contribution leads every merged list on every rank)"""
+    if keys.size and (np.asarray(keys).reshape(keys.shape[0], -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
+        raise PeerFailedError("a rank of the collective lookup failed in its local part: the merged lists are missing its shard")
+    return keys
+
+
 class DeviceShardBackend:
     """HIP kernels on this rank's GPU, launched on a dedicated torch stream so that
     RCCL collectives issued by torch.distributed order correctly with them."""
@@ -125,6 +166,7 @@ class DeviceShardBackend:
         self.torch = torch
         self.device = int(device)
         torch.cuda.set_device(self.device)
+        self._dev = torch.device("cuda", self.device)
         self.stream = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self.stream):
             self.engine = _native.Engine(self.device, use_torch_stream=True)
@@ -152,8 +194,7 @@ class DeviceShardBackend:
             if len(self._qstage) >= 8:
                 self._qstage.clear()
             with torch.cuda.stream(self.stream):
-                slot = self._qstage[shape] = (torch.empty(shape, dtype=torch.float32).pin_memory(),
-                                              torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device)))
+                slot = self._qstage[shape] = (torch.empty(shape, dtype=torch.float32).pin_memory(), torch.empty(shape, dtype=torch.float32, device=self._dev))
         pinned, dev = slot
         self.stream.synchronize()  # (the previous lookup that read `dev` is long done in practice; cheap)
         pinned.numpy()[...] = q
@@ -210,26 +251,12 @@ class DeviceShardBackend:
     def local_search_subset(self, query: np.ndarray, local_rows: np.ndarray, positions: np.ndarray, k: int, thr: float):
         """rows of THIS shard (local numbering) that the caller's subset names, `positions[i]` = where local_rows[i] sits in the
         caller's list -> keys [1, k] carrying those positions (subset gather kernel + position remap, on the backend's stream)."""
-        torch = self.torch
-        dev = torch.device("cuda", self.device)
-        with torch.cuda.stream(self.stream):
-            if len(local_rows) == 0:
-                return torch.zeros((1, k), dtype=torch.int64, device=dev)
-            # (the copies run on the backend's stream, in front of the kernels that read them)
-            dq = torch.from_numpy(np.ascontiguousarray(query, dtype=np.float32)).to(dev)
-            rows = torch.from_numpy(np.ascontiguousarray(local_rows, dtype=np.int32)).to(dev)
-            pmap = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.int32)).to(dev)
-            keys = self._subset_keys(dq, rows, k, thr)
-            self.engine.remap_key_positions(keys, pmap)
-            self._keep = (dq, rows, pmap)  # alive until the next call (the kernels run asynchronously)
-            return keys
+        return self.local_search_subset_resident(query, self.subset_to_device(local_rows, positions), k, thr)
 
-    def _subset_keys(self, dq, dev_rows, k: int, thr: float):
-        """this shard's part of a subset -> keys [1, k] carrying positions in that part: the fused selection up to MAX_FUSED_K, the exact
-        device top-k beyond"""
-        if k <= _native.MAX_FUSED_K:
-            return self.engine.search_subset_device(dq, dev_rows, k, thr)
-        return self.engine.search_topk_device(dq.reshape(1, -1), k, thr, dev_rows=dev_rows)
+    def _zero_keys(self, nq: int, k: int):
+        """[nq, k] zero keys on the backend's stream: what a rank contributes whose part of a subset, a mask or the corpus is empty"""
+        with self.torch.cuda.stream(self.stream):
+            return self.torch.zeros((nq, k), dtype=self.torch.int64, device=self._dev)
 
     def subset_to_device(self, local_rows: np.ndarray, positions: np.ndarray):
         """This shard's part of a caller's subset as device tensors (rows int32 [S], positions int32 [S]) -- a handle for
@@ -237,20 +264,21 @@ class DeviceShardBackend:
         torch = self.torch
         if len(local_rows) == 0:
             return None
-        dev = torch.device("cuda", self.device)
-        with torch.cuda.stream(self.stream):
-            return (torch.from_numpy(np.ascontiguousarray(local_rows, dtype=np.int32)).to(dev),
-                    torch.from_numpy(np.ascontiguousarray(positions, dtype=np.int32)).to(dev))
+        with torch.cuda.stream(self.stream):  # (the copies run on the backend's stream, in front of the kernels that read them)
+            return (torch.from_numpy(np.ascontiguousarray(local_rows, dtype=np.int32)).to(self._dev),
+                    torch.from_numpy(np.ascontiguousarray(positions, dtype=np.int32)).to(self._dev))
 
     def local_search_subset_resident(self, query: np.ndarray, handle, k: int, thr: float):
-        """`local_search_subset` over a handle of `subset_to_device`: only the query travels."""
-        torch = self.torch
-        dev = torch.device("cuda", self.device)
-        with torch.cuda.stream(self.stream):
-            if handle is None:
-                return torch.zeros((1, k), dtype=torch.int64, device=dev)
-            dq = torch.from_numpy(np.ascontiguousarray(query, dtype=np.float32)).to(dev)
-            keys = self._subset_keys(dq, handle[0], k, thr)
+        """`local_search_subset` over a handle of `subset_to_device`: only the query travels.  The fused selection up to MAX_FUSED_K, the
+        exact device top-k beyond; either gives keys carrying positions in this shard's part, remapped to the caller's positions."""
+        if handle is None:
+            return self._zero_keys(1, k)
+        with self.torch.cuda.stream(self.stream):
+            dq = self.torch.from_numpy(np.ascontiguousarray(query, dtype=np.float32)).to(self._dev)
+            if _fused_k(k):
+                keys = self.engine.search_subset_device(dq, handle[0], k, thr)
+            else:
+                keys = self.engine.search_topk_device(dq.reshape(1, -1), k, thr, dev_rows=handle[0])
             self.engine.remap_key_positions(keys, handle[1])
             self._keep = (dq, handle)  # alive until the next call (the kernels run asynchronously)
             return keys
@@ -273,13 +301,10 @@ class DeviceShardBackend:
         """A batch of queries (host float32 [nq, dim]; thrs: one threshold per query) over a handle of `mask_to_device`: ONE
         tavb_search_subset_batch_device on the backend's stream -> keys [nq, k] carrying GLOBAL ordinals (the engine's ordinal_base is this
         rank's row_offset).  Asynchronous; an empty part (handle None) gives zero keys."""
-        torch = self.torch
-        nq = int(np.shape(queries)[0])
         if handle is None:
-            with torch.cuda.stream(self.stream):
-                return torch.zeros((nq, k), dtype=torch.int64, device=torch.device("cuda", self.device))
+            return self._zero_keys(int(np.shape(queries)[0]), k)
         dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
-        with torch.cuda.stream(self.stream):
+        with self.torch.cuda.stream(self.stream):
             keys = self.engine.search_subset_batch_device(dq, handle, k, thrs, remap=True)
         self._keep = (dq, handle, keys)  # alive until the next call (the kernels run asynchronously)
         return keys
@@ -295,20 +320,25 @@ class DeviceShardBackend:
         buf = getattr(self, "_no_rows", None)
         if buf is None:
             with self.torch.cuda.stream(self.stream):
-                buf = self._no_rows = self.torch.empty(0, dtype=self.torch.int32, device=self.torch.device("cuda", self.device))
+                buf = self._no_rows = self.torch.empty(0, dtype=self.torch.int32, device=self._dev)
         return buf
+
+    def _pinned_keys(self, shape):
+        """the pinned host buffer of merged keys for `shape`, reused from call to call"""
+        shape = tuple(int(n) for n in shape)
+        pinned = self._pinned.get(shape)
+        if pinned is None:
+            pinned = self._pinned[shape] = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
+        return pinned
 
     def local_top_messages(self, queries: np.ndarray, k: int, thrs, handle=None, masked: bool = False):
         """A batch of queries (host float32 [nq, dim]; thrs: one threshold per query) over this rank's shard, or, with `masked`, over a
         handle of `mask_to_device` (None: this rank's part of the mask is empty -> zero keys): ONE tavb_search_top_messages_device on
         the backend's stream -> keys [nq, k] carrying GLOBAL message ordinals.  Asynchronous."""
-        torch = self.torch
-        nq = int(np.shape(queries)[0])
         if (masked and handle is None) or self.engine.rows == 0:
-            with torch.cuda.stream(self.stream):
-                return torch.zeros((nq, k), dtype=torch.int64, device=torch.device("cuda", self.device))
+            return self._zero_keys(int(np.shape(queries)[0]), k)
         dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
-        with torch.cuda.stream(self.stream):
+        with self.torch.cuda.stream(self.stream):
             keys = self.engine.search_top_messages_device(dq, k, thrs, dev_rows=handle if masked else None)
         self._keep = (dq, handle, keys)  # alive until the next call (the kernels run asynchronously)
         return keys
@@ -324,10 +354,7 @@ class DeviceShardBackend:
         """This rank's best k messages -> ncclAllGather -> the top-messages merge inside libtavb (tavb_search_top_messages_allgather), merged
         keys written into a reused pinned host buffer: -> int64 [nq, k] (host view, valid until the next call)."""
         dq = self.stage_queries(np.ascontiguousarray(queries, dtype=np.float32))
-        shape = (int(dq.shape[0]), int(k))
-        pinned = self._pinned.get(shape)
-        if pinned is None:
-            pinned = self._pinned[shape] = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
+        pinned = self._pinned_keys((dq.shape[0], k))
         rows = None if not masked else (self._empty_rows() if handle is None else handle)
         with self.torch.cuda.stream(self.stream):
             self.engine.search_top_messages_allgather(dq, k, thrs, out_keys=pinned, dev_rows=rows)
@@ -353,41 +380,28 @@ class DeviceShardBackend:
     def keys_to_device(self, keys: np.ndarray):
         torch = self.torch
         with torch.cuda.stream(self.stream):
-            return torch.from_numpy(np.ascontiguousarray(keys).view(np.int64)).to(torch.device("cuda", self.device))
+            return torch.from_numpy(np.ascontiguousarray(keys).view(np.int64)).to(self._dev)
 
     def search_allgather(self, queries, k: int, thr: float):
         """scan -> ncclAllGather -> merge inside libtavb, merged keys written into a reused pinned host buffer: -> int64 [nq, k] (host view,
         valid until the next call)."""
-        shape = (int(queries.shape[0]), int(k))
-        pinned = self._pinned.get(shape)
-        if pinned is None:
-            pinned = self._pinned[shape] = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
-        if k <= _native.MAX_FUSED_K:
-            self.engine.search_allgather(queries, k, thr, out_keys=pinned)
-        else:
-            self.engine.search_topk_allgather(queries, k, thr, out_keys=pinned)
+        pinned = self._pinned_keys((queries.shape[0], k))
+        call = self.engine.search_allgather if _fused_k(k) else self.engine.search_topk_allgather
+        call(queries, k, thr, out_keys=pinned)
         self.engine.synchronize()
         return pinned.numpy()
 
     def local_search(self, queries, k: int, thr: float):
         with self.torch.cuda.stream(self.stream):
-            if k <= _native.MAX_FUSED_K:
-                return self.engine.search_device(queries, k, thr)
-            return self.engine.search_topk_device(queries, k, thr)
+            return (self.engine.search_device if _fused_k(k) else self.engine.search_topk_device)(queries, k, thr)
 
     def merge(self, gathered):
         with self.torch.cuda.stream(self.stream):
-            if gathered.shape[2] <= _native.MAX_FUSED_K:
-                return self.engine.merge_device(gathered)
-            return self.engine.merge_topk_device(gathered)
+            return (self.engine.merge_device if _fused_k(gathered.shape[2]) else self.engine.merge_topk_device)(gathered)
 
     def to_host(self, keys) -> np.ndarray:
         # pinned staging buffer, reused: one async copy + one stream sync, no allocation per lookup
-        shape = tuple(keys.shape)
-        pinned = self._pinned.get(shape)
-        if pinned is None:
-            pinned = self.torch.empty(shape, dtype=self.torch.int64).pin_memory()
-            self._pinned[shape] = pinned
+        pinned = self._pinned_keys(keys.shape)
         with self.torch.cuda.stream(self.stream):
             pinned.copy_(keys, non_blocking=True)
         self.stream.synchronize()
@@ -400,7 +414,7 @@ class DeviceShardBackend:
         buf = self._failed.get((nq, k))
         with self.torch.cuda.stream(self.stream):
             if buf is None:
-                buf = self._failed[(nq, k)] = self.torch.empty((nq, k), dtype=self.torch.int64, device=self.torch.device("cuda", self.device))
+                buf = self._failed[(nq, k)] = self.torch.empty((nq, k), dtype=self.torch.int64, device=self._dev)
             buf.fill_(PEER_FAILED_KEY)
         return buf
 
@@ -409,7 +423,7 @@ class DeviceShardBackend:
         buf = self._gather.get(shape)
         if buf is None:
             with self.torch.cuda.stream(self.stream):
-                buf = self.torch.empty(shape, dtype=self.torch.int64, device=self.torch.device("cuda", self.device))
+                buf = self.torch.empty(shape, dtype=self.torch.int64, device=self._dev)
             self._gather[shape] = buf
         return buf
 
@@ -437,38 +451,17 @@ class ShardedSearcher:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
 
-    def search_keys(self, queries, k: int, min_score: float = 0.0):
-        """-> backend tensor int64 [nq, k] of merged keys (still on the device, async)."""
-        _check_k(k, "k")
-        thr = float(_native.f32_threshold(min_score))
-        collective = not (self.world == 1 and not (self.always_collective and self.dist.is_initialized()))
-        failure = None
-        try:
-            local = self.backend.local_search(queries, k, thr)
-        except Exception as exc:  # noqa: BLE001 -- whatever the backend raised: the peers must not be left waiting in the all-gather
-            if not collective:
-                raise
-            # the protocol of tavb_search_allgather (include/tavb.h): this rank joins the exchange with TAVB_KEY_PEER_FAILED in every slot -- it
-            # sorts above every real key, so it leads every merged list on every rank -- and raises its own error afterwards
-            failure = exc
-            local = self.backend.failed_lists(int(queries.shape[0]), k)
-        if not collective:
-            return local
-        nq = local.shape[0]
-        if self.gather_fn is not None:
-            merged = self.backend.merge(self.gather_fn(local))
-        else:
-            gathered = self.backend.empty_gather(self.world, nq, k)
-            stream = getattr(self.backend, "stream", None)
-            if stream is not None:
-                with self.backend.torch.cuda.stream(stream):
-                    self.dist.all_gather_into_tensor(gathered.view(-1), local.contiguous().view(-1), group=self.group)
-            else:
-                self.dist.all_gather_into_tensor(gathered.view(-1), local.contiguous().view(-1), group=self.group)
-            merged = self.backend.merge(gathered)
-        if failure is not None:
-            raise failure
-        return merged
+    @property
+    def native(self) -> bool:
+        """the library's own communicator carries this searcher's exchanges (`gather_fn` overrides it)"""
+        return bool(getattr(self.backend, "native_comm", False)) and self.gather_fn is None
+
+    @property
+    def collective(self) -> bool:
+        """Does a call exchange?  With a communicator of the library, with `gather_fn`, with more than one rank, or when asked to
+        (`always_collective` under an initialised torch.distributed).  Where it does not, `exchange` returns the local lists and an error
+        of the local part is raised at once: nobody waits for this rank."""
+        return self.native or self.gather_fn is not None or self.world > 1 or (self.always_collective and self.dist.is_initialized())
 
     def _merge_top_messages(self, gathered):
         """[world, nq, k] top-messages lists -> [nq, k] on the backend's device: the backend's own merge, or the host merge of libtavb"""
@@ -480,41 +473,61 @@ class ShardedSearcher:
     def exchange(self, local_keys, messages: bool = False):
         """this rank's sorted lists [nq, k] (global ordinals / positions) -> the lists merged over all ranks, on every rank.  messages: the
         keys carry MESSAGE ordinals -- one message may stand in several ranks' lists: one maximum per message, then the best k."""
-        if messages:
-            if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
-                return self.backend.engine.allgather_merge_top_messages(local_keys)
-            if self.gather_fn is not None:
-                return self._merge_top_messages(self.gather_fn(local_keys))
-            if self.world == 1 and not (self.always_collective and self.dist.is_initialized()):
-                return local_keys
-            nq, k = local_keys.shape
-            gathered = self.backend.empty_gather(self.world, nq, k)
-            self.dist.all_gather_into_tensor(gathered.view(-1), local_keys.contiguous().view(-1), group=self.group)
-            return self._merge_top_messages(gathered)
-        if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
-            if local_keys.shape[1] <= _native.MAX_FUSED_K:
-                return self.backend.engine.allgather_merge(local_keys)
-            return self.backend.engine.allgather_merge_topk(local_keys)
-        if self.gather_fn is not None:
-            return self.backend.merge(self.gather_fn(local_keys))
-        if self.world == 1 and not (self.always_collective and self.dist.is_initialized()):
-            return local_keys
+        backend = self.backend
         nq, k = local_keys.shape
-        gathered = self.backend.empty_gather(self.world, nq, k)
-        self.dist.all_gather_into_tensor(gathered.view(-1), local_keys.contiguous().view(-1), group=self.group)
-        return self.backend.merge(gathered)
+        # what differs by key family, chosen once: the library's call and the merge
+        native_call = "allgather_merge_top_messages" if messages else ("allgather_merge" if _fused_k(k) else "allgather_merge_topk")
+        merge = self._merge_top_messages if messages else backend.merge
+        if self.native:
+            return getattr(backend.engine, native_call)(local_keys)
+        if self.gather_fn is not None:
+            return merge(self.gather_fn(local_keys))
+        if not self.collective:
+            return local_keys
+        gathered = backend.empty_gather(self.world, nq, k)
+        # on the backend's stream, where it has one: behind the kernels that wrote `local_keys`, in front of the merge and `to_host`
+        stream = getattr(backend, "stream", None)
+        with contextlib.nullcontext() if stream is None else backend.torch.cuda.stream(stream):
+            self.dist.all_gather_into_tensor(gathered.view(-1), local_keys.contiguous().view(-1), group=self.group)
+        return merge(gathered)
+
+    def _join(self, local, nq: int, k: int, messages: bool = False):
+        """`local()` -> this rank's [nq, k] keys -> the exchange -> merged keys on the backend's device.  The protocol of tavb_search_allgather
+        (include/tavb.h): a rank whose local part raises in a collective call joins the exchange with TAVB_KEY_PEER_FAILED in every slot
+        and raises ITS error afterwards -- the peers are not left waiting in the all-gather."""
+        failure = None
+        try:
+            keys = local()
+        except Exception as exc:  # noqa: BLE001 -- whatever the backend or the caller's predicate raised
+            if not self.collective:
+                raise
+            failure = exc
+            keys = self.backend.failed_lists(nq, k)
+        merged = self.exchange(keys, messages=True) if messages else self.exchange(keys)  # (`exchange` may be replaced by a one-argument hook)
+        if failure is not None:
+            raise failure
+        return merged
+
+    def lookup_keys(self, local, nq: int, k: int, messages: bool = False) -> np.ndarray:
+        """The whole failure protocol, for every lookup form: `_join`, then the merged keys on the host (int64 [nq, k], a copy) -- or
+        `PeerFailedError` where another rank joined with failure lists: nobody returns an answer that misses a shard."""
+        return _raise_if_peer_failed(self.backend.to_host(self._join(local, nq, k, messages)))
+
+    def search_keys(self, queries, k: int, min_score: float = 0.0):
+        """-> backend tensor int64 [nq, k] of merged keys (still on the device, async)."""
+        _check_k(k, "k")
+        thr = float(_native.f32_threshold(min_score))
+        return self._join(lambda: self.backend.local_search(queries, k, thr), int(queries.shape[0]), k)
 
     def search(self, queries, k: int, min_score: float = 0.0) -> ShardedResult:
-        if getattr(self.backend, "native_comm", False) and self.gather_fn is None:
+        _check_k(k, "k")
+        thr = float(_native.f32_threshold(min_score))
+        if self.native:
             # the product path: one C-ABI call (no torch.distributed, no torch op), results land in pinned host memory
-            _check_k(k, "k")
-            keys = self.backend.search_allgather(queries, k, float(_native.f32_threshold(min_score)))
+            keys = _raise_if_peer_failed(self.backend.search_allgather(queries, k, thr))
         else:
-            keys = self.backend.to_host(self.search_keys(queries, k, min_score))
-        if keys.size and (np.asarray(keys).reshape(keys.shape[0], -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
-            raise PeerFailedError("a rank of the collective lookup failed in its local search: the merged lists are missing its shard")
-        ords, scs, cnts = _native.decode_keys(keys)
-        return ShardedResult(ords, scs, cnts)
+            keys = self.lookup_keys(lambda: self.backend.local_search(queries, k, thr), int(queries.shape[0]), k)
+        return ShardedResult(*_native.decode_keys(keys))
 
 
 class ShardedVectorBase:
@@ -549,6 +562,11 @@ class ShardedVectorBase:
     @property
     def _rank(self) -> int:
         return self.searcher.rank
+
+    @property
+    def _layout(self) -> tuple[int, int, int]:
+        """(total rows, this rank's offset, this rank's rows): what device-resident handles -- subset, mask, message map -- were cut under"""
+        return (self.total_rows, self.row_offset, self.local_rows)
 
     def add_embeddings(self, keys, embeddings) -> None:
         """vectorbase.py:130-148 over row shards: the new rows get the next global ordinals and go to the LAST rank's shard (contiguous
@@ -653,16 +671,34 @@ class ShardedVectorBase:
             return _t.from_numpy(a)
         return torch.from_numpy(a).to(torch.device("cuda", self.backend.device))
 
+    @staticmethod
+    def _per_query(embeddings, thresholds=None):
+        """-> (q float32 [nq, dim], the caller's threshold of every query: `thresholds` is one for all, or one per query)"""
+        q = np.asarray(embeddings, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
+        per_query = thresholds is not None and not np.isscalar(thresholds) and np.ndim(thresholds) == 1
+        if per_query and len(thresholds) != len(q):
+            raise ValueError(f"Number of thresholds {len(thresholds)} does not match number of embeddings {len(q)}")
+        return q, list(thresholds) if per_query else [thresholds] * len(q)
+
+    def _batch_args(self, embeddings, max_k, thresholds, what: str):
+        """The arguments of a batched lookup -> (q float32 [nq, dim], nq, k, float32 thresholds [nq]).  `max_k`: None -> 10, checked by
+        `_check_k` under the parameter's name `what`; `thresholds`: one (None -> 0.0) or one per query.  Argument errors are the same on
+        every rank and raise before anything collective."""
+        q, each = self._per_query(embeddings, thresholds)
+        k = 10 if max_k is None else int(max_k)
+        _check_k(k, what)
+        return q, len(q), k, np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in each], dtype=np.float32)
+
     def fuzzy_lookup_embeddings(self, embeddings, max_hits: int | None = None, min_score: float | None = None):
         if max_hits is None:
             max_hits = 10
         if min_score is None:
             min_score = 0.0
-        q = np.asarray(embeddings, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
+        q, _ = self._per_query(embeddings)
         if self.total_rows == 0 or len(q) == 0:
-            return [[] for _ in range(len(q))]
+            return [[] for _ in range(len(q))]  # (before max_hits is checked: an empty index answers max_hits = 0 too)
         _check_k(int(max_hits), "max_hits")  # (before anything collective: every rank makes the same call)
         res = self.searcher.search(self._queries(q), int(max_hits), min_score)
         from .vectorbase import _scored_lists  # (the lists are built in C: csrc/tavb_pyhits.c)
@@ -689,35 +725,13 @@ class ShardedVectorBase:
             ids, scs = (np.zeros(0, np.int64), np.zeros(0, np.float32)) if self.local_rows == 0 else self.backend.local_survivors(q, thr)
             order = np.lexsort((ids,))  # ascending ordinal: the order of np.flatnonzero (:193)
             keep = np.fromiter((bool(predicate(int(i))) for i in ids[order]), dtype=bool, count=len(order))
-            ids, scs = ids[order][keep], scs[order][keep]
-            keys = (scs.astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - ids.astype(np.uint64))
             local = np.zeros((1, k), dtype=np.uint64)
-            best = np.sort(keys)[::-1][:k]
+            best = np.sort(_pack_keys(scs[order][keep], ids[order][keep]))[::-1][:k]
             local[0, : len(best)] = best
             return self.backend.keys_to_device(local)
 
-        ords, sc, cnt = self._exchange_or_fail(local_lists, 1, k)
+        ords, sc, cnt = _native.decode_keys(self.searcher.lookup_keys(local_lists, 1, k))
         return [ScoredInt(int(o), float(s_)) for o, s_ in zip(ords[0, : cnt[0]].tolist(), sc[0, : cnt[0]].tolist())]
-
-    def _exchange_or_fail(self, local_lists, nq: int, k: int, messages: bool = False):
-        """The collective forms beside the plain lookup (subset, predicate): `local_lists()` -> this rank's [nq, k] keys -> exchange -> decoded
-        merged lists.  The failure protocol of `ShardedSearcher.search_keys` / tavb_search_allgather: a rank whose local part raises -- the
-        caller's predicate included -- still joins the exchange, with PEER_FAILED_KEY lists, then raises ITS error; the others raise
-        `PeerFailedError` instead of waiting for ever or returning an answer that misses a shard."""
-        failure = None
-        try:
-            local = local_lists()
-        except Exception as exc:  # noqa: BLE001
-            if self._world == 1 and not getattr(self.backend, "native_comm", False):
-                raise
-            failure = exc
-            local = self.backend.failed_lists(nq, k)
-        merged = self.backend.to_host(self.searcher.exchange(local, messages=True) if messages else self.searcher.exchange(local))
-        if failure is not None:
-            raise failure
-        if merged.size and (np.asarray(merged).reshape(merged.shape[0], -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
-            raise PeerFailedError("a rank of the collective lookup failed in its local part: the merged lists are missing its shard")
-        return _native.decode_keys(merged)
 
     def fuzzy_lookup_embedding_in_subset(self, embedding, ordinals_of_subset, max_hits: int | None = None, min_score: float | None = None):
         """vectorbase.py:203-230 over the row-sharded corpus: every rank gathers the rows of the caller's subset that lie in its shard,
@@ -733,7 +747,7 @@ class ShardedVectorBase:
         q = np.ascontiguousarray(embedding, dtype=np.float32)
         # the same subset object with the same content again (the memory provider's scope list per query term,
         # storage/memory/messageindex.py:173-183): this shard's part of it stays on the device (as VectorBase does it)
-        layout = (self.total_rows, self.row_offset, self.local_rows)
+        layout = self._layout
         cached = self._subset_cache
         resident = hasattr(self.backend, "subset_to_device") and isinstance(ordinals_of_subset, (list, np.ndarray))
         if (resident and cached is not None and cached[0] is ordinals_of_subset and cached[2] == layout and len(cached[1]) == len(ordinals_of_subset)
@@ -765,7 +779,7 @@ class ShardedVectorBase:
             else:
                 def local_lists():
                     return self.backend.local_search_subset(q, rows[mine] - self.row_offset, mine, k, thr)
-        pos, sc, cnt = self._exchange_or_fail(local_lists, 1, k)
+        pos, sc, cnt = _native.decode_keys(self.searcher.lookup_keys(local_lists, 1, k))
         return [ScoredInt(int(subset[p]), float(s_)) for p, s_ in zip(pos[0, : cnt[0]].tolist(), sc[0, : cnt[0]].tolist())]
 
     # ---- masked lookups: with a backend that offers `mask_to_device` / `local_search_masked`, this rank's slice of the mask stays on its
@@ -782,7 +796,12 @@ class ShardedVectorBase:
         from .vectorbase import RowMask
 
         backend = self._masked_backend()
-        bits = None
+
+        def device_mask(mask, bits, count):
+            """the device-backed form: this rank's slice of `mask` expanded on its device, the whole mask as `bits`, the GLOBAL count"""
+            local = mask[self.row_offset : self.row_offset + self.local_rows]
+            return RowMask(self, self.total_rows, count, dev_rows=backend.mask_to_device(local), layout=self._layout, bits=bits)
+
         if hasattr(allowed, "is_cuda") and hasattr(allowed, "dtype"):  # a torch tensor
             if "bool" not in str(allowed.dtype):
                 raise TypeError(f"a mask must be bool, got {allowed.dtype}")
@@ -795,9 +814,7 @@ class ShardedVectorBase:
                 backend.torch.cuda.current_stream(backend.device).synchronize()
                 with backend.torch.cuda.stream(backend.stream):
                     bits = backend.engine.pack_mask_tensor(allowed).cpu().numpy().view(np.uint32)
-                local = allowed[self.row_offset : self.row_offset + self.local_rows]
-                return RowMask(self, self.total_rows, _popcount(bits), dev_rows=backend.mask_to_device(local),
-                               layout=(self.total_rows, self.row_offset, self.local_rows), bits=bits)
+                return device_mask(allowed, bits, _popcount(bits))
             allowed = allowed.cpu().numpy()
         a = np.asarray(allowed)
         if a.dtype != np.bool_:
@@ -805,10 +822,7 @@ class ShardedVectorBase:
         if a.ndim != 1 or a.shape[0] != self.total_rows:
             raise ValueError(f"mask covers {a.shape[0] if a.ndim else 0} rows, the index has {self.total_rows}")
         if backend is not None:
-            bits = _native.pack_mask_bits(a)
-            local = a[self.row_offset : self.row_offset + self.local_rows]
-            return RowMask(self, self.total_rows, int(np.count_nonzero(a)), dev_rows=backend.mask_to_device(local),
-                           layout=(self.total_rows, self.row_offset, self.local_rows), bits=bits)
+            return device_mask(a, _native.pack_mask_bits(a), int(np.count_nonzero(a)))
         flat = np.flatnonzero(a)
         return RowMask(self, self.total_rows, len(flat), flat=flat)
 
@@ -827,7 +841,7 @@ class ShardedVectorBase:
         """This rank's part of a device-backed mask as the backend's handle (None: an empty part).  A handle cut under another layout
         (the rows were re-dealt since) is cut again from its packed bits: this rank's slice, expanded on its device.  May raise on ONE
         rank: call it inside the local part of a collective."""
-        layout = (self.total_rows, self.row_offset, self.local_rows)
+        layout = self._layout
         if mask.layout != layout:
             lo, n = self.row_offset, self.local_rows
             part = np.unpackbits(mask.bits.view(np.uint8)[lo // 8 : (lo + n + 7) // 8], bitorder="little")[lo % 8 : lo % 8 + n]
@@ -840,19 +854,11 @@ class ShardedVectorBase:
         threshold, or one per query); `allowed`: a mask or the `RowMask` made from one.  With a backend that offers the masked route the
         whole batch is one local call per rank and ONE exchange (a rank whose part of the mask is empty still joins); a handle cut under
         another layout (`rebalance()`) is cut again from its packed bits, on every rank alike and without a collective."""
-        q = np.asarray(embeddings, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
-        per_query = min_score is not None and not np.isscalar(min_score) and np.ndim(min_score) == 1
-        if per_query and len(min_score) != len(q):
-            raise ValueError(f"Number of thresholds {len(min_score)} does not match number of embeddings {len(q)}")
+        from .vectorbase import _scored_lists
+
         backend = self._masked_backend()
         if backend is not None:
-            k = 10 if max_hits is None else int(max_hits)
-            _check_k(k, "max_hits")  # (before anything collective: every rank makes the same call)
-            nq = len(q)
-            each = list(min_score) if per_query else [min_score] * nq
-            thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in each], dtype=np.float32)
+            q, nq, k, thr = self._batch_args(embeddings, max_hits, min_score, "max_hits")
             mask = self._resolve_mask(allowed)
             if mask.bits is not None:
                 if mask.count == 0 or nq == 0 or self.total_rows == 0:
@@ -861,12 +867,11 @@ class ShardedVectorBase:
                 def local_lists():
                     return backend.local_search_masked(q, self._mask_part(mask, backend), k, thr)
 
-                from .vectorbase import _scored_lists
-
-                ords, scs, cnts = self._exchange_or_fail(local_lists, nq, k)
-                return _scored_lists(ords, scs, cnts, k)
+                return _scored_lists(*_native.decode_keys(self.searcher.lookup_keys(local_lists, nq, k)), k)
+        # no masked route: the subset lookup per query, which checks max_hits and converts the threshold itself
+        q, each = self._per_query(embeddings, min_score)
         flat = self._resolve_mask(allowed).flat()
-        return [self.fuzzy_lookup_embedding_in_subset(e, flat, max_hits, min_score[i] if per_query else min_score) for i, e in enumerate(q)]
+        return [self.fuzzy_lookup_embedding_in_subset(e, flat, max_hits, each[i]) for i, e in enumerate(q)]
 
     def fuzzy_lookup_embedding_masked(self, embedding, allowed, max_hits: int | None = None, min_score: float | None = None):
         e = np.asarray(embedding, dtype=np.float32)
@@ -888,7 +893,7 @@ class ShardedVectorBase:
 
     def _sync_row_messages(self) -> None:
         """this rank's slice of the map on its device, under the current layout (may raise on ONE rank: call it inside the local part)"""
-        layout = (self.total_rows, self.row_offset, self.local_rows)
+        layout = self._layout
         if self._row_messages_layout != layout and hasattr(self.backend, "set_row_messages"):
             self.backend.set_row_messages(self._row_messages[self.row_offset : self.row_offset + self.local_rows], self._n_messages())
         self._row_messages_layout = layout
@@ -897,8 +902,7 @@ class ShardedVectorBase:
     def _message_keys(msgs: np.ndarray, scs: np.ndarray, k: int) -> np.ndarray:
         """(message ordinal, float32 score) pairs -> the sorted, zero-padded top-messages list uint64 [k]: per message its best score"""
         keep = msgs >= 0
-        keys = (scs[keep].astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - msgs[keep].astype(np.uint64))
-        keys = np.sort(keys)[::-1]
+        keys = np.sort(_pack_keys(scs[keep], msgs[keep]))[::-1]
         _, first = np.unique(keys & np.uint64(0xFFFFFFFF), return_index=True)  # a message's first key in that order is its largest
         best = keys[np.sort(first)][:k]
         out = np.zeros(k, dtype=np.uint64)
@@ -918,15 +922,7 @@ class ShardedVectorBase:
         `PeerFailedError`."""
         from .vectorbase import _scored_lists
 
-        q = np.asarray(embeddings, dtype=np.float32)
-        if q.ndim != 2:
-            raise ValueError(f"Expected 2D embeddings array, got {q.ndim}D")
-        nq = len(q)
-        per_query = threshold_score is not None and not np.isscalar(threshold_score) and np.ndim(threshold_score) == 1
-        if per_query and len(threshold_score) != nq:
-            raise ValueError(f"Number of thresholds {len(threshold_score)} does not match number of embeddings {nq}")
-        k = 10 if max_messages is None else int(max_messages)
-        _check_k(k, "max_messages")  # (before anything collective: every rank makes the same call)
+        q, nq, k, thr = self._batch_args(embeddings, max_messages, threshold_score, "max_messages")
         if self._row_messages is None:
             raise RuntimeError("set_row_messages() first")
         if len(self._row_messages) < self.total_rows:
@@ -935,25 +931,22 @@ class ShardedVectorBase:
         # (global quantities only: every rank decides alike, nobody waits in an exchange)
         if nq == 0 or self.total_rows == 0 or self._n_messages() == 0 or (mask is not None and mask.count == 0):
             return [[] for _ in range(nq)]
-        each = list(threshold_score) if per_query else [threshold_score] * nq
-        thr = np.asarray([_native.f32_threshold(0.0 if m is None else m) for m in each], dtype=np.float32)
         backend = self.backend
         on_device = hasattr(backend, "local_top_messages") and (mask is None or mask.bits is not None)
 
         def handle():
             return None if mask is None else self._mask_part(mask, backend)
 
-        if on_device and getattr(backend, "native_comm", False) and self.searcher.gather_fn is None and hasattr(backend, "search_top_messages_allgather"):
-            try:  # the product path: one C call; what can fail on ONE rank before it still joins the collectives
+        if on_device and self.searcher.native and hasattr(backend, "search_top_messages_allgather"):
+            try:  # the product path: one C call; what can fail on ONE rank before it still joins the collectives -- `join_failed_top_messages`
+                # is those collectives with failure lists, not a copy of `ShardedSearcher.lookup_keys`
                 self._sync_row_messages()
                 rows = handle()
             except Exception:  # noqa: BLE001
                 self._row_messages_layout = None
                 backend.join_failed_top_messages(nq, k, self._n_messages())
                 raise
-            keys = backend.search_top_messages_allgather(q, k, thr, rows, masked=mask is not None)
-            if keys.size and (np.asarray(keys).reshape(nq, -1)[:, 0].view(np.int64) == PEER_FAILED_KEY).any():
-                raise PeerFailedError("a rank of the collective lookup failed in its local search: the merged lists are missing its shard")
+            keys = _raise_if_peer_failed(backend.search_top_messages_allgather(q, k, thr, rows, masked=mask is not None))
             return _scored_lists(*_native.decode_keys(keys), k)
 
         if on_device:
@@ -978,8 +971,7 @@ class ShardedVectorBase:
                     local[i] = self._message_keys(self._row_messages[ids], scs, k)
                 return backend.keys_to_device(local)
 
-        msgs, scs, cnts = self._exchange_or_fail(local_lists, nq, k, messages=True)
-        return _scored_lists(msgs, scs, cnts, k)
+        return _scored_lists(*_native.decode_keys(self.searcher.lookup_keys(local_lists, nq, k, messages=True)), k)
 
     def lookup_top_messages_by_embedding(self, embedding, max_messages: int | None = None, threshold_score: float | None = None, allowed=None):
         """The one-query form of `lookup_top_messages_by_embeddings`."""
