@@ -239,6 +239,13 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   every key, + 2)
  *   "compact_pass_rows" 0 .. 2^31 - 2 (default 0 = auto: about 64 MiB of rows): rows per pass of an in-place tavb_compact_rows or tavb_expand_rows,
  *                   rounded up to a multiple of 64; their staging workspace holds one pass
+ *   "rows_query"    (default 1; the binding reads it) 1 = fuzzy_lookup_rows / near_duplicate_pairs of a single-GPU index are calls of
+ *                   tavb_search_rows / tavb_search_rows_sorted; 0 = the binding takes its host route (the rows to the host, widened to float32,
+ *                   back as a query batch of max_hits + 1, the own row taken out by hand) -- for A/B runs in one process
+ *   "rows_query_wave"  1 .. 2^20 (default 4096): most rows one wave of tavb_search_rows gathers and looks up; the float32 query batch of a
+ *                   wave is rows_query_wave x dim x 4 bytes whatever n is (tests set it small to split a small call into waves)
+ *   "rows_query_launches"  (read only) gather launches (= waves) of the last tavb_search_rows / _device / _sorted / tavb_gather_rows_f32 call; 0
+ *                   before the first and after any tavb_search_batch, tavb_search_topk or tavb_search_sorted (what the host route calls)
  */
 int tavb_set_option(tavb_ctx* ctx, const char* name, int64_t value);
 int tavb_get_option(tavb_ctx* ctx, const char* name, int64_t* out_value);
@@ -970,6 +977,38 @@ int tavb_allgather_merge_top_messages(tavb_ctx* ctx, const tavb_key* dev_local_k
  * (tavb_search_subset_device) numbers the part of the caller's subset that lies in its shard; the map leads back to the positions in the
  * caller's whole list.  In place, asynchronous.  The map must be monotonic for the lists to stay sorted among equal scores. */
 int tavb_remap_key_positions(tavb_ctx* ctx, tavb_key* dev_keys, int64_t count, const int32_t* dev_map, int64_t map_len);
+
+/* ---- rows of the corpus as queries: "more like row 17", near-duplicate detection ------------------------------------------------
+ * The nearest neighbours of rows ALREADY in the corpus, without a round trip of the rows through the host (a device-only corpus has no
+ * host matrix at all).  Per wave of at most "rows_query_wave" rows: ONE gather launch (the rows -> a dense float32 query batch in a
+ * workspace of the context; fp16 rows widened exactly, fp32 rows copied: bit for bit the values the kernels multiply), the lookup every
+ * device-resident batch takes -- tavb_search_device's routing up to TAVB_MAX_FUSED_K keys, tavb_search_topk's passes beyond -- and, with
+ * exclude_self, ONE launch that takes the query's own row out of its list.  exclude_self != 0: the lookup asks for k + 1 keys, the key
+ * whose ordinal is the query's own row is removed where the list holds it, the gap closed, the first k kept.  That is exact, no tolerance:
+ * the k + 1 best of all rows always hold the k best of the OTHER rows -- with the own row in the list the rest are those, without it
+ * (more than k exact duplicates of lower ordinal tie with it; a zero or un-normalised row that is not its own best match; an own score
+ * below min_score) the first k are.  exclude_self == 0: the plain lookup with the rows as queries, k keys, nothing removed.
+ * The rows follow the PRECONDITION on device-resident queries above (every element rounds to a finite fp16 value): the library never sees
+ * them on the host.  A row listed twice is answered twice.
+ *
+ * tavb_search_rows: positions_host int32 [n], each in [0, rows) (checked here: TAVB_E_INVALID), min_scores float32 [n] on the host, 1 <= k <=
+ * TAVB_MAX_LARGE_K - 1 with exclude_self (k + 1 stays inside what tavb_search_topk serves), TAVB_MAX_LARGE_K without; outputs [n, k] / [n] as
+ * tavb_search_batch (ordinals carry ordinal_base).  The positions are staged, every wave enqueued, the keys copied back ONCE: one
+ * synchronise at the end and none in between on routes that have none.  n == 0 or an empty corpus: zero counts, nothing launched.
+ * tavb_search_rows_device: the positions on the device (int32 [n]; the CALLER guarantees their range -- a position outside [0, rows) is
+ * gathered as a row of zeros), out keys [n, k] sorted and zero-padded, carrying ordinal_base + row (below 2^32 - 1), and counts int32 [n]
+ * (optional, NULL: not written) in device or device-writable pinned memory.  Asynchronous, like the other *_device forms.
+ * tavb_search_rows_sorted: every survivor per row (max_hits == 0, the `[-0:]` quirk) through tavb_search_sorted's passes; outputs,
+ * max_total and the synchronises are that call's.  Its results are concatenated lists of any length, which the drop launch does not take:
+ * with exclude_self the own row is removed ON THE HOST, after the copy (one pass over the results).
+ * tavb_gather_rows_f32: the gather on its own -- dev_positions int32 [n] -> dev_out float32 [n, dim].  Asynchronous. */
+int tavb_search_rows(tavb_ctx* ctx, const int32_t* positions_host, int64_t n, int32_t k, int32_t exclude_self, const float* min_scores,
+                     int64_t* out_ordinals, float* out_scores, int32_t* out_counts);
+int tavb_search_rows_device(tavb_ctx* ctx, const int32_t* dev_positions, int64_t n, int32_t k, int32_t exclude_self, const float* min_scores /*host*/,
+                            tavb_key* dev_out_keys, int32_t* dev_out_counts);
+int tavb_search_rows_sorted(tavb_ctx* ctx, const int32_t* positions_host, int64_t n, int32_t exclude_self, const float* min_scores, int64_t max_total,
+                            int64_t* out_ordinals, float* out_scores, int64_t* out_counts, int64_t* out_total);
+int tavb_gather_rows_f32(tavb_ctx* ctx, const int32_t* dev_positions, int64_t n, float* dev_out);
 
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels this context launches, on the stream they run on.

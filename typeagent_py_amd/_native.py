@@ -147,6 +147,10 @@ _SIGNATURES = [
     ("tavb_search_top_messages_allgather", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_allgather_merge_top_messages", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("tavb_remap_key_positions", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64]),
+    ("tavb_search_rows", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_rows_device", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("tavb_search_rows_sorted", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    ("tavb_gather_rows_f32", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     ("tavb_profile_enable", c_int, [c_void_p, c_int32]),
     ("tavb_profile_reset", c_int, [c_void_p]),
     ("tavb_profile_read", c_int, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int64)]),
@@ -1031,6 +1035,73 @@ class Engine:
         total = c_int64(0)
         with self._lock:
             rc = self.lib.tavb_search_sorted(self._h, _addr(a), nq, int(k), _addr(t), bound, _addr(ords), _addr(scs), _addr(cnts), byref(total))
+        _check(self.lib, rc)
+        m = int(total.value)
+        return ords[:m], scs[:m], cnts
+
+    # -- rows of the corpus as queries ---------------------------------------
+    def _positions(self, positions) -> np.ndarray:
+        """Corpus rows (wrapped and range-checked by the caller) -> contiguous int32 [n]."""
+        return np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+
+    def gather_rows(self, dev_positions, out=None):
+        """Corpus rows dev_positions (torch int32 [n] on this device, each in [0, rows)) -> torch float32 [n, dim] on the device: the values the
+        kernels multiply, fp16 rows widened exactly (tavb_gather_rows_f32).  Async: `synchronize()` before reading."""
+        ptr, n = self._row_list(dev_positions)
+        if out is None:
+            out = self._torch.empty((n, self.dim), dtype=self._torch.float32, device=dev_positions.device)
+        assert out.dtype == self._torch.float32 and out.is_contiguous() and out.numel() >= n * self.dim
+        if n:
+            with self._lock:
+                rc = self.lib.tavb_gather_rows_f32(self._h, ptr, n, c_void_p(out.data_ptr()))
+            _check(self.lib, rc)
+        return out
+
+    def search_rows(self, positions, k: int, thrs, exclude_self: bool = True):
+        """The neighbours of corpus rows `positions` (int [n], each in [0, rows)) without the rows leaving the device (tavb_search_rows):
+        thrs float32 [n] (or one for all); exclude_self: the row's own entry is taken out (1 <= k <= MAX_LARGE_K - 1), else the plain lookup
+        with the rows as queries (k <= MAX_LARGE_K) -> (ordinals [n,k], scores [n,k], counts [n]), the layout of `search_batch`."""
+        p = self._positions(positions)
+        n = p.shape[0]
+        t = batch_thresholds(thrs, n)
+        ords, scs, cnts = np.empty((n, k), dtype=np.int64), np.empty((n, k), dtype=np.float32), np.zeros(n, dtype=np.int32)
+        with self._lock:
+            rc = self.lib.tavb_search_rows(self._h, _addr(p), n, k, 1 if exclude_self else 0, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
+        _check(self.lib, rc)
+        return ords, scs, cnts
+
+    def search_rows_device(self, dev_positions, k: int, thrs, exclude_self: bool = True, out_keys=None, out_counts=None):
+        """`search_rows` with the positions on the device (torch int32 [n]; the CALLER guarantees their range) and nothing waited for
+        (tavb_search_rows_device) -> (torch int64 [n, k] sorted, zero-padded keys carrying global ordinals, torch int32 [n] counts).
+        Async: `synchronize()` before reading."""
+        torch = self._torch
+        ptr, n = self._row_list(dev_positions)
+        t = batch_thresholds(thrs, n)
+        out_keys = self._out_keys(out_keys, n, k, dev_positions.device)
+        if out_counts is None:
+            out_counts = torch.empty(n, dtype=torch.int32, device=dev_positions.device)
+        assert out_counts.dtype == torch.int32 and out_counts.is_contiguous() and out_counts.numel() >= n
+        if n:
+            with self._lock:
+                rc = self.lib.tavb_search_rows_device(self._h, ptr, n, k, 1 if exclude_self else 0, _addr(t), c_void_p(out_keys.data_ptr()),
+                                                      c_void_p(out_counts.data_ptr()))
+            _check(self.lib, rc)
+        return out_keys, out_counts
+
+    def search_rows_sorted(self, positions, thrs, exclude_self: bool = True):
+        """Every survivor per row (max_hits == 0), sorted on the device (tavb_search_rows_sorted) -> (ordinals int64 [total], scores float32
+        [total], counts int64 [n]), the layout of `search_sorted`."""
+        p = self._positions(positions)
+        n = p.shape[0]
+        t = batch_thresholds(thrs, n)
+        bound = n * self.rows
+        ords = np.empty(max(bound, 1), dtype=np.int64)
+        scs = np.empty(max(bound, 1), dtype=np.float32)
+        cnts = np.zeros(n, dtype=np.int64)
+        total = c_int64(0)
+        with self._lock:
+            rc = self.lib.tavb_search_rows_sorted(self._h, _addr(p), n, 1 if exclude_self else 0, _addr(t), bound, _addr(ords), _addr(scs), _addr(cnts),
+                                                  byref(total))
         _check(self.lib, rc)
         m = int(total.value)
         return ords[:m], scs[:m], cnts

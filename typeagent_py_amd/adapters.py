@@ -148,6 +148,23 @@ def uninstall_remove_term() -> None:
             setattr(cls, name, original)
 
 
+def find_duplicate_terms(index, min_score: float, max_per_row: int = 16) -> list[tuple[str, str, float]]:
+    """Near-identical terms of one of typeagent's two fuzzy related-terms indexes -- the memory provider's `TermEmbeddingIndex`
+    (`_vectorbase`, `_texts`) or the sqlite provider's `SqliteRelatedTermsFuzzy` (`_vector_base`, `_terms_list`) -- whose `add_terms`
+    de-duplicates by text only: (term, other term, score) for every pair of rows scoring at least min_score, the earlier term first, in
+    `VectorBase.near_duplicate_pairs`' order.  Needs an index whose vector base is this package's (`install()`)."""
+    if hasattr(index, "_vectorbase") and hasattr(index, "_texts"):
+        vector_base, texts = index._vectorbase, index._texts
+    elif hasattr(index, "_vector_base") and hasattr(index, "_terms_list"):
+        vector_base, texts = index._vector_base, index._terms_list
+    else:
+        raise TypeError(f"{type(index).__name__} is neither of the fuzzy related-terms indexes")
+    if not hasattr(vector_base, "near_duplicate_pairs"):
+        raise TypeError("the index' vector base is not typeagent_py_amd's VectorBase (call install() first)")
+    i, j, s = vector_base.near_duplicate_pairs(min_score, max_per_row)
+    return [(texts[a], texts[b], float(c)) for a, b, c in zip(i.tolist(), j.tolist(), s.tolist())]
+
+
 def best_score_per_message(
     hits: Sequence[ScoredInt],
     row_to_message: Callable[[int], int] | Sequence[int] | np.ndarray,

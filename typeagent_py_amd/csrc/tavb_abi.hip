@@ -263,6 +263,9 @@ const Option kOptions[] = {
     RANGE("top_messages_tile_min_batch", top_messages_tile_min_batch, 1, 1 << 20),
     RANGE("scope_wave_bytes", scope_wave_bytes, 1, (int64_t)1 << 40),
     RANGE("compact_pass_rows", compact_pass_rows, 0, 0x7FFFFFFE),
+    SWITCH("rows_query", rows_query),
+    RANGE("rows_query_wave", rows_query_wave, 1, 1 << 20),
+    READ_ONLY("rows_query_launches", last_rows_query),
     READ_ONLY("norm_rows", norm_rows),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),

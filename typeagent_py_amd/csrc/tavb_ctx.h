@@ -1,7 +1,7 @@
 // What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the fused-k lookups and the
 // staging), tavb_lookup_topk.hip (the large-k and sorted lookups), tavb_lookup_masked.hip (the batched resident subset, the masked and
 // scoped batches), tavb_row_edits.hip (row compaction, expansion and scattered writes), tavb_mask_entry.hip (the row masks and the scope
-// algebra), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
+// algebra), tavb_lookup_rows.hip (rows of the corpus as queries), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
 // context itself and the internal functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
 // tavb_search_device_dispatch lives in tavb::host, whose symbols stay inside the library.
 #pragma once
@@ -186,6 +186,12 @@ struct tavb_ctx {
   Buffer d_mask_counts;  // row masks (tavb_mask_expand, tavb_mask.hip): set rows per workgroup chunk of the mask
   Buffer d_compact;      // row compaction in place (tavb_compact_rows): the kept rows of one pass, densely, before they are written back further down
   int64_t compact_pass_rows = 0;  // option: rows per pass of an in-place compaction, rounded up to a multiple of 64 (0 = auto: about 64 MiB of rows)
+  // rows of the corpus as queries (tavb_search_rows, tavb_lookup_rows.hip): the positions of a call, the float32 query batch of one wave of at
+  // most rows_query_wave rows, that wave's lists of k + 1 keys, and the lists of k keys of the whole call before they are copied out
+  Buffer d_rows_pos, d_rows_query, d_rows_keys, d_rows_out;
+  int64_t rows_query = 1;            // option: 1 = the binding sends fuzzy_lookup_rows / near_duplicate_pairs through tavb_search_rows, 0 = through the host route (rows to the host, a query batch back)
+  int64_t rows_query_wave = 4096;    // option: most rows one wave of tavb_search_rows gathers and looks up (its batch is wave x dim x 4 bytes)
+  int64_t last_rows_query = 0;       // option "rows_query_launches" (get): gather launches of the last rows lookup; 0 after any other host-synchronous lookup of the unmasked routes
   Buffer d_scope;        // scope algebra (tavb_mask_from_ranges): the merged {start, end} intervals of a scope's collections, one after another
   // scoped batches (tavb_search_scoped_batch): per pass the union of its queries' masks, that union's ascending row list and one membership
   // byte per list position (tavb_mask.hip scope_member_kernel); pinned: every pass' total, then its chunks' MaskChunkInfo
@@ -293,7 +299,7 @@ struct tavb_ctx {
   void for_each_buffer(F&& f) {
     for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
                       &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk, &d_msg_best,
-                      &d_sort_keys, &d_sort_ws, &d_mask_counts, &d_compact, &d_scope, &d_scope_bits, &d_scope_rows, &d_scope_member, &d_scope_planes, &h_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
+                      &d_sort_keys, &d_sort_ws, &d_rows_pos, &d_rows_query, &d_rows_keys, &d_rows_out, &d_mask_counts, &d_compact, &d_scope, &d_scope_bits, &d_scope_rows, &d_scope_member, &d_scope_planes, &h_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
                       &d_local, &d_xlocal, &d_gather})
       f(*b);
   }
@@ -559,6 +565,11 @@ int top_messages_tile_pass(tavb_ctx* c, const float* d_q, int n, const float* mi
 // same list.  ONE synchronise per wave (the unions' sizes); everything else is enqueued and not waited for.
 int search_scoped_topk_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const uint32_t* const* masks,
                             uint32_t index_base, u64_t* work, u64_t* out, int32_t* out_rounds);
+
+// tavb_search_sorted's passes with the queries on the device (k: 1 .. c->rows, the whole corpus; results carry base + row): synchronises per
+// group of queries and per piece of results, as tavb_search_sorted does
+int search_sorted_device(tavb_ctx* c, const float* d_q, int nq, int64_t k, const float* min_scores /*host, nq*/, int64_t base, int64_t max_total,
+                         int64_t* out_ords, float* out_scores, int64_t* out_counts, int64_t* out_total);
 
 // ---- tavb_lookup_masked.hip
 // what the scoped entry points check after their own head: 1 <= k <= k_max, the masks; *empty: nothing to scan

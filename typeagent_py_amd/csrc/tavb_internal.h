@@ -184,6 +184,14 @@ hipError_t launch_merge_scatter(const unsigned long long* lists, int n_lists, in
 hipError_t launch_remap_positions(const unsigned long long* src, unsigned long long* dst, int64_t n, const int32_t* map, int64_t map_len, uint32_t base,
                                   hipStream_t stream);
 
+// Rows of the corpus as queries (tavb_rows_query.hip).  rows_to_queries: corpus rows positions[j] (each in [0, rows); anything else gives a row
+// of zeros) -> out [n, dim] float32, fp16 rows widened exactly.  drop_self: lists in [n][k + 1] (with_self) of sorted, zero-padded keys carrying
+// index_base + row -> out [n][k] without the key of row index_base + positions[q], the gap closed, the first k kept, + counts [n] (optional:
+// keys left per query); without with_self the lists hold k keys, nothing is removed (in == out allowed) and only the counts are written.
+hipError_t launch_rows_to_queries(const void* corpus, bool f16, int64_t rows, int dim, const int32_t* positions, int64_t n, float* out, hipStream_t stream);
+hipError_t launch_drop_self(const unsigned long long* in, bool with_self, const int32_t* positions, uint32_t index_base, int64_t n, int k,
+                            unsigned long long* out, int32_t* counts, hipStream_t stream);
+
 // Row masks (tavb_mask.hip).  mask_expand: bits (uint32 words, row r = bit r & 31 of word r >> 5; bits at or beyond `rows` ignored) -> out
 // [0 .. min(total, cap)) = the set rows ascending, *total_out = their number (device-writable memory, e.g. pinned); counts: workspace of
 // mask_blocks(rows) words.  Two launches, grids fixed by `rows`.  mask_pack: bytes [rows] (non-zero = set) -> those words.

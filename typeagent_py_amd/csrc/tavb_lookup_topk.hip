@@ -424,6 +424,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   if (!queries_host || !min_scores || !out_ordinals || !out_scores || !out_counts) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
+  c->last_rows_query = 0;
   if (c->rows == 0) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
   const float* d_q;
@@ -673,6 +674,7 @@ int tavb_search_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, int64
   if (!queries_host || !min_scores || !out_counts || (max_total > 0 && (!out_ordinals || !out_scores))) return fail(TAVB_E_INVALID, "null argument");
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
+  c->last_rows_query = 0;
   for (int q = 0; q < nq; ++q) out_counts[q] = 0;
   if (c->rows == 0) return TAVB_OK;
   DeviceGuard guard(c->device);
@@ -957,3 +959,12 @@ int tavb_sort_keys_device(tavb_ctx* c, tavb_key* dev_keys, int64_t n) {
 }
 
 }  // extern "C"
+
+namespace tavb {
+namespace host __attribute__((visibility("hidden"))) {
+int search_sorted_device(tavb_ctx* c, const float* d_q, int nq, int64_t k, const float* min_scores, int64_t base, int64_t max_total, int64_t* out_ords,
+                         float* out_scores, int64_t* out_counts, int64_t* out_total) {
+  return search_sorted_impl(c, d_q, nq, k, min_scores, nullptr, c->rows, base, max_total, out_ords, out_scores, out_counts, out_total);
+}
+}  // namespace host
+}  // namespace tavb

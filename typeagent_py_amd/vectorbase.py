@@ -838,6 +838,163 @@ class VectorBase:
         eng = self._sync_device()
         return self._batch_result(*eng.search_batch(queries, max_hits, thr), max_hits, as_arrays)
 
+    # ------------------------------------------------------------------ rows of the index as queries (additive)
+    @staticmethod
+    def _rows_native(eng) -> bool:
+        """A single-GPU engine with the "rows_query" option on (the default) takes tavb_search_rows; device groups, test doubles and
+        "rows_query" = 0 take the host route."""
+        return isinstance(eng, _native.Engine) and hasattr(eng, "search_rows") and eng.get_option("rows_query") != 0
+
+    def _rows_as_queries(self, pos: np.ndarray) -> np.ndarray:
+        """Host route: rows `pos` as the float32 values the kernels multiply -- the host matrix' rows, through float16 where the corpus is
+        stored as fp16 (the conversion the load path applies: round to nearest even)."""
+        if self._device_only is not None:
+            self._materialize_host()
+        rows = np.ascontiguousarray(self._host[: self._count][pos], dtype=np.float32)
+        if self._dtype == _native.TAVB_F16:
+            with np.errstate(over="ignore"):
+                rows = rows.astype(np.float16).astype(np.float32)
+        return rows
+
+    def _lookup_rows_arrays(self, eng, pos: np.ndarray, k: int, thr, exclude_self: bool, native: bool):
+        """1 <= k: the best k neighbours of rows `pos` -> (ordinals [n, k] carrying the engine's ordinal base, scores [n, k], counts [n]).
+        native: ONE call of tavb_search_rows.  Host route, the definition: the rows as a float32 query batch through
+        `fuzzy_lookup_embeddings` with one hit more, the row's own entry removed, the first k kept."""
+        if native:
+            return eng.search_rows(pos, k, thr, exclude_self)
+        queries = self._rows_as_queries(pos)
+        kk = k + (1 if exclude_self else 0)
+        if kk <= _PAGE:
+            ords, scs, cnts = self.fuzzy_lookup_embeddings(queries, kk, thr, as_arrays=True)
+        else:
+            ords, scs, cnts = self._lists_as_rows(self.fuzzy_lookup_embeddings(queries, kk, thr), kk)
+        if not exclude_self:
+            return ords, scs, cnts
+        own = pos + int(getattr(eng, "ordinal_base", 0))
+        slot = np.arange(k + 1)[None, :]
+        is_self = (ords == own[:, None]) & (slot < cnts[:, None])
+        self_slot = np.where(is_self.any(axis=1), is_self.argmax(axis=1), k + 1)
+        src = np.arange(k)[None, :] + (np.arange(k)[None, :] >= self_slot[:, None])
+        out_cnts = np.minimum(cnts - is_self.any(axis=1), k).astype(np.int32)
+        return np.take_along_axis(ords, src, axis=1), np.take_along_axis(scs, src, axis=1), out_cnts
+
+    @staticmethod
+    def _lists_as_rows(lists, k: int):
+        """Q lists of ScoredInt -> (ordinals int64 [Q, k], float32 scores [Q, k], counts int32 [Q]), zero-padded."""
+        ords = np.zeros((len(lists), k), np.int64)
+        scs = np.zeros((len(lists), k), np.float32)
+        cnts = np.zeros(len(lists), np.int32)
+        for i, hits in enumerate(lists):
+            m = len(hits)
+            ords[i, :m] = [h.item for h in hits]
+            scs[i, :m] = [h.score for h in hits]
+            cnts[i] = m
+        return ords, scs, cnts
+
+    def fuzzy_lookup_rows(
+        self,
+        ordinals,
+        max_hits: int | None = None,
+        min_score: float | None = None,
+        exclude_self: bool = True,
+    ) -> list[list[ScoredInt]]:
+        """The nearest neighbours of rows ALREADY in the index ("more like this"): per ordinal what
+        `fuzzy_lookup_embedding(row, max_hits + 1, min_score)` returns with the row's own entry removed, cut to max_hits -- exactly, ties
+        included.  `ordinals` index the rows as numpy would (negatives wrap, out of range raises IndexError, duplicates are answered
+        twice; an int is a list of one).  exclude_self=False: the plain lookup with the rows as queries.  On a single-GPU engine the rows
+        never leave the device (tavb_search_rows: gather, lookup, the own row dropped, one copy back); device groups, host-only doubles and
+        the option "rows_query" = 0 take the host route, which is the definition and gives the same lists."""
+        max_hits, thr = self._limits(max_hits, min_score)
+        if isinstance(ordinals, (int, np.integer)):
+            ordinals = [int(ordinals)]
+        if len(ordinals) == 0:
+            return []
+        _, pos = self._wrap_subset(ordinals, self._count)  # (an empty index: every ordinal is out of range)
+        eng = self._sync_device()
+        native = self._rows_native(eng)
+        extra = 1 if exclude_self else 0
+        if 1 <= max_hits <= _native.MAX_LARGE_K - extra:
+            ords, scs, cnts = self._lookup_rows_arrays(eng, pos, max_hits, thr, exclude_self, native)
+            return _scored_lists(np.ascontiguousarray(ords), np.ascontiguousarray(scs), np.ascontiguousarray(cnts, dtype=np.int32), max_hits)
+        if native and max_hits == 0 and eng.get_option("sort_all") != 0:  # every survivor: the sorted route, the own row dropped after the copy
+            return _sorted_lists(*eng.search_rows_sorted(pos, thr, exclude_self))
+        # every survivor (max_hits == 0) and max_hits beyond the large-k route, or engines without it: the plain lookups, the own entry removed by hand
+        lists = self.fuzzy_lookup_embeddings(self._rows_as_queries(pos), max_hits + extra if max_hits else 0, thr)
+        if not exclude_self:
+            return lists
+        own = (pos + int(getattr(eng, "ordinal_base", 0))).tolist()
+        out = []
+        for o, hits in zip(own, lists):
+            at = next((i for i, h in enumerate(hits) if h.item == o), None)
+            if at is not None:
+                hits = hits[:at] + hits[at + 1:]
+            out.append(hits[:max_hits] if max_hits else hits)
+        return out
+
+    def near_duplicate_pairs(self, min_score: float, max_per_row: int = 16, among=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Near-duplicate detection: (i, j, score) with i < j, one entry per unordered pair -- for every row i (of `among`, a `RowMask`
+        or anything `row_mask` takes, where given) the max_per_row best rows j > i (of `among`) scoring at least min_score; sorted by
+        (i, score descending, j ascending).
+
+        The rows are looked up in waves of the engine's "rows_query_wave" through the UNRESTRICTED lookup (`fuzzy_lookup_rows`' arrays):
+        a wave asks for k best others per row; a row is settled when its list is not full (it holds every survivor) or holds
+        max_per_row admissible j -- the admissible entries of the k best overall, in order, are the best admissible ones -- and the rows
+        that are not are asked again with four times the k, at last for every survivor.  Nothing is approximated."""
+        if max_per_row < 1:
+            raise ValueError("max_per_row must be >= 1")
+        _, thr = self._limits(1, min_score)
+        n = self._count
+        empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
+        if n == 0:
+            return empty
+        allowed = None if among is None else self._mask_bools(self._resolve_mask(among))
+        rows = np.arange(n, dtype=np.int64) if allowed is None else np.flatnonzero(allowed).astype(np.int64)
+        rows = rows[rows < n - 1]  # (the last row has no j > i)
+        if len(rows) == 0:
+            return empty
+        eng = self._sync_device()
+        native = self._rows_native(eng)
+        base = int(getattr(eng, "ordinal_base", 0))
+        wave = int(eng.get_option("rows_query_wave")) if native else 4096
+        k_max = min(_native.MAX_LARGE_K - 1, max(n - 1, 1))  # (n - 1: every other row)
+        out_i, out_j, out_s = [], [], []
+
+        def admit(i: int, js: np.ndarray, ss: np.ndarray):
+            ok = js > i
+            if allowed is not None:
+                ok &= allowed[js]
+            return js[ok], ss[ok]
+
+        def settle(i: int, js: np.ndarray, ss: np.ndarray) -> None:
+            js, ss = js[:max_per_row], ss[:max_per_row]
+            out_i.append(np.full(len(js), i, np.int64))
+            out_j.append(js)
+            out_s.append(ss)
+
+        for w0 in range(0, len(rows), wave):
+            todo = rows[w0:w0 + wave]
+            k = min(max_per_row + 1, k_max)
+            done: dict[int, tuple] = {}
+            while len(todo):
+                ords, scs, cnts = self._lookup_rows_arrays(eng, todo, k, thr, True, native)
+                again = []
+                for r, i in enumerate(todo.tolist()):
+                    m = int(cnts[r])
+                    js, ss = admit(i, ords[r, :m] - base, scs[r, :m])
+                    if m < k or k >= n - 1 or len(js) >= max_per_row:
+                        done[i] = (js, ss)
+                    else:
+                        again.append(i)
+                todo = np.asarray(again, dtype=np.int64)
+                if len(todo) and k == k_max:  # every survivor of the rows still open
+                    for i, hits in zip(todo.tolist(), self.fuzzy_lookup_rows(todo, 0, min_score)):
+                        done[i] = admit(i, np.asarray([h.item for h in hits], np.int64) - base, np.asarray([h.score for h in hits], np.float32))
+                    break
+                k = min(4 * k, k_max)
+            for i in rows[w0:w0 + wave].tolist():
+                settle(i, *done[i])
+        return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_s).astype(np.float32)
+
     # ------------------------------------------------------------------ masked lookups (additive)
     def row_mask(self, allowed) -> RowMask:
         """An allow-mask -- a bool array or sequence of length len(self), or a torch bool tensor (on the engine's device it never visits the
