@@ -246,6 +246,16 @@ int tavb_synchronize(tavb_ctx* ctx);
  *                   wave is rows_query_wave x dim x 4 bytes whatever n is (tests set it small to split a small call into waves)
  *   "rows_query_launches"  (read only) gather launches (= waves) of the last tavb_search_rows / _device / _sorted / tavb_gather_rows_f32 call; 0
  *                   before the first and after any tavb_search_batch, tavb_search_topk or tavb_search_sorted (what the host route calls)
+ *   "pairs_join"    (default 1; the binding reads it) 1 = similarity_join / near_duplicate_pairs of a single-GPU index are calls of tavb_join_pairs
+ *                   where tavb_plan_pairs_join says so; 0 = the binding keeps the row lookups (tavb_search_rows) -- for A/B runs in one process
+ *   "pairs_join_min_rows"  1 .. 2^31 - 2 (default 8192, PROVISIONAL: not measured yet, tools/pairs_join_sweep.py): fewest rows
+ *                   tavb_plan_pairs_join sends to the join (tests set it to 1)
+ *   "pairs_join_capacity"  1 .. 2^30 (default 2^22): candidate pairs the binding reserves for a call of tavb_join_pairs (20 bytes each)
+ *   "pairs_join_max_capacity"  1 .. 2^30 (default 2^25): the most the binding's ONE retry of a call that did not fit may reserve; a call
+ *                   that needs more keeps the row lookups
+ *   "pairs_join_launches"  (read only) join launches of the last tavb_join_pairs call (1, or 0 when it refused or had nothing to do); 0 after any
+ *                   tavb_search_rows / tavb_search_batch / tavb_search_topk / tavb_search_sorted (what the other route calls)
+ *   "pairs_join_candidates"  (read only) candidate pairs the last join launch counted (more than the call's capacity: it did not fit)
  */
 int tavb_set_option(tavb_ctx* ctx, const char* name, int64_t value);
 int tavb_get_option(tavb_ctx* ctx, const char* name, int64_t* out_value);
@@ -1009,6 +1019,37 @@ int tavb_search_rows_device(tavb_ctx* ctx, const int32_t* dev_positions, int64_t
 int tavb_search_rows_sorted(tavb_ctx* ctx, const int32_t* positions_host, int64_t n, int32_t exclude_self, const float* min_scores, int64_t max_total,
                             int64_t* out_ordinals, float* out_scores, int64_t* out_counts, int64_t* out_total);
 int tavb_gather_rows_f32(tavb_ctx* ctx, const int32_t* dev_positions, int64_t n, float* dev_out);
+
+/* ---- near-duplicate self-join (additive) ----------------------------------------
+ * Every pair of corpus rows i < j whose score reaches min_score -- the whole-corpus form of "which rows are near-duplicates", which the row
+ * lookups above answer with one unrestricted top-k per row.  No reference counterpart.
+ *
+ * tavb_join_pairs: ONE launch computes the tiles tj >= ti of X16 . X16^T on the matrix cores (X16: an fp16 corpus itself, an fp32 corpus'
+ * fp16 shadow -- built as the 128/256-query filter tile builds it, option "f32_shadow") and admits, per element, the pairs j > i whose
+ * approximate score reaches min_score - 2 delta; delta is ONE rigorous bound for the whole launch on |approximate - exact| (the filter
+ * tile's bound with the query replaced by a corpus row: csrc/tavb_pairs_join.hip).  A second launch scores every candidate exactly -- row j
+ * against row i as the query, in the streaming kernels' arithmetic -- and keeps those reaching min_score (compared as float32): the score of a
+ * pair is bit for bit what tavb_search_sorted reports for row j with row i as the query.  dev_mask_bits (optional, NULL: every row): a packed
+ * mask over the corpus' rows (tavb_mask_expand's layout, 4-byte aligned); only pairs whose BOTH rows are set are reported.
+ * Host-synchronous.  out_i / out_j (int64, carrying ordinal_base) / out_scores (float32): room for `capacity` (1 .. 2^30) entries each;
+ * *out_total pairs are written, in ARBITRARY order.  *out_needed = the candidate pairs the join counted.  Returns
+ *   TAVB_OK             the pairs are complete (also: fewer than two rows, or a NaN min_score -- no pairs, nothing launched);
+ *   TAVB_PAIRS_NO_FIT   *out_needed > capacity: nothing was written (*out_total = 0); a call with capacity >= *out_needed fits;
+ *   TAVB_PAIRS_REFUSED  delta is not finite (a row holds inf / NaN, or overflows fp16), or there is no memory for the shadow or the
+ *                       workspace: nothing can be proven or built, nothing was launched, the caller keeps the row lookups;
+ * both positive: they are answers, not failures, and set no message.  rows that are not a multiple of 64 elements, an fp32 corpus under
+ * "f32_shadow" = 0: TAVB_E_UNSUPPORTED; NULL outputs, a capacity out of range, a misaligned mask: TAVB_E_INVALID.  Timed under
+ * TAVB_KERNEL_MFMA (the join) and TAVB_KERNEL_RESCORE (the maxima, the rescoring).
+ *
+ * tavb_plan_pairs_join: whether the binding sends an index to the join under option "pairs_join" = 1.  1 when dim is a multiple of 64 (up
+ * to 16384: the filter tile's width rule), 2 <= rows < 2^31 - 1, rows >= min_rows (the option "pairs_join_min_rows"), the engine is a single
+ * GPU (single_gpu != 0: device groups and row shards keep the row lookups) and, for TAVB_F32, the shadow exists or may be built (has_shadow
+ * != 0: "f32_shadow" >= 1).  0 otherwise; negative: an argument out of range.  A pure function, needs no context and no GPU. */
+#define TAVB_PAIRS_NO_FIT 1
+#define TAVB_PAIRS_REFUSED 2
+int tavb_join_pairs(tavb_ctx* ctx, float min_score, const uint32_t* dev_mask_bits, int64_t capacity, int64_t* out_i, int64_t* out_j, float* out_scores,
+                    int64_t* out_total, int64_t* out_needed);
+int tavb_plan_pairs_join(int64_t rows, int32_t dim, int32_t dtype, int32_t has_shadow, int32_t single_gpu, int64_t min_rows);
 
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels this context launches, on the stream they run on.

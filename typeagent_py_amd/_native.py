@@ -151,6 +151,8 @@ _SIGNATURES = [
     ("tavb_search_rows_device", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     ("tavb_search_rows_sorted", c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     ("tavb_gather_rows_f32", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("tavb_join_pairs", c_int, [c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    ("tavb_plan_pairs_join", c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int64]),
     ("tavb_profile_enable", c_int, [c_void_p, c_int32]),
     ("tavb_profile_reset", c_int, [c_void_p]),
     ("tavb_profile_read", c_int, [c_void_p, c_int32, POINTER(c_double), POINTER(c_int64)]),
@@ -266,6 +268,19 @@ def plan_masked(nq: int, k: int, dim: int, dtype: int, allowed: int, span: int, 
     "mask_tile" = 1, False: the gather route (tavb_plan_masked; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
     lib = load_library(preload_torch=False)
     r = lib.tavb_plan_masked(int(nq), int(k), int(dim), int(dtype), int(allowed), int(span), int(min_bytes), int(pct))
+    _check(lib, r if r < 0 else 0)
+    return bool(r)
+
+
+PAIRS_JOIN_MIN_ROWS = 8192  # the default of the option "pairs_join_min_rows" (provisional: tools/pairs_join_sweep.py has not run yet)
+PAIRS_NO_FIT, PAIRS_REFUSED = 1, 2  # tavb_join_pairs' two answers that are no failures (include/tavb.h)
+
+
+def plan_pairs_join(rows: int, dim: int, dtype: int, has_shadow: bool = True, single_gpu: bool = True, min_rows: int = PAIRS_JOIN_MIN_ROWS) -> bool:
+    """True: `similarity_join` / `near_duplicate_pairs` of an index of `rows` x `dim` rows take the self-join under option "pairs_join" = 1,
+    False: the row lookups (tavb_plan_pairs_join; dtype TAVB_F32 / TAVB_F16).  Needs no GPU."""
+    lib = load_library(preload_torch=False)
+    r = lib.tavb_plan_pairs_join(int(rows), int(dim), int(dtype), int(bool(has_shadow)), int(bool(single_gpu)), int(min_rows))
     _check(lib, r if r < 0 else 0)
     return bool(r)
 
@@ -1069,6 +1084,36 @@ class Engine:
             rc = self.lib.tavb_search_rows(self._h, _addr(p), n, k, 1 if exclude_self else 0, _addr(t), _addr(ords), _addr(scs), _addr(cnts))
         _check(self.lib, rc)
         return ords, scs, cnts
+
+    def plans_pairs_join(self) -> bool:
+        """Whether this engine's corpus takes the self-join: the switch "pairs_join" and tavb_plan_pairs_join under this engine's options."""
+        return self.get_option("pairs_join") != 0 and plan_pairs_join(self.rows, self.dim, self.dtype, self.get_option("f32_shadow") != 0, True,
+                                                                      self.get_option("pairs_join_min_rows"))
+
+    def join_pairs(self, min_score, mask=None):
+        """Every pair of corpus rows i < j scoring at least min_score (float32), both in `mask` where given (torch int32 packed mask on this
+        device) -> (i int64 [m], j int64 [m], scores float32 [m]) in ARBITRARY order (tavb_join_pairs).  A call whose candidates do not fit
+        "pairs_join_capacity" is made once more with the size it asked for, if that is within "pairs_join_max_capacity".  None: the join
+        refused (a non-finite row: its bound proves nothing) or needs more than that -- the caller keeps the row lookups."""
+        if mask is not None:
+            self._check_device_words(mask, "the mask")
+        cap = int(self.get_option("pairs_join_capacity"))
+        for _ in range(2):
+            out_i, out_j, out_s = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.float32)
+            total, needed = c_int64(0), c_int64(0)
+            with self._lock:
+                rc = self.lib.tavb_join_pairs(self._h, c_float(float(min_score)), None if mask is None else c_void_p(mask.data_ptr()), cap, _addr(out_i),
+                                              _addr(out_j), _addr(out_s), byref(total), byref(needed))
+            if rc == PAIRS_REFUSED:
+                return None
+            if rc != PAIRS_NO_FIT:
+                _check(self.lib, rc)
+                m = int(total.value)
+                return out_i[:m].copy(), out_j[:m].copy(), out_s[:m].copy()
+            if needed.value <= cap or needed.value > self.get_option("pairs_join_max_capacity"):
+                return None
+            cap = int(needed.value)
+        return None
 
     def search_rows_device(self, dev_positions, k: int, thrs, exclude_self: bool = True, out_keys=None, out_counts=None):
         """`search_rows` with the positions on the device (torch int32 [n]; the CALLER guarantees their range) and nothing waited for

@@ -152,7 +152,8 @@ def find_duplicate_terms(index, min_score: float, max_per_row: int = 16) -> list
     """Near-identical terms of one of typeagent's two fuzzy related-terms indexes -- the memory provider's `TermEmbeddingIndex`
     (`_vectorbase`, `_texts`) or the sqlite provider's `SqliteRelatedTermsFuzzy` (`_vector_base`, `_terms_list`) -- whose `add_terms`
     de-duplicates by text only: (term, other term, score) for every pair of rows scoring at least min_score, the earlier term first, in
-    `VectorBase.near_duplicate_pairs`' order.  Needs an index whose vector base is this package's (`install()`)."""
+    `VectorBase.near_duplicate_pairs`' order (on a single-GPU engine with enough rows of a multiple of 64 elements that is one
+    triangular self-join on the matrix cores, `VectorBase.similarity_join`; elsewhere one lookup per row).  Needs an index whose vector base is this package's (`install()`)."""
     if hasattr(index, "_vectorbase") and hasattr(index, "_texts"):
         vector_base, texts = index._vectorbase, index._texts
     elif hasattr(index, "_vector_base") and hasattr(index, "_terms_list"):

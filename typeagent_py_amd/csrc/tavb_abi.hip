@@ -266,6 +266,12 @@ const Option kOptions[] = {
     SWITCH("rows_query", rows_query),
     RANGE("rows_query_wave", rows_query_wave, 1, 1 << 20),
     READ_ONLY("rows_query_launches", last_rows_query),
+    SWITCH("pairs_join", pairs_join),
+    RANGE("pairs_join_min_rows", pairs_join_min_rows, 1, 0x7FFFFFFE),
+    RANGE("pairs_join_capacity", pairs_join_capacity, 1, (int64_t)1 << 30),
+    RANGE("pairs_join_max_capacity", pairs_join_max_capacity, 1, (int64_t)1 << 30),
+    READ_ONLY("pairs_join_launches", last_pairs_join),
+    READ_ONLY("pairs_join_candidates", pairs_join_candidates),
     READ_ONLY("norm_rows", norm_rows),
     READ_ONLY("last_direct", last_direct),
     READ_ONLY("last_graph", last_graph),

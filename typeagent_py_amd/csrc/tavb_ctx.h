@@ -1,7 +1,7 @@
 // What the host files of libtavb.so share -- tavb_abi.hip (context, options, corpus, load path), tavb_lookup.hip (the fused-k lookups and the
 // staging), tavb_lookup_topk.hip (the large-k and sorted lookups), tavb_lookup_masked.hip (the batched resident subset, the masked and
 // scoped batches), tavb_row_edits.hip (row compaction, expansion and scattered writes), tavb_mask_entry.hip (the row masks and the scope
-// algebra), tavb_lookup_rows.hip (rows of the corpus as queries), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
+// algebra), tavb_lookup_rows.hip (rows of the corpus as queries), tavb_lookup_pairs.hip (the near-duplicate self-join), tavb_route.hip (the routing of a device-resident batch) and tavb_comm.hip (RCCL): error reporting, the workspaces, the
 // context itself and the internal functions that cross files.  Private to csrc/; host code only.  Everything here but `struct tavb_ctx` (the C ABI's opaque handle) and
 // tavb_search_device_dispatch lives in tavb::host, whose symbols stay inside the library.
 #pragma once
@@ -89,6 +89,9 @@ constexpr int64_t kMfmaMinBatch = 65;
 // measured -- at 8 queries over 1M x 1536 rows no cell loses, threshold 0 (every pair an atomic) included: 1.08 .. 3.2 x
 // (profiles/r27_top_messages_tile.md); smaller batches were not measured
 constexpr int64_t kTopMessagesTileMinBatch = 8;
+// fewest rows tavb_plan_pairs_join sends to the self-join (option "pairs_join_min_rows"): PROVISIONAL, not measured -- tools/pairs_join_sweep.py
+// finds the smallest swept row count at which the join beats the row lookups; tests/test_gpu_lookup_rows.py needs it above 2000
+constexpr int64_t kPairsJoinMinRows = 8192;
 constexpr int kPlanComputeUnits = 256;
 
 struct PendingTiming {
@@ -192,6 +195,15 @@ struct tavb_ctx {
   int64_t rows_query = 1;            // option: 1 = the binding sends fuzzy_lookup_rows / near_duplicate_pairs through tavb_search_rows, 0 = through the host route (rows to the host, a query batch back)
   int64_t rows_query_wave = 4096;    // option: most rows one wave of tavb_search_rows gathers and looks up (its batch is wave x dim x 4 bytes)
   int64_t last_rows_query = 0;       // option "rows_query_launches" (get): gather launches of the last rows lookup; 0 after any other host-synchronous lookup of the unmasked routes
+  // near-duplicate self-join (tavb_join_pairs, tavb_lookup_pairs.hip): two 64-bit counters (candidates, pairs kept), the candidate pairs and the
+  // kept (i, j, score) of one call, each sized by the call's capacity
+  Buffer d_pairs;
+  int64_t pairs_join = 1;                          // option: 1 = the binding sends similarity_join / near_duplicate_pairs through tavb_join_pairs where tavb_plan_pairs_join says so, 0 = through the row lookups
+  int64_t pairs_join_min_rows = tavb::host::kPairsJoinMinRows;  // option: fewest rows tavb_plan_pairs_join sends to the join
+  int64_t pairs_join_capacity = (int64_t)1 << 22;  // option: candidate pairs a call reserves by default (20 bytes each)
+  int64_t pairs_join_max_capacity = (int64_t)1 << 25;  // option: the most one retry of the binding may ask for
+  int64_t last_pairs_join = 0;                     // option "pairs_join_launches" (get): join launches of the last tavb_join_pairs call; 0 after a refused one and after any row lookup
+  int64_t pairs_join_candidates = 0;               // option (get): candidate pairs the last join launch counted
   Buffer d_scope;        // scope algebra (tavb_mask_from_ranges): the merged {start, end} intervals of a scope's collections, one after another
   // scoped batches (tavb_search_scoped_batch): per pass the union of its queries' masks, that union's ascending row list and one membership
   // byte per list position (tavb_mask.hip scope_member_kernel); pinned: every pass' total, then its chunks' MaskChunkInfo
@@ -299,7 +311,7 @@ struct tavb_ctx {
   void for_each_buffer(F&& f) {
     for (Buffer* b : {&d_queries, &d_queries_f16, &d_lists, &d_out, &d_rows, &d_cand, &d_thr, &d_sample_keys, &d_counts, &d_delta, &d_approx, &d_flag,
                       &d_fb_queries, &d_norm, &d_minscores, &d_fb_cand, &d_shadow, &d_queries_pad, &d_accept, &d_bits, &d_emit, &d_topk_scores, &d_topk, &d_msg_best,
-                      &d_sort_keys, &d_sort_ws, &d_rows_pos, &d_rows_query, &d_rows_keys, &d_rows_out, &d_mask_counts, &d_compact, &d_scope, &d_scope_bits, &d_scope_rows, &d_scope_member, &d_scope_planes, &h_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
+                      &d_sort_keys, &d_sort_ws, &d_rows_pos, &d_rows_query, &d_rows_keys, &d_rows_out, &d_pairs, &d_mask_counts, &d_compact, &d_scope, &d_scope_bits, &d_scope_rows, &d_scope_member, &d_scope_planes, &h_scope, &h_sort_info, &h_topk_rounds, &h_ring[0], &h_ring[1], &d_ring[0], &d_ring[1], &h_stage, &h_out, &h_lists, &h_flag,
                       &d_local, &d_xlocal, &d_gather})
       f(*b);
   }
@@ -392,6 +404,9 @@ struct DirectGroupPlan {
 };
 DirectGroupPlan plan_direct_group(const tavb_ctx* c, int nq, int k, int full_blocks, bool host);
 // Core: queries on device (f32 [nq, dim]) -> sorted key lists d_out [nq, k] (async on the stream).
+// The self-join's operand and bound (tavb_lookup_pairs.hip): the cached row-norm maxima in d_norm brought up to the corpus' rows and, for an
+// fp32 corpus, its fp16 shadow in d_shadow -- reserved and filled the way the wide route does it; enqueued, nothing waited for.
+int prepare_join_operand(tavb_ctx* c);
 int search_device_impl(tavb_ctx* c, const float* d_q, int nq, int k, const float* min_scores /*host, nq*/, const int32_t* d_row_ids, int64_t n_pos,
                        uint32_t index_base, u64_t* d_out, u64_t key_bound = ~0ull);
 

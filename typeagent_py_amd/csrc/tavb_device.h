@@ -113,6 +113,43 @@ __device__ __forceinline__ float wave_uniform(float v) {
 }
 
 // ---------------------------------------------------------------------------
+// the streaming kernels' arithmetic of one row: lane l takes the 16-byte slices l, l + 64, ... of the row, one fmaf chain per lane in
+// element order, then wave_sum (tavb_scan.hip; rescore_pairs_kernel of tavb_pairs_join.hip)
+// ---------------------------------------------------------------------------
+template <typename T>
+struct Elem;
+template <>
+struct Elem<float> {
+  static constexpr int EPL = 4;  // elements in a lane's 16-byte slice
+};
+template <>
+struct Elem<_Float16> {
+  static constexpr int EPL = 8;
+};
+
+// acc += <lane's 16-byte corpus slice, matching query slice>; f16 values are
+// widened exactly to f32, products and sums are f32 FMAs.
+template <typename T>
+__device__ __forceinline__ float dot_slice(f32x4 raw, const float* __restrict__ qf, float acc);
+
+template <>
+__device__ __forceinline__ float dot_slice<float>(f32x4 raw, const float* __restrict__ qf, float acc) {
+  acc = fmaf(raw.x, qf[0], acc);
+  acc = fmaf(raw.y, qf[1], acc);
+  acc = fmaf(raw.z, qf[2], acc);
+  acc = fmaf(raw.w, qf[3], acc);
+  return acc;
+}
+
+template <>
+__device__ __forceinline__ float dot_slice<_Float16>(f32x4 raw, const float* __restrict__ qf, float acc) {
+  const f16x8 h = __builtin_bit_cast(f16x8, raw);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc = fmaf((float)h[i], qf[i], acc);
+  return acc;
+}
+
+// ---------------------------------------------------------------------------
 // One wavefront's running top-K, K = 64 * KPL, kept sorted best-first and spread
 // over the lanes: rank r lives in slot r / 64 of lane r % 64.
 // ---------------------------------------------------------------------------

@@ -192,7 +192,46 @@ hipError_t launch_rows_to_queries(const void* corpus, bool f16, int64_t rows, in
 hipError_t launch_drop_self(const unsigned long long* in, bool with_self, const int32_t* positions, uint32_t index_base, int64_t n, int k,
                             unsigned long long* out, int32_t* counts, hipStream_t stream);
 
-// Row masks (tavb_mask.hip).  mask_expand: bits (uint32 words, row r = bit r & 31 of word r >> 5; bits at or beyond `rows` ignored) -> out
+// Near-duplicate self-join (tavb_pairs_join.hip; geometry, work list and the bound are described there).  launch_pairs_join: rows16 = the n x dim
+// fp16 operand (16-byte aligned, dim a multiple of 64), mask optional (packed, word aligned), thr the inclusive admission threshold on the
+// approximate score; *counter (zeroed by the caller) counts every admitted pair, the first `capacity` of them are stored at cand as
+// (uint32 i, uint32 j).  n_tiles / work / per_wg are filled in by the launcher.  launch_rescore_pairs: counters[0] = that count, counters[1]
+// (zeroed by the caller) = the pairs whose exact score reaches min_score, compacted to out_i / out_j / out_s (room for `capacity` each);
+// nothing is scored when the count passed the capacity.
+struct PairsJoinParams {
+  const void* rows16;
+  int64_t n;
+  int32_t dim;
+  const uint32_t* mask;
+  float thr;
+  unsigned long long capacity;
+  unsigned long long* counter;
+  uint2* cand;
+  int64_t n_tiles, work, per_wg;
+};
+bool pairs_join_supported(int dim);
+hipError_t launch_pairs_join(PairsJoinParams p, int n_cu, hipStream_t stream);
+hipError_t launch_rescore_pairs(const void* corpus, bool f32_rows, int dim, unsigned long long* counters, unsigned long long capacity, const void* cand,
+                                float min_score, uint32_t* out_i, uint32_t* out_j, float* out_s, int n_cu, hipStream_t stream);
+// The join's one bound and its threshold, in float32 as query_prepare_kernel computes its own (the derivation heads tavb_pairs_join.hip):
+// norm_sq = the cached maxima {max ||x16||^2, max ||x - x16||^2}.  delta is +inf where it is not finite (nothing can be proven).
+inline float pairs_join_delta(const float norm_sq[2], int dim) {
+  const float R = __builtin_sqrtf(norm_sq[0]), E = __builtin_sqrtf(norm_sq[1]);
+  const float d = 0.5f * (E * R * 1.0001f + E * (R + E) * 1.0001f + 2.0f * (float)(dim / 8 + 8) * 5.9604645e-8f * (R + E) * (R + E)) + 1.2e-7f;
+  return (d < __builtin_inff()) ? d : __builtin_inff();
+}
+inline float pairs_join_threshold(float min_score, float delta) {
+  const float lo = min_score - 2.0f * delta;
+  if (!(lo > 0.0f)) return -__builtin_inff();
+  uint32_t bits;
+  __builtin_memcpy(&bits, &lo, sizeof bits);
+  --bits;  // one ulp down, as the filter's own threshold
+  float t;
+  __builtin_memcpy(&t, &bits, sizeof t);
+  return t;
+}
+
+// Row masks (tavb_mask.hip). mask_expand: bits (uint32 words, row r = bit r & 31 of word r >> 5; bits at or beyond `rows` ignored) -> out
 // [0 .. min(total, cap)) = the set rows ascending, *total_out = their number (device-writable memory, e.g. pinned); counts: workspace of
 // mask_blocks(rows) words.  Two launches, grids fixed by `rows`.  mask_pack: bytes [rows] (non-zero = set) -> those words.
 int mask_blocks(int64_t rows);

@@ -321,6 +321,7 @@ int tavb_search_batch(tavb_ctx* c, const float* queries_host, int32_t nq, int32_
   c->last_graph = 0;
   c->last_direct = 0;
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   // ---- small corpus, one query: replay the captured (H2D, scan, merge) graph -- one submission instead of three
   const int64_t corpus_bytes = c->rows * c->dim * (c->dtype == TAVB_F16 ? 2 : 4);
   const bool streaming = nq == 1 && !(c->dtype == TAVB_F32 && c->f32_shadow >= 2 && corpus_bytes >= c->f32_shadow_min_bytes);

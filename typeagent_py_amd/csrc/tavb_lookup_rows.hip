@@ -54,6 +54,7 @@ int search_rows_impl(tavb_ctx* c, const int32_t* d_pos, int64_t n, int k, bool e
     if (int rc = c->d_rows_keys.reserve((size_t)wave * kk * sizeof(u64_t))) return rc;
   float* const d_q = reinterpret_cast<float*>(c->d_rows_query.ptr);
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   c->last_graph = 0;
   c->last_direct = 0;
   for (int64_t w0 = 0; w0 < n; w0 += wave) {
@@ -88,6 +89,7 @@ int tavb_gather_rows_f32(tavb_ctx* c, const int32_t* dev_positions, int64_t n, f
   if (c->rows == 0) return fail(TAVB_E_INVALID, "the corpus has no rows to gather");
   DeviceGuard guard(c->device);
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   return gather_wave(c, dev_positions, n, dev_out);
 }
 
@@ -144,6 +146,7 @@ int tavb_search_rows_sorted(tavb_ctx* c, const int32_t* positions_host, int64_t 
   if (int rc = c->d_rows_query.reserve((size_t)wave * c->dim * sizeof(float))) return rc;
   float* const d_q = reinterpret_cast<float*>(c->d_rows_query.ptr);
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   c->last_graph = 0;
   c->last_direct = 0;
   int64_t total = 0;

@@ -425,6 +425,7 @@ int tavb_search_topk(tavb_ctx* c, const float* queries_host, int32_t nq, int32_t
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;  // (an asynchronous large-k call before this one no longer reports: the option speaks of the LAST lookup)
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   if (c->rows == 0) return empty_counts(out_counts, nq);
   DeviceGuard guard(c->device);
   const float* d_q;
@@ -675,6 +676,7 @@ int tavb_search_sorted(tavb_ctx* c, const float* queries_host, int32_t nq, int64
   c->last_topk_refine = 0;
   c->topk_rounds_pending = 0;
   c->last_rows_query = 0;
+  c->last_pairs_join = 0;
   for (int q = 0; q < nq; ++q) out_counts[q] = 0;
   if (c->rows == 0) return TAVB_OK;
   DeviceGuard guard(c->device);

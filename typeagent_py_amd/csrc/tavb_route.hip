@@ -627,6 +627,41 @@ int rerun_flagged(tavb_ctx* c, const int* d_nflag, int cap, const float* d_q, fl
   return TAVB_OK;
 }
 
+// The per-corpus caches brought up to the corpus' rows: the row-norm maxima (d_norm, reserved by the caller) and, from norm_rows on, the fp16
+// shadow of an fp32 corpus or the zero-padded copy of an fp16 one of an odd width (`padded`; d_shadow, reserved by the caller).
+int update_corpus_stats(tavb_ctx* c, bool padded) {
+  const bool f32c = (c->dtype == TAVB_F32);
+  float* d_norm = reinterpret_cast<float*>(c->d_norm.ptr);
+  if (c->norm_rows > c->rows || c->norm_rows == 0) {  // first use on this corpus (or it shrank: the old maxima are still upper bounds, but start over)
+    TAVB_HIP(hipMemsetAsync(d_norm, 0, 2 * sizeof(float), c->stream));
+    c->norm_rows = 0;
+  }
+  if (c->norm_rows < c->rows) {  // rows appended since: extend the maxima (and the shadow)
+    hipError_t e;
+    const int sdim = ((c->dim + 63) / 64) * 64;  // halves per shadow row
+    char* shadow_new = c->d_shadow.ptr ? reinterpret_cast<char*>(c->d_shadow.ptr) + (size_t)c->norm_rows * sdim * 2 : nullptr;
+    if (f32c) {
+      e = tavb::launch_shadow_convert(reinterpret_cast<const float*>(c->corpus) + (size_t)c->norm_rows * c->dim, c->rows - c->norm_rows, c->dim, shadow_new, sdim,
+                                      d_norm, c->stream);
+    } else {
+      if (padded) {  // fp16 rows of an odd width: the same values, rows zero-padded to whole K steps
+        const size_t n_new = (size_t)(c->rows - c->norm_rows);
+        TAVB_HIP(hipMemsetAsync(shadow_new, 0, n_new * sdim * 2, c->stream));
+        TAVB_HIP(hipMemcpy2DAsync(shadow_new, (size_t)sdim * 2, reinterpret_cast<const char*>(c->corpus) + (size_t)c->norm_rows * c->dim * 2, (size_t)c->dim * 2,
+                                  (size_t)c->dim * 2, n_new, hipMemcpyDeviceToDevice, c->stream));
+      }
+      // (the norm kernel loads 16 bytes at a time: widths that are no multiple of 8 are read from the padded copy -- zeros add nothing to a norm)
+      const bool norm_from_pad = padded && (c->dim % 8 != 0);
+      e = norm_from_pad ? tavb::launch_corpus_max_norm(shadow_new, c->rows - c->norm_rows, sdim, d_norm, c->stream)
+                        : tavb::launch_corpus_max_norm(reinterpret_cast<const char*>(c->corpus) + (size_t)c->norm_rows * c->dim * 2, c->rows - c->norm_rows,
+                                                       c->dim, d_norm, c->stream);
+    }
+    if (e != hipSuccess) return fail(TAVB_E_HIP, "corpus norm / shadow launch failed: %s", hipGetErrorString(e));
+    c->norm_rows = c->rows;
+  }
+  return TAVB_OK;
+}
+
 // ... of a SCOPED batch (search_wide_exact with `sw`): re-run on the row-list scoped route with their own masks (search_scoped_impl: what
 // tavb_search_scoped_batch would have answered for them), their lists copied into the callers' rows of d_out.  *n_out: how many there were.
 int rerun_flagged_scoped(tavb_ctx* c, const int* d_nflag, int cap, const float* d_q, float* fq32, int k, const float* min_scores /*host*/,
@@ -735,33 +770,7 @@ int search_wide_exact(tavb_ctx* c, const float* d_q, int nq, int k, const float*
   int* d_flagged = d_nflag + 64;
   {
     Timed t(c, TAVB_KERNEL_RESCORE);
-    if (c->norm_rows > c->rows || c->norm_rows == 0) {  // first use on this corpus (or it shrank: the old maxima are still upper bounds, but start over)
-      TAVB_HIP(hipMemsetAsync(d_norm, 0, 2 * sizeof(float), c->stream));
-      c->norm_rows = 0;
-    }
-    if (c->norm_rows < c->rows) {  // rows appended since: extend the maxima (and the shadow)
-      hipError_t e;
-      const int sdim = ((c->dim + 63) / 64) * 64;  // halves per shadow row
-      char* shadow_new = c->d_shadow.ptr ? reinterpret_cast<char*>(c->d_shadow.ptr) + (size_t)c->norm_rows * sdim * 2 : nullptr;
-      if (f32c) {
-        e = tavb::launch_shadow_convert(reinterpret_cast<const float*>(c->corpus) + (size_t)c->norm_rows * c->dim, c->rows - c->norm_rows, c->dim, shadow_new, sdim,
-                                        d_norm, c->stream);
-      } else {
-        if (padded) {  // fp16 rows of an odd width: the same values, rows zero-padded to whole K steps
-          const size_t n_new = (size_t)(c->rows - c->norm_rows);
-          TAVB_HIP(hipMemsetAsync(shadow_new, 0, n_new * sdim * 2, c->stream));
-          TAVB_HIP(hipMemcpy2DAsync(shadow_new, (size_t)sdim * 2, reinterpret_cast<const char*>(c->corpus) + (size_t)c->norm_rows * c->dim * 2, (size_t)c->dim * 2,
-                                    (size_t)c->dim * 2, n_new, hipMemcpyDeviceToDevice, c->stream));
-        }
-        // (the norm kernel loads 16 bytes at a time: widths that are no multiple of 8 are read from the padded copy -- zeros add nothing to a norm)
-        const bool norm_from_pad = padded && (c->dim % 8 != 0);
-        e = norm_from_pad ? tavb::launch_corpus_max_norm(shadow_new, c->rows - c->norm_rows, sdim, d_norm, c->stream)
-                          : tavb::launch_corpus_max_norm(reinterpret_cast<const char*>(c->corpus) + (size_t)c->norm_rows * c->dim * 2, c->rows - c->norm_rows,
-                                                         c->dim, d_norm, c->stream);
-      }
-      if (e != hipSuccess) return fail(TAVB_E_HIP, "corpus norm / shadow launch failed: %s", hipGetErrorString(e));
-      c->norm_rows = c->rows;
-    }
+    if (int rc = update_corpus_stats(c, padded)) return rc;
     // ONE launch: the filter's query operand (padding slots zero), delta / relaxed thresholds / band widths, the selection's counters zeroed,
     // the work list's header zeroed, a uniform batch's thresholds filled in (round 6: a fill kernel, three memsets and this kernel until then)
     if (small) TAVB_HIP(hipMemsetAsync(c->d_queries_f16.ptr, 0, q16_bytes, c->stream));  // (the split planes' padding queries: launch_f32_split_f16 writes the live ones)
@@ -958,6 +967,15 @@ int reserve_shadow(tavb_ctx* c) {
 }
 
 }  // namespace
+
+// tavb_lookup_pairs.hip: the self-join's operand and bound -- the maxima, and for an fp32 corpus its fp16 shadow, as the wide route builds them
+int tavb::host::prepare_join_operand(tavb_ctx* c) {
+  if (c->dtype == TAVB_F32)
+    if (int rc = reserve_shadow(c)) return rc;
+  if (int rc = c->d_norm.reserve(256)) return rc;
+  Timed t(c, TAVB_KERNEL_RESCORE);
+  return update_corpus_stats(c, false);
+}
 
 // Routes a device-resident query batch: streaming scan (few queries), 32/64-query tile (small batches; every batch on
 // fp32 corpora), or the 256-query fp16 tile with exact rescoring (large batches on fp16 corpora).  Not part of the public ABI.

@@ -27,17 +27,7 @@
 
 namespace tavb {
 
-template <typename T>
-struct Elem;
-template <>
-struct Elem<float> {
-  static constexpr int EPL = 4;  // elements in a lane's 16-byte slice
-};
-template <>
-struct Elem<_Float16> {
-  static constexpr int EPL = 8;
-};
-
+// (Elem<T> and dot_slice<T>, the per-slice routine of a row's dot product, live in tavb_device.h: tavb_pairs_join.hip shares them)
 template <bool NT>
 __device__ __forceinline__ f32x4 ld16(const void* p) {
   const f32x4* q = reinterpret_cast<const f32x4*>(p);
@@ -45,28 +35,6 @@ __device__ __forceinline__ f32x4 ld16(const void* p) {
     return __builtin_nontemporal_load(q);
   else
     return *q;
-}
-
-// acc += <lane's 16-byte corpus slice, matching query slice>; f16 values are
-// widened exactly to f32, products and sums are f32 FMAs.
-template <typename T>
-__device__ __forceinline__ float dot_slice(f32x4 raw, const float* __restrict__ qf, float acc);
-
-template <>
-__device__ __forceinline__ float dot_slice<float>(f32x4 raw, const float* __restrict__ qf, float acc) {
-  acc = fmaf(raw.x, qf[0], acc);
-  acc = fmaf(raw.y, qf[1], acc);
-  acc = fmaf(raw.z, qf[2], acc);
-  acc = fmaf(raw.w, qf[3], acc);
-  return acc;
-}
-
-template <>
-__device__ __forceinline__ float dot_slice<_Float16>(f32x4 raw, const float* __restrict__ qf, float acc) {
-  const f16x8 h = __builtin_bit_cast(f16x8, raw);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc = fmaf((float)h[i], qf[i], acc);
-  return acc;
 }
 
 // Per-wave selection state for NQ queries.

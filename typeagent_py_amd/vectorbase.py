@@ -936,7 +936,10 @@ class VectorBase:
         or anything `row_mask` takes, where given) the max_per_row best rows j > i (of `among`) scoring at least min_score; sorted by
         (i, score descending, j ascending).
 
-        The rows are looked up in waves of the engine's "rows_query_wave" through the UNRESTRICTED lookup (`fuzzy_lookup_rows`' arrays):
+        On a single-GPU engine whose index `tavb_plan_pairs_join` takes (option "pairs_join"; rows of a multiple of 64 elements, at least
+        "pairs_join_min_rows" of them) the pairs come from ONE triangular self-join on the matrix cores (`similarity_join`), sorted and cut
+        here without a per-row loop.  Everywhere else -- device groups, row shards, host-only doubles, a join that refused -- the rows are
+        looked up in waves of the engine's "rows_query_wave" through the UNRESTRICTED lookup (`fuzzy_lookup_rows`' arrays):
         a wave asks for k best others per row; a row is settled when its list is not full (it holds every survivor) or holds
         max_per_row admissible j -- the admissible entries of the k best overall, in order, are the best admissible ones -- and the rows
         that are not are asked again with four times the k, at last for every survivor.  Nothing is approximated."""
@@ -947,6 +950,9 @@ class VectorBase:
         empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
         if n == 0:
             return empty
+        joined = self._join_pairs_native(thr, among)
+        if joined is not None:  # the self-join: the same pairs by definition -- every admissible pair, ordered, each row's run cut
+            return self._order_pairs(*joined, max_per_row)
         allowed = None if among is None else self._mask_bools(self._resolve_mask(among))
         rows = np.arange(n, dtype=np.int64) if allowed is None else np.flatnonzero(allowed).astype(np.int64)
         rows = rows[rows < n - 1]  # (the last row has no j > i)
@@ -993,6 +999,75 @@ class VectorBase:
                 k = min(4 * k, k_max)
             for i in rows[w0:w0 + wave].tolist():
                 settle(i, *done[i])
+        return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_s).astype(np.float32)
+
+    def _join_pairs_native(self, thr, among):
+        """The self-join where it serves this index (a single-GPU engine, `Engine.plans_pairs_join`, a mask held on the device) ->
+        (i, j, scores) in arbitrary order, positions without the engine's ordinal base; None: the caller takes the row lookups."""
+        eng = self._sync_device()
+        if not (isinstance(eng, _native.Engine) and hasattr(eng, "join_pairs") and eng.plans_pairs_join()):
+            return None
+        dev_bits = None
+        if among is not None:
+            dev_bits = self._resolve_mask(among).dev_bits
+            if dev_bits is None:
+                return None
+        got = eng.join_pairs(thr, dev_bits)
+        if got is None:
+            return None
+        base = int(getattr(eng, "ordinal_base", 0))
+        return got[0] - base, got[1] - base, got[2]
+
+    @staticmethod
+    def _order_pairs(i: np.ndarray, j: np.ndarray, s: np.ndarray, max_per_row: int | None):
+        """Pairs in any order -> sorted by (i, score descending, j ascending), every row's run cut to its first max_per_row (None: whole)."""
+        i, j, s = np.asarray(i, np.int64), np.asarray(j, np.int64), np.asarray(s, np.float32)
+        order = np.lexsort((j, -s, i))
+        i, j, s = i[order], j[order], s[order]
+        if max_per_row is not None and len(i):
+            at = np.arange(len(i))
+            start = np.maximum.accumulate(np.where(np.concatenate([[True], i[1:] != i[:-1]]), at, 0))  # where each row's run begins
+            keep = at - start < max_per_row
+            i, j, s = i[keep], j[keep], s[keep]
+        return i, j, s
+
+    def similarity_join(self, min_score: float, among=None, max_per_row: int | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The self-join of the index: EVERY pair (i, j, score) with i < j (both in `among`, a `RowMask` or anything `row_mask` takes, where
+        given) scoring at least min_score, sorted by (i, score descending, j ascending); max_per_row cuts every row's run to its best
+        max_per_row.  A pair's score is what `fuzzy_lookup_embedding(row i, 0, min_score)` reports for row j.
+
+        A single-GPU engine computes only the upper triangle of the rows' product on the matrix cores, tests the threshold there and
+        scores exactly the few pairs that pass (tavb_join_pairs; `tavb_plan_pairs_join` and the option "pairs_join" decide).  Device
+        groups, row shards, host-only doubles, rows that are no multiple of 64 elements, a corpus with a non-finite row and a result beyond
+        "pairs_join_max_capacity" candidates take the row lookups: `near_duplicate_pairs`' route, every survivor per row for
+        max_per_row=None."""
+        if max_per_row is not None:
+            return self.near_duplicate_pairs(min_score, max_per_row, among)
+        _, thr = self._limits(1, min_score)
+        n = self._count
+        empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
+        if n == 0:
+            return empty
+        joined = self._join_pairs_native(thr, among)
+        if joined is not None:
+            return self._order_pairs(*joined, None)
+        allowed = None if among is None else self._mask_bools(self._resolve_mask(among))
+        rows = np.arange(n, dtype=np.int64) if allowed is None else np.flatnonzero(allowed).astype(np.int64)
+        rows = rows[rows < n - 1]
+        if len(rows) == 0:
+            return empty
+        base = int(getattr(self._sync_device(), "ordinal_base", 0))
+        out_i, out_j, out_s = [], [], []
+        for w0 in range(0, len(rows), 4096):  # every survivor of every row, the admissible ones kept in the lookup's order
+            todo = rows[w0:w0 + 4096]
+            for i, hits in zip(todo.tolist(), self.fuzzy_lookup_rows(todo, 0, min_score)):
+                js = np.asarray([h.item for h in hits], np.int64) - base
+                ok = js > i
+                if allowed is not None:
+                    ok &= allowed[js]
+                out_i.append(np.full(int(ok.sum()), i, np.int64))
+                out_j.append(js[ok])
+                out_s.append(np.asarray([h.score for h in hits], np.float32)[ok])
         return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_s).astype(np.float32)
 
     # ------------------------------------------------------------------ masked lookups (additive)
